@@ -8,10 +8,16 @@ A "step" is one full training iteration on a synthetic NeRF-OSR-lk2-shaped batch
 proposal sampling -> hash encode -> SDF/albedo MLPs -> illumination decode -> DDF hemisphere visibility ->
 hemisphere integral + composite -> all losses -> backward -> gradient all-reduce (N>1) -> 5 Adam groups.
 Inputs are generated on the device before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the headline (value, ms_per_step, ...).  --full adds everything else
+the line can carry: the RCCL self-check, per-kernel roofline timings and HBM counters, device power, the exact-fp32 step, the
+extra configurations and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed (dump_outputs); the inputs
+depend on the arguments alone, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -803,8 +809,8 @@ def live_pmc_traffic(timeout_s: float = 240.0):
         for c in ("FETCH_SIZE", "WRITE_SIZE"):
             dirs[c] = os.path.join(base, c)
             cmd = [exe, "--kernel-trace", "--pmc", c, "--output-format", "csv", "-d", dirs[c], "--", sys.executable, os.path.abspath(__file__),
-                   "--no-spawn", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-graph", "--no-exact-f32", "--no-extra-configs",
-                   "--no-live-pmc"]
+                   "--no-spawn", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-graph", "--no-exact-f32",
+                   "--no-extra-configs", "--no-live-pmc"]
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout_s)
             if r.returncode != 0:
                 return None, f"rocprofv3 --pmc {c} pass exited with code {r.returncode}"
@@ -812,8 +818,8 @@ def live_pmc_traffic(timeout_s: float = 240.0):
         try:  # third pass: matrix-pipe busy cycles and the effective clock per kernel family
             dirs["SQ"] = os.path.join(base, "SQ")
             cmd = [exe, "--kernel-trace", "--pmc", "SQ_VALU_MFMA_BUSY_CYCLES", "GRBM_GUI_ACTIVE", "--output-format", "csv", "-d", dirs["SQ"], "--",
-                   sys.executable, os.path.abspath(__file__), "--no-spawn", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-graph",
-                   "--no-exact-f32", "--no-extra-configs", "--no-live-pmc"]
+                   sys.executable, os.path.abspath(__file__), "--no-spawn", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+                   "--no-graph", "--no-exact-f32", "--no-extra-configs", "--no-live-pmc"]
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout_s)
             out["mfma"] = pmc_mfma(dirs["SQ"]) if r.returncode == 0 else {"error": f"SQ pass exited with code {r.returncode}"}
         except Exception as exc:  # noqa: BLE001
@@ -889,11 +895,112 @@ def cpu_baseline(seconds_budget=25.0):
                       f"{DIRECTIONS} directions + 16 DDF-fit + 8 sky rays; Adam excluded; {dt:.2f} s/step"}
 
 
+def roofline_fields(args, timer, world, ms_step):
+    """--full: the roofline of the kernel family with the largest time in the eager timing iterations, its top three, the whole
+    step's algorithmic rate and counter traffic, and the eight largest families -> {"roofline": ..., "kernels": ...}"""
+    import neusky_amd.ops as ops
+    kernels = timer.summary()
+    peak = PEAK_BF16_MFMA_TFLOPS / 3.0
+    for k in kernels:
+        k["frac_of_833_tflops"] = k["achieved_tflops"] / peak
+    # a family's share of the step = its launches of ONE iteration (the timing iterations are three repeats of the same step)
+    iters = 3
+    for k in kernels:
+        k["ms_per_step"] = k["total_ms"] / iters
+        k["frac_of_8000_GBs"] = k["achieved_GBs"] / HBM_PEAK_GBS if "achieved_GBs" in k else None
+    traffic, whole_step_gb, tsrc = None, None, os.path.join(ROOT, "profiles", PMC_TRAFFIC_FILE)
+    traffic_src = {"file": "profiles/" + PMC_TRAFFIC_FILE, "collected": "committed rocprofv3 --pmc passes (tools/pmc_bench.sh), not this run"}
+    dom = kernels[0]
+    tj = json.load(open(tsrc)) if os.path.exists(tsrc) else None
+    live_note = "not attempted (--no-live-pmc / --no-extra-configs / N > 1)"
+    if world == 1 and not args.no_live_pmc and not args.no_extra_configs:
+        live, live_note = live_pmc_traffic()
+        if live is not None:
+            committed_gb = tj.get("whole_step_GB") if tj is not None else None
+            tj = dict(live, kernel_sources_sha=_sources_sha(step_kernel_sources()))
+            traffic_src = {"collected": live_note, "committed_file_whole_step_GB": committed_gb, "file": "profiles/" + PMC_TRAFFIC_FILE + " (for comparison)"}
+    traffic_src["live_collection"] = live_note
+    if tj is not None:  # HBM bytes per launch from the rocprofv3 --pmc passes; the check that they describe THESE kernels is a field
+        traffic = tj.get("bytes_per_launch", {}).get(dom["kernel"].split(" ")[0])
+        whole_step_gb = tj.get("whole_step_GB")
+        sha = _sources_sha(step_kernel_sources())
+        traffic_src.update({"kernel_sources_sha": sha, "counters_kernel_sources_sha": tj.get("kernel_sources_sha"),
+                            "describes_these_kernels": tj.get("kernel_sources_sha") == sha})
+        for k in kernels:
+            k["pmc_bytes_per_launch"] = tj.get("bytes_per_launch", {}).get(k["kernel"].split(" ")[0])
+            m = (tj.get("mfma") or {}).get(k["kernel"].split(" ")[0]) or {}
+            k["mfma_busy"], k["clock_mhz_under_counters"] = m.get("mfma_busy"), m.get("clock_mhz")
+
+    def bound_of(k):
+        hb = k.get("algorithmic_bytes_per_launch")
+        if hb is not None and hb / (HBM_PEAK_GBS * 1e9) > k["algorithmic_flops_per_launch"] / (peak * 1e12):
+            return "hbm"
+        return "mfma"
+
+    roof = {"bound": "mfma", "achieved": dom["achieved_tflops"], "peak": peak, "unit": "TFLOP/s", "frac": dom["achieved_tflops"] / peak}
+    if bound_of(dom) == "hbm":
+        roof = {"bound": "hbm", "achieved": dom["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": dom["achieved_GBs"] / HBM_PEAK_GBS}
+    top3 = [{"kernel": k["kernel"], "ms_per_step": k["ms_per_step"], "launches_per_step": k["launches"] / iters, "bound": bound_of(k),
+             "mfma_frac_of_833_tflops": k["frac_of_833_tflops"], "hbm_frac_of_8000_GBs": k["frac_of_8000_GBs"],
+             "pmc_bytes_per_launch": k.get("pmc_bytes_per_launch"),
+             "mfma_busy": k.get("mfma_busy"), "clock_mhz": k.get("clock_mhz_under_counters")} for k in kernels[:3]]
+    step_roof = {"algorithmic_tflop": STEP_ALGORITHMIC_TFLOP, "tf_s": STEP_ALGORITHMIC_TFLOP / (ms_step * 1e-3),
+                 "frac_of_833": STEP_ALGORITHMIC_TFLOP / (ms_step * 1e-3) / peak,
+                 "GB": whole_step_gb, "tb_s": None if whole_step_gb is None else whole_step_gb / ms_step,
+                 "frac_of_8": None if whole_step_gb is None else whole_step_gb / ms_step / (HBM_PEAK_GBS * 1e-3),
+                 "note": "algorithmic FLOPs of one step (BASELINE.md section 4: forward 762 G x 3) and the whole step's counter traffic, both over ms_per_step"}
+    return {
+        "roofline": {**roof, "traffic": traffic,
+                     "traffic_unit": "bytes/launch (2*FETCH_SIZE + WRITE_SIZE)", "traffic_source": traffic_src,
+                     "kernel": dom["kernel"] + " = the kernel family with the largest total time per step in the three eager timing iterations "
+                                               "(every launch of every family timed; per launch: the median of the three)",
+                     "top3": top3, "step": step_roof,
+                     "peak_note": ("HBM3E ~8 TB/s; achieved = algorithmic bytes (inputs, saved activations and outputs once each) / launch time; "
+                                   "the kernel's byte floor exceeds its flop floor at 833.3 TFLOP/s") if roof["bound"] == "hbm" else
+                                  "fp16 dense MFMA peak 2500 TFLOP/s / 3 MFMAs per fp32-grade product = 833.3 TFLOP/s of algorithmic FLOPs",
+                     "algorithmic_bytes_per_launch": dom.get("algorithmic_bytes_per_launch"),
+                     "precision_policy": ops._POLICY, "launches_timed": dom["launches"], "avg_launch_ms": dom["avg_launch_ms"],
+                     "algorithmic_flops_per_launch": dom["algorithmic_flops_per_launch"],
+                     "executed_flops_per_launch": dom["executed_flops_per_launch"]},
+        "kernels": kernels[:8]}
+
+
+DUMP_SAMPLE = 1 << 19  # elements per optimizer group: five arrays of at most 2 MB
+
+
+def dump_outputs(out_dir, loss, loss_dict, metrics, opt) -> None:
+    """--dump-outputs: what the last timed step hands its caller (the loss, every loss term, every numeric metric) and the
+    parameters its Adam step left in each optimizer group, as float32 DIR/<name>.npy.  Groups larger than DUMP_SAMPLE are sampled
+    at indices drawn from a fixed seed, the same in every run."""
+    import re
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss}
+    arrays.update({f"loss_{k}": v for k, v in loss_dict.items()})
+    arrays.update({f"metric_{k}": v for k, v in metrics.items() if torch.is_tensor(v) or isinstance(v, (int, float))})
+    g = torch.Generator().manual_seed(0)
+    for grp in opt.groups:
+        n = grp.flat_p.numel()
+        idx = torch.arange(n) if n <= DUMP_SAMPLE else torch.randperm(n, generator=g)[:DUMP_SAMPLE].sort().values
+        idx = idx.to(grp.flat_p.device)
+        arrays[f"param_{grp.name}"] = grp.flat_p[idx]
+    for name, v in arrays.items():
+        a = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float32)
+        np.save(os.path.join(out_dir, re.sub(r"[^\w.-]", "_", name) + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline step time: the RCCL self-check, per-kernel roofline timings (plus HBM counters), "
+                         "device power, the exact-fp32 step, the extra configurations and the CPU baseline (each --no-* flag below then "
+                         "drops its part); without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32): the loss, every loss "
+                         "term and metric, and a fixed, seeded sample of each optimizer group's parameters")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from the host instead of replaying the captured HIP graph")
     ap.add_argument("--no-exact-f32", action="store_true", help="skip the three extra eager steps under the exact-fp32 policy")
@@ -1053,7 +1160,7 @@ def main():
         pipe.grad_sync.broadcast_parameters()
     opt = Optimizers(neusky_optimizers(), pipe.get_param_groups(), world_size=world)
     selfcheck = None
-    if launched and dist.is_initialized():
+    if args.full and launched and dist.is_initialized():
         from neusky_amd.distributed import broadcast_module_state
         selfcheck = rccl_selfcheck(opt, pipe, world, rank, device, backend)
         if world == 1:  # (the pipeline only broadcasts at N > 1: here the one-rank broadcast is part of the check)
@@ -1083,46 +1190,48 @@ def main():
         except Exception as exc:  # noqa: BLE001
             use_graph, graph_note = False, f" (HIP graph capture failed: {type(exc).__name__}: {str(exc)[:120]})"
             torch.cuda.synchronize()
-    if use_graph:
-        for i in range(args.warmup):
-            stepper.step(1000 + i, batches[i][0], batches[i][1], skies[i])
+
+    def run_step(i, step):
+        rb, b = batches[i]
+        if use_graph:
+            return stepper.step(step, rb, b, skies[i])
+        return train_iteration(pipe, opt, step, ray_bundle=rb, batch=b)
+
+    # The kernels sum gradients with float atomics, so each step's result varies in its last bits from run to run, and Adam
+    # amplifies that over the steps (where |g| is small its update is about lr * sign(g)).  The last timed step therefore starts
+    # again from the model state before the warm-up: its inputs, that state included, are the same in every run, and what it
+    # computes (final_loss, --dump-outputs) differs between runs by rounding alone.  Cost: one copy of the parameter and moment
+    # slabs inside the timed region.
+    start_state = [(g, g.flat_p.clone(), g.m.clone(), g.v.clone(), g.steps) for g in opt.groups]
+
+    def restore_start_state():
+        for g, p, m, v, steps in start_state:
+            g.flat_p.copy_(p)
+            g.m.copy_(m)
+            g.v.copy_(v)
+            g.steps = steps
+
+    for i in range(args.warmup):
+        run_step(i, 1000 + i)
+    barrier()
+    power = PowerSampler(dev_index) if args.full else None  # (a sampling thread: only where its figures are asked for)
+    with power if power is not None else contextlib.nullcontext():
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            if i == args.steps - 1:
+                restore_start_state()
+            loss, loss_dict, metrics = run_step(args.warmup + i, 2000 + i)
         barrier()
-        power = PowerSampler(dev_index)
-        with power:
-            t0 = time.perf_counter()
-            for i in range(args.steps):
-                j = args.warmup + i
-                loss, _, _ = stepper.step(2000 + i, batches[j][0], batches[j][1], skies[j])
-            barrier()
-            dt = time.perf_counter() - t0
+        dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:  # before anything below steps the optimizer again
+        dump_outputs(args.dump_outputs, loss, loss_dict, metrics, opt)
+    if args.full:
         # HIP events cannot be read back from inside a replayed graph: the heavy kernels' launches are timed with events on
         # one extra EAGER iteration of the same step (same kernels, shapes and stream) right after the timed region
         timer.install()
         pipe.model.second_stream = False  # one stream: every timed kernel has the chip to itself
         ops.ASYNC_WGRAD = False           # (the weight-gradient launches too: in line, not beside the next nodes' kernels)
         for it in range(3):  # (three launches per kernel: a single launch's event time varies by 10 % from run to run)
-            train_iteration(pipe, opt, 3000 + it, ray_bundle=batches[-1][0], batch=batches[-1][1])
-        torch.cuda.synchronize()
-        pipe.model.second_stream = True
-        ops.ASYNC_WGRAD = _async_wgrad
-        timer.uninstall()
-    else:
-        for i in range(args.warmup):
-            rb, b = batches[i]
-            train_iteration(pipe, opt, 1000 + i, ray_bundle=rb, batch=b)
-        barrier()
-        power = PowerSampler(dev_index)
-        with power:
-            t0 = time.perf_counter()
-            for i in range(args.steps):
-                rb, b = batches[args.warmup + i]
-                loss, _, _ = train_iteration(pipe, opt, 2000 + i, ray_bundle=rb, batch=b)
-            barrier()
-            dt = time.perf_counter() - t0
-        timer.install()
-        pipe.model.second_stream = False
-        ops.ASYNC_WGRAD = False
-        for it in range(3):
             train_iteration(pipe, opt, 3000 + it, ray_bundle=batches[-1][0], batch=batches[-1][1])
         torch.cuda.synchronize()
         pipe.model.second_stream = True
@@ -1136,7 +1245,7 @@ def main():
 
     # the same step with EXACT fp32 products everywhere (v_mfma_f32_32x32x2_f32, per-layer kernels): a few eager steps, rank 0
     exact = None
-    if rank == 0 and world == 1 and not args.no_exact_f32 and ops._POLICY != "f32":  # (N = 1 only: a train iteration all-reduces, and the other ranks are done)
+    if args.full and rank == 0 and world == 1 and not args.no_exact_f32 and ops._POLICY != "f32":  # (N = 1 only: a train iteration all-reduces, and the other ranks are done)
         policy = ops._POLICY
         ops.set_precision_policy("f32")
         try:
@@ -1155,57 +1264,6 @@ def main():
 
     if rank == 0:
         rays_total = RAYS * world * args.steps
-        kernels = timer.summary()
-        peak = PEAK_BF16_MFMA_TFLOPS / 3.0
-        for k in kernels:
-            k["frac_of_833_tflops"] = k["achieved_tflops"] / peak
-        # a family's share of the step = its launches of ONE iteration (the timing iterations are three repeats of the same step)
-        iters = 3
-        for k in kernels:
-            k["ms_per_step"] = k["total_ms"] / iters
-            k["frac_of_8000_GBs"] = k["achieved_GBs"] / HBM_PEAK_GBS if "achieved_GBs" in k else None
-        traffic, whole_step_gb, tsrc = None, None, os.path.join(ROOT, "profiles", PMC_TRAFFIC_FILE)
-        traffic_src = {"file": "profiles/" + PMC_TRAFFIC_FILE, "collected": "committed rocprofv3 --pmc passes (tools/pmc_bench.sh), not this run"}
-        dom = kernels[0]
-        tj = json.load(open(tsrc)) if os.path.exists(tsrc) else None
-        live_note = "not attempted (--no-live-pmc / --no-extra-configs / N > 1)"
-        if world == 1 and not args.no_live_pmc and not args.no_extra_configs:
-            live, live_note = live_pmc_traffic()
-            if live is not None:
-                committed_gb = tj.get("whole_step_GB") if tj is not None else None
-                tj = dict(live, kernel_sources_sha=_sources_sha(step_kernel_sources()))
-                traffic_src = {"collected": live_note, "committed_file_whole_step_GB": committed_gb, "file": "profiles/" + PMC_TRAFFIC_FILE + " (for comparison)"}
-        traffic_src["live_collection"] = live_note
-        if tj is not None:  # HBM bytes per launch from the rocprofv3 --pmc passes; the check that they describe THESE kernels is a field
-            traffic = tj.get("bytes_per_launch", {}).get(dom["kernel"].split(" ")[0])
-            whole_step_gb = tj.get("whole_step_GB")
-            sha = _sources_sha(step_kernel_sources())
-            traffic_src.update({"kernel_sources_sha": sha, "counters_kernel_sources_sha": tj.get("kernel_sources_sha"),
-                                "describes_these_kernels": tj.get("kernel_sources_sha") == sha})
-            for k in kernels:
-                k["pmc_bytes_per_launch"] = tj.get("bytes_per_launch", {}).get(k["kernel"].split(" ")[0])
-                m = (tj.get("mfma") or {}).get(k["kernel"].split(" ")[0]) or {}
-                k["mfma_busy"], k["clock_mhz_under_counters"] = m.get("mfma_busy"), m.get("clock_mhz")
-
-        def bound_of(k):
-            hb = k.get("algorithmic_bytes_per_launch")
-            if hb is not None and hb / (HBM_PEAK_GBS * 1e9) > k["algorithmic_flops_per_launch"] / (peak * 1e12):
-                return "hbm"
-            return "mfma"
-
-        roof = {"bound": "mfma", "achieved": dom["achieved_tflops"], "peak": peak, "unit": "TFLOP/s", "frac": dom["achieved_tflops"] / peak}
-        if bound_of(dom) == "hbm":
-            roof = {"bound": "hbm", "achieved": dom["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": dom["achieved_GBs"] / HBM_PEAK_GBS}
-        top3 = [{"kernel": k["kernel"], "ms_per_step": k["ms_per_step"], "launches_per_step": k["launches"] / iters, "bound": bound_of(k),
-                 "mfma_frac_of_833_tflops": k["frac_of_833_tflops"], "hbm_frac_of_8000_GBs": k["frac_of_8000_GBs"],
-                 "pmc_bytes_per_launch": k.get("pmc_bytes_per_launch"),
-                 "mfma_busy": k.get("mfma_busy"), "clock_mhz": k.get("clock_mhz_under_counters")} for k in kernels[:3]]
-        ms_step = 1e3 * dt / args.steps
-        step_roof = {"algorithmic_tflop": STEP_ALGORITHMIC_TFLOP, "tf_s": STEP_ALGORITHMIC_TFLOP / (ms_step * 1e-3),
-                     "frac_of_833": STEP_ALGORITHMIC_TFLOP / (ms_step * 1e-3) / peak,
-                     "GB": whole_step_gb, "tb_s": None if whole_step_gb is None else whole_step_gb / ms_step,
-                     "frac_of_8": None if whole_step_gb is None else whole_step_gb / ms_step / (HBM_PEAK_GBS * 1e-3),
-                     "note": "algorithmic FLOPs of one step (BASELINE.md section 4: forward 762 G x 3) and the whole step's counter traffic, both over ms_per_step"}
         fwd = "fp16 hi + residual split, 3 x v_mfma_f32_32x32x16_f16 per product on power-of-two pre-scaled operands, one fp32 accumulator (~2^-22): FiLM-SIREN chains and the SDF / albedo field alike"
         bwd = ("the same fp16 split on per-row / per-matrix pre-scaled gradients (fp32-grade) for the FiLM-SIREN chains, the SDF / albedo field and all their weight gradients; "
                "proposal layers and all N <= 64 heads: exact fp32 MFMA")
@@ -1221,43 +1279,32 @@ def main():
                        "rays_per_gpu": RAYS, "samples_per_ray": SAMPLES, "illumination_directions": DIRECTIONS,
                        "parallelism": f"ray-sharded dp{world}", "final_loss": final_loss, "launcher": launcher,
                        "launch": "HIP graph replay (1 graph/step + all-reduce + 5 Adam launches)" if use_graph else "eager (host launches every kernel)" + graph_note},
-            "roofline": {**roof, "traffic": traffic,
-                         "traffic_unit": "bytes/launch (2*FETCH_SIZE + WRITE_SIZE)", "traffic_source": traffic_src,
-                         "kernel": dom["kernel"] + " = the kernel family with the largest total time per step in the three eager timing iterations "
-                                                   "(every launch of every family timed; per launch: the median of the three)",
-                         "top3": top3, "step": step_roof,
-                         "peak_note": ("HBM3E ~8 TB/s; achieved = algorithmic bytes (inputs, saved activations and outputs once each) / launch time; "
-                                       "the kernel's byte floor exceeds its flop floor at 833.3 TFLOP/s") if roof["bound"] == "hbm" else
-                                      "fp16 dense MFMA peak 2500 TFLOP/s / 3 MFMAs per fp32-grade product = 833.3 TFLOP/s of algorithmic FLOPs",
-                         "algorithmic_bytes_per_launch": dom.get("algorithmic_bytes_per_launch"),
-                         "precision_policy": ops._POLICY, "launches_timed": dom["launches"], "avg_launch_ms": dom["avg_launch_ms"],
-                         "algorithmic_flops_per_launch": dom["algorithmic_flops_per_launch"],
-                         "executed_flops_per_launch": dom["executed_flops_per_launch"]},
-            "kernels": kernels[:8],
-            "device_state": power.summary(),  # package power / shader clock level sampled during the timed region
-            "fp32_exact": exact,
-            # the process group the step's gradient exchange runs on (0 ranks: --no-spawn, no group) and its collectives exercised
-            # before the timed region (rccl_selfcheck)
+            # the process group the step's gradient exchange runs on (0 ranks: --no-spawn, no group); --full adds its collectives,
+            # exercised before the timed region (rccl_selfcheck)
             "rccl_ranks": dist.get_world_size() if dist.is_initialized() else 0,
             "dist_backend": (backend + (" (RCCL)" if backend == "nccl" else "")) if dist.is_initialized() else None,
-            "rccl_selfcheck": selfcheck if selfcheck is not None else pg_note,
         }
-        if world == 1 and not args.no_extra_configs:
-            line["envmap_decode"] = envmap_decode_line(device)
-            line["attention_decoder"] = attention_decoder_line(device)
-            line["global_batch_8192_one_gpu"] = global_batch_line(device)
-            line["trainer_surface"] = trainer_surface_line(device)
-            line["forward_only"] = forward_only_line(pipe, device)
-            line["render_1080p"] = render_1080p_line(pipe, device)
-            if not args.no_live_pmc:  # the saves-free forward's HBM traffic, from counters
-                rp, note = render_pmc_traffic()
-                line["render_1080p"]["pmc_traffic"] = rp if rp is not None else {"error": note}
-                if rp is not None:
-                    gb = rp["GB_per_1080p_frame_scaled_x16"]
-                    line["render_1080p"]["hbm"] = {"GB_per_frame": gb, "tb_s": gb / line["render_1080p"]["ms_per_frame"],
-                                                   "frac_of_8": gb / line["render_1080p"]["ms_per_frame"] / (HBM_PEAK_GBS * 1e-3)}
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            line.update(roofline_fields(args, timer, world, line["ms_per_step"]))
+            line["device_state"] = power.summary()  # package power / shader clock level sampled during the timed region
+            line["fp32_exact"] = exact
+            line["rccl_selfcheck"] = selfcheck if selfcheck is not None else pg_note
+            if world == 1 and not args.no_extra_configs:
+                line["envmap_decode"] = envmap_decode_line(device)
+                line["attention_decoder"] = attention_decoder_line(device)
+                line["global_batch_8192_one_gpu"] = global_batch_line(device)
+                line["trainer_surface"] = trainer_surface_line(device)
+                line["forward_only"] = forward_only_line(pipe, device)
+                line["render_1080p"] = render_1080p_line(pipe, device)
+                if not args.no_live_pmc:  # the saves-free forward's HBM traffic, from counters
+                    rp, note = render_pmc_traffic()
+                    line["render_1080p"]["pmc_traffic"] = rp if rp is not None else {"error": note}
+                    if rp is not None:
+                        gb = rp["GB_per_1080p_frame_scaled_x16"]
+                        line["render_1080p"]["hbm"] = {"GB_per_frame": gb, "tb_s": gb / line["render_1080p"]["ms_per_frame"],
+                                                       "frac_of_8": gb / line["render_1080p"]["ms_per_frame"] / (HBM_PEAK_GBS * 1e-3)}
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline()
         line_out.write(json.dumps(line) + "\n")
         line_out.flush()
     if dist.is_initialized():

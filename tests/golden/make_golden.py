@@ -81,12 +81,26 @@ def g2_sphere():
     # grazing / outside cases for the clamped variant
     p2 = p.copy()
     p2[:4] = np.array([[1.2, 0, 0], [0, 1.0, 0], [0.999, 0, 0.04], [0, 0, -1.5]], np.float32)
-    # free function neusky/utils/utils.py:68-93 (no normalisation, no clamp) -> inside-sphere unit dirs only
-    y_free = ru.ray_sphere_intersection(T(p), T(d_unit), 1.0)
-    # method neusky/models/neusky_model.py:1590-1622 (normalises, clamps discriminant)
-    y_meth = rnm.NeuSkyFactoModel.ray_sphere_intersection(None, T(p2), T(d_raw), 1.0)
-    y_meth_r2 = rnm.NeuSkyFactoModel.ray_sphere_intersection(None, T(p2), T(d_raw), 2.0)
+    # torch's float32 sqrt on the CPU is not correctly rounded and its last bit depends on the CPU model: every (argument, result)
+    # of the reference's torch.sqrt calls is kept in g2_sqrt, so a test on another CPU can replay the generating CPU's roundings
+    calls, sqrt = [], torch.sqrt
+
+    def recording_sqrt(x):
+        y = sqrt(x)
+        calls.append((x.numpy().ravel().copy(), y.numpy().ravel().copy()))
+        return y
+
+    torch.sqrt = recording_sqrt
+    try:
+        # free function neusky/utils/utils.py:68-93 (no normalisation, no clamp) -> inside-sphere unit dirs only
+        y_free = ru.ray_sphere_intersection(T(p), T(d_unit), 1.0)
+        # method neusky/models/neusky_model.py:1590-1622 (normalises, clamps discriminant)
+        y_meth = rnm.NeuSkyFactoModel.ray_sphere_intersection(None, T(p2), T(d_raw), 1.0)
+        y_meth_r2 = rnm.NeuSkyFactoModel.ray_sphere_intersection(None, T(p2), T(d_raw), 2.0)
+    finally:
+        torch.sqrt = sqrt
     save("g2_sphere", p=p, d_unit=d_unit, d_raw=d_raw, p2=p2, y_free=y_free, y_meth=y_meth, y_meth_r2=y_meth_r2)
+    save("g2_sqrt", x=np.concatenate([c[0] for c in calls]), y=np.concatenate([c[1] for c in calls]))
 
 
 # ----------------------------------------------------------------------------- G3

@@ -39,7 +39,7 @@ def test_bench_spawns_its_own_two_ranks_on_one_gpu():
     env = dict(os.environ, NSKY_BENCH_DEVICE="0", NSKY_DIST_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     d = _line(out)
     _check_two_ranks(d)
@@ -50,7 +50,7 @@ def test_bench_one_rank_through_the_spawn_path_over_rccl():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "NSKY_BENCH_DEVICE", "NSKY_DIST_BACKEND"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"] + FAST,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"] + FAST,
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     d = _line(out)
     assert d["n_gpus"] == 1 and d["config"]["launcher"] == "self-spawned" and d["config"]["parallelism"] == "ray-sharded dp1"
@@ -68,8 +68,36 @@ def test_bench_one_rank_through_the_spawn_path_over_rccl():
 def test_bench_two_ranks_under_torchrun_one_gpu():
     env = dict(os.environ, NSKY_BENCH_DEVICE="0", NSKY_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29653", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           "--master-port", "29653", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     d = _line(out)
     _check_two_ranks(d)
     assert d["config"]["launcher"] == "external (torch.distributed.run)"
+
+
+def test_plain_bench_times_the_steps_alone_and_dumps_the_last_one(tmp_path):
+    """without --full the line carries the headline and nothing that needs runs of its own; --dump-outputs writes the last timed
+    step's loss, loss terms, metrics and parameter samples as float32 .npy files, 64 MB at most, and two runs with the same
+    arguments write the same arrays up to rounding"""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "NSKY_BENCH_DEVICE", "NSKY_DIST_BACKEND"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                              "--dump-outputs", str(tmp_path / f"dump{run}")], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+        d = _line(out)
+        assert d["steps"] == 3 and d["warmup"] == 2 and d["unit"] == "rays/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - 1024 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert not {"roofline", "kernels", "device_state", "fp32_exact", "rccl_selfcheck", "forward_only", "cpu_baseline"} & set(d), sorted(d)
+        files = {f: np.load(tmp_path / f"dump{run}" / f) for f in os.listdir(tmp_path / f"dump{run}")}
+        assert {"loss.npy", "param_fields.npy", "metric_psnr.npy"} <= set(files), sorted(files)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert float(files["loss.npy"]) == d["config"]["final_loss"]
+        dumps.append(files)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for name, a in dumps[0].items():  # (gradients are summed with float atomics: the last bits may differ)
+        err = float(np.abs(a.astype(np.float64) - dumps[1][name]).max()) / max(float(np.abs(a).max()), 1e-30)
+        assert err <= 1e-5, (name, err)

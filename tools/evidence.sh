@@ -14,7 +14,7 @@ done)
 python3 $R/tools/pmc_step_traffic.py 0 r06_pmc_traffic.json > $O/pmc_traffic.txt 2>&1; cp $R/profiles/r06_pmc_traffic.json $O/ 2>/dev/null
 cd $R
 python -c "import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-python bench.py > $O/bench_line.json 2> $O/bench.err
+python bench.py --full > $O/bench_line.json 2> $O/bench.err
 tail -1 $O/bench_line.json
 python tools/bench_forward_only.py > $O/forward_only.json 2> $O/forward_only.err; tail -1 $O/forward_only.json
 python tools/bench_render.py > $O/bench_render.log 2>&1; tail -2 $O/bench_render.log

@@ -16,7 +16,7 @@ int main(int argc, char** argv) {
   if (mode == 2) { free(p); p[3] = 7; for (int i = 0; i < 40000; ++i) free(malloc(32)); puts("evicted"); return 0; } /* stale write */
   if (mode == 3) { free(p); free(p); }          /* double free */
   if (mode == 4) { memset(p, 0x41, 26); printf("sweep -> %ld\n", ((sweep_t)dlsym(RTLD_DEFAULT, "heap_guard_sweep"))("selftest")); return 0; }
-  if (mode == 5) { p[-30] = 9; }                 /* underrun */
+  if (mode == 5) { p[-30] ^= 0x5a; }             /* underrun (flips bits: a constant could equal the byte already there) */
   free(p);
   puts("clean exit");
   return 0;
