@@ -702,6 +702,28 @@ int nsky_ddf_losses_fwd(const nsky_ddf_losses_desc* d, float* terms, nsky_stream
 int nsky_ddf_losses_bwd(const nsky_ddf_losses_desc* d, const float* d_terms, float* d_expected, float* d_sdf, float* d_mv_expected,
                         float* d_sky_expected, float* d_term, float* d_mv_term, nsky_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Marching cubes over a dense fp32 volume [nx, ny, nz] (C-contiguous, z fastest; every dimension >= 2).  No counterpart in the
+ * reference (it has no mesh export); the package's exporter (neusky_amd/exporter) drives these three passes.
+ *   inside: value < level.  Point (i, j, k) owns its +x, +y, +z edges; one vertex per owned edge whose ends differ, at
+ *   t = (level - v_a) / (v_b - v_a).  Vertices ordered by owner flat index, then axis; faces by cell (= its minimum point's) flat
+ *   index, then case-table order; faces wind counter-clockwise seen from the outside (increasing value) side.
+ *   Points are processed in tiles of NSKY_MC_TILE consecutive flat indices; n_tiles = ceil(nx ny nz / NSKY_MC_TILE).
+ * nsky_mc_count:    tile_counts[4][n_tiles] = { vertices, faces, non-finite values, 0 } of each tile (rows: scanned in place by the
+ *                   caller, an inner-dimension scan).
+ * nsky_mc_vertices: tile_vertex_offsets[n_tiles] = exclusive scan of the tile vertex counts; writes vertices[V][3] (point
+ *                   (i, j, k) at box_min + (i, j, k) / (n - 1) * (box_max - box_min)), base[nx ny nz] (first vertex id of each
+ *                   point) and edge_mask[nx ny nz] (bit a: the point's +a edge crosses).
+ * nsky_mc_faces:    tile_face_offsets[n_tiles] = exclusive scan of the tile face counts; writes faces[F][3] (vertex ids).
+ * V and F must fit int32 (the caller checks the totals before the second pass). */
+#define NSKY_MC_TILE 256
+int nsky_mc_count(const float* volume, int64_t nx, int64_t ny, int64_t nz, float level, int32_t* tile_counts, nsky_stream_t stream);
+int nsky_mc_vertices(const float* volume, int64_t nx, int64_t ny, int64_t nz, float level, float min_x, float min_y, float min_z,
+                     float max_x, float max_y, float max_z, const int64_t* tile_vertex_offsets, int32_t* base, uint8_t* edge_mask,
+                     float* vertices, nsky_stream_t stream);
+int nsky_mc_faces(const float* volume, int64_t nx, int64_t ny, int64_t nz, float level, const int64_t* tile_face_offsets,
+                  const int32_t* base, const uint8_t* edge_mask, int32_t* faces, nsky_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,10 @@
+"""Mesh export of the learned surface: a dense SDF grid from the field's fused value chain, marching cubes on the GPU
+(csrc/mesh.hip), per-vertex normals and albedo from the field, and a binary PLY writer.
+
+  python -m neusky_amd.exporter --checkpoint CKPT --output mesh.ply   (flags named as nerfstudio's `ns-export marching-cubes`)
+"""
+from .marching_cubes import marching_cubes
+from .mesh import Mesh, extract_mesh, load_field_state, sdf_grid
+from .ply import write_ply
+
+__all__ = ["Mesh", "extract_mesh", "load_field_state", "marching_cubes", "sdf_grid", "write_ply"]

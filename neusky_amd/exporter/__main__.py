@@ -1,0 +1,58 @@
+"""python -m neusky_amd.exporter --checkpoint CKPT --output mesh.ply: the SDF field of a checkpoint as a PLY mesh.
+
+The flags carry the names of nerfstudio's `ns-export marching-cubes`.  The field is built from the `neusky` method's config; no
+dataset is needed (the scene box and the number of training images come from the checkpoint)."""
+from __future__ import annotations
+
+import argparse
+import sys
+import time
+
+
+def build_field(state, device):
+    from ..configs.neusky_config import NeuSky
+    cfg = NeuSky.config.pipeline.model.sdf_field
+    aabb = state["_model.field.aabb"].float()
+    emb = state.get("_model.field.embedding_appearance.weight", state.get("_model.field.embedding_appearance.embedding.weight"))
+    num_images = int(emb.shape[0]) if emb is not None else 1
+    return cfg.setup(aabb=aabb, num_images=num_images, spatial_distortion=None).to(device)
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m neusky_amd.exporter", description=__doc__.splitlines()[0])
+    ap.add_argument("--checkpoint", required=True, help="a nerfstudio-layout checkpoint (step-*.ckpt) of the neusky method")
+    ap.add_argument("--output", required=True, help="the .ply file to write")
+    ap.add_argument("--resolution", type=int, default=512)
+    ap.add_argument("--bounding-box-min", type=float, nargs=3, default=(-1.0, -1.0, -1.0))
+    ap.add_argument("--bounding-box-max", type=float, nargs=3, default=(1.0, 1.0, 1.0))
+    ap.add_argument("--isosurface-threshold", type=float, default=0.0)
+    ap.add_argument("--no-attributes", action="store_true", help="write positions and faces only (no normals, no colours)")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+
+    import torch
+    from . import extract_mesh, load_field_state, write_ply
+
+    t0 = time.perf_counter()
+    ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
+    state = ckpt["pipeline"] if "pipeline" in ckpt else ckpt
+    field = build_field(state, args.device)
+    loaded, unmapped = load_field_state(field, state)
+    if not loaded:
+        raise SystemExit(f"{args.checkpoint}: no _model.field.* entries")
+    if unmapped:
+        print(f"warning: {len(unmapped)} field entries not mapped: {unmapped[:4]}", file=sys.stderr)
+    t_load = time.perf_counter() - t0
+    timings = {}
+    mesh = extract_mesh(field, args.resolution, args.bounding_box_min, args.bounding_box_max, args.isosurface_threshold,
+                        attributes=not args.no_attributes, timings=timings)
+    t1 = time.perf_counter()
+    write_ply(args.output, mesh)
+    t_write = time.perf_counter() - t1
+    parts = " ".join(f"{k} {v:.3f}s" for k, v in timings.items())
+    print(f"{args.output}: V {mesh.vertices.shape[0]} F {mesh.faces.shape[0]} | load {t_load:.3f}s {parts} write {t_write:.3f}s")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

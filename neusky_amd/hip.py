@@ -1094,3 +1094,32 @@ def film_chain_bwd_map(net: FilmNet, stream_buf, table, M, dfp, dfp_rowmax, h_sa
     check(_film_bwd_map(C.byref(net), ptr(stream_buf), ptr(table), M, ptr(dfp), ptr(dfp_rowmax), _ptr_array(h_save, net.n_map),
                         _ptr_array(dpre_save, net.n_map), ptr(d_cond), ld(d_cond) if d_cond is not None else 0, ptr(gmax), stream_ptr()),
           "nsky_film_chain_bwd_map")
+
+
+# ---- marching cubes (exporter/marching_cubes.py drives the three passes)
+MC_TILE = 256  # NSKY_MC_TILE
+_mc_count = _sig("nsky_mc_count", C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p)
+_mc_vertices = _sig("nsky_mc_vertices", C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
+                    C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_mc_faces = _sig("nsky_mc_faces", C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                 C.c_void_p, C.c_void_p)
+
+
+def mc_count(volume, level: float, tile_counts):
+    """volume: contiguous fp32 [nx, ny, nz]; tile_counts: int32 [4, ceil(nx ny nz / MC_TILE)] <- rows (vertices, faces, non-finite, 0)"""
+    nx, ny, nz = volume.shape
+    check(_mc_count(ptr(volume), nx, ny, nz, level, ptr(tile_counts), stream_ptr()), "nsky_mc_count")
+
+
+def mc_vertices(volume, level: float, box_min, box_max, tile_vertex_offsets, base, edge_mask, vertices):
+    """tile_vertex_offsets: int64 [n_tiles] exclusive scan; base: int32 [nx ny nz]; edge_mask: uint8 [nx ny nz]; vertices: fp32 [V, 3]"""
+    nx, ny, nz = volume.shape
+    check(_mc_vertices(ptr(volume), nx, ny, nz, level, *[float(v) for v in box_min], *[float(v) for v in box_max], ptr(tile_vertex_offsets),
+                       ptr(base), ptr(edge_mask), ptr(vertices), stream_ptr()), "nsky_mc_vertices")
+
+
+def mc_faces(volume, level: float, tile_face_offsets, base, edge_mask, faces):
+    """tile_face_offsets: int64 [n_tiles] exclusive scan; faces: int32 [F, 3]"""
+    nx, ny, nz = volume.shape
+    check(_mc_faces(ptr(volume), nx, ny, nz, level, ptr(tile_face_offsets), ptr(base), ptr(edge_mask), ptr(faces), stream_ptr()),
+          "nsky_mc_faces")
