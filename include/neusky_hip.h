@@ -724,6 +724,42 @@ int nsky_mc_vertices(const float* volume, int64_t nx, int64_t ny, int64_t nz, fl
 int nsky_mc_faces(const float* volume, int64_t nx, int64_t ny, int64_t nz, float level, const int64_t* tile_face_offsets,
                   const int32_t* base, const uint8_t* edge_mask, int32_t* faces, nsky_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Relighting under an equirectangular HDR environment map.  No counterpart in the reference (it lights frames with RENI++ latents
+ * only); the package's relight module (neusky_amd/relight) drives these kernels.
+ *   map:         fp32 [H, W, 3] linear radiance, C-contiguous, row 0 at the top.
+ *   texel (i,j): theta_i = pi (i + 0.5) / H from +z (the scene's up axis); u_j = (j + 0.5) / W; the azimuth phi from +x toward +y is
+ *                NSKY_ENVMAP_NEUSKY: phi = 2 pi u,   NSKY_ENVMAP_BLENDER: phi = pi - 2 pi u   (Blender's world-texture mapping);
+ *                direction (sin theta cos phi, sin theta sin phi, cos theta).
+ *   solid angle: omega_i = (2 pi / W) (cos(pi i / H) - cos(pi (i + 1) / H)) = (2 pi / W) 2 sin(theta_i) sin(pi / (2 H)); sums to 4 pi.
+ *   rotation:    R (fp32 [3][3] row-major, device memory; NULL = identity): direction d is lit by the map at R d, as the `rotation=`
+ *                of the RENI path.  exposure: fp32 scalar in device memory (NULL = 1), multiplies every output.  Both are read by
+ *                the kernels, so a captured graph replays with new values.
+ *   label(t):    argmax_k <t, R d_k> over the D directions, ties to the lower k; fp32 with one fixed expression order:
+ *                R d = (fma(R02, dz, fma(R01, dy, R00 dx)), ...), <t, e> = fma(tz, ez, fma(ty, ey, tx ex)).
+ *   c_k:         exposure * sum_{label(t)=k} omega_t L_t / sum_{label(t)=k} omega_t (fp64 sums); a cell without a texel centre takes
+ *                the bilinear lookup at R d_k.  cell_weight_k = sum_{label(t)=k} omega_t (0 for an empty cell).
+ *   lookup(v):   v = R ray_dir (any length); x = u(phi(v)) W - 0.5, y = theta(v) / pi H - 0.5 (u inverted per convention);
+ *                bilinear, columns wrap modulo W, rows clamp to [0, H-1]; times exposure.  Coordinates in fp64; a non-finite v
+ *                gives NaN and reads nothing.
+ * Flat texel indices are int64 (maps up to 2^31 texels).  No atomics: every output is bitwise repeatable.
+ * nsky_envmap_label:  labels[H W] (int16) of every texel, D <= NSKY_ENVMAP_MAX_DIRECTIONS.
+ * nsky_envmap_reduce: sorted_labels[H W] = the labels sorted ascending, order[H W] = the texel index of each sorted entry (a stable
+ *                     sort: ascending texel index within a cell); one workgroup per direction finds its segment and writes
+ *                     colours[D][3] and cell_weight[D].  The per-cell sum runs in a fixed order: strided per-thread partials, then
+ *                     a fixed tree.
+ * nsky_envmap_lookup: out[N][3] = lookup(R directions[n]). */
+#define NSKY_ENVMAP_NEUSKY 0
+#define NSKY_ENVMAP_BLENDER 1
+#define NSKY_ENVMAP_MAX_DIRECTIONS 1024
+int nsky_envmap_label(const float* directions, int32_t D, const float* rotation, int64_t H, int64_t W, int32_t convention, int16_t* labels,
+                      nsky_stream_t stream);
+int nsky_envmap_reduce(const float* map, int64_t H, int64_t W, int32_t convention, const float* directions, int32_t D, const float* rotation,
+                       const float* exposure, const int16_t* sorted_labels, const int64_t* order, float* colours, float* cell_weight,
+                       nsky_stream_t stream);
+int nsky_envmap_lookup(const float* map, int64_t H, int64_t W, int32_t convention, const float* directions, int64_t N, const float* rotation,
+                       const float* exposure, float* out, nsky_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

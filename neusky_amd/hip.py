@@ -1123,3 +1123,33 @@ def mc_faces(volume, level: float, tile_face_offsets, base, edge_mask, faces):
     nx, ny, nz = volume.shape
     check(_mc_faces(ptr(volume), nx, ny, nz, level, ptr(tile_face_offsets), ptr(base), ptr(edge_mask), ptr(faces), stream_ptr()),
           "nsky_mc_faces")
+
+
+# ---- environment-map relighting (relight/envmap.py drives label -> stable sort -> reduce, and the lookup)
+ENVMAP_NEUSKY, ENVMAP_BLENDER = 0, 1  # NSKY_ENVMAP_NEUSKY / _BLENDER
+ENVMAP_MAX_DIRECTIONS = 1024  # NSKY_ENVMAP_MAX_DIRECTIONS
+_envmap_label = _sig("nsky_envmap_label", C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
+_envmap_reduce = _sig("nsky_envmap_reduce", C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_envmap_lookup = _sig("nsky_envmap_lookup", C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                      C.c_void_p, C.c_void_p)
+
+
+def envmap_label(directions, rotation, H: int, W: int, convention: int, labels):
+    """directions: fp32 [D, 3]; rotation: fp32 [3, 3] or None; labels: int16 [H W] <- the cell of every texel"""
+    check(_envmap_label(ptr(directions), directions.shape[0], ptr(rotation), H, W, convention, ptr(labels), stream_ptr()), "nsky_envmap_label")
+
+
+def envmap_reduce(data, convention: int, directions, rotation, exposure, sorted_labels, order, colours, cell_weight):
+    """data: fp32 [H, W, 3]; exposure: fp32 [1] or None; sorted_labels int16 / order int64 [H W] (stable sort of the labels);
+    colours: fp32 [D, 3], cell_weight: fp32 [D]"""
+    H, W = data.shape[:2]
+    check(_envmap_reduce(ptr(data), H, W, convention, ptr(directions), directions.shape[0], ptr(rotation), ptr(exposure), ptr(sorted_labels),
+                         ptr(order), ptr(colours), ptr(cell_weight), stream_ptr()), "nsky_envmap_reduce")
+
+
+def envmap_lookup(data, convention: int, directions, rotation, exposure, out):
+    """data: fp32 [H, W, 3]; directions: fp32 [N, 3]; out: fp32 [N, 3]"""
+    H, W = data.shape[:2]
+    check(_envmap_lookup(ptr(data), H, W, convention, ptr(directions), directions.shape[0], ptr(rotation), ptr(exposure), ptr(out),
+                         stream_ptr()), "nsky_envmap_lookup")

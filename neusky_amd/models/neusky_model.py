@@ -264,7 +264,13 @@ class NeuSkyFactoModel(ModelBase):
             dirs, cols, sel, cam, rot_f = frame
             self._upper_sel = sel
             R = camera_indices.shape[0]
-            bg = self.illumination_field.forward_camera(ray_directions, latents[cam], scales[cam], rot_f)
+            env = getattr(self, "_frame_envmap", None)
+            if env is not None:  # the sky of the rays is the environment map itself (relight.envmap_lookup), read through static buffers
+                data, conv, rot_s, exposure = env
+                bg = torch.empty(R, 3, dtype=torch.float32, device=dirs.device)
+                hip.envmap_lookup(data, conv, ray_directions.contiguous(), rot_s, exposure, bg)
+            else:
+                bg = self.illumination_field.forward_camera(ray_directions, latents[cam], scales[cam], rot_f)
             return dirs, cols, torch.zeros(R, dtype=torch.int32, device=dirs.device), bg
         if not self.training and self.config.fix_test_illumination_directions:
             dirs, sel = self.illumination_sampler.on_device(self.device, apply_random_rotation=False)  # :451-454
@@ -862,15 +868,20 @@ class NeuSkyFactoModel(ModelBase):
             ops.retire_graph(locals().get("graph"))  # never destroyed next to its last replay (ops.retire_graph: a runtime use-after-free)
         return trace
 
-    def begin_frame(self, camera_index: int, rotation: Optional[torch.Tensor] = None) -> None:
+    def begin_frame(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None) -> None:
         """decode the illumination of ONE camera for a whole frame (the reference re-decodes it in each of the
-        8100 chunks of a 1080p frame, neusky_model.py:1413-1432; the result is the same)"""
+        8100 chunks of a 1080p frame, neusky_model.py:1413-1432; the result is the same).
+        envmap: a relight.EnvironmentMap lighting the frame instead of the camera's latent: the light colours are the map's cell
+        averages at the frame's directions (relight.project_envmap), the rays' background its bilinear lookup."""
         latents, scales = self.get_illumination_field()
         fixed = self.config.fix_test_illumination_directions
         dirs, sel = self.illumination_sampler.on_device(self.device, apply_random_rotation=False if fixed else None)
         cam = int(camera_index)
         D = dirs.shape[0]
-        if rotation is None:
+        if envmap is not None:
+            from ..relight import project_envmap
+            cols = project_envmap(envmap, dirs, rotation)[0][None]
+        elif rotation is None:
             cols = self.illumination_field.forward_grid(dirs, latents[cam][None], scales[cam][None])
         else:
             cols = self.illumination_field.forward_camera(dirs, latents[cam], scales[cam], rotation)[None]
@@ -885,18 +896,37 @@ class NeuSkyFactoModel(ModelBase):
             self._chunk_runners = {}
         st[0].copy_(dirs); st[1].copy_(cols); st[2].copy_(sel)
         self._frame_illumination = (st[0], st[1], st[2], cam, rotation)
-        self._frame_key = (cam, None if rotation is None else tuple(rotation.reshape(-1).tolist()))
+        if envmap is None:
+            self._frame_envmap = None
+            self._frame_key = (cam, None if rotation is None else tuple(rotation.reshape(-1).tolist()))
+            return
+        # a chunk graph reads the map through its pointer and the rotation / exposure through static buffers: it is keyed on the
+        # map's storage, shape and convention only, so a new rotation or exposure replays it without a new capture
+        env_st = getattr(self, "_frame_envmap_static", None)
+        if env_st is None or env_st[0].device != envmap.device:
+            env_st = (torch.empty(3, 3, dtype=torch.float32, device=envmap.device), torch.empty(1, dtype=torch.float32, device=envmap.device))
+            self._frame_envmap_static = env_st
+        if rotation is None:
+            env_st[0].copy_(torch.eye(3, dtype=torch.float32))
+        else:
+            env_st[0].copy_(torch.as_tensor(rotation).reshape(3, 3))
+        env_st[1].copy_(envmap.exposure_tensor)
+        self._frame_envmap = (envmap.data, envmap.convention_id, env_st[0], env_st[1])
+        self._frame_key = ("envmap", envmap.data.data_ptr(), tuple(envmap.data.shape), envmap.convention_id)
 
     def end_frame(self) -> None:
         self._frame_illumination = None
+        self._frame_envmap = None
 
     @torch.no_grad()
     def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle: RayBundle, show_progress=False, rotation=None, to_cpu=False,
                                           step=None, camera_index: Optional[int] = None, chunk: Optional[int] = None,
-                                          use_graph: bool = True) -> Dict[str, torch.Tensor]:
+                                          use_graph: bool = True, envmap=None) -> Dict[str, torch.Tensor]:
         """neusky_model.py:1369-1501: chunked full-frame render.  The reference chunks at eval_num_rays_per_chunk = 256
         (8100 python iterations per 1080p frame); any chunk size gives the same image, so a larger static chunk is used
-        and its forward is captured once in a HIP graph and replayed per chunk (BASELINE config 5)."""
+        and its forward is captured once in a HIP graph and replayed per chunk (BASELINE config 5).
+        envmap: a relight.EnvironmentMap to light the frame with instead of the camera's illumination latent (begin_frame);
+        `rotation` then turns the map (direction d is lit by the map at R d)."""
         assert not self.training, "call model.eval() first"
         chunk = chunk or max(self.config.eval_num_rays_per_chunk, 4096)
         shape = camera_ray_bundle.origins.shape[:-1]
@@ -904,7 +934,7 @@ class NeuSkyFactoModel(ModelBase):
         num_rays = flat.origins.shape[0]
         if camera_index is None:
             camera_index = int(flat.camera_indices.reshape(-1)[0]) if flat.camera_indices is not None else 0
-        self.begin_frame(camera_index, rotation)
+        self.begin_frame(camera_index, rotation, envmap)
         keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"]
         out = {k: [] for k in keys}
         try:

@@ -1,0 +1,118 @@
+"""python -m neusky_amd.relight: render a checkpoint's scene along a nerfstudio camera path, lit by an HDR environment map (or by one of
+its training illumination latents), as 8-bit sRGB PNG frames.
+
+The pipeline is built from the `neusky` method's config with no dataset: the scene box comes from the checkpoint's `_model.field.aabb`,
+the numbers of train / eval latent rows and the latent dimension from its latent tables."""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import sys
+import time
+
+
+def build_pipeline(state, device):
+    """the `neusky` method's pipeline sized from a checkpoint's state dict, on a stand-in datamanager (no dataset)"""
+    import copy
+
+    import torch
+
+    from ..configs.neusky_config import NeuSky
+    from ..data.synthetic_datamanager import SyntheticDataManagerConfig
+
+    train = state.get("_model.train_illumination_latents")
+    if train is None:
+        raise SystemExit("checkpoint has no _model.train_illumination_latents")
+    evals = state.get("_model.eval_illumination_latents", train[:1])
+    aabb = state["_model.field.aabb"].float() if "_model.field.aabb" in state else torch.tensor([[-1.0] * 3, [1.0] * 3])
+
+    class _BoxedConfig(SyntheticDataManagerConfig):
+        def setup(self, **kwargs):
+            dm = super().setup(**kwargs)
+            box = {"aabb": aabb.clone()}
+            dm.train_dataset.scene_box = box
+            dm.eval_dataset.scene_box = box
+            return dm
+
+    cfg = copy.deepcopy(NeuSky.config.pipeline)
+    cfg.datamanager = _BoxedConfig(num_train_images=int(train.shape[0]), num_eval_images=int(evals.shape[0]))
+    cfg.model.illumination_field.latent_dim = int(train.shape[1])
+    return cfg.setup(device=device)
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m neusky_amd.relight", description=__doc__.splitlines()[0])
+    ap.add_argument("--checkpoint", required=True, help="a nerfstudio-layout checkpoint (step-*.ckpt) of the neusky method")
+    ap.add_argument("--camera-path", required=True, help="nerfstudio camera_path.json (perspective cameras)")
+    ap.add_argument("--output-dir", required=True)
+    light = ap.add_mutually_exclusive_group(required=True)
+    light.add_argument("--envmap", help="equirectangular map: .hdr/.pic, .pfm, .npy, .png/.jpg (sRGB), .exr (with pyexr)")
+    light.add_argument("--latent-index", type=int, help="light with this training illumination latent instead")
+    ap.add_argument("--convention", default="blender", choices=("blender", "neusky"), help="the map's azimuth convention")
+    ap.add_argument("--exposure", type=float, default=1.0)
+    ap.add_argument("--rotation-deg", type=float, default=0.0, help="turn the illumination about +z")
+    ap.add_argument("--turntable", type=int, default=1, help="frames per camera, the illumination turned through 360 degrees")
+    ap.add_argument("--save-hdr", action="store_true", help="also write the linear-light image of each frame as .npy")
+    ap.add_argument("--chunk", type=int, default=4096)
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+    if args.turntable < 1:
+        ap.error("--turntable must be >= 1")
+
+    import numpy as np
+    import torch
+    from PIL import Image
+
+    from ..utils.checkpoints import load_reference_pipeline_state
+    from . import EnvironmentMap, camera_rays, load_camera_path, srgb_to_linear, z_rotation
+
+    t0 = time.perf_counter()
+    cams = load_camera_path(args.camera_path)
+    ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
+    state = ckpt["pipeline"] if "pipeline" in ckpt else ckpt
+    pipe = build_pipeline(state, args.device)
+    loaded, unmapped = load_reference_pipeline_state(pipe, state)
+    if not loaded:
+        raise SystemExit(f"{args.checkpoint}: no pipeline entries")
+    if unmapped:
+        print(f"warning: {len(unmapped)} checkpoint entries not mapped: {unmapped[:4]}", file=sys.stderr)
+    pipe.eval()
+    model = pipe.model
+    envmap = None
+    if args.envmap is not None:
+        envmap = EnvironmentMap.from_file(args.envmap, convention=args.convention, exposure=args.exposure, device=args.device)
+    else:
+        n = model.train_illumination_latents.shape[0]
+        if not 0 <= args.latent_index < n:
+            raise SystemExit(f"--latent-index {args.latent_index}: the checkpoint has {n} training latents")
+        with torch.no_grad():  # the frame render reads eval row 0: it takes the training latent (in memory only)
+            model.eval_illumination_latents[0].copy_(model.train_illumination_latents[args.latent_index])
+            model.eval_scale[0].copy_(model.train_scale[args.latent_index])
+            if args.exposure != 1.0:
+                model.eval_scale[0].mul_(args.exposure)
+    t_load = time.perf_counter() - t0
+    os.makedirs(args.output_dir, exist_ok=True)
+    frames = 0
+    t1 = time.perf_counter()
+    for c in range(len(cams)):
+        rb = camera_rays(cams, c, args.device)
+        for f in range(args.turntable):
+            angle = math.radians(args.rotation_deg) + 2.0 * math.pi * f / args.turntable
+            rot = None if angle == 0.0 else z_rotation(angle).to(args.device)
+            out = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rot, envmap=envmap)
+            rgb = out["rgb"].clamp(0.0, 1.0).cpu().numpy()
+            stem = os.path.join(args.output_dir, f"frame_{c:04d}_{f:03d}")
+            Image.fromarray(np.round(rgb * 255.0).astype(np.uint8)).save(stem + ".png")
+            if args.save_hdr:
+                np.save(stem + ".npy", srgb_to_linear(rgb).astype(np.float32))
+            frames += 1
+    torch.cuda.synchronize()
+    t_render = time.perf_counter() - t1
+    print(f"{args.output_dir}: {frames} frames {cams.width}x{cams.height} | load {t_load:.3f}s render {t_render:.3f}s "
+          f"({t_render / max(frames, 1):.3f}s/frame)")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
