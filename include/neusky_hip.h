@@ -760,6 +760,30 @@ int nsky_envmap_reduce(const float* map, int64_t H, int64_t W, int32_t conventio
 int nsky_envmap_lookup(const float* map, int64_t H, int64_t W, int32_t convention, const float* directions, int64_t N, const float* rotation,
                        const float* exposure, float* out, nsky_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Precomputed radiance transfer of one frame (neusky_amd/relight/transfer.py, csrc/transfer.hip).  nsky_hemi_composite_fwd is linear in
+ * the light colours; with its two sums swapped,
+ *   T[r,d,c] = vis[r,d] sum_s weights[r,s] albedo[r,s,c] clamp(<normals[r,s], dirs[d]>, 0, 1) / cnt[r,s]
+ *   cnt[r,s] = #{d : clamp(<normals[r,s], dirs[d]>, 0, 1) > 0}, 1 when that is 0;        acc[r] = sum_s weights[r,s]
+ *   lin[k,r,c] = sum_d T[r,d,c] lights[k,d,c] + bg[k,r,c] (1 - acc[r]);                   rgb = clamp(linear_to_sRGB(lin), 0, 1)
+ * T and acc depend on the camera and the scene only; a new light changes `lights` and `bg` alone.
+ *   storage:  NSKY_TRANSFER_FP32: T is fp32 [rows][D][3].  NSKY_TRANSFER_FP16: row r is stored as half(T[r] 2^exponents[r]) (round to
+ *             nearest even), exponents[r] chosen so that the row maximum of |T[r]| 2^exponents[r] lies in [0.5, 1); a row of zeros
+ *             takes 0.  (Raw values are ~ weights / cnt, 1e-3 .. 1e-9: fp16 subnormals without the scale.)
+ * nsky_transfer_bake:    albedo, normals [R,S,3]; weights [R,S]; dirs [D,3]; vis [R,D] or NULL, as nsky_hemi_composite_fwd  ->
+ *                        rows [row0, row0 + R) of T; exponents [R] (fp16 storage only, else NULL); acc [R].  1 <= D <= 1024, any S >= 1.
+ * nsky_transfer_relight: T [R][D][3] (with exponents [R] for fp16), acc [R], lights [K,D,3], bg [K,R,3]  ->  rgb [K,R,3] and, unless
+ *                        NULL, lin [K,R,3].  Any K: up to 8 lights share one pass over T (fewer when K D 12 bytes exceed 64 KiB).
+ *                        D a multiple of 4 (fp32) / 8 (fp16) streams 16 bytes per lane; any other D takes a scalar kernel.
+ * Flat indices are int64 (R D 3 may exceed 2^31).  No atomics: every output is bitwise repeatable.  Nothing is read on the host. */
+#define NSKY_TRANSFER_FP32 0
+#define NSKY_TRANSFER_FP16 1
+#define NSKY_TRANSFER_MAX_DIRECTIONS 1024
+int nsky_transfer_bake(const float* albedo, const float* normals, const float* weights, const float* dirs, const float* vis, int32_t R,
+                       int32_t S, int32_t D, int32_t storage, void* T, int64_t row0, int32_t* exponents, float* acc, nsky_stream_t stream);
+int nsky_transfer_relight(const void* T, int32_t storage, const int32_t* exponents, const float* acc, const float* lights, const float* bg,
+                          int64_t R, int32_t D, int32_t K, float* rgb, float* lin, nsky_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1153,3 +1153,48 @@ def envmap_lookup(data, convention: int, directions, rotation, exposure, out):
     H, W = data.shape[:2]
     check(_envmap_lookup(ptr(data), H, W, convention, ptr(directions), directions.shape[0], ptr(rotation), ptr(exposure), ptr(out),
                          stream_ptr()), "nsky_envmap_lookup")
+
+
+# ---- precomputed radiance transfer (relight/transfer.py): bake a frame's light-independent part once, relight it per light
+TRANSFER_FP32, TRANSFER_FP16 = 0, 1  # NSKY_TRANSFER_FP32 / _FP16
+TRANSFER_MAX_DIRECTIONS = 1024  # NSKY_TRANSFER_MAX_DIRECTIONS
+_transfer_bake = _sig("nsky_transfer_bake", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                      C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_transfer_relight = _sig("nsky_transfer_relight", C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def _transfer_storage(T, exponents) -> int:
+    if T.dtype == torch.float32:
+        return TRANSFER_FP32
+    if T.dtype != torch.float16:
+        raise ValueError(f"a transfer is stored as float32 or float16, not {T.dtype}")
+    if exponents is None or exponents.dtype != torch.int32:
+        raise ValueError("float16 transfer storage needs its int32 row exponents")
+    return TRANSFER_FP16
+
+
+def transfer_bake(albedo, normals, weights, dirs, vis, T, row0: int, exponents, acc):
+    """albedo, normals: fp32 [R, S, 3]; weights [R, S]; dirs [D, 3]; vis [R, D] or None -> rows [row0, row0 + R) of T (fp32 or fp16
+    [rows, D, 3]), exponents: int32 [R] (fp16 storage, else None), acc: fp32 [R]"""
+    R, S, _ = albedo.shape
+    D = dirs.shape[0]
+    if T.dim() != 3 or tuple(T.shape[1:]) != (D, 3) or not 0 <= row0 <= T.shape[0] - R:
+        raise ValueError(f"rows [{row0}, {row0 + R}) of a transfer shaped {tuple(T.shape)} for D = {D}")
+    assert weights.shape == (R, S) and acc.shape[0] == R and (vis is None or vis.shape == (R, D))
+    assert exponents is None or exponents.shape[0] == R
+    check(_transfer_bake(_c(albedo), _c(normals), _c(weights), _c(dirs), _c(vis), R, S, D, _transfer_storage(T, exponents), _c(T), row0,
+                         _c(exponents), _c(acc), stream_ptr()), "nsky_transfer_bake")
+
+
+def transfer_relight(T, exponents, acc, lights, bg, rgb, lin=None):
+    """T: fp32 or fp16 [R, D, 3] (+ exponents int32 [R]); acc: fp32 [R]; lights: fp32 [K, D, 3]; bg: fp32 [K, R, 3] -> rgb [K, R, 3]
+    (sRGB, clamped) and, if given, lin [K, R, 3]"""
+    R, D, _ = T.shape
+    K = lights.shape[0]
+    assert lights.shape == (K, D, 3) and bg.shape == (K, R, 3) and rgb.shape == (K, R, 3) and acc.shape[0] == R
+    assert lin is None or lin.shape == (K, R, 3)
+    assert all(t.dtype == torch.float32 for t in (acc, lights, bg, rgb)) and (lin is None or lin.dtype == torch.float32)
+    assert exponents is None or exponents.shape[0] == R
+    check(_transfer_relight(_c(T), _transfer_storage(T, exponents), _c(exponents), _c(acc), _c(lights), _c(bg), R, D, K, _c(rgb), _c(lin),
+                            stream_ptr()), "nsky_transfer_relight")

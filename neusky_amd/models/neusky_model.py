@@ -571,11 +571,19 @@ class NeuSkyFactoModel(ModelBase):
         weights, ray_samples = so["weights"], so["ray_samples"]
         visibility = so["visibility_dict"]["visibility"] if self.config.use_visibility else None
         sdf_at_termination = so["visibility_dict"].get("sdf_at_termination") if self.config.use_visibility else None
-        rgb = self.lambertian_renderer.forward_compact(
-            albedos=fo[NeuSkyFieldHeadNames.ALBEDO], normals=fo[FieldHeadNames.NORMALS],
-            light_directions=so["illumination_directions"], cam_colours=so["hdr_illumination_colours"],
-            cam_of_ray=so["cam_of_ray"], visibility=visibility, background_illumination=so["hdr_background_colours"],
-            weights=weights)  # :797-805
+        bake = None if self.training else getattr(self, "_transfer_storage", None)
+        if bake is not None:
+            # relight.bake_transfer: the renderer's inputs go to the radiance-transfer bake instead (no light enters; no rgb comes out)
+            from ..relight.transfer import bake_rows
+            rgb = None
+            transfer = bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], weights[..., 0],
+                                 so["illumination_directions"], visibility, bake)
+        else:
+            rgb = self.lambertian_renderer.forward_compact(
+                albedos=fo[NeuSkyFieldHeadNames.ALBEDO], normals=fo[FieldHeadNames.NORMALS],
+                light_directions=so["illumination_directions"], cam_colours=so["hdr_illumination_colours"],
+                cam_of_ray=so["cam_of_ray"], visibility=visibility, background_illumination=so["hdr_background_colours"],
+                weights=weights)  # :797-805
         accumulation, p2p_dist = so["accumulation"], so["p2p_dist"]
         depth = p2p_dist / ray_bundle.metadata["directions_norm"]
         normal, albedo = so["normal"], so["albedo_on_white"]  # :812-813 (white background), from the same reduction pass
@@ -584,6 +592,9 @@ class NeuSkyFactoModel(ModelBase):
             "weights": weights, "hdr_background_colours": so["hdr_background_colours"],
             "directions_norm": ray_bundle.metadata["directions_norm"], "sdf_at_termination": sdf_at_termination,
         }
+        if bake is not None:
+            del outputs["rgb"]
+            outputs.update(transfer)
         if self.training:
             outputs["eik_grad"] = fo[FieldHeadNames.GRADIENT]  # :903-904
             outputs.update(so)
@@ -878,6 +889,11 @@ class NeuSkyFactoModel(ModelBase):
         dirs, sel = self.illumination_sampler.on_device(self.device, apply_random_rotation=False if fixed else None)
         cam = int(camera_index)
         D = dirs.shape[0]
+        rot_key = None if (rotation is None or envmap is not None) else tuple(rotation.reshape(-1).tolist())
+        if rot_key is not None:
+            # a chunk graph cached under this rotation's values reads the rotation through the pointer it was captured with: the
+            # first tensor seen with these values is kept, and serves every later frame that asks for them
+            rotation = self.__dict__.setdefault("_frame_rotations", {}).setdefault(rot_key, rotation)
         if envmap is not None:
             from ..relight import project_envmap
             cols = project_envmap(envmap, dirs, rotation)[0][None]
@@ -898,7 +914,7 @@ class NeuSkyFactoModel(ModelBase):
         self._frame_illumination = (st[0], st[1], st[2], cam, rotation)
         if envmap is None:
             self._frame_envmap = None
-            self._frame_key = (cam, None if rotation is None else tuple(rotation.reshape(-1).tolist()))
+            self._frame_key = (cam, rot_key)
             return
         # a chunk graph reads the map through its pointer and the rotation / exposure through static buffers: it is keyed on the
         # map's storage, shape and convention only, so a new rotation or exposure replays it without a new capture

@@ -2,10 +2,14 @@
 light directions and the bilinear sky lookup on the GPU (csrc/envmap.hip), and the frame render with `envmap=`.
 
   python -m neusky_amd.relight --checkpoint CKPT --camera-path camera_path.json --output-dir frames/ --envmap sky.hdr
+
+`bake_transfer` / `RadianceTransfer` (transfer.py, csrc/transfer.hip): a camera's frame baked once into its radiance transfer, then relit
+under any number of lights at one streaming pass over the transfer each (`--transfer fp32|fp16` on the command line).
 """
 from .cameras import CameraPath, camera_rays, load_camera_path
 from .envmap import EnvironmentMap, envmap_labels, envmap_lookup, project_envmap, z_rotation
 from .io import read_envmap, srgb_to_linear
+from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
 
-__all__ = ["CameraPath", "EnvironmentMap", "camera_rays", "envmap_labels", "envmap_lookup", "load_camera_path", "project_envmap",
-           "read_envmap", "srgb_to_linear", "z_rotation"]
+__all__ = ["CameraPath", "EnvironmentMap", "RadianceTransfer", "bake_transfer", "camera_rays", "envmap_labels", "envmap_lookup",
+           "load_camera_path", "pack_fp16", "project_envmap", "read_envmap", "srgb_to_linear", "unpack_fp16", "z_rotation"]

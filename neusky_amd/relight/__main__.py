@@ -41,7 +41,7 @@ def build_pipeline(state, device):
     return cfg.setup(device=device)
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m neusky_amd.relight", description=__doc__.splitlines()[0])
     ap.add_argument("--checkpoint", required=True, help="a nerfstudio-layout checkpoint (step-*.ckpt) of the neusky method")
     ap.add_argument("--camera-path", required=True, help="nerfstudio camera_path.json (perspective cameras)")
@@ -55,7 +55,14 @@ def main(argv=None) -> int:
     ap.add_argument("--turntable", type=int, default=1, help="frames per camera, the illumination turned through 360 degrees")
     ap.add_argument("--save-hdr", action="store_true", help="also write the linear-light image of each frame as .npy")
     ap.add_argument("--chunk", type=int, default=4096)
+    ap.add_argument("--transfer", default="off", choices=("off", "fp32", "fp16"),
+                    help="bake each camera's radiance transfer once (stored as fp32 or scaled fp16) and relight its frames from it")
     ap.add_argument("--device", default="cuda:0")
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.turntable < 1:
         ap.error("--turntable must be >= 1")
@@ -94,14 +101,31 @@ def main(argv=None) -> int:
     t_load = time.perf_counter() - t0
     os.makedirs(args.output_dir, exist_ok=True)
     frames = 0
+    t_bake = t_relight = 0.0
     t1 = time.perf_counter()
     for c in range(len(cams)):
         rb = camera_rays(cams, c, args.device)
+        rots = []
         for f in range(args.turntable):
             angle = math.radians(args.rotation_deg) + 2.0 * math.pi * f / args.turntable
-            rot = None if angle == 0.0 else z_rotation(angle).to(args.device)
-            out = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rot, envmap=envmap)
-            rgb = out["rgb"].clamp(0.0, 1.0).cpu().numpy()
+            rots.append(None if angle == 0.0 else z_rotation(angle).to(args.device))
+        if args.transfer != "off":
+            from .transfer import LIGHTS_PER_PASS, bake_transfer
+            tb = time.perf_counter()
+            baked = bake_transfer(model, rb, storage=args.transfer, chunk=args.chunk, camera_index=0)
+            torch.cuda.synchronize()
+            t_bake += time.perf_counter() - tb
+        for f in range(args.turntable):
+            if args.transfer == "off":
+                out = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[f], envmap=envmap)
+                rgb = out["rgb"].clamp(0.0, 1.0).cpu().numpy()
+            else:
+                if f % LIGHTS_PER_PASS == 0:  # one pass over the transfer lights the next 8 frames
+                    tr = time.perf_counter()
+                    batch = baked.relight(model, envmap=envmap, camera_index=0, rotations=rots[f:f + LIGHTS_PER_PASS])["rgb"]
+                    batch = batch.clamp(0.0, 1.0).cpu().numpy()
+                    t_relight += time.perf_counter() - tr
+                rgb = batch[f % LIGHTS_PER_PASS]
             stem = os.path.join(args.output_dir, f"frame_{c:04d}_{f:03d}")
             Image.fromarray(np.round(rgb * 255.0).astype(np.uint8)).save(stem + ".png")
             if args.save_hdr:
@@ -109,8 +133,9 @@ def main(argv=None) -> int:
             frames += 1
     torch.cuda.synchronize()
     t_render = time.perf_counter() - t1
+    transfer = "" if args.transfer == "off" else f" | transfer {args.transfer}: bake {t_bake:.3f}s relight {t_relight:.3f}s"
     print(f"{args.output_dir}: {frames} frames {cams.width}x{cams.height} | load {t_load:.3f}s render {t_render:.3f}s "
-          f"({t_render / max(frames, 1):.3f}s/frame)")
+          f"({t_render / max(frames, 1):.3f}s/frame){transfer}")
     return 0
 
 

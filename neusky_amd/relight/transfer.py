@@ -1,0 +1,222 @@
+"""Precomputed radiance transfer of one frame: bake the light-independent part of a camera's render once, relight it per light.
+
+The renderer is linear in the light colours (csrc/transfer.hip, include/neusky_hip.h):
+    T[r,d,c] = vis[r,d] sum_s w[r,s] alb[r,s,c] clamp(n[r,s].dir[d], 0, 1) / cnt[r,s]
+    lin[r,c] = sum_d T[r,d,c] L[d,c] + bg[r,c] (1 - acc[r]);   rgb = clamp(linear_to_sRGB(lin), 0, 1)
+`bake_transfer` runs the frame's chunked eval forward once and keeps T and acc; `RadianceTransfer.relight` then costs one streaming pass
+over T per batch of up to 8 lights.  A new latent, environment map, rotation or exposure only changes L and bg.  A new camera needs a new
+bake.  The identity needs the bake's light directions, so `fix_test_illumination_directions` must be on (the default)."""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple, Union
+
+import torch
+
+STORAGES = ("fp32", "fp16")
+LIGHTS_PER_PASS = 8
+FRAME_KEYS = ("albedo", "accumulation", "depth", "p2p_dist", "normal")  # the light-independent outputs of the frame render
+_BG_ROWS = 1 << 18  # rays per decoder pass of the latent background
+
+
+def pack_fp16(T: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """scaled fp16 storage of T [R, ...]: (half(T[r] 2^e[r]), e int32 [R]) with e[r] chosen so that the row maximum of |T[r]| 2^e[r]
+    lies in [0.5, 1); a row of zeros takes e = 0.  The scale is a power of two, so the only rounding is the one to fp16."""
+    R = T.shape[0]
+    mx = T.reshape(R, -1).abs().amax(dim=1) if T.numel() else T.new_zeros(R)
+    _, x = torch.frexp(mx)  # mx = m 2^x, m in [0.5, 1)
+    ok = (mx > 0) & torch.isfinite(mx)
+    e = torch.where(ok, -x, torch.zeros_like(x)).to(torch.int32)
+    scaled = torch.ldexp(T, e.reshape(R, *([1] * (T.dim() - 1))))
+    return scaled.to(torch.float16), e
+
+
+def unpack_fp16(half: torch.Tensor, exponents: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    R = half.shape[0]
+    return torch.ldexp(half.to(dtype), -exponents.reshape(R, *([1] * (half.dim() - 1))))
+
+
+def _storage_dtype(storage: str) -> torch.dtype:
+    if storage not in STORAGES:
+        raise ValueError(f"storage must be one of {STORAGES}, got {storage!r}")
+    return torch.float32 if storage == "fp32" else torch.float16
+
+
+def bake_rows(albedo, normals, weights, dirs, vis, storage: str) -> Dict[str, torch.Tensor]:
+    """nsky_transfer_bake on one batch of rays (the inputs of the renderer: albedo, normals [R,S,3], weights [R,S], dirs [D,3],
+    vis [R,D] or None) -> {"transfer": [R,D,3], "transfer_acc": [R,1], "transfer_exponents": int32 [R,1] (fp16 storage)}"""
+    from .. import hip
+    R, D = albedo.shape[0], dirs.shape[0]
+    dev = albedo.device
+    T = torch.empty(R, D, 3, dtype=_storage_dtype(storage), device=dev)
+    acc = torch.empty(R, 1, dtype=torch.float32, device=dev)
+    exps = torch.empty(R, 1, dtype=torch.int32, device=dev) if storage == "fp16" else None
+    hip.transfer_bake(albedo.detach().contiguous(), normals.detach().contiguous(), weights.detach().contiguous(), dirs.contiguous(),
+                      None if vis is None else vis.detach().contiguous(), T, 0, exps, acc)
+    out = {"transfer": T, "transfer_acc": acc}
+    if exps is not None:
+        out["transfer_exponents"] = exps
+    return out
+
+
+class RadianceTransfer:
+    """One baked frame: T [R, D, 3] (fp32, or fp16 with int32 row exponents [R]), acc [R], the bake's light directions [D, 3], the rays'
+    directions [R, 3] (for the background), the frame shape, and the light-independent outputs of the frame render."""
+
+    def __init__(self, T: torch.Tensor, exponents: Optional[torch.Tensor], acc: torch.Tensor, dirs: torch.Tensor,
+                 ray_directions: torch.Tensor, shape: Sequence[int], outputs: Dict[str, torch.Tensor], camera_index: int = 0):
+        if T.dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"T is stored as float32 or float16, not {T.dtype}")
+        if (T.dtype == torch.float16) != (exponents is not None):
+            raise ValueError("float16 storage comes with row exponents, float32 storage without")
+        R, D = T.shape[0], T.shape[1]
+        if tuple(T.shape) != (R, D, 3) or tuple(dirs.shape) != (D, 3) or tuple(ray_directions.shape) != (R, 3) or acc.shape[0] != R:
+            raise ValueError(f"T {tuple(T.shape)}, acc {tuple(acc.shape)}, dirs {tuple(dirs.shape)}, rays {tuple(ray_directions.shape)}")
+        n = 1
+        for v in shape:
+            n *= int(v)
+        if n != R:
+            raise ValueError(f"frame shape {tuple(shape)} does not hold {R} rays")
+        self.T, self.exponents, self.acc, self.dirs, self.ray_directions = T, exponents, acc.reshape(R), dirs, ray_directions
+        self.shape = tuple(int(v) for v in shape)
+        self.outputs = dict(outputs)
+        self.camera_index = int(camera_index)
+
+    @property
+    def storage(self) -> str:
+        return "fp32" if self.T.dtype == torch.float32 else "fp16"
+
+    @property
+    def device(self) -> torch.device:
+        return self.T.device
+
+    @property
+    def nbytes(self) -> int:
+        return self.T.numel() * self.T.element_size()
+
+    def dense(self, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """T as a plain [R, D, 3] tensor (the fp16 rows unscaled)"""
+        return self.T.to(dtype) if self.exponents is None else unpack_fp16(self.T, self.exponents, dtype)
+
+    # ------------------------------------------------------------------ persistence: plain tensors
+    def save(self, path) -> None:
+        state = {"format": 1, "T": self.T.cpu(), "exponents": None if self.exponents is None else self.exponents.cpu(),
+                 "acc": self.acc.cpu(), "dirs": self.dirs.cpu(), "ray_directions": self.ray_directions.cpu(), "shape": list(self.shape),
+                 "camera_index": self.camera_index, "outputs": {k: v.cpu() for k, v in self.outputs.items()}}
+        torch.save(state, path)
+
+    @classmethod
+    def load(cls, path, device: Union[str, torch.device] = "cuda") -> "RadianceTransfer":
+        state = torch.load(path, map_location="cpu", weights_only=True)
+        if state.get("format") != 1:
+            raise ValueError(f"{path}: not a saved RadianceTransfer")
+        to = lambda t: None if t is None else t.to(device)  # noqa: E731
+        return cls(to(state["T"]), to(state["exponents"]), to(state["acc"]), to(state["dirs"]), to(state["ray_directions"]), state["shape"],
+                   {k: to(v) for k, v in state["outputs"].items()}, state["camera_index"])
+
+    # ------------------------------------------------------------------ relighting
+    def _light(self, model, envmap, cam: int, rotation: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(L [D, 3], bg [R, 3]) of one light, built as the frame render builds them (begin_frame, sample_illumination_compact)"""
+        if envmap is not None:
+            from .envmap import envmap_lookup, project_envmap
+            return project_envmap(envmap, self.dirs, rotation)[0], envmap_lookup(envmap, self.ray_directions, rotation)
+        latents, scales = model.get_illumination_field()
+        field = model.illumination_field
+        if rotation is None:
+            L = field.forward_grid(self.dirs, latents[cam][None], scales[cam][None])[0]
+        else:
+            L = field.forward_camera(self.dirs, latents[cam], scales[cam], rotation)
+        R = self.ray_directions.shape[0]
+        bg = torch.empty(R, 3, dtype=torch.float32, device=self.device)
+        for a in range(0, R, _BG_ROWS):
+            bg[a:a + _BG_ROWS] = field.forward_camera(self.ray_directions[a:a + _BG_ROWS], latents[cam], scales[cam], rotation)
+        return L, bg
+
+    @torch.no_grad()
+    def relight(self, model=None, *, envmap=None, camera_index: Optional[int] = None, rotations=None, exposure=None,
+                return_linear: bool = False) -> Dict[str, torch.Tensor]:
+        """The frame under new light: the keys of get_outputs_for_camera_ray_bundle.  envmap: a relight.EnvironmentMap, else the
+        illumination latent of `camera_index` (default: the bake's camera) of `model`.  rotations: None or one [3, 3] matrix -> rgb
+        [*shape, 3]; a sequence or a [K, 3, 3] tensor -> rgb [K, *shape, 3], processed in batches of 8 lights per pass over T.
+        exposure: a float or a 0-d tensor multiplying the light (on top of the map's own exposure).  Nothing synchronises with the host."""
+        from .. import hip
+        if envmap is None and model is None:
+            raise ValueError("relight needs an environment map, or a model whose illumination latent lights the frame")
+        cam = self.camera_index if camera_index is None else int(camera_index)
+        single = rotations is None or (torch.is_tensor(rotations) and rotations.dim() == 2)
+        rots = [rotations] if single else list(rotations)
+        dev = self.device
+        rots = [None if r is None else torch.as_tensor(r, dtype=torch.float32).to(dev).reshape(3, 3) for r in rots]
+        gain = None if exposure is None else torch.as_tensor(exposure, dtype=torch.float32).to(dev)
+        R, D = self.T.shape[0], self.T.shape[1]
+        K = len(rots)
+        rgb = torch.empty(K, R, 3, dtype=torch.float32, device=dev)
+        lin = torch.empty(K, R, 3, dtype=torch.float32, device=dev) if return_linear else None
+        for k0 in range(0, K, LIGHTS_PER_PASS):
+            kb = min(LIGHTS_PER_PASS, K - k0)
+            lights = torch.empty(kb, D, 3, dtype=torch.float32, device=dev)
+            bg = torch.empty(kb, R, 3, dtype=torch.float32, device=dev)
+            for i in range(kb):
+                L, b = self._light(model, envmap, cam, rots[k0 + i])
+                lights[i].copy_(L if gain is None else L * gain)
+                bg[i].copy_(b if gain is None else b * gain)
+            hip.transfer_relight(self.T, self.exponents, self.acc, lights, bg, rgb[k0:k0 + kb], None if lin is None else lin[k0:k0 + kb])
+        lead = () if single else (K,)
+        out = {"rgb": rgb.view(*lead, *self.shape, 3)}
+        if lin is not None:
+            out["linear"] = lin.view(*lead, *self.shape, 3)
+        out.update(self.outputs)
+        return out
+
+
+@torch.no_grad()
+def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Optional[int] = None, use_graph: bool = True,
+                  camera_index: Optional[int] = None) -> RadianceTransfer:
+    """Run the chunked eval forward of get_outputs_for_camera_ray_bundle once, with the renderer's inputs routed into the transfer bake
+    (a mode flag on the model, off outside this call: the plain frame render and its captured chunk graphs are untouched)."""
+    from .. import ops
+    from ..models.neusky_model import _ChunkRunner
+    dtype = _storage_dtype(storage)
+    assert not model.training, "call model.eval() first"
+    if not model.config.fix_test_illumination_directions:
+        raise ValueError("bake_transfer needs fix_test_illumination_directions=True: a transfer is valid for the light directions it was "
+                         "baked with, and with the option off every frame draws new ones")
+    chunk = chunk or max(model.config.eval_num_rays_per_chunk, 4096)
+    shape = tuple(camera_ray_bundle.origins.shape[:-1])
+    flat = camera_ray_bundle.slice(0, 1 << 62)
+    R = flat.origins.shape[0]
+    if camera_index is None:
+        camera_index = int(flat.camera_indices.reshape(-1)[0]) if flat.camera_indices is not None else 0
+    dev = flat.origins.device
+    model.begin_frame(camera_index)
+    model._transfer_storage = storage
+    runner = None
+    try:
+        dirs = model._frame_illumination[0].clone()
+        D = dirs.shape[0]
+        T = torch.empty(R, D, 3, dtype=dtype, device=dev)
+        acc = torch.empty(R, dtype=torch.float32, device=dev)
+        exps = torch.empty(R, dtype=torch.int32, device=dev) if storage == "fp16" else None
+        outs = {k: [] for k in FRAME_KEYS}
+        runner = _ChunkRunner(model, chunk, flat, use_graph)  # its own runner: a captured graph of this mode is never cached on the model
+        for a in range(0, R, chunk):
+            b = min(a + chunk, R)
+            runner._load(flat, a, b)
+            if runner.graph is not None:
+                runner.graph.replay()
+                res = runner.out
+            else:
+                res = model.forward(runner.rb)
+            T[a:b].copy_(res["transfer"][:b - a])
+            acc[a:b].copy_(res["transfer_acc"][:b - a, 0])
+            if exps is not None:
+                exps[a:b].copy_(res["transfer_exponents"][:b - a, 0])
+            for k in FRAME_KEYS:
+                outs[k].append(res[k][:b - a].clone())
+    finally:
+        model._transfer_storage = None
+        model.end_frame()
+        if runner is not None and runner.graph is not None:
+            ops.retire_graph(runner.graph)
+            runner.graph = None
+    outputs = {k: torch.cat(v).view(*shape, -1) for k, v in outs.items()}
+    return RadianceTransfer(T, exps, acc, dirs, flat.directions.reshape(R, 3).contiguous().clone(), shape, outputs, camera_index)
