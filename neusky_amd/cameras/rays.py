@@ -71,3 +71,9 @@ class RayBundle:
         f = lambda t: None if t is None else t.reshape(-1, t.shape[-1])[start:end]
         return RayBundle(f(self.origins), f(self.directions), f(self.pixel_area), f(self.camera_indices), f(self.nears),
                          f(self.fars), {k: f(v) for k, v in self.metadata.items()})
+
+    def static_clone(self) -> "RayBundle":
+        """detached clones of every tensor field and metadata entry: the static input buffers of a captured HIP graph"""
+        f = lambda t: None if t is None else t.detach().clone()
+        return RayBundle(f(self.origins), f(self.directions), f(self.pixel_area), f(self.camera_indices), f(self.nears),
+                         f(self.fars), {k: f(v) for k, v in self.metadata.items()})

@@ -820,50 +820,17 @@ class NeuSkyFactoModel(ModelBase):
             loss.backward()
             return loss.detach()
 
+        graph = replay = None
         try:
             rb0, batch0, rot0 = next_bundle(0)
             if use_graph is None:
                 use_graph = randoms_per_step is None and method != "nerf_osr_envmap"
-            graph = None
             if use_graph:
-                c = lambda t: t.detach().clone()  # noqa: E731
-                srb = RayBundle(origins=c(rb0.origins), directions=c(rb0.directions), pixel_area=c(rb0.pixel_area),
-                                camera_indices=c(rb0.camera_indices), metadata={k: c(v) for k, v in rb0.metadata.items()})
-                sbatch = {"image": c(batch0["image"]), "mask": c(batch0["mask"])}
-                srnd = None
-                if randoms_per_step is not None:  # injected draws live in static buffers the graph reads
-                    keys = ("jitters", "light_rotation", "grid_perturb", "grid_dirs")
-                    srnd = {k: ([c(t) for t in v] if isinstance(v, (list, tuple)) else c(v)) for k, v in randoms_per_step[0].items() if k in keys}
-                side = ops.role_stream("capture", self.device)  # warm-up and capture on the package's capture stream (ops.role_stream)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):  # eager warm-up (allocator pools, per-step caches); no parameter is updated by it
-                    iteration(srb, sbatch, None, srnd)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                try:
-                    with torch.cuda.graph(graph, stream=side, capture_error_mode=ops.CAPTURE_MODE):
-                        gloss = iteration(srb, sbatch, None, srnd)
-                except RuntimeError as exc:  # a host-dependent op inside the iteration: run the fit with host launches instead
-                    import warnings
-                    warnings.warn(f"fit_latent_codes_for_eval: HIP graph capture refused ({str(exc)[:100]}); running eagerly")
-                    torch.cuda.synchronize()
-                    graph = None
+                graph, replay = self._capture_fit_iteration(iteration, rb0, batch0, randoms_per_step)
             for it in range(steps):
                 rb, batch, rot = (rb0, batch0, rot0) if it == 0 else next_bundle(it)
                 if graph is not None:
-                    srb.origins.copy_(rb.origins, non_blocking=True); srb.directions.copy_(rb.directions, non_blocking=True)
-                    srb.camera_indices.copy_(rb.camera_indices, non_blocking=True)
-                    for k, v in rb.metadata.items():
-                        srb.metadata[k].copy_(v, non_blocking=True)
-                    sbatch["image"].copy_(batch["image"], non_blocking=True); sbatch["mask"].copy_(batch["mask"], non_blocking=True)
-                    if srnd is not None:
-                        for k, v in srnd.items():
-                            src = randoms_per_step[it][k]
-                            for dst_t, src_t in (zip(v, src) if isinstance(v, list) else ((v, src),)):
-                                dst_t.copy_(src_t, non_blocking=True)
-                    graph.replay()
-                    loss = gloss
+                    loss = replay(it, rb, batch)
                 else:
                     loss = iteration(rb, batch, rot, None if randoms_per_step is None else randoms_per_step[it])
                 for p, (m_, v_) in zip(params, state):
@@ -876,8 +843,43 @@ class NeuSkyFactoModel(ModelBase):
             for p, g in zip(params, old_grads):
                 p.grad = g
             self.fitting_eval_latents = False  # :1588
-            ops.retire_graph(locals().get("graph"))  # never destroyed next to its last replay (ops.retire_graph: a runtime use-after-free)
+            if graph is not None:
+                graph.retire()  # (now, not whenever the last reference to it goes: this method's frame may outlive the call in a traceback)
         return trace
+
+    def _capture_fit_iteration(self, iteration, rb0, batch0, randoms_per_step):
+        """the graph of fit_latent_codes_for_eval: `iteration` on static clones of the first step's inputs, captured after one eager
+        warm-up (allocator pools, per-step caches; no parameter is updated by it) -> (graph, replay); replay(it, rb, batch) copies step
+        `it`'s inputs into the static buffers, replays and returns the graph's loss scalar.  (None, None) when the capture is refused."""
+        c = lambda t: t.detach().clone()  # noqa: E731
+        srb = RayBundle.static_clone(rb0)
+        sbatch = {"image": c(batch0["image"]), "mask": c(batch0["mask"])}
+        srnd = None
+        if randoms_per_step is not None:  # injected draws live in static buffers the graph reads
+            keys = ("jitters", "light_rotation", "grid_perturb", "grid_dirs")
+            srnd = {k: ([c(t) for t in v] if isinstance(v, (list, tuple)) else c(v)) for k, v in randoms_per_step[0].items() if k in keys}
+        try:
+            graph = ops.CapturedGraph(self.device, 1, lambda i: iteration(srb, sbatch, None, srnd))
+        except RuntimeError as exc:  # a host-dependent op inside the iteration: run the fit with host launches instead
+            import warnings
+            warnings.warn(f"fit_latent_codes_for_eval: HIP graph capture refused ({str(exc)[:100]}); running eagerly")
+            torch.cuda.synchronize()
+            return None, None
+
+        def replay(it, rb, batch):
+            srb.origins.copy_(rb.origins, non_blocking=True); srb.directions.copy_(rb.directions, non_blocking=True)
+            srb.camera_indices.copy_(rb.camera_indices, non_blocking=True)
+            for k, v in rb.metadata.items():
+                srb.metadata[k].copy_(v, non_blocking=True)
+            sbatch["image"].copy_(batch["image"], non_blocking=True); sbatch["mask"].copy_(batch["mask"], non_blocking=True)
+            if srnd is not None:
+                for k, v in srnd.items():
+                    src = randoms_per_step[it][k]
+                    for dst_t, src_t in (zip(v, src) if isinstance(v, list) else ((v, src),)):
+                        dst_t.copy_(src_t, non_blocking=True)
+            graph.replay()
+            return graph.outputs
+        return graph, replay
 
     def begin_frame(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None) -> None:
         """decode the illumination of ONE camera for a whole frame (the reference re-decodes it in each of the
@@ -907,9 +909,7 @@ class NeuSkyFactoModel(ModelBase):
         if st is None or st[0].shape != dirs.shape or st[0].device != dirs.device:
             st = (torch.empty_like(dirs), torch.empty_like(cols), torch.empty_like(sel))
             self._frame_static = st
-            for old in getattr(self, "_chunk_runners", {}).values():
-                ops.retire_graph(old.graph)
-            self._chunk_runners = {}
+            self._chunk_runners = {}  # (the dropped runners' graphs retire themselves: ops.CapturedGraph)
         st[0].copy_(dirs); st[1].copy_(cols); st[2].copy_(sel)
         self._frame_illumination = (st[0], st[1], st[2], cam, rotation)
         if envmap is None:
@@ -961,8 +961,6 @@ class NeuSkyFactoModel(ModelBase):
             if runner is None:
                 runner = _ChunkRunner(self, chunk, flat, use_graph)
                 if len(self._chunk_runners) >= 4:
-                    for old in self._chunk_runners.values():
-                        ops.retire_graph(old.graph)
                     self._chunk_runners.clear()
                 self._chunk_runners[key] = runner
             for i in range(0, num_rays, chunk):
@@ -986,22 +984,7 @@ class _ChunkRunner:
         self.rb.directions[:, 2] = 1.0
         if use_graph:
             self._load(flat, 0, min(chunk, flat.origins.shape[0]))
-            side = ops.role_stream("capture", dev)  # warm-up and capture on the package's capture stream (ops.role_stream)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self.out = model.forward(self.rb)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=side, capture_error_mode=ops.CAPTURE_MODE):
-                self.out = model.forward(self.rb)
-
-    def __del__(self):
-        try:  # (dropped with its model, possibly right behind its last replay: retired, not destroyed here -- ops.retire_graph)
-            ops.retire_graph(self.__dict__.pop("graph", None))
-        except Exception:  # noqa: BLE001
-            pass
+            self.graph = ops.CapturedGraph(dev, 2, lambda i: model.forward(self.rb))  # (retires itself when this runner is dropped)
 
     def _load(self, flat: RayBundle, a: int, b: int) -> None:
         n = b - a
@@ -1013,11 +996,20 @@ class _ChunkRunner:
             self.rb.origins[n:].copy_(self.rb.origins[:1].expand(self.chunk - n, 3))
             self.rb.directions[n:].copy_(self.rb.directions[:1].expand(self.chunk - n, 3))
 
-    def run(self, flat: RayBundle, a: int, b: int) -> Dict[str, torch.Tensor]:
+    def forward_rows(self, flat: RayBundle, a: int, b: int) -> Dict:
+        """rows a:b of `flat` through the model: the chunk's whole output dictionary, NOT cloned (under a graph: its static outputs,
+        overwritten by the next call), rows past b - a being padding"""
         self._load(flat, a, b)
+        if self.graph is None:
+            return self.model.forward(self.rb)
+        self.graph.replay()
+        return self.graph.outputs
+
+    def retire(self) -> None:
+        """for an owner that is done with the runner at a known point (bake_transfer), rather than when its last reference goes"""
         if self.graph is not None:
-            self.graph.replay()
-            out = self.out
-        else:
-            out = self.model.forward(self.rb)
+            self.graph.retire()
+
+    def run(self, flat: RayBundle, a: int, b: int) -> Dict[str, torch.Tensor]:
+        out = self.forward_rows(flat, a, b)
         return {k: v[:b - a].clone() for k, v in out.items() if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == self.chunk}

@@ -358,6 +358,42 @@ def retire_graph(obj) -> None:
         _RETIRED_GRAPHS.extend(keep)  # (the dropped entries' destructors run here, on this thread)
 
 
+class CapturedGraph:
+    """THE capture protocol of this package: the only code that constructs a torch.cuda.CUDAGraph or enters torch.cuda.graph, and the
+    owner of the graph's retirement.  `body(i)` runs `warmup` times eagerly (i = 0 .. warmup - 1: caches, autotuned paths, allocator
+    pools) and once more under capture (i = warmup); what the captured run returned -- the graph's static outputs -- is `.outputs`.
+    A refused capture raises out of the constructor unchanged, and nothing is retired for it."""
+
+    def __init__(self, device, warmup: int, body):
+        side = role_stream("capture", device)  # warm-up AND capture on the package's capture stream, never a fresh torch.cuda.Stream() (role_stream)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for i in range(warmup):
+                body(i)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side, capture_error_mode=CAPTURE_MODE):  # (the mode is read here: tools/lab.py assigns it)
+            self.outputs = body(warmup)
+        self._graph = graph
+
+    def replay(self) -> None:
+        self._graph.replay()
+
+    def retire(self) -> None:
+        """hand the graph to retire_graph, once: an owner that is done with it early calls this, __del__ does it for everybody else"""
+        graph = self.__dict__.pop("_graph", None)
+        if graph is not None:
+            retire_graph(graph)
+
+    def __del__(self):
+        # dropped with its owner, possibly right behind its last replay: retired, never destroyed here (retire_graph)
+        try:
+            self.retire()
+        except Exception:  # noqa: BLE001  (interpreter shutdown: modules may be gone; the process is ending anyway)
+            pass
+
+
 def async_weight_gradients(launch, operands) -> None:
     """run `launch()` (weight-gradient kernels only: nothing the caller returns may depend on them) on the side stream"""
     if not ASYNC_WGRAD:
@@ -514,14 +550,22 @@ def begin_step(device=None) -> None:
     a["buf"] = torch.zeros(a["cap"], device=device) if (device is not None and a["cap"] > 0 and torch.device(device).type == "cuda") else None
 
 
-def _planes(W, n_rows, n_k, transpose, precision):
-    key = (W.data_ptr(), W._version, ld(W), n_rows, n_k, transpose, precision)
-    hit = _PLANES.get(key)
+def _prepared(cache: dict, key, keep, build):
+    """THE protocol of a weight preparation (split planes, a packed stream) cached for one step and shared by its streams.  Miss:
+    `build()` launches the preparation on the current stream and the entry becomes (keep, value, ready mark, step number) -- `keep`
+    being the tensors behind the data pointers of `key`, held so that their addresses cannot be recycled within the step.  Hit: the
+    preparation may have run on another stream of this step (parallel passes share the weights): order this stream after it."""
+    hit = cache.get(key)
     if hit is None:
-        hit = _PLANES[key] = (W, hip.split_planes(W, n_rows, n_k, transpose, precision), _ready_mark(), _STEP_SEQ[0])
-    else:  # split on another stream (parallel passes of one step share the weights): order this stream after it
+        hit = cache[key] = (keep, build(), _ready_mark(), _STEP_SEQ[0])
+    else:
         _order_after(hit[2], hit[3])
     return hit[1]
+
+
+def _planes(W, n_rows, n_k, transpose, precision):
+    key = (W.data_ptr(), W._version, ld(W), n_rows, n_k, transpose, precision)
+    return _prepared(_PLANES, key, W, lambda: hip.split_planes(W, n_rows, n_k, transpose, precision))
 
 
 def ld(t):
@@ -691,17 +735,15 @@ def _film_stream(wb, n_map, n_film, mw, mb, mwo, mbo, fw, fb, ow, ob, direction=
     """per-step cache of one packed weight stream of a network (direction 0 forward, 1 FiLM backward, 2 mapping backward;
     dropped by begin_step when any of its weights is trainable: the optimiser changed them) -> (descriptor, stream bytes, bias / scale table)"""
     key = (wb[0].data_ptr(), wb[0]._version, wb[-2].data_ptr(), n_map, n_film, direction)
-    hit = _FILM_STREAMS.get(key)
-    if hit is None:
+
+    def pack():
         net = hip.film_net(mw[0].shape[1], fw[0].shape[1], ow.shape[0], mw, mb, mwo, mbo, fw, fb, ow, ob)
         nbytes, _ = hip.film_stream_layout(net, direction)
         # zero-filled once: the pad slabs of partial groups are streamed through LDS but never multiplied
         stream, table = _stream_buffers(("film", stable_id(wb[0]), n_map, n_film, direction), nbytes, hip.FILM_TABLE_FLOATS, wb[0].device)
         hip.film_pack(net, stream, table, direction)
-        hit = _FILM_STREAMS[key] = (list(wb), net, stream, table, _ready_mark(), _STEP_SEQ[0])
-    else:  # packed on another stream of the same step: order this stream after it
-        _order_after(hit[4], hit[5])
-    return hit[1], hit[2], hit[3]
+        return net, stream, table
+    return _prepared(_FILM_STREAMS, key, list(wb), pack)
 
 
 class FilmSirenFn(torch.autograd.Function):
@@ -1118,14 +1160,9 @@ _FIELD_STREAMS: dict = {}
 def _field_pack(kind, weights, layers_fn):
     """per-step cache of one packed weight stream of the field (dropped by begin_step) -> (stream, scales, groups)"""
     key = (kind,) + tuple((w.data_ptr(), w._version) for w in weights)
-    hit = _FIELD_STREAMS.get(key)
-    if hit is None:
-        dev = weights[0].device
-        pk = hip.chain_pack(layers_fn(), dev, lambda nb, nt: _stream_buffers((kind,) + tuple(stable_id(w) for w in weights), nb, nt, dev))
-        hit = _FIELD_STREAMS[key] = (weights, pk, _ready_mark(), _STEP_SEQ[0])
-    else:
-        _order_after(hit[2], hit[3])
-    return hit[1]
+    dev = weights[0].device
+    buffers = lambda nb, nt: _stream_buffers((kind,) + tuple(stable_id(w) for w in weights), nb, nt, dev)  # noqa: E731
+    return _prepared(_FIELD_STREAMS, key, weights, lambda: hip.chain_pack(layers_fn(), dev, buffers))
 
 
 def field_fused_ok(ET, W0, W1, W2, Wc0, Wc1) -> bool:
@@ -1259,17 +1296,15 @@ _SDF_STREAMS: dict = {}
 def _sdf_stream(W0, b0, W1, b1, W2, b2, GF, beta, direction):
     """per-step cache of the packed weight stream of the sdf value chain (direction 0 forward, 1 backward; dropped by begin_step)"""
     key = (W0.data_ptr(), W0._version, W1.data_ptr(), W2.data_ptr(), GF, direction)
-    hit = _SDF_STREAMS.get(key)
-    if hit is None:
-        keep = (W0, b0, W1, b1, W2, b2, W2[GF], b2[GF:GF + 1])
+    keep = (W0, b0, W1, b1, W2, b2, W2[GF], b2[GF:GF + 1])  # (the last two: the sdf row and its bias, views the descriptor points into)
+
+    def pack():
         net = hip.sdf_net(W0, b0, W1, b1, keep[6], keep[7], beta)
         nbytes, _ = hip.sdf_stream_layout(net, direction)
         stream, table = _stream_buffers(("sdf", stable_id(W0), stable_id(W1), GF, direction), nbytes, hip.FILM_TABLE_FLOATS, W0.device)
         hip.sdf_pack(net, stream, table, direction)
-        hit = _SDF_STREAMS[key] = (keep, net, stream, table, _ready_mark(), _STEP_SEQ[0])
-    else:
-        _order_after(hit[4], hit[5])
-    return hit[1], hit[2], hit[3]
+        return net, stream, table
+    return _prepared(_SDF_STREAMS, key, keep, pack)
 
 
 class SDFValueFn(torch.autograd.Function):

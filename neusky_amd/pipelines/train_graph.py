@@ -55,8 +55,7 @@ class TrainGraph:
         self.pipeline, self.slab = pipeline, slab
         dev = ray_bundle.origins.device
         c = lambda t: t.detach().clone()  # noqa: E731
-        self.rb = RayBundle(origins=c(ray_bundle.origins), directions=c(ray_bundle.directions), pixel_area=c(ray_bundle.pixel_area),
-                            camera_indices=c(ray_bundle.camera_indices), metadata={k: c(v) for k, v in ray_bundle.metadata.items()})
+        self.rb = RayBundle.static_clone(ray_bundle)  # (as a function: the caller's bundle may be nerfstudio's own class)
         self.batch = {"image": c(batch["image"]), "mask": c(batch["mask"])}
         sky = pipeline.datamanager.get_sky_ray_bundle(pipeline.config.num_sky_rays)
         self.sky = RayBundle(origins=c(sky.origins), directions=c(sky.directions))
@@ -71,26 +70,10 @@ class TrainGraph:
             self.randoms.update({k: static(v) for k, v in randoms.items() if k != "sky_ray_bundle"})
         self._anchor = torch.zeros((), device=dev, requires_grad=True)
         self._attached = True
-        side = ops.role_stream("capture", dev)  # warm-up and capture on the package's capture stream (ops.role_stream: never an alias of a role stream)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # eager warm-up on the side stream: caches, autotuned paths, allocator pools
-            for i in range(warmup):
-                self._body(start_step + i)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        # thread_local: other host threads (e.g. the RCCL watchdog) may legally touch the runtime during the capture
-        with torch.cuda.graph(self.graph, stream=side, capture_error_mode=ops.CAPTURE_MODE):
-            self.outputs, self.loss, self.loss_dict, self.metrics = self._body(start_step + warmup)
+        self.graph = ops.CapturedGraph(dev, warmup, lambda i: self._body(start_step + i))  # (retires itself when this object is dropped)
+        self.outputs, self.loss, self.loss_dict, self.metrics = self.graph.outputs
         self.used = list(slab.used)  # which parameters the captured pass gives a gradient
         torch.cuda.synchronize()
-
-    def __del__(self):
-        # a pipeline dropped right behind its last replay: the graph is retired, not destroyed here (ops.retire_graph)
-        try:
-            ops.retire_graph(self.__dict__.pop("graph", None))
-        except Exception:  # noqa: BLE001  (interpreter shutdown: modules may be gone; the process is ending anyway)
-            pass
 
     def _body(self, step):
         self.slab.zero_all()

@@ -173,7 +173,6 @@ def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Option
                   camera_index: Optional[int] = None) -> RadianceTransfer:
     """Run the chunked eval forward of get_outputs_for_camera_ray_bundle once, with the renderer's inputs routed into the transfer bake
     (a mode flag on the model, off outside this call: the plain frame render and its captured chunk graphs are untouched)."""
-    from .. import ops
     from ..models.neusky_model import _ChunkRunner
     dtype = _storage_dtype(storage)
     assert not model.training, "call model.eval() first"
@@ -200,12 +199,7 @@ def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Option
         runner = _ChunkRunner(model, chunk, flat, use_graph)  # its own runner: a captured graph of this mode is never cached on the model
         for a in range(0, R, chunk):
             b = min(a + chunk, R)
-            runner._load(flat, a, b)
-            if runner.graph is not None:
-                runner.graph.replay()
-                res = runner.out
-            else:
-                res = model.forward(runner.rb)
+            res = runner.forward_rows(flat, a, b)
             T[a:b].copy_(res["transfer"][:b - a])
             acc[a:b].copy_(res["transfer_acc"][:b - a, 0])
             if exps is not None:
@@ -215,8 +209,7 @@ def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Option
     finally:
         model._transfer_storage = None
         model.end_frame()
-        if runner is not None and runner.graph is not None:
-            ops.retire_graph(runner.graph)
-            runner.graph = None
+        if runner is not None:
+            runner.retire()
     outputs = {k: torch.cat(v).view(*shape, -1) for k, v in outs.items()}
     return RadianceTransfer(T, exps, acc, dirs, flat.directions.reshape(R, 3).contiguous().clone(), shape, outputs, camera_index)
