@@ -725,6 +725,66 @@ int nsky_mc_faces(const float* volume, int64_t nx, int64_t ny, int64_t nz, float
                   const int32_t* base, const uint8_t* edge_mask, int32_t* faces, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh simplification by vertex clustering with quadric-error placement (Lindstrom, "Out-of-core simplification of large polygonal
+ * models", SIGGRAPH 2000).  No counterpart in the reference; neusky_amd/exporter/simplify.py drives these kernels (csrc/simplify.hip).
+ *   inputs:   vertices [V][3] fp32, faces [F][3] int32 (V, F fit int32), optional normals [V][3] fp32 and colours [V][3] uint8; a grid
+ *             origin lo and a cell edge h > 0 (doubles).  All arithmetic is float64 on the fp32 inputs, coordinates relative to lo;
+ *             results are rounded to fp32 once, at the end.
+ *   1 cell:   i_a = clamp(floor((p_a - lo_a) / h), 0, 2^21 - 1) per axis; key = i_x << 42 | i_y << 21 | i_z (int64).  Output vertex j is
+ *             the j-th occupied cell in ascending key order (its rank).
+ *   2 face:   corners a, b, c; m = (b - a) x (c - a); |m| = 0 contributes nothing; else n = m / |m|, w = |m| / 2, d = n.a and the face
+ *             adds A += w n n^T, b += w d n, c += w d^2 to the cell of each of its three corners (three records per face, also when
+ *             corners share a cell).
+ *   3 place:  xbar = mean of the cell's vertices; A = sum_i lambda_i e_i e_i^T; x = xbar + sum_{i: lambda_i > tau lambda_max}
+ *             e_i e_i^T (b - A xbar) / lambda_i with tau = NSKY_MESH_TAU; x = xbar when lambda_max <= 0 or when x leaves the cell's box
+ *             [i h, (i + 1) h] on any axis.
+ *   4 faces:  every index becomes its cell's rank; a face with two equal indices is dropped; survivors are rotated (orientation kept)
+ *             so that the smallest index leads; of identical triples the first in input order stays; survivors keep the input order.
+ *   5 attrib: the cell's normal is the normalised sum of its vertices' normals ((0,0,1) for a zero sum), its colour the mean of its
+ *             vertices' colours rounded to nearest (ties to even).
+ *   6 repeat: no floating-point atomics.  A cell's sums run over records brought together by stable sorts (its vertices in ascending
+ *             vertex index; its face records 3 f + corner in ascending order): lane l of a group of G lanes adds records l, l + G, ...
+ *             in that order, then an xor butterfly adds the G partials.  Two runs on one input agree bit for bit.
+ * nsky_mesh_cell_keys:       keys[V] of all vertices.
+ * nsky_mesh_cluster_count:   *count += the faces whose three corners lie in three different cells of (lo, h); the caller zeroes *count
+ *                            (int64, device memory).  No sort, no scratch; an integer atomic per workgroup.
+ * nsky_mesh_vertex_cells:    vertex_order[V] = the permutation of a stable ascending sort of the keys, rank_sorted[V] = the rank of
+ *                            each sorted entry's cell  ->  vertex_cell[V] (int32), the rank of every vertex's cell.
+ * nsky_mesh_remap_faces:     corner_cells[F][3] = the cell ranks of every face's corners (-1 for an index outside [0, V));
+ *                            face_keys[F] = smallest << 32 | its successor in the rotated face, -1 for a dropped face.
+ * nsky_mesh_cluster_reduce:  cell_start[C + 1] = first sorted vertex of each cell; sorted_corner_cells[3 F] / corner_order[3 F] = the
+ *                            stable ascending sort of corner_cells (flat) and its permutation.  cell_sums[C][NSKY_MESH_CELL_SUMS] =
+ *                            A00 A01 A02 A11 A12 A22, b0 b1 b2, c, sum (p - lo) [3], sum normals [3], sum colours [3], vertex count.
+ *                            normals / colours may be NULL (zero sums).  group: lanes per cell, 8 or 64; 0 picks 64 when a cell holds
+ *                            more than NSKY_MESH_WIDE_GROUP_RECORDS records ((3 F + V) / C) on average, else 8.
+ * nsky_mesh_cluster_solve:   cell_keys[C] = the occupied cells' keys ascending  ->  vertices_out[C][3] and, unless NULL, normals_out[C][3]
+ *                            and colours_out[C][3].  Cyclic Jacobi, a fixed number of sweeps.
+ * nsky_mesh_flag_duplicates: sorted_keys[F] / face_order[F] = the stable ascending sort of face_keys and its permutation  ->  keep[F]
+ *                            (int32 0 / 1): not dropped and not a repetition of an earlier face.
+ * nsky_mesh_compact_faces:   ends[F] = inclusive scan of keep, F_out = ends[F - 1]  ->  faces_out[F_out][3], rotated. */
+#define NSKY_MESH_KEY_BITS 21
+#define NSKY_MESH_TAU 1e-3
+#define NSKY_MESH_CELL_SUMS 20
+#define NSKY_MESH_WIDE_GROUP_RECORDS 1024
+int nsky_mesh_cell_keys(const float* vertices, int64_t V, double lo_x, double lo_y, double lo_z, double h, int64_t* keys,
+                        nsky_stream_t stream);
+int nsky_mesh_cluster_count(const float* vertices, int64_t V, const int32_t* faces, int64_t F, double lo_x, double lo_y, double lo_z,
+                            double h, int64_t* count, nsky_stream_t stream);
+int nsky_mesh_vertex_cells(const int64_t* vertex_order, const int64_t* rank_sorted, int64_t V, int32_t* vertex_cell, nsky_stream_t stream);
+int nsky_mesh_remap_faces(const int32_t* faces, int64_t F, const int32_t* vertex_cell, int64_t V, int32_t* corner_cells,
+                          int64_t* face_keys, nsky_stream_t stream);
+int nsky_mesh_cluster_reduce(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const float* normals,
+                             const uint8_t* colours, double lo_x, double lo_y, double lo_z, double h, const int64_t* vertex_order,
+                             const int64_t* cell_start, int64_t C, const int32_t* sorted_corner_cells, const int64_t* corner_order,
+                             int32_t group, double* cell_sums, nsky_stream_t stream);
+int nsky_mesh_cluster_solve(const double* cell_sums, const int64_t* cell_keys, int64_t C, double lo_x, double lo_y, double lo_z, double h,
+                            float* vertices_out, float* normals_out, uint8_t* colours_out, nsky_stream_t stream);
+int nsky_mesh_flag_duplicates(const int32_t* corner_cells, int64_t F, const int64_t* sorted_keys, const int64_t* face_order, int32_t* keep,
+                              nsky_stream_t stream);
+int nsky_mesh_compact_faces(const int32_t* corner_cells, int64_t F, const int32_t* keep, const int64_t* ends, int64_t F_out,
+                            int32_t* faces_out, nsky_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Relighting under an equirectangular HDR environment map.  No counterpart in the reference (it lights frames with RENI++ latents
  * only); the package's relight module (neusky_amd/relight) drives these kernels.
  *   map:         fp32 [H, W, 3] linear radiance, C-contiguous, row 0 at the top.

@@ -18,7 +18,7 @@ def build_field(state, device):
     return cfg.setup(aabb=aabb, num_images=num_images, spatial_distortion=None).to(device)
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m neusky_amd.exporter", description=__doc__.splitlines()[0])
     ap.add_argument("--checkpoint", required=True, help="a nerfstudio-layout checkpoint (step-*.ckpt) of the neusky method")
     ap.add_argument("--output", required=True, help="the .ply file to write")
@@ -28,10 +28,19 @@ def main(argv=None) -> int:
     ap.add_argument("--isosurface-threshold", type=float, default=0.0)
     ap.add_argument("--no-attributes", action="store_true", help="write positions and faces only (no normals, no colours)")
     ap.add_argument("--device", default="cuda:0")
-    args = ap.parse_args(argv)
+    simplify = ap.add_mutually_exclusive_group()
+    simplify.add_argument("--target-num-faces", type=int, default=None, metavar="N",
+                          help="simplify the mesh by vertex clustering to at most N faces (nerfstudio's --target-num-faces; off by default)")
+    simplify.add_argument("--simplify-cell-size", type=float, default=None, metavar="H",
+                          help="simplify the mesh by vertex clustering on cubic cells of edge H (scene units; off by default)")
+    return ap
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
 
     import torch
-    from . import extract_mesh, load_field_state, write_ply
+    from . import extract_mesh, load_field_state, simplify_mesh, write_ply
 
     t0 = time.perf_counter()
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
@@ -44,13 +53,28 @@ def main(argv=None) -> int:
         print(f"warning: {len(unmapped)} field entries not mapped: {unmapped[:4]}", file=sys.stderr)
     t_load = time.perf_counter() - t0
     timings = {}
+    simplifying = args.target_num_faces is not None or args.simplify_cell_size is not None
+    # with simplification the attributes are evaluated once, on the vertices that are written
     mesh = extract_mesh(field, args.resolution, args.bounding_box_min, args.bounding_box_max, args.isosurface_threshold,
-                        attributes=not args.no_attributes, timings=timings)
+                        attributes=not args.no_attributes and not simplifying, timings=timings)
+    before = ""
+    if simplifying:
+        before = f"V {mesh.vertices.shape[0]} F {mesh.faces.shape[0]} -> "
+        t1 = time.perf_counter()
+        mesh = simplify_mesh(mesh, cell_size=args.simplify_cell_size, target_num_faces=args.target_num_faces)
+        torch.cuda.synchronize()
+        timings["simplify"] = time.perf_counter() - t1
+        if not args.no_attributes:
+            from .mesh import vertex_attributes
+            t1 = time.perf_counter()
+            mesh.normals, mesh.colours = vertex_attributes(field, mesh.vertices)
+            torch.cuda.synchronize()
+            timings["attributes"] = time.perf_counter() - t1
     t1 = time.perf_counter()
     write_ply(args.output, mesh)
     t_write = time.perf_counter() - t1
     parts = " ".join(f"{k} {v:.3f}s" for k, v in timings.items())
-    print(f"{args.output}: V {mesh.vertices.shape[0]} F {mesh.faces.shape[0]} | load {t_load:.3f}s {parts} write {t_write:.3f}s")
+    print(f"{args.output}: {before}V {mesh.vertices.shape[0]} F {mesh.faces.shape[0]} | load {t_load:.3f}s {parts} write {t_write:.3f}s")
     return 0
 
 

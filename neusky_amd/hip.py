@@ -1125,6 +1125,97 @@ def mc_faces(volume, level: float, tile_face_offsets, base, edge_mask, faces):
           "nsky_mc_faces")
 
 
+# ---- mesh simplification by vertex clustering (exporter/simplify.py drives keys -> sort -> reduce -> solve, remap -> sort -> compact)
+MESH_KEY_BITS = 21  # NSKY_MESH_KEY_BITS
+MESH_CELL_SUMS = 20  # NSKY_MESH_CELL_SUMS
+_GRID = (C.c_double, C.c_double, C.c_double, C.c_double)
+_mesh_cell_keys = _sig("nsky_mesh_cell_keys", C.c_void_p, C.c_int64, *_GRID, C.c_void_p, C.c_void_p)
+_mesh_cluster_count = _sig("nsky_mesh_cluster_count", C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, *_GRID, C.c_void_p, C.c_void_p)
+_mesh_vertex_cells = _sig("nsky_mesh_vertex_cells", C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
+_mesh_remap_faces = _sig("nsky_mesh_remap_faces", C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_mesh_cluster_reduce = _sig("nsky_mesh_cluster_reduce", C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, *_GRID,
+                            C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
+_mesh_cluster_solve = _sig("nsky_mesh_cluster_solve", C.c_void_p, C.c_void_p, C.c_int64, *_GRID, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.c_void_p)
+_mesh_flag_duplicates = _sig("nsky_mesh_flag_duplicates", C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_mesh_compact_faces = _sig("nsky_mesh_compact_faces", C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
+
+
+def _mesh_grid(lo, h):
+    return [float(lo[0]), float(lo[1]), float(lo[2]), float(h)]
+
+
+def _typed(t, dtype, *shape):
+    """a contiguous tensor of this dtype and shape (None passes): what the mesh entry points index without a stride argument"""
+    if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+        raise ValueError(f"expected a contiguous {dtype} tensor shaped {shape}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def mesh_cell_keys(vertices, lo, h: float, keys):
+    """vertices: fp32 [V, 3]; keys: int64 [V] <- the cell key of every vertex"""
+    V = vertices.shape[0]
+    check(_mesh_cell_keys(ptr(_typed(vertices, torch.float32, V, 3)), V, *_mesh_grid(lo, h), ptr(_typed(keys, torch.int64, V)), stream_ptr()),
+          "nsky_mesh_cell_keys")
+
+
+def mesh_cluster_count(vertices, faces, lo, h: float, count):
+    """count: int64 [1], zeroed by the caller, += the faces with corners in three different cells"""
+    V, F = vertices.shape[0], faces.shape[0]
+    check(_mesh_cluster_count(ptr(_typed(vertices, torch.float32, V, 3)), V, ptr(_typed(faces, torch.int32, F, 3)), F, *_mesh_grid(lo, h),
+                              ptr(_typed(count, torch.int64, 1)), stream_ptr()), "nsky_mesh_cluster_count")
+
+
+def mesh_vertex_cells(vertex_order, rank_sorted, vertex_cell):
+    """vertex_order, rank_sorted: int64 [V] (stable sort of the keys; rank of each sorted entry's cell); vertex_cell: int32 [V]"""
+    V = vertex_order.shape[0]
+    check(_mesh_vertex_cells(ptr(_typed(vertex_order, torch.int64, V)), ptr(_typed(rank_sorted, torch.int64, V)), V,
+                             ptr(_typed(vertex_cell, torch.int32, V)), stream_ptr()), "nsky_mesh_vertex_cells")
+
+
+def mesh_remap_faces(faces, vertex_cell, corner_cells, face_keys):
+    """faces: int32 [F, 3]; vertex_cell: int32 [V]; corner_cells: int32 [F, 3]; face_keys: int64 [F]"""
+    F, V = faces.shape[0], vertex_cell.shape[0]
+    check(_mesh_remap_faces(ptr(_typed(faces, torch.int32, F, 3)), F, ptr(_typed(vertex_cell, torch.int32, V)), V,
+                            ptr(_typed(corner_cells, torch.int32, F, 3)), ptr(_typed(face_keys, torch.int64, F)), stream_ptr()),
+          "nsky_mesh_remap_faces")
+
+
+def mesh_cluster_reduce(vertices, faces, normals, colours, lo, h: float, vertex_order, cell_start, sorted_corner_cells, corner_order,
+                        cell_sums, group: int = 0):
+    """cell_start: int64 [C + 1]; sorted_corner_cells: int32 [3 F], corner_order: int64 [3 F]; cell_sums: fp64 [C, MESH_CELL_SUMS];
+    normals fp32 [V, 3] / colours uint8 [V, 3] or None; group: lanes per cell (0: chosen from the mean cell size, 8 or 64)"""
+    V, F, Cn = vertices.shape[0], faces.shape[0], cell_sums.shape[0]
+    check(_mesh_cluster_reduce(ptr(_typed(vertices, torch.float32, V, 3)), V, ptr(_typed(faces, torch.int32, F, 3)), F,
+                               ptr(_typed(normals, torch.float32, V, 3)), ptr(_typed(colours, torch.uint8, V, 3)), *_mesh_grid(lo, h),
+                               ptr(_typed(vertex_order, torch.int64, V)), ptr(_typed(cell_start, torch.int64, Cn + 1)), Cn,
+                               ptr(_typed(sorted_corner_cells, torch.int32, 3 * F)), ptr(_typed(corner_order, torch.int64, 3 * F)), group,
+                               ptr(_typed(cell_sums, torch.float64, Cn, MESH_CELL_SUMS)), stream_ptr()), "nsky_mesh_cluster_reduce")
+
+
+def mesh_cluster_solve(cell_sums, cell_keys, lo, h: float, vertices_out, normals_out=None, colours_out=None):
+    """cell_sums: fp64 [C, MESH_CELL_SUMS]; cell_keys: int64 [C] -> vertices_out fp32 [C, 3], normals_out fp32 / colours_out uint8 [C, 3]"""
+    Cn = cell_sums.shape[0]
+    check(_mesh_cluster_solve(ptr(_typed(cell_sums, torch.float64, Cn, MESH_CELL_SUMS)), ptr(_typed(cell_keys, torch.int64, Cn)), Cn,
+                              *_mesh_grid(lo, h), ptr(_typed(vertices_out, torch.float32, Cn, 3)), ptr(_typed(normals_out, torch.float32, Cn, 3)),
+                              ptr(_typed(colours_out, torch.uint8, Cn, 3)), stream_ptr()), "nsky_mesh_cluster_solve")
+
+
+def mesh_flag_duplicates(corner_cells, sorted_keys, face_order, keep):
+    """sorted_keys, face_order: int64 [F] (stable sort of the face keys); keep: int32 [F] <- 1 for a face that stays"""
+    F = corner_cells.shape[0]
+    check(_mesh_flag_duplicates(ptr(_typed(corner_cells, torch.int32, F, 3)), F, ptr(_typed(sorted_keys, torch.int64, F)),
+                                ptr(_typed(face_order, torch.int64, F)), ptr(_typed(keep, torch.int32, F)), stream_ptr()),
+          "nsky_mesh_flag_duplicates")
+
+
+def mesh_compact_faces(corner_cells, keep, ends, faces_out):
+    """ends: int64 [F], the inclusive scan of keep; faces_out: int32 [ends[-1], 3]"""
+    F, Fo = corner_cells.shape[0], faces_out.shape[0]
+    check(_mesh_compact_faces(ptr(_typed(corner_cells, torch.int32, F, 3)), F, ptr(_typed(keep, torch.int32, F)), ptr(_typed(ends, torch.int64, F)),
+                              Fo, ptr(_typed(faces_out, torch.int32, Fo, 3)), stream_ptr()), "nsky_mesh_compact_faces")
+
+
 # ---- environment-map relighting (relight/envmap.py drives label -> stable sort -> reduce, and the lookup)
 ENVMAP_NEUSKY, ENVMAP_BLENDER = 0, 1  # NSKY_ENVMAP_NEUSKY / _BLENDER
 ENVMAP_MAX_DIRECTIONS = 1024  # NSKY_ENVMAP_MAX_DIRECTIONS
