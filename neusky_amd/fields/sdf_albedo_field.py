@@ -7,7 +7,7 @@ weight_v/bias`, `clin{l}.*`, `deviation_network.variance`) so a reference state_
 
 What differs underneath: the tcnn hash grid, the weight-normed Softplus geo MLP (inherited from
 nerfstudio `SDFField`), `torch.autograd.grad(sdf, x, create_graph=True)` and the colour MLP are one
-chain of HIP kernels (`ops.HashEncodeFn` -> `ops.SDFAlbedoFn`) that carries the input Jacobian in
+chain of HIP kernels (`ops.HashEncodeFn` -> `ops.field_apply`) that carries the input Jacobian in
 forward mode, so normals and the eikonal term need no autograd double backward.
 """
 from __future__ import annotations
@@ -230,7 +230,7 @@ class SDFAlbedoField(FieldBase):
         """sdf_albedo_field.py:169-174 -> [P,1]; differentiable w.r.t. the field AND the positions."""
         x = positions.reshape(-1, 3)
         E = self._encode(x, False, x.requires_grad)
-        sdf = ops.SDFValueFn.apply(E, *self._geo_weights(), self.softplus_beta, True)
+        sdf = ops.sdf_value_apply(E, *self._geo_weights(), self.softplus_beta, True)
         return sdf[:, None]
 
     def field_values(self, positions_flat: torch.Tensor, want_albedo: bool = True):
@@ -242,7 +242,7 @@ class SDFAlbedoField(FieldBase):
     def get_colors(self, points: torch.Tensor, geo_features: torch.Tensor) -> torch.Tensor:
         """sdf_albedo_field.py:185-209: albedo of the colour network at `points` given their geometric features:
         [x | PE6(x) | feat] -> Linear+ReLU -> Linear+ReLU... -> sigmoid.  (The training step reaches the same three dense
-        layers fused behind the geo network inside ops.SDFAlbedoFn; this entry point serves callers written against the reference.)"""
+        layers fused behind the geo network inside ops.field_apply's nodes; this entry point serves callers written against the reference.)"""
         from .directional_distance_field import nerf_encoding
         x = points.reshape(-1, 3)
         feat = geo_features.reshape(x.shape[0], -1)

@@ -7,7 +7,7 @@ submodule whose directory is EMPTY in the reference tree and whose pretrained we
     for `num_directions=512` is unknown) with an optional random SO(3) rotation (neusky_config.py:97-101);
   * decoder: FiLM-SIREN over a z-rotation-invariant representation of (latent Z [L,3], direction d):
     cond = per latent row (|Z_xy|, Z_z, Z_xy . d_xy), x = (|d_xy|, d_z) + NeRF(2 freqs); 3 log-HDR outputs;
-    `unnormalise` = exp; per-image `scale` multiplies the HDR value.  Runs on ops.FilmSirenFn (MFMA).
+    `unnormalise` = exp; per-image `scale` multiplies the HDR value.  Runs on ops.film_apply (MFMA).
 """
 from __future__ import annotations
 

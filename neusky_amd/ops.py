@@ -55,12 +55,6 @@ def pad4(n: int) -> int:
     return (n + 3) // 4 * 4
 
 
-def _slab_resident(sk) -> bool:
-    """`sk` (a registered slab parameter) holds its pre-zeroed slab view as .grad and takes gradients in place (from its second pass on)"""
-    g = sk.grad
-    return g is not None and getattr(sk, "_nsky_sunk", False) and g.shape == sk.shape and g.is_contiguous()
-
-
 class _PadFn(torch.autograd.Function):
     """zero padding of a small weight / bias to multiples of 4: one copy into a zero-filled (arena) buffer forward, a VIEW of the
     incoming gradient backward (torch's F.pad costs a pad kernel each way).  When the padded tensor is a slab parameter, the backward
@@ -76,8 +70,8 @@ class _PadFn(torch.autograd.Function):
         else:
             out[:w.shape[0]].copy_(w)
         ctx.orig = tuple(w.shape)
-        ctx.sink = w if getattr(w, "_nsky_grad_sink", False) else None
-        ctx.set_materialize_grads(False)  # (a consumer that deferred its share itself sends nothing: FilmSirenFn)
+        ctx.sink = _sink_param(w)
+        ctx.set_materialize_grads(False)  # (a consumer that deferred its share itself sends nothing: FilmChainFn)
         return out
 
     @staticmethod
@@ -86,20 +80,18 @@ class _PadFn(torch.autograd.Function):
             return None, None, None
         o = ctx.orig
         gs = g[:o[0], :o[1]] if len(o) == 2 else g[:o[0]]
-        sk = ctx.sink
-        if sk is not None:
-            if _slab_resident(sk):
-                _DEFERRED_PADS.append((gs, sk.grad))
-                _queue_end_of_pass()
-                return None, None, None
-            sk._nsky_sunk = True  # (slab-resident from the next zero fill on)
+        view = _sink_grad(ctx.sink, from_first_pass=False)  # (None: slab-resident from the next zero fill on)
+        if view is not None:
+            _DEFERRED_PADS.append((gs, view))
+            _queue_end_of_pass()
+            return None, None, None
         join_weight_gradients()  # (g may be a weight-gradient accumulator of the side stream)
         return gs, None, None
 
 
 def _padded(w, shape, persistent):
     out = _PadFn.apply(w, shape, persistent)
-    out._nsky_pad_of = w if getattr(w, "_nsky_grad_sink", False) else None  # (read by the consumer's forward: FilmSirenFn)
+    out._nsky_pad_of = _sink_param(w)  # (read by the consumer's forward: FilmChainFn)
     return out
 
 
@@ -149,10 +141,8 @@ def grad_weight(dZ, X, M, n_out, k_in, like, bias_like=None, bias_rows=None, acc
     if acc is not None:
         dW, db = acc
     else:
-        if bias_like is not None:  # one zero-filled slab for both accumulators (16-byte aligned views)
-            nw = (like.numel() + 3) // 4 * 4
-            flat = zeros(nw + bias_like.numel(), device=like.device)
-            dW, db = flat[:like.numel()].view_as(like), flat[nw:].view_as(bias_like)
+        if bias_like is not None:
+            (dW, db), _ = _carve_grads((like, bias_like), (None, None))
         else:
             dW, db = zeros_like(like), None
     if (_POLICY == "splith" and a_native_nt == 0 and b_native_nt == 0 and a_scale_max is None and M >= WGRAD_STREAM_MIN_ROWS
@@ -217,7 +207,66 @@ def _grad_sink_of(t):
     return sk
 
 
-_PASS = {"queued": False}  # the end-of-pass callback of the running backward pass has been queued
+def _sink_param(t, by="object"):
+    """the slab parameter behind `t`, or None.  by: "object" -- `t` itself; "pad" -- the parameter `t` is a padding copy of (_padded);
+    "base" -- `t` itself, or the flat parameter `t` is the [n, 2] view of (tcnn's `params` layout: its gradient view is the same memory);
+    "address" -- the registered parameter at t's address with t's shape (a saved tensor: attributes need not survive)"""
+    if t is None:
+        return None
+    if by == "pad":
+        return getattr(t, "_nsky_pad_of", None)
+    if by == "address":
+        return _grad_sink_of(t)
+    if getattr(t, "_nsky_grad_sink", False):
+        return t
+    base = t._base if by == "base" else None
+    if base is not None and getattr(base, "_nsky_grad_sink", False) and base.numel() == t.numel() \
+            and base.is_contiguous() and t.is_contiguous() and base.data_ptr() == t.data_ptr():
+        return base
+    return None
+
+
+def _sink_grads(tensors, *, from_first_pass, by="object", all_or_none=False, mark=True, bias=False):
+    """THE rule of where a parameter's gradient goes (DESIGN section 4 lists the callers side by side) -> per tensor the slab view its
+    gradient accumulates into IN PLACE (the node then returns None for it), or None (the node allocates an accumulator and hands it to
+    autograd).  A view is usable when it is there, contiguous and of the parameter's shape -- and, unless from_first_pass, when the
+    parameter is already marked `_nsky_sunk`: in a pipeline's first pass every parameter still holds its view, and a node whose
+    accumulator other nodes or the side stream share must not take it then.  all_or_none: one kernel writes all the gradients.
+    Marks `_nsky_sunk` (GradientSlab.zero_all then keeps .grad as the slab view) on a parameter whose view is taken, whose .grad is None
+    (first used after step 0: it sinks from the next zero fill on) and, for the callers that wait for the mark, on every one they decline;
+    mark=False only asks.  bias: the views taken are recorded for first_only / join_unless_sunk."""
+    sinks = [_sink_param(t, by) for t in tensors]
+    views = [None if sk is None or sk.grad is None or not sk.grad.is_contiguous() or sk.grad.shape != sk.shape
+             or not (from_first_pass or getattr(sk, "_nsky_sunk", False)) else sk.grad for sk in sinks]
+    if all_or_none and any(v is None for v in views):
+        views = [None] * len(views)
+    for sk, v in zip(sinks, views):
+        if mark and sk is not None and (v is not None or sk.grad is None or not from_first_pass):
+            sk._nsky_sunk = True
+        if bias and v is not None:
+            _SUNK_BIAS.add(v.data_ptr())
+    return views
+
+
+def _sink_grad(t, **how):
+    return _sink_grads((t,), **how)[0]
+
+
+def _carve_grads(tensors, sinks):
+    """-> (grads, sunk): the accumulator of every tensor -- its sink view where it has one, otherwise a 16-byte aligned view of ONE
+    zero-filled (arena) buffer -- and which of them are sink views (the node returns None for those)"""
+    sunk = [v is not None for v in sinks]
+    sizes = [0 if s else (t.numel() + 3) // 4 * 4 for t, s in zip(tensors, sunk)]
+    flat = zeros(max(sum(sizes), 4), device=tensors[0].device)
+    grads, off = list(sinks), 0
+    for i, t in enumerate(tensors):
+        if not sunk[i]:
+            grads[i] = flat[off:off + t.numel()].view_as(t)
+            off += sizes[i]
+    return grads, sunk
+
+
+_PASS ={"queued": False}  # the end-of-pass callback of the running backward pass has been queued
 
 
 def _queue_end_of_pass() -> None:
@@ -267,19 +316,10 @@ def shared_grad(like, bias_like):
     if hit is not None:
         return hit[1], hit[2], False
     _queue_end_of_pass()  # forget the shared accumulators when the pass ends
-    db = None
-    sk = _grad_sink_of(bias_like) if bias_like is not None else None
-    if sk is not None:
-        if sk.grad is not None and sk.grad.shape == bias_like.shape and sk.grad.is_contiguous() and getattr(sk, "_nsky_sunk", False):
-            db = sk.grad  # the slab view, zeroed by zero_grad_all
-            _SUNK_BIAS.add(db.data_ptr())
-        else:
-            sk._nsky_sunk = True  # sinks from the next zero_grad_all on (which then keeps .grad as the slab view)
-    nw = (like.numel() + 3) // 4 * 4
-    flat = zeros(nw + (bias_like.numel() if (bias_like is not None and db is None) else 0), device=like.device)
-    dW = flat[:like.numel()].view_as(like)
-    if db is None and bias_like is not None:
-        db = flat[nw:].view_as(bias_like)
+    if bias_like is None:
+        (dW,), db = _carve_grads((like,), (None,))[0], None
+    else:  # (the bias: its slab view, zeroed by zero_grad_all, once the parameter is marked -- which this call does)
+        (dW, db), _ = _carve_grads((like, bias_like), (None, _sink_grad(bias_like, by="address", from_first_pass=False, bias=True)))
     _SHARED_GRADS[key] = (like, dW, db)
     return dW, db, True
 
@@ -641,12 +681,7 @@ class HashEncodeFn(torch.autograd.Function):
         ctx.cfg = (geom, mode, include_x, pe_freqs, pe_max_exp, tangents, need_dx, P, ldy)
         # Parameters re-homed into an optimizer slab (engine._Group) own a pre-zeroed gradient view: the backward scatters
         # straight into it instead of zero-filling a 49 MB table of its own and adding that to .grad afterwards
-        sink = table if getattr(table, "_nsky_grad_sink", False) else None
-        base = table._base
-        if sink is None and base is not None and getattr(base, "_nsky_grad_sink", False) and base.numel() == table.numel() \
-                and base.is_contiguous() and table.is_contiguous() and base.data_ptr() == table.data_ptr():
-            sink = base  # the [n, 2] view of a flat parameter (tcnn's `params` layout): its gradient view is the same memory
-        ctx.sink = sink
+        ctx.sink = _sink_param(table, "base")
         return out
 
     @staticmethod
@@ -660,13 +695,11 @@ class HashEncodeFn(torch.autograd.Function):
             hip.encode_bwd(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, d_out.contiguous()[:P], None, None, dx)
             return dx, None, None, None, None, None, None, None, None
         d_out = d_out.contiguous()
-        sink = ctx.sink
-        accumulate = sink is not None and sink.grad is not None and sink.grad.is_contiguous() and sink.grad.numel() == table.numel()
-        if accumulate or (sink is not None and sink.grad is None):
-            # engine.Optimizers.zero_grad_all: this parameter's .grad stays its slab view.  (A parameter first used after step 0 -- a
-            # loss enabled later -- arrives here with .grad dropped: it takes the slow path once and sinks from the next step on.)
-            sink._nsky_sunk = True
-        dtable = sink.grad.view_as(table) if accumulate else zeros_like(table)
+        # engine.Optimizers.zero_grad_all: a sunk parameter's .grad stays its slab view.  (A parameter first used after step 0 -- a
+        # loss enabled later -- arrives here with .grad dropped: it takes the slow path once and sinks from the next step on.)
+        view = _sink_grad(ctx.sink, from_first_pass=True)
+        accumulate = view is not None
+        dtable = view.view_as(table) if accumulate else zeros_like(table)
         dx = torch.empty(P, 3, device=x.device) if need_dx else None
         dT = d_out[P:].view(3, P, ldy) if tangents else None
         hip.encode_bwd(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, d_out[:P], dT, dtable, dx)
@@ -714,6 +747,44 @@ class DenseFn(torch.autograd.Function):
 
 
 # =============================================================================================
+# the three networks with two kernel sets: ONE autograd node per kernel set -- the fused chain kernels, and the per-layer kernels
+# (the exact-fp32 set behind set_precision_policy("f32"), and the shapes the chains do not take) -- chosen per call, here
+# =============================================================================================
+def _film_fused_ok(x, cond, n_map, n_film, wb) -> bool:
+    mw, _, _, _, fw, _, ow, _, _ = _film_unpack(wb, n_map, n_film)
+    return (FWD_PRECISION == hip.PREC_F16X2 and ld(x) <= 16
+            and hip.film_supported(fw[0].shape[0], mw[0].shape[0], n_map, n_film, mw[0].shape[1], fw[0].shape[1], ow.shape[0])
+            and ld(x) >= fw[0].shape[1] and ld(cond) >= mw[0].shape[1])
+
+
+def field_fused_ok(ET, W0, W1, W2, Wc0, Wc1) -> bool:
+    return (FWD_PRECISION == hip.PREC_F16X2 and ET.shape[0] >= 4 and ld(ET) == W0.shape[1]
+            and hip.field_supported(W0.shape[1], W0.shape[0], W2.shape[0] - 4, Wc1.shape[0], Wc0.shape[1]))
+
+
+def sdf_fused_ok(E, W0) -> bool:
+    Hd, Kin = W0.shape
+    return FWD_PRECISION == hip.PREC_F16X2 and hip.sdf_supported(Kin, Hd) and ld(E) >= Kin and ld(E) % 4 == 0
+
+
+def film_apply(x, cond, n_map, n_film, train_weights, need_dcond, *wb):
+    """a FiLM-SIREN (FilmChainFn's arguments): the fused chain kernels where they apply, otherwise the per-layer path"""
+    node = FilmChainFn if _film_fused_ok(x, cond, n_map, n_film, wb) else FilmLayersFn
+    return node.apply(x, cond, n_map, n_film, train_weights, need_dcond, *wb)
+
+
+def field_apply(ET, *args):
+    """the field on stacked encode rows: the fused chain kernels where they apply, otherwise the per-layer path"""
+    W0, _, W1, _, W2, _, Wc0, _, Wc1 = args[:9]
+    return (FieldChainFn if field_fused_ok(ET, W0, W1, W2, Wc0, Wc1) else SDFAlbedoFn).apply(ET, *args)
+
+
+def sdf_value_apply(E, W0, *args):
+    """the sdf value chain on encode rows (SdfChainFn's arguments): the fused value chain where it applies, otherwise the per-layer path"""
+    return (SdfChainFn if sdf_fused_ok(E, W0) else SdfLayersFn).apply(E, W0, *args)
+
+
+# =============================================================================================
 # FiLM-SIREN (DDF network, RENI-shaped illumination decoder)
 # =============================================================================================
 _FILM_STREAMS: dict = {}
@@ -725,18 +796,23 @@ def forget_film_streams(wb) -> None:
         del _FILM_STREAMS[key]
 
 
-def _film_fused_ok(M, H, Hm, n_map, n_film, mw, fw, ow, x, cond) -> bool:
-    return (FWD_PRECISION == hip.PREC_F16X2 and ld(x) <= 16
-            and hip.film_supported(H, Hm, n_map, n_film, mw[0].shape[1], fw[0].shape[1], ow.shape[0])
-            and ld(x) >= fw[0].shape[1] and ld(cond) >= mw[0].shape[1])
+def _film_unpack(wb, n_map, n_film):
+    mw = [wb[2 * i] for i in range(n_map)]
+    mb = [wb[2 * i + 1] for i in range(n_map)]
+    mwo, mbo = wb[2 * n_map], wb[2 * n_map + 1]
+    o = 2 * n_map + 2
+    fw = [wb[o + 2 * i] for i in range(n_film)]
+    fb = [wb[o + 2 * i + 1] for i in range(n_film)]
+    return mw, mb, mwo, mbo, fw, fb, wb[o + 2 * n_film], wb[o + 2 * n_film + 1], o
 
 
-def _film_stream(wb, n_map, n_film, mw, mb, mwo, mbo, fw, fb, ow, ob, direction=0):
+def _film_stream(wb, n_map, n_film, direction=0):
     """per-step cache of one packed weight stream of a network (direction 0 forward, 1 FiLM backward, 2 mapping backward;
     dropped by begin_step when any of its weights is trainable: the optimiser changed them) -> (descriptor, stream bytes, bias / scale table)"""
     key = (wb[0].data_ptr(), wb[0]._version, wb[-2].data_ptr(), n_map, n_film, direction)
 
     def pack():
+        mw, mb, mwo, mbo, fw, fb, ow, ob, _ = _film_unpack(wb, n_map, n_film)
         net = hip.film_net(mw[0].shape[1], fw[0].shape[1], ow.shape[0], mw, mb, mwo, mbo, fw, fb, ow, ob)
         nbytes, _ = hip.film_stream_layout(net, direction)
         # zero-filled once: the pad slabs of partial groups are streamed through LDS but never multiplied
@@ -746,52 +822,137 @@ def _film_stream(wb, n_map, n_film, mw, mb, mwo, mbo, fw, fb, ow, ob, direction=
     return _prepared(_FILM_STREAMS, key, list(wb), pack)
 
 
-class FilmSirenFn(torch.autograd.Function):
-    """neusky/utils/siren.py:108-208 as a chain of fp32-MFMA layers with fused epilogues.
+class FilmChainFn(torch.autograd.Function):
+    """neusky/utils/siren.py:108-208 on the fused chain kernels (csrc/film_chain.hip): one launch for the whole network forward, two
+    backward plus the weight gradients.
 
-    args: x [M, pad4(in)], cond [M, pad4(cond)], n_map, n_film, train_weights, then padded tensors
+    args: x [M, pad4(in)], cond [M, pad4(cond)], n_map, n_film, train_weights, need_dcond, then padded tensors
           map_w0,map_b0,...,map_wo,map_bo, film_w0,film_b0,...,out_w,out_b.
     Returns the raw head output [M, pad4(out)] (activation applied by the caller)."""
 
     @staticmethod
-    def _unpack(wb, n_map, n_film):
-        mw = [wb[2 * i] for i in range(n_map)]
-        mb = [wb[2 * i + 1] for i in range(n_map)]
-        mwo, mbo = wb[2 * n_map], wb[2 * n_map + 1]
-        o = 2 * n_map + 2
-        fw = [wb[o + 2 * i] for i in range(n_film)]
-        fb = [wb[o + 2 * i + 1] for i in range(n_film)]
-        return mw, mb, mwo, mbo, fw, fb, wb[o + 2 * n_film], wb[o + 2 * n_film + 1], o
+    def forward(ctx, x, cond, n_map, n_film, train_weights, need_dcond, *wb):
+        M = x.shape[0]
+        dev = x.device
+        mw, _, _, _, fw, _, ow, _, _ = _film_unpack(wb, n_map, n_film)
+        H, Hm, n_out_p = fw[0].shape[0], mw[0].shape[0], ow.shape[0]
+        # nothing has to survive the call when no input needs a gradient (render / eval): two ping-pong activation
+        # buffers, no pre-activation side output
+        save = any(ctx.needs_input_grad)
+        # the [M, 2 n_film H] frequency / phase matrix is never formed and no activation makes a round trip through HBM between
+        # layers; kept for the backward: mapping activations, FiLM pre-activations and outputs
+        net, stream, scales = _film_stream(wb, n_map, n_film)
+        Mp = hip.film_rows(M)  # saved activations are tile-native [ceil32(M), H] matrices (include/neusky_hip.h)
+        ys = [torch.empty(Mp, H, device=dev) for _ in range(n_film if save else min(2, n_film))]
+        hs = [torch.empty(Mp, Hm, device=dev) for _ in range(n_map)] if save else None
+        zs = [torch.empty(Mp, H, device=dev) for _ in range(n_film)] if save else None
+        res = torch.empty(M, n_out_p, device=dev)
+        hip.film_chain_fwd(net, stream, scales, cond, x, M, hs, zs, ys if save else [ys[i % len(ys)] for i in range(n_film)], res)
+        if not save:
+            return res
+        ctx.save_for_backward(x, cond, *hs, *ys, *zs, *wb)
+        ctx.cfg = (n_map, n_film, train_weights, need_dcond, M, H, Hm, x.requires_grad)
+        # weights that ARE optimizer-slab parameters (no padding copy in between) take their gradient in place
+        ctx.sinks = [_sink_param(w) for w in wb]
+        ctx.pad_sinks = [_sink_param(w, "pad") for w in wb]  # slab parameters behind a padding copy (_PadFn defers)
+        return res
+
+    @staticmethod
+    def backward(ctx, d_res):
+        """two chain kernels (csrc/film_chain.hip) produce every pre-activation gradient as a tile-native matrix (F / phase are
+        re-formed in registers: no [M, 2 n_film H] matrix is read or recomputed through HBM) and d_cond; the parameter gradients
+        are weight-gradient GEMMs straight over those matrices."""
+        n_map, n_film, train_w, need_dcond, M, H, Hm, need_dx = ctx.cfg
+        train_w = train_w and any(ctx.needs_input_grad[6:])  # (frozen weights -- the eval-latent fit -- take no gradient)
+        sv = ctx.saved_tensors
+        x, cond = sv[0], sv[1]
+        hs = list(sv[2:2 + n_map])
+        ys = list(sv[2 + n_map:2 + n_map + n_film])
+        zs = list(sv[2 + n_map + n_film:2 + n_map + 2 * n_film])
+        wb = sv[2 + n_map + 2 * n_film:]
+        mw, mb, mwo, mbo, fw, fb, ow, ob, o = _film_unpack(wb, n_map, n_film)
+        dev = x.device
+        Mp = hip.film_rows(M)
+        d_res = d_res.contiguous()
+        net1, s1, t1 = _film_stream(wb, n_map, n_film, 1)
+        net2, s2, t2 = _film_stream(wb, n_map, n_film, 2)
+        dzs = [torch.empty(Mp, H, device=dev) for _ in range(n_film)]
+        dfp = torch.empty(Mp, 2 * n_film * H, device=dev)
+        rowmax = torch.empty(Mp, device=dev)
+        gmax = zeros(n_film + 1 + n_map, device=dev)
+        d_x = torch.empty(M, ld(x), device=dev) if need_dx else None  # the DDF's multi-view rays (ddf_model.py:297-322)
+        hip.film_chain_bwd_film(net1, s1, t1, M, d_res, hs[-1], zs, dzs, dfp, rowmax, gmax[:n_film + 1], d_x)
+        d_cond = torch.empty(M, ld(cond), device=dev) if need_dcond else None
+        want_map = need_dcond or train_w
+        dpres = [torch.empty(Mp, Hm, device=dev) for _ in range(n_map)] if want_map else None
+        if want_map:
+            hip.film_chain_bwd_map(net2, s2, t2, M, dfp, rowmax, hs, dpres, d_cond, gmax[n_film + 1:])
+        if not train_w:
+            return (d_x, d_cond, None, None, None, None, *[None] * len(wb))
+        grads, sunk = _carve_grads(wb, _sink_grads(ctx.sinks, from_first_pass=True))
+        nt, ntm = H // 32, Hm // 32
+        # layers whose two operands are tile-native (FiLM layers 1.., the mapping head, mapping layers 1..): ONE launch of the
+        # streaming weight-gradient kernel for all of them; the rest (row-major d_res / x / cond operands) per layer
+        native = []
+
+        def wgrad(dZ, X, n_out, k_in, like, bias_like, iw, a_nt, b_nt, smax, x_scale=64.0):
+            # x_scale: power of two applied to X before its fp16 split: 2^6 for sine outputs (|y| <= 1), 2^3 for the mapping
+            # network's LeakyReLU activations (unbounded in principle: |h| up to 8000 stays inside fp16's range)
+            if a_nt > 0 and b_nt > 0 and a_nt % 4 == 0 and b_nt % 4 == 0 and smax is not None:
+                native.append(hip.wgrad_problem(dZ, a_nt, X, b_nt, M, grads[iw], grads[iw + 1], smax, x_scale))
+            elif a_nt == 0 and b_nt > 0 and n_out <= 4 and dZ.dim() == 2 and dZ.shape[1] == 4 and dZ.is_contiguous():
+                # the narrow head (1 or 3 outputs, padded to 4): a column sum of the tile-native activation under the rows' weights,
+                # exact fp32 on the vector units in one pass (the exact-fp32 GEMM spent 0.22 ms on this [M, 4]^T [M, H] product)
+                hip.native_weighted_colsum(X, b_nt, M, grads[iw], grads[iw + 1], w4=dZ, n_out=n_out)
+            else:
+                grad_weight(dZ, X, M, n_out, k_in, like, bias_like, acc=(grads[iw], grads[iw + 1]), a_native_nt=a_nt, b_native_nt=b_nt,
+                            a_scale_max=smax)
+
+        def launch():
+            wgrad(d_res, ys[-1], ow.shape[0], H, ow, ob, o + 2 * n_film, 0, nt, None)
+            for i in range(n_film - 1, 0, -1):
+                wgrad(dzs[i], ys[i - 1], H, H, fw[i], fb[i], o + 2 * i, nt, nt, gmax[i:i + 1])
+            wgrad(dzs[0], x, H, fw[0].shape[1], fw[0], fb[0], o, nt, 0, None)
+            wgrad(dfp, hs[-1], 2 * n_film * H, Hm, mwo, mbo, 2 * n_map, 2 * n_film * nt, ntm, gmax[n_film:n_film + 1], 8.0)
+            for l in range(n_map - 1, 0, -1):
+                wgrad(dpres[l], hs[l - 1], Hm, Hm, mw[l], mb[l], 2 * l, ntm, ntm, gmax[n_film + 1 + l:n_film + 2 + l], 8.0)
+            k0 = mw[0].shape[1]
+            wgrad(dpres[0], cond, Hm, k0, mw[0], mb[0], 0, ntm, 0, gmax[n_film + 1:n_film + 2] if k0 > 64 else None)
+            if native:
+                hip.wgrad_native_batch(native, M)
+
+        # every gradient lands in the optimizer slab -- directly, or (a padded copy of a slab parameter) as an add of this node's
+        # accumulator deferred to the end of the pass -- so nothing the backward pass runs before its end depends on the launches: they
+        # go to the side stream.  (The deferred share is NOT handed to autograd: the padding node may have a second producer -- the
+        # DDF-fit rows are a node of their own -- and autograd would sum the two accumulators while this one is still being written.)
+        pads = _sink_grads(ctx.pad_sinks, from_first_pass=False, mark=False)  # (what _PadFn.backward would defer into: it does the marking)
+        if all(sunk[i] or pads[i] is not None for i in range(len(wb))):
+            async_weight_gradients(launch, [d_res, x, cond, dfp, gmax, *ys, *hs, *dzs, *(dpres or [])])
+            for i, view in enumerate(pads):
+                if not sunk[i]:
+                    shp = view.shape
+                    _DEFERRED_PADS.append((grads[i][:shp[0], :shp[1]] if len(shp) == 2 else grads[i][:shp[0]], view))
+                    sunk[i] = True
+            _queue_end_of_pass()
+        else:
+            launch()
+        return (d_x, d_cond, None, None, None, None, *[None if sunk[i] else g for i, g in enumerate(grads)])
+
+
+class FilmLayersFn(torch.autograd.Function):
+    """FilmChainFn's contract (same arguments, same output) as a chain of per-layer dense kernels with fused epilogues: the exact-fp32
+    kernel set of set_precision_policy("f32"), and the shapes the chain kernels do not take."""
 
     @staticmethod
     def forward(ctx, x, cond, n_map, n_film, train_weights, need_dcond, *wb):
         M = x.shape[0]
-        ctx.need_dx = x.requires_grad
         dev = x.device
-        mw, mb, mwo, mbo, fw, fb, ow, ob, o = FilmSirenFn._unpack(wb, n_map, n_film)
+        mw, mb, mwo, mbo, fw, fb, ow, ob, _ = _film_unpack(wb, n_map, n_film)
         H, Hm = fw[0].shape[0], mw[0].shape[0]
         n_out_p = ow.shape[0]
         # nothing has to survive the call when no input needs a gradient (render / eval): two ping-pong activation
         # buffers, no pre-activation side output
         save = any(ctx.needs_input_grad)
-        if _film_fused_ok(M, H, Hm, n_map, n_film, mw, fw, ow, x, cond):
-            # one launch for the whole network (csrc/film_chain.hip): the [M, 2 n_film H] frequency / phase matrix is never
-            # formed and no activation makes a round trip through HBM between layers; kept for the backward: mapping
-            # activations, FiLM pre-activations and outputs
-            net, stream, scales = _film_stream(wb, n_map, n_film, mw, mb, mwo, mbo, fw, fb, ow, ob)
-            Mp = hip.film_rows(M)  # saved activations are tile-native [ceil32(M), H] matrices (include/neusky_hip.h)
-            ys = [torch.empty(Mp, H, device=dev) for _ in range(n_film if save else min(2, n_film))]
-            hs = [torch.empty(Mp, Hm, device=dev) for _ in range(n_map)] if save else None
-            zs = [torch.empty(Mp, H, device=dev) for _ in range(n_film)] if save else None
-            res = torch.empty(M, n_out_p, device=dev)
-            hip.film_chain_fwd(net, stream, scales, cond, x, M, hs, zs, ys if save else [ys[i % len(ys)] for i in range(n_film)], res)
-            if not save:
-                return res
-            ctx.save_for_backward(x, cond, x.new_empty(0), *hs, *ys, *zs, *wb)
-            ctx.cfg = (n_map, n_film, train_weights, need_dcond, M, H, Hm)
-            ctx.sinks = [w if getattr(w, "_nsky_grad_sink", False) else None for w in wb]
-            ctx.pad_sinks = [getattr(w, "_nsky_pad_of", None) for w in wb]  # slab parameters behind a padding copy (_PadFn defers)
-            return res
         if save:
             hs = [torch.empty(M, Hm, device=dev) for _ in range(n_map)]
             ys = [torch.empty(M, H, device=dev) for _ in range(n_film)]
@@ -803,122 +964,30 @@ class FilmSirenFn(torch.autograd.Function):
             zs = [None] * n_film
         FP = torch.empty(M, 2 * n_film * H, device=dev)
         res = zeros(M, n_out_p, device=dev)
-        for r0, r1 in [(0, M)]:
-            m = r1 - r0
-            # mapping network: (Linear, LeakyReLU(0.2)) * n  -> Linear to 2*n_film*H  (siren.py:114-119)
-            h = cond[r0:r1]
-            for i in range(n_map):
-                fgemm(h, mw[i], hs[i][r0:r1], m, Hm, mw[i].shape[1], bias=mb[i], epi=hip.EPI_LEAKY, p0=0.2)
-                h = hs[i][r0:r1]
-            fp = FP[r0:r1]
-            fgemm(h, mwo, fp, m, 2 * n_film * H, Hm, bias=mbo)
-            # FiLM layers: sin((15 F + 30) (W y + b) + P)  (siren.py:141-144, :200)
-            y = x[r0:r1]
-            for i in range(n_film):
-                fgemm(y, fw[i], ys[i][r0:r1], m, H, fw[i].shape[1], bias=fb[i], epi=hip.EPI_FILM, p0=15.0, p1=30.0,
-                      aux0=fp[:, i * H:(i + 1) * H], aux1=fp[:, (n_film + i) * H:(n_film + i + 1) * H],
-                      out1=zs[i][r0:r1] if save else None)
-                y = ys[i][r0:r1]
-            fgemm(y, ow, res[r0:r1], m, n_out_p, H, bias=ob)
+        # mapping network: (Linear, LeakyReLU(0.2)) * n  -> Linear to 2*n_film*H  (siren.py:114-119)
+        h = cond
+        for i in range(n_map):
+            fgemm(h, mw[i], hs[i], M, Hm, mw[i].shape[1], bias=mb[i], epi=hip.EPI_LEAKY, p0=0.2)
+            h = hs[i]
+        fgemm(h, mwo, FP, M, 2 * n_film * H, Hm, bias=mbo)
+        # FiLM layers: sin((15 F + 30) (W y + b) + P)  (siren.py:141-144, :200)
+        y = x
+        for i in range(n_film):
+            fgemm(y, fw[i], ys[i], M, H, fw[i].shape[1], bias=fb[i], epi=hip.EPI_FILM, p0=15.0, p1=30.0,
+                  aux0=FP[:, i * H:(i + 1) * H], aux1=FP[:, (n_film + i) * H:(n_film + i + 1) * H], out1=zs[i])
+            y = ys[i]
+        fgemm(y, ow, res, M, n_out_p, H, bias=ob)
         if not save:
             return res
         ctx.save_for_backward(x, cond, FP, *hs, *ys, *zs, *wb)
-        ctx.cfg = (n_map, n_film, train_weights, need_dcond, M, H, Hm)
+        ctx.cfg = (n_map, n_film, train_weights, need_dcond, M, H, Hm, x.requires_grad)
         # weights that ARE optimizer-slab parameters (no padding copy in between) take their gradient in place
-        ctx.sinks = [w if getattr(w, "_nsky_grad_sink", False) else None for w in wb]
+        ctx.sinks = [_sink_param(w) for w in wb]
         return res
 
     @staticmethod
-    def _backward_fused(ctx, d_res, x, cond, hs, ys, zs, wb, mw, mb, mwo, mbo, fw, fb, ow, ob, o):
-        """backward of the fused forward: two chain kernels (csrc/film_chain.hip) produce every pre-activation gradient as a
-        tile-native matrix (F / phase are re-formed in registers: no [M, 2 n_film H] matrix is read or recomputed through HBM)
-        and d_cond; the parameter gradients are weight-gradient GEMMs straight over those matrices."""
-        n_map, n_film, train_w, need_dcond, M, H, Hm = ctx.cfg
-        train_w = train_w and any(ctx.needs_input_grad[6:])  # (frozen weights -- the eval-latent fit -- take no gradient)
-        dev = x.device
-        Mp = hip.film_rows(M)
-        d_res = d_res.contiguous()
-        net1, s1, t1 = _film_stream(wb, n_map, n_film, mw, mb, mwo, mbo, fw, fb, ow, ob, 1)
-        net2, s2, t2 = _film_stream(wb, n_map, n_film, mw, mb, mwo, mbo, fw, fb, ow, ob, 2)
-        dzs = [torch.empty(Mp, H, device=dev) for _ in range(n_film)]
-        dfp = torch.empty(Mp, 2 * n_film * H, device=dev)
-        rowmax = torch.empty(Mp, device=dev)
-        gmax = zeros(n_film + 1 + n_map, device=dev)
-        d_x = torch.empty(M, ld(x), device=dev) if ctx.need_dx else None  # the DDF's multi-view rays (ddf_model.py:297-322)
-        hip.film_chain_bwd_film(net1, s1, t1, M, d_res, hs[-1], zs, dzs, dfp, rowmax, gmax[:n_film + 1], d_x)
-        d_cond = torch.empty(M, ld(cond), device=dev) if need_dcond else None
-        want_map = need_dcond or train_w
-        dpres = [torch.empty(Mp, Hm, device=dev) for _ in range(n_map)] if want_map else None
-        if want_map:
-            hip.film_chain_bwd_map(net2, s2, t2, M, dfp, rowmax, hs, dpres, d_cond, gmax[n_film + 1:])
-        grads: List[Optional[torch.Tensor]] = [None] * len(wb)
-        sunk = [False] * len(wb)
-        if train_w:
-            for idx, t in enumerate(wb):
-                sk = ctx.sinks[idx]
-                if sk is not None and sk.grad is not None and sk.grad.shape == t.shape and sk.grad.is_contiguous():
-                    grads[idx], sunk[idx] = sk.grad, True
-                    sk._nsky_sunk = True
-                elif sk is not None and sk.grad is None:
-                    sk._nsky_sunk = True  # (first used after step 0: sinks from the next zero_grad_all on)
-            sizes = [0 if sunk[idx] else (t.numel() + 3) // 4 * 4 for idx, t in enumerate(wb)]
-            flat = zeros(max(sum(sizes), 4), device=dev)
-            off = 0
-            for idx, t in enumerate(wb):
-                if not sunk[idx]:
-                    grads[idx] = flat[off:off + t.numel()].view_as(t)
-                    off += sizes[idx]
-            acc = lambda iw: (grads[iw], grads[iw + 1])  # noqa: E731
-            nt, ntm = H // 32, Hm // 32
-            # layers whose two operands are tile-native (FiLM layers 1.., the mapping head, mapping layers 1..): ONE launch of the
-            # streaming weight-gradient kernel for all of them; the rest (row-major d_res / x / cond operands) per layer
-            native = []
-
-            def wgrad(dZ, X, n_out, k_in, like, bias_like, iw, a_nt, b_nt, smax, x_scale=64.0):
-                # x_scale: power of two applied to X before its fp16 split: 2^6 for sine outputs (|y| <= 1), 2^3 for the mapping
-                # network's LeakyReLU activations (unbounded in principle: |h| up to 8000 stays inside fp16's range)
-                if a_nt > 0 and b_nt > 0 and a_nt % 4 == 0 and b_nt % 4 == 0 and smax is not None:
-                    native.append(hip.wgrad_problem(dZ, a_nt, X, b_nt, M, grads[iw], grads[iw + 1], smax, x_scale))
-                elif a_nt == 0 and b_nt > 0 and n_out <= 4 and dZ.dim() == 2 and dZ.shape[1] == 4 and dZ.is_contiguous():
-                    # the narrow head (1 or 3 outputs, padded to 4): a column sum of the tile-native activation under the rows' weights,
-                    # exact fp32 on the vector units in one pass (the exact-fp32 GEMM spent 0.22 ms on this [M, 4]^T [M, H] product)
-                    hip.native_weighted_colsum(X, b_nt, M, grads[iw], grads[iw + 1], w4=dZ, n_out=n_out)
-                else:
-                    grad_weight(dZ, X, M, n_out, k_in, like, bias_like, acc=acc(iw), a_native_nt=a_nt, b_native_nt=b_nt, a_scale_max=smax)
-
-            def launch():
-                wgrad(d_res, ys[-1], ow.shape[0], H, ow, ob, o + 2 * n_film, 0, nt, None)
-                for i in range(n_film - 1, 0, -1):
-                    wgrad(dzs[i], ys[i - 1], H, H, fw[i], fb[i], o + 2 * i, nt, nt, gmax[i:i + 1])
-                wgrad(dzs[0], x, H, fw[0].shape[1], fw[0], fb[0], o, nt, 0, None)
-                wgrad(dfp, hs[-1], 2 * n_film * H, Hm, mwo, mbo, 2 * n_map, 2 * n_film * nt, ntm, gmax[n_film:n_film + 1], 8.0)
-                for l in range(n_map - 1, 0, -1):
-                    wgrad(dpres[l], hs[l - 1], Hm, Hm, mw[l], mb[l], 2 * l, ntm, ntm, gmax[n_film + 1 + l:n_film + 2 + l], 8.0)
-                k0 = mw[0].shape[1]
-                wgrad(dpres[0], cond, Hm, k0, mw[0], mb[0], 0, ntm, 0, gmax[n_film + 1:n_film + 2] if k0 > 64 else None)
-                if native:
-                    hip.wgrad_native_batch(native, M)
-
-            # every gradient lands in the optimizer slab -- directly, or (a padded copy of a slab parameter) as an add of this node's
-            # accumulator deferred to the end of the pass -- so nothing the backward pass runs before its end depends on the launches: they
-            # go to the side stream.  (The deferred share is NOT handed to autograd: the padding node may have a second producer -- the
-            # DDF-fit rows are a node of their own -- and autograd would sum the two accumulators while this one is still being written.)
-            pad = [(not sunk[i]) and ctx.pad_sinks[i] is not None and _slab_resident(ctx.pad_sinks[i]) for i in range(len(wb))]
-            if all(sunk[i] or pad[i] for i in range(len(wb))):
-                async_weight_gradients(launch, [d_res, x, cond, dfp, gmax, *ys, *hs, *dzs, *(dpres or [])])
-                for i, t in enumerate(wb):
-                    if pad[i]:
-                        o = ctx.pad_sinks[i].shape
-                        _DEFERRED_PADS.append((grads[i][:o[0], :o[1]] if len(o) == 2 else grads[i][:o[0]], ctx.pad_sinks[i].grad))
-                        sunk[i] = True
-                _queue_end_of_pass()
-            else:
-                launch()
-        return (d_x, d_cond, None, None, None, None, *[None if sunk[i] else g for i, g in enumerate(grads)])
-
-    @staticmethod
     def backward(ctx, d_res):
-        n_map, n_film, train_w, need_dcond, M, H, Hm = ctx.cfg
+        n_map, n_film, train_w, need_dcond, M, H, Hm, need_dx = ctx.cfg
         train_w = train_w and any(ctx.needs_input_grad[6:])  # (frozen weights -- the eval-latent fit -- take no gradient)
         sv = ctx.saved_tensors
         x, cond, FP = sv[0], sv[1], sv[2]
@@ -926,81 +995,56 @@ class FilmSirenFn(torch.autograd.Function):
         ys = list(sv[3 + n_map:3 + n_map + n_film])
         zs = list(sv[3 + n_map + n_film:3 + n_map + 2 * n_film])
         wb = sv[3 + n_map + 2 * n_film:]
-        mw, mb, mwo, mbo, fw, fb, ow, ob, o = FilmSirenFn._unpack(wb, n_map, n_film)
+        mw, mb, mwo, mbo, fw, fb, ow, ob, o = _film_unpack(wb, n_map, n_film)
         dev = x.device
-        if FP.numel() == 0:
-            return FilmSirenFn._backward_fused(ctx, d_res, x, cond, hs, ys, zs, wb, mw, mb, mwo, mbo, fw, fb, ow, ob, o)
-        grads: List[Optional[torch.Tensor]] = [None] * len(wb)
         d_res = d_res.contiguous()
         n_out_p = ow.shape[0]
         NF = 2 * n_film * H
-        sunk = [False] * len(wb)
-        if train_w:  # gradient accumulators shared by every row chunk: the parameter's own .grad view where the weight is an
-            # optimizer-slab parameter, otherwise views of ONE zero-filled slab
-            for idx, t in enumerate(wb):
-                sk = ctx.sinks[idx]
-                if sk is not None and sk.grad is not None and sk.grad.shape == t.shape and sk.grad.is_contiguous():
-                    grads[idx], sunk[idx] = sk.grad, True
-                    sk._nsky_sunk = True
-                elif sk is not None and sk.grad is None:
-                    sk._nsky_sunk = True  # (first used after step 0: sinks from the next zero_grad_all on)
-            sizes = [0 if sunk[idx] else (t.numel() + 3) // 4 * 4 for idx, t in enumerate(wb)]
-            flat = zeros(max(sum(sizes), 4), device=dev)
-            off = 0
-            for idx, t in enumerate(wb):
-                if not sunk[idx]:
-                    grads[idx] = flat[off:off + t.numel()].view_as(t)
-                    off += sizes[idx]
+        grads, sunk = [None] * len(wb), [False] * len(wb)
+        if train_w:  # the parameter's own .grad view where the weight is an optimizer-slab parameter, otherwise views of ONE zero-filled slab
+            grads, sunk = _carve_grads(wb, _sink_grads(ctx.sinks, from_first_pass=True))
         acc = (lambda iw: (grads[iw], grads[iw + 1])) if train_w else (lambda iw: None)
-        d_x = torch.empty(M, fw[0].shape[1], device=dev) if ctx.need_dx else None
+        d_x = torch.empty(M, fw[0].shape[1], device=dev) if need_dx else None
         d_cond = torch.empty(M, mw[0].shape[1], device=dev) if need_dcond else None
-        chunks = [(0, M)]
-        mc = max(r1 - r0 for r0, r1 in chunks)
-        dFP_buf = torch.empty(mc, NF, device=dev)
-        dZa, dZb = torch.empty(mc, H, device=dev), torch.empty(mc, H, device=dev)
-        dPa, dPb = torch.empty(mc, Hm, device=dev), torch.empty(mc, Hm, device=dev)
-        for r0, r1 in chunks:
-            m = r1 - r0
-            fp, dFP = FP[r0:r1], dFP_buf[:m]
-            dr = d_res[r0:r1]
+        dFP = torch.empty(M, NF, device=dev)
+        dZ, dZo = torch.empty(M, H, device=dev), torch.empty(M, H, device=dev)
+        dpre, dpo = torch.empty(M, Hm, device=dev), torch.empty(M, Hm, device=dev)
+        if train_w:
+            grad_weight(d_res, ys[-1], M, n_out_p, H, ow, ob, acc=acc(o + 2 * n_film))
+        # walk the FiLM layers backwards; each dX GEMM applies the FiLM backward epilogue of the layer below
+        i = n_film - 1
+        grad_input(d_res, ow, M, H, n_out_p, dZ, epi=hip.EPI_BWD_FILM, p0=15.0, p1=30.0, aux0=zs[i],
+                   aux1=FP[:, i * H:(i + 1) * H], aux2=FP[:, (n_film + i) * H:(n_film + i + 1) * H],
+                   out1=dFP[:, i * H:(i + 1) * H], out2=dFP[:, (n_film + i) * H:(n_film + i + 1) * H])
+        while True:
+            y_in = ys[i - 1] if i > 0 else x
+            k_in = fw[i].shape[1]
             if train_w:
-                grad_weight(dr, ys[-1][r0:r1], m, n_out_p, H, ow, ob, acc=acc(o + 2 * n_film))
-            # walk the FiLM layers backwards; each dX GEMM applies the FiLM backward epilogue of the layer below
-            i = n_film - 1
-            dZ, dZo = dZa[:m], dZb[:m]
-            grad_input(dr, ow, m, H, n_out_p, dZ, epi=hip.EPI_BWD_FILM, p0=15.0, p1=30.0, aux0=zs[i][r0:r1],
-                       aux1=fp[:, i * H:(i + 1) * H], aux2=fp[:, (n_film + i) * H:(n_film + i + 1) * H],
-                       out1=dFP[:, i * H:(i + 1) * H], out2=dFP[:, (n_film + i) * H:(n_film + i + 1) * H])
-            while True:
-                y_in = ys[i - 1][r0:r1] if i > 0 else x[r0:r1]
-                k_in = fw[i].shape[1]
-                if train_w:
-                    grad_weight(dZ, y_in, m, H, k_in, fw[i], fb[i], acc=acc(o + 2 * i))
-                if i == 0:
-                    if d_x is not None:  # gradient w.r.t. the encoded direction rows (DDF multi-view rays, ddf_model.py:297-322)
-                        grad_input(dZ, fw[0], m, k_in, H, d_x[r0:r1])
-                    break
-                j = i - 1
-                grad_input(dZ, fw[i], m, H, H, dZo, epi=hip.EPI_BWD_FILM, p0=15.0, p1=30.0, aux0=zs[j][r0:r1],
-                           aux1=fp[:, j * H:(j + 1) * H], aux2=fp[:, (n_film + j) * H:(n_film + j + 1) * H],
-                           out1=dFP[:, j * H:(j + 1) * H], out2=dFP[:, (n_film + j) * H:(n_film + j + 1) * H])
-                dZ, dZo = dZo, dZ
-                i = j
-            # mapping network
+                grad_weight(dZ, y_in, M, H, k_in, fw[i], fb[i], acc=acc(o + 2 * i))
+            if i == 0:
+                if d_x is not None:  # gradient w.r.t. the encoded direction rows (DDF multi-view rays, ddf_model.py:297-322)
+                    grad_input(dZ, fw[0], M, k_in, H, d_x)
+                break
+            j = i - 1
+            grad_input(dZ, fw[i], M, H, H, dZo, epi=hip.EPI_BWD_FILM, p0=15.0, p1=30.0, aux0=zs[j],
+                       aux1=FP[:, j * H:(j + 1) * H], aux2=FP[:, (n_film + j) * H:(n_film + j + 1) * H],
+                       out1=dFP[:, j * H:(j + 1) * H], out2=dFP[:, (n_film + j) * H:(n_film + j + 1) * H])
+            dZ, dZo = dZo, dZ
+            i = j
+        # mapping network
+        if train_w:
+            grad_weight(dFP, hs[-1], M, NF, Hm, mwo, mbo, acc=acc(2 * n_map))
+        grad_input(dFP, mwo, M, Hm, NF, dpre, epi=hip.EPI_BWD_LEAKY, p0=0.2, aux0=hs[-1])
+        for i in range(n_map - 1, -1, -1):
+            h_in = hs[i - 1] if i > 0 else cond
+            k_in = mw[i].shape[1]
             if train_w:
-                grad_weight(dFP, hs[-1][r0:r1], m, NF, Hm, mwo, mbo, acc=acc(2 * n_map))
-            dpre, dpo = dPa[:m], dPb[:m]
-            grad_input(dFP, mwo, m, Hm, NF, dpre, epi=hip.EPI_BWD_LEAKY, p0=0.2, aux0=hs[-1][r0:r1])
-            for i in range(n_map - 1, -1, -1):
-                h_in = hs[i - 1][r0:r1] if i > 0 else cond[r0:r1]
-                k_in = mw[i].shape[1]
-                if train_w:
-                    grad_weight(dpre, h_in, m, Hm, k_in, mw[i], mb[i], acc=acc(2 * i))
-                if i > 0:
-                    grad_input(dpre, mw[i], m, Hm, Hm, dpo, epi=hip.EPI_BWD_LEAKY, p0=0.2, aux0=hs[i - 1][r0:r1])
-                    dpre, dpo = dpo, dpre
-                elif d_cond is not None:
-                    grad_input(dpre, mw[0], m, k_in, Hm, d_cond[r0:r1])
+                grad_weight(dpre, h_in, M, Hm, k_in, mw[i], mb[i], acc=acc(2 * i))
+            if i > 0:
+                grad_input(dpre, mw[i], M, Hm, Hm, dpo, epi=hip.EPI_BWD_LEAKY, p0=0.2, aux0=hs[i - 1])
+                dpre, dpo = dpo, dpre
+            elif d_cond is not None:
+                grad_input(dpre, mw[0], M, k_in, Hm, d_cond)
         return (d_x, d_cond, None, None, None, None, *[None if sunk[i] else g for i, g in enumerate(grads)])
 
 
@@ -1165,11 +1209,6 @@ def _field_pack(kind, weights, layers_fn):
     return _prepared(_FIELD_STREAMS, key, weights, lambda: hip.chain_pack(layers_fn(), dev, buffers))
 
 
-def field_fused_ok(ET, W0, W1, W2, Wc0, Wc1) -> bool:
-    return (FWD_PRECISION == hip.PREC_F16X2 and ET.shape[0] >= 4 and ld(ET) == W0.shape[1]
-            and hip.field_supported(W0.shape[1], W0.shape[0], W2.shape[0] - 4, Wc1.shape[0], Wc0.shape[1]))
-
-
 class FieldChainFn(torch.autograd.Function):
     """SDFAlbedoFn's contract (same arguments, same outputs) on the fused field kernels: geometry network with forward-mode tangents
     in the quad layout, colour path, and the hand-derived reverse of both; every product fp32-grade (fp16 hi + residual planes on
@@ -1178,14 +1217,18 @@ class FieldChainFn(torch.autograd.Function):
     NPE = 39  # x (3) + PE6 (36): the leading columns of an encode row that also feed the colour net
 
     @staticmethod
+    def _net(Kin, beta, b0, b1, W2, b2, bc0, bc1, Wc2, bc2):
+        GF = W2.shape[0] - 4  # (row GF of the last geometry layer is the sdf row)
+        return hip.field_net(Kin, FieldChainFn.NPE, beta, b0, b1, W2[GF], b2[GF:GF + 1], b2[:GF], bc0, bc1, Wc2, bc2)
+
+    @staticmethod
     def forward(ctx, ET, W0, b0, W1, b1, W2, b2, Wc0, bc0, Wc1, bc1, Wc2, bc2, beta, want_albedo=True):
         N = ET.shape[0] // 4
         dev = ET.device
         GF = W2.shape[0] - 4
         Kin = W0.shape[1]
         save = any(ctx.needs_input_grad)
-        w_sdf, b_sdf = W2[GF], b2[GF:GF + 1]
-        net = hip.field_net(Kin, FieldChainFn.NPE, beta, b0, b1, w_sdf, b_sdf, b2[:GF], bc0, bc1, Wc2, bc2)
+        net = FieldChainFn._net(Kin, beta, b0, b1, W2, b2, bc0, bc1, Wc2, bc2)
         Mq, Mp = hip.film_rows(4 * N), hip.film_rows(N)
         a0q, a1q = torch.empty(Mq, 256, device=dev), torch.empty(Mq, 256, device=dev)
         Eq = torch.empty(Mq, 128, device=dev) if save else None
@@ -1225,7 +1268,7 @@ class FieldChainFn(torch.autograd.Function):
         N, GF, Kin, beta = ctx.cfg
         dev = ET.device
         colour = ctx.want_albedo and g_alb is not None
-        net = hip.field_net(Kin, FieldChainFn.NPE, beta, b0, b1, W2[GF], b2[GF:GF + 1], b2[:GF], bc0, bc1, Wc2, bc2)
+        net = FieldChainFn._net(Kin, beta, b0, b1, W2, b2, bc0, bc1, Wc2, bc2)
         Mq, Mp = hip.film_rows(4 * N), hip.film_rows(N)
         gmax = zeros(8, device=dev)
         g_sdf = None if g_sdf is None else g_sdf.contiguous()
@@ -1282,14 +1325,6 @@ class FieldChainFn(torch.autograd.Function):
                 k(f_c1, dWc1), k(f_c1, dbc1), k(f_c2, dWc2), k(f_c2, dbc2), None, None)
 
 
-def field_apply(ET, *args):
-    """the field on stacked encode rows: the fused chain kernels where they apply, otherwise the per-layer path"""
-    W0, _, W1, _, W2, _, Wc0, _, Wc1 = args[:9]
-    if field_fused_ok(ET, W0, W1, W2, Wc0, Wc1):
-        return FieldChainFn.apply(ET, *args)
-    return SDFAlbedoFn.apply(ET, *args)
-
-
 _SDF_STREAMS: dict = {}
 
 
@@ -1307,9 +1342,9 @@ def _sdf_stream(W0, b0, W1, b1, W2, b2, GF, beta, direction):
     return _prepared(_SDF_STREAMS, key, keep, pack)
 
 
-class SDFValueFn(torch.autograd.Function):
-    """get_sdf_at_pos (sdf_albedo_field.py:169-174): value-only geo net on encode rows E [M,72] -> sdf [M].
-    Long batches (the DDF termination points) run the fused value chain: one kernel each way plus the weight gradients."""
+class SdfChainFn(torch.autograd.Function):
+    """get_sdf_at_pos (sdf_albedo_field.py:169-174): value-only geo net on encode rows E [M,72] -> sdf [M], on the fused value chain:
+    one kernel each way plus the weight gradients.  args: E, W0, b0, W1, b1, W2, b2, beta, train_weights"""
 
     @staticmethod
     def forward(ctx, E, W0, b0, W1, b1, W2, b2, beta, train_weights):
@@ -1317,33 +1352,22 @@ class SDFValueFn(torch.autograd.Function):
         dev = E.device
         Hd, Kin = W0.shape
         GF = W2.shape[0] - 4
-        ctx.fused = (FWD_PRECISION == hip.PREC_F16X2 and hip.sdf_supported(Kin, Hd)
-                     and ld(E) >= Kin and ld(E) % 4 == 0)
         ctx.cfg = (M, Hd, Kin, GF, beta, train_weights)
-        if ctx.fused:
-            net, stream, table = _sdf_stream(W0, b0, W1, b1, W2, b2, GF, beta, 0)
-            Mp = hip.film_rows(M)
-            A0 = torch.empty(Mp, Hd, device=dev); A1 = torch.empty(Mp, Hd, device=dev)
-            sdf = torch.empty(M, device=dev)
-            hip.sdf_chain_fwd(net, stream, table, E, M, A0, A1, sdf)
-            if any(ctx.needs_input_grad):
-                # the backward's stream is packed here, in a quiet stretch of the step: launched from the backward, its 11 small
-                # workgroups (34 KB of LDS each) queue behind the illumination decoder's chain kernels on the second stream, which hold
-                # every CU's LDS (0.28 ms on the timeline for 10 us of work)
-                _sdf_stream(W0, b0, W1, b1, W2, b2, GF, beta, 1)
-            ctx.save_for_backward(E, A0, A1, W0, b0, W1, b1, W2, b2)
-            return sdf
-        A0 = torch.empty(M, Hd, device=dev); S0 = torch.empty(M, Hd, device=dev)
-        fgemm(E, W0, A0, M, Hd, Kin, bias=b0, epi=hip.EPI_SOFTPLUS, p0=beta, out1=S0)
-        A1 = torch.empty(M, Hd, device=dev); S1 = torch.empty(M, Hd, device=dev)
-        fgemm(A0, W1, A1, M, Hd, Hd, bias=b1, epi=hip.EPI_SOFTPLUS, p0=beta, out1=S1)
-        out = zeros(M, 4, device=dev)
-        fgemm(A1, W2[GF:GF + 1], out, M, 1, Hd, bias=b2[GF:GF + 1])
-        ctx.save_for_backward(E, A0, S0, A1, S1, W0, b0, W1, b1, W2, b2)
-        return out[:, 0]
+        net, stream, table = _sdf_stream(W0, b0, W1, b1, W2, b2, GF, beta, 0)
+        Mp = hip.film_rows(M)
+        A0 = torch.empty(Mp, Hd, device=dev); A1 = torch.empty(Mp, Hd, device=dev)
+        sdf = torch.empty(M, device=dev)
+        hip.sdf_chain_fwd(net, stream, table, E, M, A0, A1, sdf)
+        if any(ctx.needs_input_grad):
+            # the backward's stream is packed here, in a quiet stretch of the step: launched from the backward, its 11 small
+            # workgroups (34 KB of LDS each) queue behind the illumination decoder's chain kernels on the second stream, which hold
+            # every CU's LDS (0.28 ms on the timeline for 10 us of work)
+            _sdf_stream(W0, b0, W1, b1, W2, b2, GF, beta, 1)
+        ctx.save_for_backward(E, A0, A1, W0, b0, W1, b1, W2, b2)
+        return sdf
 
     @staticmethod
-    def _backward_fused(ctx, g_sdf):
+    def backward(ctx, g_sdf):
         E, A0, A1, W0, b0, W1, b1, W2, b2 = ctx.saved_tensors
         M, Hd, Kin, GF, beta, train_w = ctx.cfg
         train_w = train_w and any(ctx.needs_input_grad[1:7])  # (frozen weights -- the eval-latent fit -- take no gradient)
@@ -1371,16 +1395,31 @@ class SDFValueFn(torch.autograd.Function):
 
             async_weight_gradients(launch, [dZ1, A0, dZ0, E, gmax])
             join_unless_sunk(db0, db1)  # (db2's share came from the chain kernel above, on this stream)
-            if not f2: dW2 = None
-            if not f1: dW1 = None
-            if not f0: dW0 = None
-            db0, db1, db2 = first_only(f0, db0), first_only(f1, db1), first_only(f2, db2)
-        return dE, dW0, db0, dW1, db1, dW2, db2, None, None
+        k = first_only  # later nodes of the pass added in place; slab-resident biases return nothing
+        return dE, k(f0, dW0), k(f0, db0), k(f1, dW1), k(f1, db1), k(f2, dW2), k(f2, db2), None, None
+
+
+class SdfLayersFn(torch.autograd.Function):
+    """SdfChainFn's contract (same arguments, same output) on the per-layer dense kernels"""
+
+    @staticmethod
+    def forward(ctx, E, W0, b0, W1, b1, W2, b2, beta, train_weights):
+        M = E.shape[0]
+        dev = E.device
+        Hd, Kin = W0.shape
+        GF = W2.shape[0] - 4
+        ctx.cfg = (M, Hd, Kin, GF, beta, train_weights)
+        A0 = torch.empty(M, Hd, device=dev); S0 = torch.empty(M, Hd, device=dev)
+        fgemm(E, W0, A0, M, Hd, Kin, bias=b0, epi=hip.EPI_SOFTPLUS, p0=beta, out1=S0)
+        A1 = torch.empty(M, Hd, device=dev); S1 = torch.empty(M, Hd, device=dev)
+        fgemm(A0, W1, A1, M, Hd, Hd, bias=b1, epi=hip.EPI_SOFTPLUS, p0=beta, out1=S1)
+        out = zeros(M, 4, device=dev)
+        fgemm(A1, W2[GF:GF + 1], out, M, 1, Hd, bias=b2[GF:GF + 1])
+        ctx.save_for_backward(E, A0, S0, A1, S1, W0, b0, W1, b1, W2, b2)
+        return out[:, 0]
 
     @staticmethod
     def backward(ctx, g_sdf):
-        if ctx.fused:
-            return SDFValueFn._backward_fused(ctx, g_sdf)
         E, A0, S0, A1, S1, W0, b0, W1, b1, W2, b2 = ctx.saved_tensors
         M, Hd, Kin, GF, beta, train_w = ctx.cfg
         train_w = train_w and any(ctx.needs_input_grad[1:7])
@@ -1396,6 +1435,7 @@ class SDFValueFn(torch.autograd.Function):
         dE = torch.empty(M, Kin, device=dev)
         grad_input(dZ0, W0, M, Kin, Hd, dE)
         dW0 = db0 = dW1 = db1 = dW2 = db2 = None
+        f0 = f1 = f2 = False
         if train_w:
             join_weight_gradients()  # (as in SDFAlbedoFn.backward: adds on the current stream)
             dW2, db2, f2 = shared_grad(W2, b2)
@@ -1407,11 +1447,8 @@ class SDFValueFn(torch.autograd.Function):
             dW0, db0, f0 = shared_grad(W0, b0)
             grad_weight(dZ0, E, M, Hd, Kin, W0, b0, acc=(dW0, db0), batch=wq)
             flush_wgrad(wq)
-            if not f2: dW2 = None
-            if not f1: dW1 = None
-            if not f0: dW0 = None
-            db0, db1, db2 = first_only(f0, db0), first_only(f1, db1), first_only(f2, db2)
-        return dE, dW0, db0, dW1, db1, dW2, db2, None, None
+        k = first_only  # later nodes of the pass added in place; slab-resident biases return nothing
+        return dE, k(f0, dW0), k(f0, db0), k(f1, dW1), k(f1, db1), k(f2, dW2), k(f2, db2), None, None
 
 
 # =============================================================================================
@@ -1850,31 +1887,21 @@ class ProposalMLPFn(torch.autograd.Function):
         raw = torch.empty(feat.shape[0], 1, device=feat.device)
         hip.proposal_mlp_fwd(feat, w0c, b0.detach(), w1c, b1.detach(), raw)
         ctx.save_for_backward(feat, w0c, b0.detach(), w1c, b1.detach())
-        ctx.sinks = [t if getattr(t, "_nsky_grad_sink", False) else None for t in (w0, b0, w1, b1)]
+        ctx.sinks = [_sink_param(t) for t in (w0, b0, w1, b1)]
         return raw
 
     @staticmethod
     def backward(ctx, d_raw):
         feat, w0, b0, w1, b1 = ctx.saved_tensors
-        sinks = ctx.sinks
-        if all(sk is not None and sk.grad is not None and sk.grad.is_contiguous() for sk in sinks):
-            # optimizer-slab parameters: the kernel accumulates straight into their .grad views of the (zero-filled) gradient slab --
-            # no AccumulateGrad copy per parameter, nothing for collect_grads to gather
-            for sk in sinks:
-                sk._nsky_sunk = True
-            d_feat = torch.empty_like(feat) if ctx.needs_input_grad[0] else None
-            hip.proposal_mlp_bwd(feat, w0, b0, w1, b1, d_raw.contiguous(), d_feat, sinks[0].grad, sinks[1].grad, sinks[2].grad, sinks[3].grad)
-            return d_feat, None, None, None, None
-        for sk in sinks:
-            if sk is not None and sk.grad is None:
-                sk._nsky_sunk = True  # (sinks from the next zero_grad_all on)
-        flat = zeros(w0.numel() + b0.numel() + w1.numel() + 4, device=feat.device)
-        n0, nb = w0.numel(), b0.numel()
-        dw0, db0 = flat[:n0].view_as(w0), flat[n0:n0 + nb]
-        dw1, db1 = flat[n0 + nb:n0 + nb + w1.numel()].view_as(w1), flat[n0 + nb + w1.numel():n0 + nb + w1.numel() + 1]
+        # optimizer-slab parameters: the kernel accumulates straight into their .grad views of the (zero-filled) gradient slab --
+        # no AccumulateGrad copy per parameter, nothing for collect_grads to gather.  All four, or none.
+        grads = _sink_grads(ctx.sinks, from_first_pass=True, all_or_none=True)
+        sunk = grads[0] is not None
+        if not sunk:
+            grads, _ = _carve_grads((w0, b0, w1, b1), grads)
         d_feat = torch.empty_like(feat) if ctx.needs_input_grad[0] else None
-        hip.proposal_mlp_bwd(feat, w0, b0, w1, b1, d_raw.contiguous(), d_feat, dw0, db0, dw1, db1)
-        return d_feat, dw0, db0, dw1, db1
+        hip.proposal_mlp_bwd(feat, w0, b0, w1, b1, d_raw.contiguous(), d_feat, *grads)
+        return (d_feat, None, None, None, None) if sunk else (d_feat, *grads)
 
 
 class DensityWeightsFn(torch.autograd.Function):

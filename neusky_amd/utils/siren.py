@@ -2,7 +2,7 @@
 neusky/utils/siren.py:108-208 (`DDFFiLMSiren`, `CustomMappingNetwork`, `FiLMLayer`); the configured
 network is `reni.field_components.film_siren.FiLMSiren` whose source is absent (SURVEY.md A9 - parity
 unpinned beyond siren.py).  Same sub-module / parameter names as siren.py so its state_dict loads.
-The forward runs in `ops.FilmSirenFn` (fp32 MFMA layers with fused LeakyReLU / FiLM-sine epilogues)."""
+The forward runs in `ops.film_apply` (fp32 MFMA layers with fused LeakyReLU / FiLM-sine epilogues)."""
 from __future__ import annotations
 
 import math
@@ -100,6 +100,5 @@ class FiLMSiren(nn.Module):
         """x [M, pad4(in_dim)], conditioning_input [M, pad4(cond_dim)] (zero padded columns) -> [M, out_dim]
         (padded_output: the kernels' own [M, pad4(out_dim)] matrix, for a caller whose next kernel reads it as it is)"""
         need_dcond = conditioning_input.requires_grad
-        out = ops.FilmSirenFn.apply(x, conditioning_input, self.n_map, self.n_film, train_weights, need_dcond,
-                                    *self.padded_weights())
+        out = ops.film_apply(x, conditioning_input, self.n_map, self.n_film, train_weights, need_dcond, *self.padded_weights())
         return out if padded_output else out[:, :self.out_dim]

@@ -41,7 +41,7 @@ def _run(E, ws, g_sdf, fused=True):
     try:
         ops.begin_step(DEV)
         Eg = E.clone().requires_grad_(True)
-        sdf = ops.SDFValueFn.apply(Eg, *ws, BETA, True)
+        sdf = ops.sdf_value_apply(Eg, *ws, BETA, True)
         grads = torch.autograd.grad((sdf * g_sdf).sum(), [Eg] + list(ws))
         torch.cuda.synchronize()
     finally:

@@ -43,7 +43,7 @@ def main():
         flops = 2.0 * M * (cd * H + (n_map - 1) * H * H + H * 2 * n_film * H + xd * H + (n_film - 1) * H * H + H * od)
         wb = net.padded_weights()
         with torch.no_grad():
-            t_old = timeit(lambda: ops.FilmSirenFn.apply(x, cond, n_map, n_film, False, False, *wb))
+            t_old = timeit(lambda: ops.FilmLayersFn.apply(x, cond, n_map, n_film, False, False, *wb))
         print(f"{name}: M={M} stream {nbytes/1e6:.2f} MB, pack {t_pack*1e3:.1f} us, fused fwd (saving) {t_save:.3f} ms = {flops/t_save/1e9:.1f} TFLOP/s, "
               f"fused fwd (no saves) {t_nosave:.3f} ms = {flops/t_nosave/1e9:.1f} TFLOP/s, per-layer path (no grad) {t_old:.3f} ms")
 

@@ -46,7 +46,7 @@ def apply() -> None:
         from neusky_amd.models.neusky_model import NeuSkyFactoModel
         NeuSkyFactoModel.start_ddf_fit = lambda self, prep: None
     if os.environ.get("NSKY_FILM_ASYNC", "1") == "0":
-        orig = ops.FilmSirenFn._backward_fused
+        orig = ops.FilmChainFn.backward
 
         def in_line(*a, **k):
             keep, ops.ASYNC_WGRAD = ops.ASYNC_WGRAD, False
@@ -54,7 +54,7 @@ def apply() -> None:
                 return orig(*a, **k)
             finally:
                 ops.ASYNC_WGRAD = keep
-        ops.FilmSirenFn._backward_fused = staticmethod(in_line)
+        ops.FilmChainFn.backward = staticmethod(in_line)
     if os.environ.get("NSKY_RETIRE_SECONDS"):
         ops.RETIRE_SECONDS = float(os.environ["NSKY_RETIRE_SECONDS"])
     if os.environ.get("NSKY_ORDER_BY_STREAM") == "1":
