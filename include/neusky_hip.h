@@ -785,6 +785,36 @@ int nsky_mesh_compact_faces(const int32_t* corner_cells, int64_t F, const int32_
                             int32_t* faces_out, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Texture baking on a per-triangle-pair atlas (the layout of nerfstudio's textured-mesh export, with a gutter).  No counterpart in
+ * the reference; neusky_amd/exporter/texture.py drives these two kernels (csrc/texture.hip) around the field's fused value chain.
+ *   layout:   P = px_per_uv_triangle >= 1; a square has Q = P + 3 texels per side; faces 2 s (lower) and 2 s + 1 (upper) share square s;
+ *             S = ceil(sqrt(ceil(F / 2))) squares per row, square s at column s % S, row s / S; the image is W x W, W = S Q <=
+ *             NSKY_TEXTURE_MAX_SIZE, row 0 at the top, uint8 [W][W][3].
+ *   corners:  texel (i, j) of a square = column i, row j, a texel's centre being its index.  lower: v0 (0, 0), v1 (P, 0), v2 (0, P),
+ *             owns i + j <= P + 2; upper: v0 (P+2, P+2), v1 (2, P+2), v2 (P+2, 2), owns i + j >= P + 3.  A bilinear lookup anywhere in
+ *             a face's triangle (edges and corners included) reads only texels that face owns.  Squares past ceil(F / 2), and the
+ *             upper half of the last square of an odd F, have no owner and are never written.
+ *   point:    lower: b1 = i / P, b2 = j / P; upper: b1 = (P + 2 - i) / P, b2 = (P + 2 - j) / P; b0 = 1 - b1 - b2; negative components
+ *             become 0 and the rest are divided by their sum (gutter texels sample the nearest edge or corner of their own triangle);
+ *             evaluated as integer numerators over their integer sum, one fp32 division each; position =
+ *             fma(b2, v2, fma(b1, v1, b0 v0)) per axis.
+ *   encoding: colour = clamp(rint(clamp(srgb(x), 0, 1) * 255), 0, 255) with srgb(x) = x <= 0.0031308 ? 12.92 x : 1.055 |x|^(1/2.4) - 0.055,
+ *             fp32, every operation rounded on its own (what the exporter's vertex colours go through); normal = the same
+ *             quantisation of g / max(|g|, 1e-12) * 0.5 + 0.5, |g| = sqrt((gx gx + gy gy) + gz gz).
+ * nsky_texture_texel_points: the texels of squares [s0, s1), s1 <= S^2, in square-major order (row-major inside a square), n =
+ *                            (s1 - s0) Q^2 of them  ->  owner[n] (the face, -1 without one or when the face's indices leave [0, V)),
+ *                            offset[n] = y W + x (int64) and points[n][3] (zeros without an owner).
+ * nsky_texture_texel_store:  albedo[n][3] (linear), gradient[n][3] (read only with a normal image), owner[n], offset[n]  ->  image and,
+ *                            unless NULL, normal_image, both uint8 [W][W][3]; texels with owner -1 (or an offset outside the image)
+ *                            are skipped. */
+#define NSKY_TEXTURE_MAX_SIZE 16384
+int nsky_texture_texel_points(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int32_t px_per_uv_triangle,
+                              int64_t squares_per_row, int64_t s0, int64_t s1, int32_t* owner, int64_t* offset, float* points,
+                              nsky_stream_t stream);
+int nsky_texture_texel_store(const float* albedo, const float* gradient, const int32_t* owner, const int64_t* offset, int64_t n, int64_t W,
+                             uint8_t* image, uint8_t* normal_image, nsky_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Relighting under an equirectangular HDR environment map.  No counterpart in the reference (it lights frames with RENI++ latents
  * only); the package's relight module (neusky_amd/relight) drives these kernels.
  *   map:         fp32 [H, W, 3] linear radiance, C-contiguous, row 0 at the top.

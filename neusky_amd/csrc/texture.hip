@@ -1,0 +1,133 @@
+// Texture baking for the mesh exporter (neusky_amd/exporter/texture.py): a per-triangle-pair atlas.  Definitions:
+// include/neusky_hip.h (nsky_texture_*).
+//
+//   texel_points  one thread per texel of the squares [s0, s1), square-major, row-major inside a square: the owning face, the
+//                 texel's flat offset in the W x W image and the point of the face it samples (clamped barycentrics, fp32)
+//   texel_store   one thread per texel: the sRGB-encoded colour (and the encoded unit gradient) to its offset; unowned texels skipped
+// Both are streaming kernels: thread t reads and writes record t of every per-texel array (owner 4 B, offset 8 B, the three floats
+// of a point or a colour as 12 contiguous bytes per lane, 768 per wave); the only scattered traffic is the 3-byte image store,
+// in runs of Q texels.  Every index that is multiplied by W is 64-bit.  No atomics, nothing here synchronises with the host.
+// The encodings repeat the exporter's torch expressions operation by operation (no contraction into fmas), so that a texel at a
+// vertex carries that vertex's colour.
+#include "common.h"
+#include "../../include/neusky_hip.h"
+
+#pragma STDC FP_CONTRACT OFF
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxGrid = 1 << 16;
+
+__global__ __launch_bounds__(kThreads) void texel_points_kernel(const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ faces,
+                                                                 int64_t F, int32_t P, int64_t S, int64_t s0, int64_t n,
+                                                                 int32_t* __restrict__ owner, int64_t* __restrict__ offset,
+                                                                 float* __restrict__ points) {
+  const int32_t Q = P + 3, QQ = Q * Q;
+  const int64_t W = S * Q;
+  for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < n; t += (int64_t)gridDim.x * kThreads) {
+    const int64_t s = s0 + t / QQ;
+    const int32_t r = (int32_t)(t % QQ), j = r / Q, i = r - j * Q;
+    offset[t] = ((s / S) * Q + j) * W + (s % S) * Q + i;
+    const bool lower = i + j <= P + 2;
+    const int64_t f = 2 * s + (lower ? 0 : 1);
+    // barycentrics as integer numerators over P: b1 = n1 / P, b2 = n2 / P, b0 = 1 - b1 - b2; negative ones become 0, the rest
+    // divided by their sum (one rounding each)
+    int32_t n1 = lower ? i : P + 2 - i, n2 = lower ? j : P + 2 - j;
+    int32_t n0 = P - n1 - n2;
+    n0 = n0 < 0 ? 0 : n0;
+    n1 = n1 < 0 ? 0 : n1;
+    n2 = n2 < 0 ? 0 : n2;
+    int32_t own = -1;
+    float px = 0.0f, py = 0.0f, pz = 0.0f;
+    if (f < F) {
+      const int32_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+      if (a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V) {
+        own = (int32_t)f;
+        const float sum = (float)(n0 + n1 + n2);  // >= 1: the three cannot all be clamped
+        const float b0 = (float)n0 / sum, b1 = (float)n1 / sum, b2 = (float)n2 / sum;
+        const float* va = verts + 3 * (int64_t)a;
+        const float* vb = verts + 3 * (int64_t)b;
+        const float* vc = verts + 3 * (int64_t)c;
+        px = fmaf(b2, vc[0], fmaf(b1, vb[0], b0 * va[0]));
+        py = fmaf(b2, vc[1], fmaf(b1, vb[1], b0 * va[1]));
+        pz = fmaf(b2, vc[2], fmaf(b1, vb[2], b0 * va[2]));
+      }
+    }
+    owner[t] = own;
+    points[3 * t] = px;
+    points[3 * t + 1] = py;
+    points[3 * t + 2] = pz;
+  }
+}
+
+// (linear_to_sRGB(x) * 255).round().clamp(0, 255) of the exporter's vertex colours: every product and sum rounded on its own
+__device__ __forceinline__ uint8_t srgb_level(float x) {
+  float y = x <= 0.0031308f ? 12.92f * x : 1.055f * powf(fabsf(x), (float)(1.0 / 2.4)) - 0.055f;
+  y = fminf(fmaxf(y, 0.0f), 1.0f);
+  return (uint8_t)fminf(fmaxf(rintf(y * 255.0f), 0.0f), 255.0f);
+}
+
+__device__ __forceinline__ uint8_t unit_level(float n) {
+  return (uint8_t)fminf(fmaxf(rintf((n * 0.5f + 0.5f) * 255.0f), 0.0f), 255.0f);
+}
+
+__global__ __launch_bounds__(kThreads) void texel_store_kernel(const float* __restrict__ albedo, const float* __restrict__ gradient,
+                                                                const int32_t* __restrict__ owner, const int64_t* __restrict__ offset,
+                                                                int64_t n, int64_t texels, uint8_t* __restrict__ image,
+                                                                uint8_t* __restrict__ normal_image) {
+  for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < n; t += (int64_t)gridDim.x * kThreads) {
+    if (owner[t] < 0) continue;
+    const int64_t o = offset[t];
+    if (o < 0 || o >= texels) continue;
+    uint8_t* px = image + 3 * o;
+    px[0] = srgb_level(albedo[3 * t]);
+    px[1] = srgb_level(albedo[3 * t + 1]);
+    px[2] = srgb_level(albedo[3 * t + 2]);
+    if (normal_image) {
+      const float gx = gradient[3 * t], gy = gradient[3 * t + 1], gz = gradient[3 * t + 2];
+      const float len = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-12f);  // a zero gradient encodes as (128, 128, 128)
+      uint8_t* pn = normal_image + 3 * o;
+      pn[0] = unit_level(gx / len);
+      pn[1] = unit_level(gy / len);
+      pn[2] = unit_level(gz / len);
+    }
+  }
+}
+
+int grid_of(int64_t n) {
+  const int64_t b = (n + kThreads - 1) / kThreads;
+  return (int)(b < 1 ? 1 : b < kMaxGrid ? b : kMaxGrid);
+}
+
+}  // namespace
+
+extern "C" int nsky_texture_texel_points(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int32_t px_per_uv_triangle,
+                                         int64_t squares_per_row, int64_t s0, int64_t s1, int32_t* owner, int64_t* offset, float* points,
+                                         nsky_stream_t stream) {
+  const int64_t P = px_per_uv_triangle, S = squares_per_row, Q = P + 3;
+  NSKY_CHECK_ARG(V >= 0 && V <= INT32_MAX && F >= 0 && F <= INT32_MAX, "nsky_texture_texel_points: V %ld F %ld", (long)V, (long)F);
+  NSKY_CHECK_ARG(P >= 1 && S >= 0 && S * Q <= NSKY_TEXTURE_MAX_SIZE, "nsky_texture_texel_points: px_per_uv_triangle %ld, squares_per_row %ld (side %ld, at most %d)",
+                 (long)P, (long)S, (long)(S * Q), NSKY_TEXTURE_MAX_SIZE);
+  NSKY_CHECK_ARG(s0 >= 0 && s0 <= s1 && s1 <= S * S, "nsky_texture_texel_points: squares [%ld, %ld) of %ld", (long)s0, (long)s1, (long)(S * S));
+  const int64_t n = (s1 - s0) * Q * Q;
+  if (n == 0) return NSKY_OK;
+  NSKY_CHECK_ARG(owner && offset && points, "nsky_texture_texel_points: NULL output");
+  NSKY_CHECK_ARG(F == 0 || (vertices && faces), "nsky_texture_texel_points: NULL vertices / faces");
+  hipLaunchKernelGGL(texel_points_kernel, dim3(grid_of(n)), dim3(kThreads), 0, (hipStream_t)stream, vertices, V, faces, F, (int32_t)P, S, s0, n,
+                     owner, offset, points);
+  NSKY_CHECK_LAUNCH("nsky_texture_texel_points");
+  return NSKY_OK;
+}
+
+extern "C" int nsky_texture_texel_store(const float* albedo, const float* gradient, const int32_t* owner, const int64_t* offset, int64_t n,
+                                        int64_t W, uint8_t* image, uint8_t* normal_image, nsky_stream_t stream) {
+  NSKY_CHECK_ARG(n >= 0 && W >= 0 && W <= NSKY_TEXTURE_MAX_SIZE, "nsky_texture_texel_store: n %ld W %ld", (long)n, (long)W);
+  if (n == 0 || W == 0) return NSKY_OK;
+  NSKY_CHECK_ARG(albedo && owner && offset && image, "nsky_texture_texel_store: NULL argument");
+  NSKY_CHECK_ARG(!normal_image || gradient, "nsky_texture_texel_store: a normal image needs the gradient");
+  hipLaunchKernelGGL(texel_store_kernel, dim3(grid_of(n)), dim3(kThreads), 0, (hipStream_t)stream, albedo, gradient, owner, offset, n, W * W,
+                     image, normal_image);
+  NSKY_CHECK_LAUNCH("nsky_texture_texel_store");
+  return NSKY_OK;
+}

@@ -1,5 +1,7 @@
 """python -m neusky_amd.exporter --checkpoint CKPT --output mesh.ply: the SDF field of a checkpoint as a PLY mesh.
 
+An --output ending in .obj writes a textured Wavefront OBJ instead (mesh.obj, mesh.mtl, mesh.png): the albedo baked into a
+per-triangle-pair atlas on the mesh that is written, that is after --target-num-faces / --simplify-cell-size.
 The flags carry the names of nerfstudio's `ns-export marching-cubes`.  The field is built from the `neusky` method's config; no
 dataset is needed (the scene box and the number of training images come from the checkpoint)."""
 from __future__ import annotations
@@ -21,7 +23,7 @@ def build_field(state, device):
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m neusky_amd.exporter", description=__doc__.splitlines()[0])
     ap.add_argument("--checkpoint", required=True, help="a nerfstudio-layout checkpoint (step-*.ckpt) of the neusky method")
-    ap.add_argument("--output", required=True, help="the .ply file to write")
+    ap.add_argument("--output", required=True, help="the .ply file to write, or a .obj file for a textured mesh (.obj, .mtl, .png)")
     ap.add_argument("--resolution", type=int, default=512)
     ap.add_argument("--bounding-box-min", type=float, nargs=3, default=(-1.0, -1.0, -1.0))
     ap.add_argument("--bounding-box-max", type=float, nargs=3, default=(1.0, 1.0, 1.0))
@@ -33,14 +35,24 @@ def build_parser() -> argparse.ArgumentParser:
                           help="simplify the mesh by vertex clustering to at most N faces (nerfstudio's --target-num-faces; off by default)")
     simplify.add_argument("--simplify-cell-size", type=float, default=None, metavar="H",
                           help="simplify the mesh by vertex clustering on cubic cells of edge H (scene units; off by default)")
+    ap.add_argument("--px-per-uv-triangle", type=int, default=None, metavar="P",
+                    help=".obj output: texels along a leg of each face's texture triangle (nerfstudio's --px-per-uv-triangle; default 4)")
+    ap.add_argument("--texture-normal-map", action="store_true",
+                    help=".obj output: also write <stem>_normal.png, the unit SDF gradient as an object-space normal map")
     return ap
 
 
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    textured = args.output.lower().endswith(".obj")
+    if not textured and (args.px_per_uv_triangle is not None or args.texture_normal_map):
+        ap.error("--px-per-uv-triangle and --texture-normal-map need an --output ending in .obj")
+    if args.px_per_uv_triangle is not None and args.px_per_uv_triangle < 1:
+        ap.error("--px-per-uv-triangle must be >= 1")
 
     import torch
-    from . import extract_mesh, load_field_state, simplify_mesh, write_ply
+    from . import bake_texture, extract_mesh, load_field_state, simplify_mesh, write_obj, write_ply
 
     t0 = time.perf_counter()
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
@@ -70,11 +82,21 @@ def main(argv=None) -> int:
             mesh.normals, mesh.colours = vertex_attributes(field, mesh.vertices)
             torch.cuda.synchronize()
             timings["attributes"] = time.perf_counter() - t1
+    atlas, size = None, ""
+    if textured and not args.no_attributes:
+        t1 = time.perf_counter()
+        atlas = bake_texture(mesh, field, px_per_uv_triangle=args.px_per_uv_triangle or 4, normal_map=args.texture_normal_map)
+        torch.cuda.synchronize()
+        timings["texture"] = time.perf_counter() - t1
+        size = f" texture {atlas.image.shape[1]} x {atlas.image.shape[0]}"
     t1 = time.perf_counter()
-    write_ply(args.output, mesh)
+    if textured:
+        write_obj(args.output, mesh, atlas)
+    else:
+        write_ply(args.output, mesh)
     t_write = time.perf_counter() - t1
     parts = " ".join(f"{k} {v:.3f}s" for k, v in timings.items())
-    print(f"{args.output}: {before}V {mesh.vertices.shape[0]} F {mesh.faces.shape[0]} | load {t_load:.3f}s {parts} write {t_write:.3f}s")
+    print(f"{args.output}: {before}V {mesh.vertices.shape[0]} F {mesh.faces.shape[0]}{size} | load {t_load:.3f}s {parts} write {t_write:.3f}s")
     return 0
 
 

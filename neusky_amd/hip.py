@@ -1216,6 +1216,34 @@ def mesh_compact_faces(corner_cells, keep, ends, faces_out):
                               Fo, ptr(_typed(faces_out, torch.int32, Fo, 3)), stream_ptr()), "nsky_mesh_compact_faces")
 
 
+# ---- texture baking on a per-triangle-pair atlas (exporter/texture.py drives texel points -> the field's value chain -> texel store)
+TEXTURE_MAX_SIZE = 16384  # NSKY_TEXTURE_MAX_SIZE
+_texture_texel_points = _sig("nsky_texture_texel_points", C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                             C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_texture_texel_store = _sig("nsky_texture_texel_store", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                            C.c_void_p, C.c_void_p)
+
+
+def texture_texel_points(vertices, faces, px_per_uv_triangle: int, squares_per_row: int, s0: int, s1: int, owner, offset, points):
+    """vertices: fp32 [V, 3]; faces: int32 [F, 3]; the n = (s1 - s0) (P + 3)^2 texels of squares [s0, s1) -> owner: int32 [n] (-1: none),
+    offset: int64 [n] (y W + x), points: fp32 [n, 3]"""
+    V, F = vertices.shape[0], faces.shape[0]
+    n = (int(s1) - int(s0)) * (int(px_per_uv_triangle) + 3) ** 2
+    check(_texture_texel_points(ptr(_typed(vertices, torch.float32, V, 3)), V, ptr(_typed(faces, torch.int32, F, 3)), F, int(px_per_uv_triangle),
+                                int(squares_per_row), int(s0), int(s1), ptr(_typed(owner, torch.int32, n)), ptr(_typed(offset, torch.int64, n)),
+                                ptr(_typed(points, torch.float32, n, 3)), stream_ptr()), "nsky_texture_texel_points")
+
+
+def texture_texel_store(albedo, gradient, owner, offset, image, normal_image=None):
+    """albedo (linear), gradient: fp32 [n, 3] (gradient may be None without a normal image); owner: int32 [n]; offset: int64 [n];
+    image, normal_image: uint8 [W, W, 3], written at the offsets of the owned texels"""
+    n, W = owner.shape[0], image.shape[0]
+    check(_texture_texel_store(ptr(_typed(albedo, torch.float32, n, 3)), ptr(_typed(gradient, torch.float32, n, 3)),
+                               ptr(_typed(owner, torch.int32, n)), ptr(_typed(offset, torch.int64, n)), n, W,
+                               ptr(_typed(image, torch.uint8, W, W, 3)), ptr(_typed(normal_image, torch.uint8, W, W, 3)), stream_ptr()),
+          "nsky_texture_texel_store")
+
+
 # ---- environment-map relighting (relight/envmap.py drives label -> stable sort -> reduce, and the lookup)
 ENVMAP_NEUSKY, ENVMAP_BLENDER = 0, 1  # NSKY_ENVMAP_NEUSKY / _BLENDER
 ENVMAP_MAX_DIRECTIONS = 1024  # NSKY_ENVMAP_MAX_DIRECTIONS
