@@ -126,8 +126,12 @@ int nsky_weighted_colsum_f32(const float* X, int32_t M, int32_t N, int32_t ldx, 
  *        floats, 16-byte aligned): every bias of the network followed by one reciprocal scale per tile.
  *   nsky_film_chain_fwd: cond [M, ldcond] (first cond_dim columns), x [M, ldx] -> res [M, ldres] (first out_dim columns,
  *        raw head output; columns out_dim..3 are written too).  Side outputs, each a TILE-NATIVE [ceil32(M), hidden] matrix
- *        (below): y_save[i] (FiLM layer outputs; REQUIRED: they are also the hand-off to the next layer), z_save[i] (FiLM
- *        pre-activations W y + b; optional), h_save[l] (mapping activations after LeakyReLU(0.2); optional).
+ *        (below): y_save[i] (FiLM layer outputs, also the hand-off to the next layer), z_save[i] (FiLM pre-activations
+ *        W y + b; optional), h_save[l] (mapping activations after LeakyReLU(0.2); optional).
+ *        Only the weight gradients read the kept y_save[i].  A caller that does not need them (frozen weights, no gradient)
+ *        passes, at hidden 128, y_save = NULL or every entry NULL: the hand-off stays in registers and no output is written;
+ *        at hidden 256 (no registers to spare) two ping-pong buffers, y_save[i] = buffer i % 2 (entries may alias: a wave
+ *        reads a layer's tiles back before it stores the next layer's).  A mix of NULL and non-NULL entries is an error.
  *        Products are fp32-grade (three fp16 MFMAs on power-of-two pre-scaled hi / residual planes, fp32 accumulate).
  *   Tile-native layout of a [rows, width] fp32 matrix (rows padded to a multiple of 32, width % 32 == 0): 32 x 32 blocks of
  *        4 KB, block (R, t) at float offset (R * (width / 32) + t) * 1024; inside a block element (row c, feature f) at
@@ -160,6 +164,14 @@ int nsky_film_chain_fwd(const nsky_film_net* net, const void* stream_buf, const 
  *        (tile-native) and d_cond [M, ldcond] (row-major, pad columns zeroed; optional).
  * gmax (caller zero-fills): largest magnitude of each gradient matrix, for nsky_gemm_f32's a_scale_max -- bwd_film writes
  *        [i] = max |dz_save[i]| (i < n_film) and [n_film] = max |dfp|; bwd_map writes [l] = max |dpre_save[l]| (l < n_map).
+ * Frozen weights (only the weight gradients read dz_save / dpre_save; d_x, dfp, dfp_rowmax, gmax[n_film] and d_cond are the same
+ *        bits either way):
+ *        bwd_film, hidden 128 or 256: dz_save = NULL or every entry NULL -> no dz is stored and gmax[i], i < n_film, stays as passed.
+ *        bwd_map, hidden 128: dpre_save = NULL or every entry NULL -> dpre stays in registers from layer to layer.
+ *        bwd_map, hidden 256: every dpre_save[l] the SAME [ceil32(M), hidden] buffer (n_map > 1; scratch: a wave reads only the tiles
+ *        it stored, and has layer l in registers before it stores the first tile of layer l - 1).  Also accepted at hidden 128.
+ *        In both forms bwd_map leaves gmax[l] as passed.  A mix of NULL and non-NULL entries, or of shared and distinct ones, is
+ *        an error, and so is a NULL dpre_save at hidden 256.
  * hidden must be a multiple of 128 for the backward streams.  d_x (optional, [M, ldx], ldx <= 16): gradient w.r.t. the FiLM input
  * rows (the DDF's multi-view rays differentiate through their direction rows, neusky/models/ddf_model.py:297-322). */
 int nsky_film_chain_bwd_film(const nsky_film_net* net, const void* stream_buf, const float* table, int32_t M, const float* d_res,

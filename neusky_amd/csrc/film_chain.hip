@@ -204,12 +204,15 @@ struct FwdArgs {
   int M;
   float* h_save[MAXL];  // mapping activations (after LeakyReLU), native [ceil32(M), H]; NULL = not kept
   float* z_save[MAXL];  // FiLM pre-activations W y + b, native [ceil32(M), H]; NULL = not kept
-  float* y_save[MAXL];  // FiLM outputs, native [ceil32(M), H]; never NULL: also the hand-off to the next layer
+  float* y_save[MAXL];  // FiLM outputs, native [ceil32(M), H]: also the hand-off to the next layer (entries may alias two ping-pong
+                        // buffers when nothing is kept); all NULL = film_fwd_kernel<.., KEEP_Y = false>, the hand-off stays in registers
   float* res; int ldres;
 };
 
 
-template <int H, int KSC>
+// KEEP_Y = false (frozen weights: only the weight gradients read the kept FiLM outputs; H = 128, where the registers are there): a
+// layer's output is scaled and split into the next layer's operand planes tile by tile as it is formed and never goes to memory
+template <int H, int KSC, bool KEEP_Y = true>
 __global__ __launch_bounds__(256, 1) void film_fwd_kernel(const FwdArgs a) {
   constexpr int NT = H / 32, KS = H / 16;
   __shared__ __attribute__((aligned(16))) unsigned char smem[RING_BYTES + (BIAS_FLOATS + SCALE_FLOATS) * 4];
@@ -337,7 +340,8 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(const FwdArgs a) {
     const float* bZ = bias_film + i * H;
     // a wave whose tile lies wholly beyond M stores nothing and reads tile 0 back (in bounds; its results are never stored)
     float* zblk = a.z_save[i] ? a.z_save[i] + (wave_live ? rt : 0) * NT * 1024 : nullptr;
-    float* yblk = a.y_save[i] + (wave_live ? rt : 0) * NT * 1024;
+    float* yblk = KEEP_Y ? a.y_save[i] + (wave_live ? rt : 0) * NT * 1024 : nullptr;
+    f16x8 nh[KEEP_Y ? 1 : KS], nl[KEEP_Y ? 1 : KS];  // (KEEP_Y = false) the planes of this layer's output
     for (int t = 0; t < NT; ++t) {
       f32x16 aF, aP, aZ;
 #pragma unroll
@@ -372,8 +376,27 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(const FwdArgs a) {
       }
       if (wave_live) {
         if (zblk) store_tile_nt(zblk + t * 1024, lane, zz);
-        store_tile(yblk + t * 1024, lane, yy);
+        if constexpr (KEEP_Y) store_tile(yblk + t * 1024, lane, yy);
       }
+      if constexpr (!KEEP_Y) {
+        // the values and the arithmetic of the read-back below; t is wave-uniform, the plane registers are indexed statically
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt)
+          if (t == tt) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              float x8[8];
+#pragma unroll
+              for (int j = 0; j < 8; ++j) x8[j] = yy[8 * u + j] * Y_SCALE;
+              split8(x8, nh[2 * tt + u], nl[2 * tt + u]);
+            }
+          }
+      }
+    }
+    if constexpr (!KEEP_Y) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) { yh[ks] = nh[ks]; yl[ks] = nl[ks]; }
+      continue;
     }
     // hand-off: this lane reads back exactly the 16-byte pieces it stored (k-step ks, half u = register group 2 (ks & 1) + u of
     // tile ks / 2)
@@ -426,10 +449,10 @@ struct BwdFilmArgs {
   const float* d_res; int ldres;   // [M, ldres] gradient of the raw head output (first out_dim columns)
   const float* h_last;             // native [ceil32(M), H]
   const float* z_save[MAXL];       // native
-  float* dz_save[MAXL];            // native [ceil32(M), H]
+  float* dz_save[MAXL];            // native [ceil32(M), H]; all NULL = film_bwd4_kernel<H, KEEP = false>
   float* dfp;                      // native [ceil32(M), 2 n_film H]: dF of layer i in columns i H .., dphase in (n_film + i) H ..
   float* dfp_rowmax;               // [ceil32(M)] max |dfp| per batch row
-  float* gmax;                     // zero-initialised by the caller: [i] = max |dz_save[i]|, [n_film] = max |dfp|
+  float* gmax;                     // zero-initialised by the caller: [i] = max |dz_save[i]| (KEEP only), [n_film] = max |dfp|
   float* d_x; int ldx;             // optional [M, ldx]: gradient w.r.t. the FiLM input rows (pad columns zeroed)
   int full_wgs, tail_wgs, tail_k;  // (unused by the four-wave kernel)
 };
@@ -487,7 +510,8 @@ __device__ __forceinline__ void hidden_load4_s(f32x4& q, const float* sbase, int
   asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "+v"(q) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
 }
 
-template <int H, bool ACTIVE>
+// KEEP = false (frozen weights): dz is the weight gradients' operand alone -- it is neither stored nor is its maximum published
+template <int H, bool ACTIVE, bool KEEP>
 __device__ __forceinline__ void film_bwd4_tile(const BwdFilmArgs& a, WStream& ws, const float* bl, const float* sl, const float* wo, long rt, int lane) {
   constexpr int NT = H / 32, KS = H / 16, GH = (KS + GSLABS - 1) / GSLABS, PW = 4;
   const nsky_film_net& net = a.net;
@@ -558,7 +582,7 @@ __device__ __forceinline__ void film_bwd4_tile(const BwdFilmArgs& a, WStream& ws
     const float* bP = bias_mo + (n_film + i) * H;
     // wave-uniform bases (scalar registers) + ONE per-lane offset: eight 64-bit per-lane pointers were what the loop kept reloading from scratch
     const float* zp = a.z_save[i] + rt * NT * 1024;
-    float* dzp = a.dz_save[i] + rt * NT * 1024;
+    float* dzp = KEEP ? a.dz_save[i] + rt * NT * 1024 : nullptr;
     float* dFp = a.dfp + (rt * (2 * n_film * NT) + (long)i * NT) * 1024;
     float* dPp = a.dfp + (rt * (2 * n_film * NT) + (long)(n_film + i) * NT) * 1024;
     float dz_max = 0.0f;
@@ -606,9 +630,14 @@ __device__ __forceinline__ void film_bwd4_tile(const BwdFilmArgs& a, WStream& ws
               dz_max = fmaxf(dz_max, fabsf(dzv[q]));
               fp_max = fmaxf(fp_max, fmaxf(fabsf(dFv[q]), fabsf(gc)));
             }
-            stg4(dzt + (g * 256 + lane * 4), make_float4(dzv[0], dzv[1], dzv[2], dzv[3]));
-            stg4(dFt + (g * 256 + lane * 4), make_float4(dFv[0], dFv[1], dFv[2], dFv[3]));
-            stg4(dPt + (g * 256 + lane * 4), make_float4(dPv[0], dPv[1], dPv[2], dPv[3]));
+            if constexpr (KEEP) {
+              stg4(dzt + (g * 256 + lane * 4), make_float4(dzv[0], dzv[1], dzv[2], dzv[3]));
+              stg4(dFt + (g * 256 + lane * 4), make_float4(dFv[0], dFv[1], dFv[2], dFv[3]));
+              stg4(dPt + (g * 256 + lane * 4), make_float4(dPv[0], dPv[1], dPv[2], dPv[3]));
+            } else {  // (as vectors: without the dz store between them the float4 forms are emitted as two 8-byte stores each)
+              *reinterpret_cast<f32x4*>(dFt + (g * 256 + lane * 4)) = f32x4{dFv[0], dFv[1], dFv[2], dFv[3]};
+              *reinterpret_cast<f32x4*>(dPt + (g * 256 + lane * 4)) = f32x4{dPv[0], dPv[1], dPv[2], dPv[3]};
+            }
             asm volatile("" : "+v"(dz_max), "+v"(fp_max));
           }
         }
@@ -620,7 +649,7 @@ __device__ __forceinline__ void film_bwd4_tile(const BwdFilmArgs& a, WStream& ws
       float dz_inv = 1.0f;
       f16x8 dh_[KS], dl_[KS];
       if (ACTIVE) {
-        publish_max(a.gmax + i, dz_max, live, true, lane);
+        if constexpr (KEEP) publish_max(a.gmax + i, dz_max, live, true, lane);
         const float s = row_scale(dz_max, dz_inv);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -663,7 +692,7 @@ __device__ __forceinline__ void film_bwd4_tile(const BwdFilmArgs& a, WStream& ws
   }
 }
 
-template <int H>
+template <int H, bool KEEP = true>
 __global__ __launch_bounds__(256, 1) void film_bwd4_kernel(const BwdFilmArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[RING_BYTES + (BIAS_FLOATS + SCALE_FLOATS) * 4 + 4 * H * 4];
   float* bl = reinterpret_cast<float*>(smem + RING_BYTES);
@@ -692,8 +721,8 @@ __global__ __launch_bounds__(256, 1) void film_bwd4_kernel(const BwdFilmArgs a) 
   ws_begin(ws);
   const long n_tiles = (a.M + 31) / 32;
   const long rt = (long)blockIdx.x * 4 + wave;
-  if (rt < n_tiles) film_bwd4_tile<H, true>(a, ws, bl, sl, wo, rt, lane);
-  else film_bwd4_tile<H, false>(a, ws, bl, sl, wo, 0, lane);
+  if (rt < n_tiles) film_bwd4_tile<H, true, KEEP>(a, ws, bl, sl, wo, rt, lane);
+  else film_bwd4_tile<H, false, KEEP>(a, ws, bl, sl, wo, 0, lane);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 }
 
@@ -703,6 +732,10 @@ __global__ __launch_bounds__(256, 1) void film_bwd4_kernel(const BwdFilmArgs a) 
 // ONCE), then the
 // mapping layers backwards, hidden state in registers as in the forward: dpre = dh * leaky'(h) is stored tile-native (weight
 // gradients), split, and multiplied by the transposed weight tiles; the last product yields d_cond (row-major).
+// KEEP = false (frozen weights: nothing reads dpre after the launch) publishes no maxima.  At H = 128 the layer's NT = 4 tiles of dpre
+// then stay in registers from the epilogue that forms them to the split (dpre_save all NULL; the operand planes are 64 registers there
+// against 128 at H = 256).  At H = 256 the store and the read-back remain, and every dpre_save[l] may be the SAME buffer: a wave reads
+// only the tiles it stored, and the planes of layer l are in its registers before the first tile of layer l - 1 is stored.
 struct BwdMapArgs {
   nsky_film_net net;
   const unsigned char* stream;
@@ -711,15 +744,17 @@ struct BwdMapArgs {
   const float* dfp;          // native [ceil32(M), 2 n_film H]
   const float* dfp_rowmax;   // [ceil32(M)]
   const float* h_save[MAXL]; // native
-  float* dpre_save[MAXL];    // native [ceil32(M), H]
+  float* dpre_save[MAXL];    // native [ceil32(M), H]; KEEP = false: all NULL (H = 128) or all one buffer
   float* d_cond; int ldcond; // [M, ldcond] or NULL
-  float* gmax;               // zero-initialised by the caller: [l] = max |dpre_save[l]|
+  float* gmax;               // zero-initialised by the caller: [l] = max |dpre_save[l]| (KEEP only)
   int full_wgs, tail_wgs, tail_k;  // tail_plan of the launch
 };
 
-template <int H, bool ACTIVE>
+template <int H, bool ACTIVE, bool KEEP>
 __device__ __forceinline__ void film_bwd_map_tile(const BwdMapArgs& a, WStream& ws, const float* sl, long rt, int lane) {
   constexpr int NT = H / 32, KS = H / 16, PW = 2;
+  constexpr bool REGS = !KEEP && H <= 128;
+  float dreg[REGS ? NT : 1][16];  // (REGS) dpre of the layer at hand
   const nsky_film_net& net = a.net;
   const int c = lane & 31, h = lane >> 5;
   const long row = rt * 32 + c;
@@ -804,7 +839,12 @@ __device__ __forceinline__ void film_bwd_map_tile(const BwdMapArgs& a, WStream& 
         dv[r] = hv[r] > 0.0f ? g : 0.2f * g;
         m = fmaxf(m, fabsf(dv[r]));
       }
-      store_tile(a.dpre_save[top] + (rt * NT + u) * 1024, lane, dv);
+      if constexpr (REGS) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dreg[u][r] = dv[r];
+      } else {
+        store_tile(a.dpre_save[top] + (rt * NT + u) * 1024, lane, dv);
+      }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
@@ -814,13 +854,18 @@ __device__ __forceinline__ void film_bwd_map_tile(const BwdMapArgs& a, WStream& 
     float d_inv = 1.0f;
     f16x8 ph[KS], pl[KS];
     if (ACTIVE) {
-      publish_max(a.gmax + l, m, live, true, lane);
+      if constexpr (KEEP) publish_max(a.gmax + l, m, live, true, lane);
       const float s = row_scale(m, d_inv);
       // B planes of dpre_l: its NT tiles come back from where this wave stored them
 #pragma unroll
       for (int u = 0; u < NT; ++u) {
         float dv[16];
-        load_tile(a.dpre_save[l] + (rt * NT + u) * 1024, lane, dv);
+        if constexpr (REGS) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dv[r] = dreg[u][r];
+        } else {
+          load_tile(a.dpre_save[l] + (rt * NT + u) * 1024, lane, dv);
+        }
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
           float x8[8];
@@ -846,7 +891,16 @@ __device__ __forceinline__ void film_bwd_map_tile(const BwdMapArgs& a, WStream& 
             dv[r] = hv[r] > 0.0f ? g : 0.2f * g;
             m = fmaxf(m, fabsf(dv[r]));
           }
-          store_tile(a.dpre_save[l - 1] + (rt * NT + u) * 1024, lane, dv);
+          if constexpr (REGS) {  // u is wave-uniform: the tile registers are indexed statically
+#pragma unroll
+            for (int uu = 0; uu < NT; ++uu)
+              if (u == uu) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) dreg[uu][r] = dv[r];
+              }
+          } else {
+            store_tile(a.dpre_save[l - 1] + (rt * NT + u) * 1024, lane, dv);
+          }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         ++tile;
@@ -871,12 +925,13 @@ __device__ __forceinline__ void film_bwd_map_tile(const BwdMapArgs& a, WStream& 
   }
 }
 
-template <int H>
+template <int H, bool KEEP = true>
 __global__ __launch_bounds__(512, 2) void film_bwd_map_kernel(const BwdMapArgs a) {
   // Eight waves (two per SIMD, 256 registers each) share one weight stream over 256 batch rows.  The register budget is met as in
   // the FiLM backward: the head product keeps its NT accumulator tiles and only 64 head rows of operand planes at a time, and no
   // layer's matrix stays in registers -- a finished tile of dpre is stored (tile-native, also the weight gradient's operand) and the
-  // layer below reads the tiles back (the lane that stored a piece loads it).  The remainder of the last round runs in tail workgroups.
+  // layer below reads the tiles back (the lane that stored a piece loads it; KEEP = false at H = 128 has the registers to hold them
+  // instead).  The remainder of the last round runs in tail workgroups.
   constexpr int PW = 2;
   __shared__ __attribute__((aligned(16))) unsigned char smem[RING_BYTES + SCALE_FLOATS * 4];
   float* sl = reinterpret_cast<float*>(smem + RING_BYTES);
@@ -892,8 +947,8 @@ __global__ __launch_bounds__(512, 2) void film_bwd_map_kernel(const BwdMapArgs a
   ws_begin<PW>(ws);
   const long n_tiles = (a.M + 31) / 32;
   const long rt = tail_tile(a.full_wgs, a.tail_wgs, a.tail_k, n_tiles, wave);
-  if (rt >= 0 && rt < n_tiles) film_bwd_map_tile<H, true>(a, ws, sl, rt, lane);
-  else film_bwd_map_tile<H, false>(a, ws, sl, 0, lane);
+  if (rt >= 0 && rt < n_tiles) film_bwd_map_tile<H, true, KEEP>(a, ws, sl, rt, lane);
+  else film_bwd_map_tile<H, false, KEEP>(a, ws, sl, 0, lane);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 }
 
@@ -1280,7 +1335,7 @@ extern "C" int nsky_film_chain_fwd(const nsky_film_net* net, const void* stream_
                                    int32_t ldcond, const float* x, int32_t ldx, int32_t M, float* const* h_save, float* const* z_save,
                                    float* const* y_save, float* res, int32_t ldres, nsky_stream_t stream) {
   if (int rc = check_net(net, "nsky_film_chain_fwd")) return rc;
-  NSKY_CHECK_ARG(stream_buf && table && cond && x && res && y_save && M > 0, "nsky_film_chain_fwd: null operand / empty batch");
+  NSKY_CHECK_ARG(stream_buf && table && cond && x && res && M > 0, "nsky_film_chain_fwd: null operand / empty batch");
   NSKY_CHECK_ARG(ldcond % 4 == 0 && ldcond >= ((net->cond_dim + 3) & ~3) && ldx % 4 == 0 && ldx >= ((net->x_dim + 3) & ~3) && ldres >= 4 && ldres % 4 == 0,
                  "nsky_film_chain_fwd: leading dimensions (cond %d, x %d, res %d) must be multiples of 4 covering the padded widths", ldcond, ldx, ldres);
   NSKY_CHECK_ARG(((uintptr_t)cond % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)res % 16) == 0 && ((uintptr_t)stream_buf % 16) == 0 && ((uintptr_t)table % 16) == 0,
@@ -1292,14 +1347,19 @@ extern "C" int nsky_film_chain_fwd(const nsky_film_net* net, const void* stream_
   for (int l = 0; l < MAXL; ++l) {
     a.h_save[l] = (h_save && l < net->n_map) ? h_save[l] : nullptr;
     a.z_save[l] = (z_save && l < net->n_film) ? z_save[l] : nullptr;
-    a.y_save[l] = l < net->n_film ? y_save[l] : nullptr;
-    if (l < net->n_film) NSKY_CHECK_ARG(a.y_save[l] && ((uintptr_t)a.y_save[l] % 16) == 0, "nsky_film_chain_fwd: y_save[%d] missing / unaligned", l);
+    a.y_save[l] = (y_save && l < net->n_film) ? y_save[l] : nullptr;
   }
+  // FiLM outputs not kept: all of y_save NULL, the hand-off in registers (hidden 128 only; at 256 the caller passes ping-pong buffers)
+  const bool keep_y = a.y_save[0] != nullptr;
+  NSKY_CHECK_ARG(keep_y || net->hidden == 128, "nsky_film_chain_fwd: NULL y_save needs hidden 128 (hidden %d: pass two ping-pong buffers)", net->hidden);
+  for (int l = 0; l < net->n_film; ++l)
+    NSKY_CHECK_ARG((a.y_save[l] != nullptr) == keep_y && ((uintptr_t)a.y_save[l] % 16) == 0, "nsky_film_chain_fwd: y_save[%d] missing / unaligned", l);
   const dim3 grid(ceil_div(M, 128));
   const int ksc = ksteps_of(net->cond_dim);
-#define NSKY_FILM_FWD(HH, KK) hipLaunchKernelGGL((film_fwd_kernel<HH, KK>), grid, dim3(256), 0, (hipStream_t)stream, a)
-  if (net->hidden == 256) { if (ksc <= 4) NSKY_FILM_FWD(256, 4); else NSKY_FILM_FWD(256, 20); }
-  else { if (ksc <= 4) NSKY_FILM_FWD(128, 4); else NSKY_FILM_FWD(128, 20); }
+#define NSKY_FILM_FWD(HH, KK, KEEP) hipLaunchKernelGGL((film_fwd_kernel<HH, KK, KEEP>), grid, dim3(256), 0, (hipStream_t)stream, a)
+  if (net->hidden == 256) { if (ksc <= 4) NSKY_FILM_FWD(256, 4, true); else NSKY_FILM_FWD(256, 20, true); }
+  else if (keep_y) { if (ksc <= 4) NSKY_FILM_FWD(128, 4, true); else NSKY_FILM_FWD(128, 20, true); }
+  else { if (ksc <= 4) NSKY_FILM_FWD(128, 4, false); else NSKY_FILM_FWD(128, 20, false); }
 #undef NSKY_FILM_FWD
   NSKY_CHECK_LAUNCH("nsky_film_chain_fwd");
   return NSKY_OK;
@@ -1310,7 +1370,7 @@ extern "C" int nsky_film_chain_bwd_film(const nsky_film_net* net, const void* st
                                         int32_t ldres, const float* h_last, const float* const* z_save, float* const* dz_save, float* dfp,
                                         float* dfp_rowmax, float* gmax, float* d_x, int32_t ldx, nsky_stream_t stream) {
   if (int rc = check_net(net, "nsky_film_chain_bwd_film")) return rc;
-  NSKY_CHECK_ARG(stream_buf && table && d_res && h_last && z_save && dz_save && dfp && dfp_rowmax && gmax && M > 0, "nsky_film_chain_bwd_film: null operand / empty batch");
+  NSKY_CHECK_ARG(stream_buf && table && d_res && h_last && z_save && dfp && dfp_rowmax && gmax && M > 0, "nsky_film_chain_bwd_film: null operand / empty batch");
   NSKY_CHECK_ARG(ldres >= 4 && ldres % 4 == 0 && ((uintptr_t)d_res % 16) == 0 && ((uintptr_t)h_last % 16) == 0 && ((uintptr_t)dfp % 16) == 0 &&
                      ((uintptr_t)stream_buf % 16) == 0 && ((uintptr_t)table % 16) == 0, "nsky_film_chain_bwd_film: alignment / ldres");
   NSKY_CHECK_ARG(net->hidden % 128 == 0, "nsky_film_chain_bwd_film: hidden %% 128");
@@ -1320,13 +1380,17 @@ extern "C" int nsky_film_chain_bwd_film(const nsky_film_net* net, const void* st
   if (d_x) NSKY_CHECK_ARG(ldx % 4 == 0 && ldx >= ((net->x_dim + 3) & ~3) && ldx <= 16 && ((uintptr_t)d_x % 16) == 0, "nsky_film_chain_bwd_film: d_x layout (ldx %d)", ldx);
   for (int l = 0; l < MAXL; ++l) {
     a.z_save[l] = l < net->n_film ? z_save[l] : nullptr;
-    a.dz_save[l] = l < net->n_film ? dz_save[l] : nullptr;
-    if (l < net->n_film) NSKY_CHECK_ARG(a.z_save[l] && a.dz_save[l] && ((uintptr_t)a.z_save[l] % 16) == 0 && ((uintptr_t)a.dz_save[l] % 16) == 0, "nsky_film_chain_bwd_film: z_save / dz_save[%d]", l);
+    a.dz_save[l] = (dz_save && l < net->n_film) ? dz_save[l] : nullptr;
   }
+  const bool keep = a.dz_save[0] != nullptr;  // dz not kept (frozen weights): all of dz_save NULL
+  for (int l = 0; l < net->n_film; ++l)
+    NSKY_CHECK_ARG(a.z_save[l] && (a.dz_save[l] != nullptr) == keep && ((uintptr_t)a.z_save[l] % 16) == 0 && ((uintptr_t)a.dz_save[l] % 16) == 0, "nsky_film_chain_bwd_film: z_save / dz_save[%d]", l);
   a.full_wgs = a.tail_wgs = a.tail_k = 0;  // (four row tiles per workgroup, one per wave: no tail plan)
   const dim3 grid(ceil_div(ceil_div(M, 32), 4));
-  if (net->hidden == 256) hipLaunchKernelGGL((film_bwd4_kernel<256>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((film_bwd4_kernel<128>), grid, dim3(256), 0, (hipStream_t)stream, a);
+#define NSKY_FILM_BWD4(HH, KEEP) hipLaunchKernelGGL((film_bwd4_kernel<HH, KEEP>), grid, dim3(256), 0, (hipStream_t)stream, a)
+  if (net->hidden == 256) { if (keep) NSKY_FILM_BWD4(256, true); else NSKY_FILM_BWD4(256, false); }
+  else { if (keep) NSKY_FILM_BWD4(128, true); else NSKY_FILM_BWD4(128, false); }
+#undef NSKY_FILM_BWD4
   NSKY_CHECK_LAUNCH("nsky_film_chain_bwd_film");
   return NSKY_OK;
 }
@@ -1335,7 +1399,7 @@ extern "C" int nsky_film_chain_bwd_map(const nsky_film_net* net, const void* str
                                        const float* dfp_rowmax, const float* const* h_save, float* const* dpre_save, float* d_cond,
                                        int32_t ldcond, float* gmax, nsky_stream_t stream) {
   if (int rc = check_net(net, "nsky_film_chain_bwd_map")) return rc;
-  NSKY_CHECK_ARG(stream_buf && table && dfp && dfp_rowmax && h_save && dpre_save && gmax && M > 0, "nsky_film_chain_bwd_map: null operand / empty batch");
+  NSKY_CHECK_ARG(stream_buf && table && dfp && dfp_rowmax && h_save && gmax && M > 0, "nsky_film_chain_bwd_map: null operand / empty batch");
   NSKY_CHECK_ARG(((uintptr_t)dfp % 16) == 0 && ((uintptr_t)stream_buf % 16) == 0 && ((uintptr_t)table % 16) == 0, "nsky_film_chain_bwd_map: alignment");
   if (d_cond) NSKY_CHECK_ARG(ldcond % 4 == 0 && ldcond >= ((net->cond_dim + 3) & ~3) && ((uintptr_t)d_cond % 16) == 0, "nsky_film_chain_bwd_map: d_cond layout");
   NSKY_CHECK_ARG(net->hidden % 128 == 0, "nsky_film_chain_bwd_map: hidden %% 128");
@@ -1344,14 +1408,22 @@ extern "C" int nsky_film_chain_bwd_map(const nsky_film_net* net, const void* str
   a.d_cond = d_cond; a.ldcond = ldcond; a.gmax = gmax;
   for (int l = 0; l < MAXL; ++l) {
     a.h_save[l] = l < net->n_map ? h_save[l] : nullptr;
-    a.dpre_save[l] = l < net->n_map ? dpre_save[l] : nullptr;
-    if (l < net->n_map) NSKY_CHECK_ARG(a.h_save[l] && a.dpre_save[l] && ((uintptr_t)a.h_save[l] % 16) == 0 && ((uintptr_t)a.dpre_save[l] % 16) == 0, "nsky_film_chain_bwd_map: h_save / dpre_save[%d]", l);
+    a.dpre_save[l] = (dpre_save && l < net->n_map) ? dpre_save[l] : nullptr;
   }
+  // dpre not kept (frozen weights): all of dpre_save NULL (hidden 128: register hand-off), or every entry the same buffer (n_map > 1)
+  const bool regs = a.dpre_save[0] == nullptr;
+  const bool keep = !regs && !(net->n_map > 1 && a.dpre_save[1] == a.dpre_save[0]);
+  NSKY_CHECK_ARG(!regs || net->hidden == 128, "nsky_film_chain_bwd_map: NULL dpre_save needs hidden 128 (hidden %d: pass one shared buffer)", net->hidden);
+  for (int l = 0; l < net->n_map; ++l)
+    NSKY_CHECK_ARG(a.h_save[l] && (a.dpre_save[l] == nullptr) == regs && (keep || a.dpre_save[l] == a.dpre_save[0]) && ((uintptr_t)a.h_save[l] % 16) == 0 &&
+                       ((uintptr_t)a.dpre_save[l] % 16) == 0, "nsky_film_chain_bwd_map: h_save / dpre_save[%d]", l);
   const TailPlan tp = tail_plan(ceil_div(M, 32), device_cus());
   a.full_wgs = tp.full_wgs; a.tail_wgs = tp.tail_wgs; a.tail_k = tp.tail_k;
   const dim3 grid(tp.full_wgs + tp.tail_wgs);
-  if (net->hidden == 256) hipLaunchKernelGGL((film_bwd_map_kernel<256>), grid, dim3(512), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((film_bwd_map_kernel<128>), grid, dim3(512), 0, (hipStream_t)stream, a);
+#define NSKY_FILM_BWD_MAP(HH, KEEP) hipLaunchKernelGGL((film_bwd_map_kernel<HH, KEEP>), grid, dim3(512), 0, (hipStream_t)stream, a)
+  if (net->hidden == 256) { if (keep) NSKY_FILM_BWD_MAP(256, true); else NSKY_FILM_BWD_MAP(256, false); }
+  else { if (keep) NSKY_FILM_BWD_MAP(128, true); else NSKY_FILM_BWD_MAP(128, false); }
+#undef NSKY_FILM_BWD_MAP
   NSKY_CHECK_LAUNCH("nsky_film_chain_bwd_map");
   return NSKY_OK;
 }

@@ -1054,8 +1054,16 @@ def _ptr_array(ts, n):
     return arr
 
 
+def film_keepless(hidden: int) -> str:
+    """how the chain kernels of this width run when the weights take no gradient and the weight gradients' operands (y_save, dz_save,
+    dpre_save) are not kept: "registers" -- y_save, dz_save and dpre_save are None, the hand-offs between layers never leave the
+    wave -- or "buffers": dz_save is None, y_save cycles two ping-pong buffers and every dpre_save entry is one shared buffer"""
+    return "registers" if hidden == 128 else "buffers"
+
+
 def film_chain_fwd(net: FilmNet, stream_buf, scales, cond, x, M, h_save, z_save, y_save, res):
-    """see include/neusky_hip.h; h_save / z_save: lists (entries may be None) or None; y_save: list of [M, hidden] tensors"""
+    """see include/neusky_hip.h; h_save / z_save: lists (entries may be None) or None; y_save: list of [M, hidden] tensors, or None
+    (film_keepless(hidden) == "registers")"""
     check(_film_fwd(C.byref(net), ptr(stream_buf), ptr(scales), ptr(cond), ld(cond), ptr(x), ld(x), M,
                     _ptr_array(h_save, net.n_map), _ptr_array(z_save, net.n_film), _ptr_array(y_save, net.n_film), ptr(res), ld(res),
                     stream_ptr()), "nsky_film_chain_fwd")
@@ -1083,14 +1091,16 @@ def film_rows_to_native(x, width: int):
 
 
 def film_chain_bwd_film(net: FilmNet, stream_buf, table, M, d_res, h_last, z_save, dz_save, dfp, dfp_rowmax, gmax, d_x=None):
-    """gmax: zero-filled float tensor [n_film + 1]; d_x: optional [M, ldx] output; see include/neusky_hip.h"""
+    """gmax: zero-filled float tensor [n_film + 1]; d_x: optional [M, ldx] output; dz_save: None = not kept (frozen weights; only
+    gmax[n_film] is written); see include/neusky_hip.h"""
     check(_film_bwd_film(C.byref(net), ptr(stream_buf), ptr(table), M, ptr(d_res), ld(d_res), ptr(h_last), _ptr_array(z_save, net.n_film),
                          _ptr_array(dz_save, net.n_film), ptr(dfp), ptr(dfp_rowmax), ptr(gmax), ptr(d_x), ld(d_x) if d_x is not None else 0,
                          stream_ptr()), "nsky_film_chain_bwd_film")
 
 
 def film_chain_bwd_map(net: FilmNet, stream_buf, table, M, dfp, dfp_rowmax, h_save, dpre_save, d_cond, gmax):
-    """gmax: zero-filled float tensor [n_map]"""
+    """gmax: zero-filled float tensor [n_map]; dpre_save: None (film_keepless(hidden) == "registers") or one shared buffer in every
+    entry = not kept (frozen weights; gmax is not written)"""
     check(_film_bwd_map(C.byref(net), ptr(stream_buf), ptr(table), M, ptr(dfp), ptr(dfp_rowmax), _ptr_array(h_save, net.n_map),
                         _ptr_array(dpre_save, net.n_map), ptr(d_cond), ld(d_cond) if d_cond is not None else 0, ptr(gmax), stream_ptr()),
           "nsky_film_chain_bwd_map")

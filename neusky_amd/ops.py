@@ -839,19 +839,29 @@ class FilmChainFn(torch.autograd.Function):
         # nothing has to survive the call when no input needs a gradient (render / eval): two ping-pong activation
         # buffers, no pre-activation side output
         save = any(ctx.needs_input_grad)
+        # frozen weights (the illumination decoder, the eval-latent fit) take no gradient: the FiLM outputs, which only the weight
+        # gradients read, are not kept either -- no buffer at all where the kernel hands them on in registers (hip.film_keepless)
+        train_w = train_weights and any(ctx.needs_input_grad[6:])
+        keep_y = save and train_w
         # the [M, 2 n_film H] frequency / phase matrix is never formed and no activation makes a round trip through HBM between
-        # layers; kept for the backward: mapping activations, FiLM pre-activations and outputs
+        # layers; kept for the backward: mapping activations, FiLM pre-activations and (trained weights) outputs
         net, stream, scales = _film_stream(wb, n_map, n_film)
         Mp = hip.film_rows(M)  # saved activations are tile-native [ceil32(M), H] matrices (include/neusky_hip.h)
-        ys = [torch.empty(Mp, H, device=dev) for _ in range(n_film if save else min(2, n_film))]
+        if keep_y:
+            ys = [torch.empty(Mp, H, device=dev) for _ in range(n_film)]
+        elif save and hip.film_keepless(H) == "registers":
+            ys = None
+        else:
+            pp = [torch.empty(Mp, H, device=dev) for _ in range(min(2, n_film))]
+            ys = [pp[i % len(pp)] for i in range(n_film)]
         hs = [torch.empty(Mp, Hm, device=dev) for _ in range(n_map)] if save else None
         zs = [torch.empty(Mp, H, device=dev) for _ in range(n_film)] if save else None
         res = torch.empty(M, n_out_p, device=dev)
-        hip.film_chain_fwd(net, stream, scales, cond, x, M, hs, zs, ys if save else [ys[i % len(ys)] for i in range(n_film)], res)
+        hip.film_chain_fwd(net, stream, scales, cond, x, M, hs, zs, ys, res)
         if not save:
             return res
-        ctx.save_for_backward(x, cond, *hs, *ys, *zs, *wb)
-        ctx.cfg = (n_map, n_film, train_weights, need_dcond, M, H, Hm, x.requires_grad)
+        ctx.save_for_backward(x, cond, *hs, *(ys if keep_y else []), *zs, *wb)
+        ctx.cfg = (n_map, n_film, train_w, need_dcond, M, H, Hm, x.requires_grad)
         # weights that ARE optimizer-slab parameters (no padding copy in between) take their gradient in place
         ctx.sinks = [_sink_param(w) for w in wb]
         ctx.pad_sinks = [_sink_param(w, "pad") for w in wb]  # slab parameters behind a padding copy (_PadFn defers)
@@ -862,21 +872,21 @@ class FilmChainFn(torch.autograd.Function):
         """two chain kernels (csrc/film_chain.hip) produce every pre-activation gradient as a tile-native matrix (F / phase are
         re-formed in registers: no [M, 2 n_film H] matrix is read or recomputed through HBM) and d_cond; the parameter gradients
         are weight-gradient GEMMs straight over those matrices."""
-        n_map, n_film, train_w, need_dcond, M, H, Hm, need_dx = ctx.cfg
-        train_w = train_w and any(ctx.needs_input_grad[6:])  # (frozen weights -- the eval-latent fit -- take no gradient)
+        n_map, n_film, train_w, need_dcond, M, H, Hm, need_dx = ctx.cfg  # (train_w: the weights take gradients, see forward)
         sv = ctx.saved_tensors
         x, cond = sv[0], sv[1]
         hs = list(sv[2:2 + n_map])
-        ys = list(sv[2 + n_map:2 + n_map + n_film])
-        zs = list(sv[2 + n_map + n_film:2 + n_map + 2 * n_film])
-        wb = sv[2 + n_map + 2 * n_film:]
+        n_ys = n_film if train_w else 0
+        ys = list(sv[2 + n_map:2 + n_map + n_ys])
+        zs = list(sv[2 + n_map + n_ys:2 + n_map + n_ys + n_film])
+        wb = sv[2 + n_map + n_ys + n_film:]
         mw, mb, mwo, mbo, fw, fb, ow, ob, o = _film_unpack(wb, n_map, n_film)
         dev = x.device
         Mp = hip.film_rows(M)
         d_res = d_res.contiguous()
         net1, s1, t1 = _film_stream(wb, n_map, n_film, 1)
         net2, s2, t2 = _film_stream(wb, n_map, n_film, 2)
-        dzs = [torch.empty(Mp, H, device=dev) for _ in range(n_film)]
+        dzs = [torch.empty(Mp, H, device=dev) for _ in range(n_film)] if train_w else None  # (the weight gradients' operand alone)
         dfp = torch.empty(Mp, 2 * n_film * H, device=dev)
         rowmax = torch.empty(Mp, device=dev)
         gmax = zeros(n_film + 1 + n_map, device=dev)
@@ -884,7 +894,12 @@ class FilmChainFn(torch.autograd.Function):
         hip.film_chain_bwd_film(net1, s1, t1, M, d_res, hs[-1], zs, dzs, dfp, rowmax, gmax[:n_film + 1], d_x)
         d_cond = torch.empty(M, ld(cond), device=dev) if need_dcond else None
         want_map = need_dcond or train_w
-        dpres = [torch.empty(Mp, Hm, device=dev) for _ in range(n_map)] if want_map else None
+        if train_w:
+            dpres = [torch.empty(Mp, Hm, device=dev) for _ in range(n_map)]
+        elif want_map and hip.film_keepless(Hm) == "buffers":
+            dpres = [torch.empty(Mp, Hm, device=dev)] * n_map  # not kept: one buffer carries every layer's hand-off
+        else:
+            dpres = None
         if want_map:
             hip.film_chain_bwd_map(net2, s2, t2, M, dfp, rowmax, hs, dpres, d_cond, gmax[n_film + 1:])
         if not train_w:

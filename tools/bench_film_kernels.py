@@ -1,5 +1,5 @@
 """standalone times of the three FiLM-SIREN chain kernels (forward with saves, FiLM backward, mapping backward) at the step's sizes,
-one stream, HIP events: python tools/bench_film_kernels.py [ddf|illum] [reps]   (NSKY_LIB selects an experimental library build)"""
+trained (every weight-gradient operand kept) and frozen (none kept: hip.film_keepless), one stream, HIP events: python tools/bench_film_kernels.py [ddf|illum] [reps]   (NSKY_LIB selects an experimental library build)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -63,7 +63,13 @@ def main():
         dpres = [torch.empty(Mp, H, device=DEV) for _ in range(nm)]
         d_cond = torch.empty(M, cond.stride(0), device=DEV)
         t_bm = timeit(lambda: hip.film_chain_bwd_map(desc, packs[2][0], packs[2][1], M, dfp, rowmax, hs, dpres, d_cond, gmax[n_film + 1:]), reps)
-        print(f"{name}: M={M} H={H}  fwd {t_fwd*1e3:7.1f} us   bwd_film {t_bf*1e3:7.1f} us   bwd_map {t_bm*1e3:7.1f} us   sum {(t_fwd+t_bf+t_bm)*1e3:7.1f} us", flush=True)
+        print(f"{name}: M={M} H={H} trained  fwd {t_fwd*1e3:7.1f} us   bwd_film {t_bf*1e3:7.1f} us   bwd_map {t_bm*1e3:7.1f} us   sum {(t_fwd+t_bf+t_bm)*1e3:7.1f} us", flush=True)
+        regs = hip.film_keepless(H) == "registers"
+        ys_f, dpres_f = (None, None) if regs else ([ys[i % 2] for i in range(n_film)], [dpres[0]] * nm)
+        t_fwd = timeit(lambda: hip.film_chain_fwd(desc, packs[0][0], packs[0][1], cond, x, M, hs, zs, ys_f, res), reps)
+        t_bf = timeit(lambda: hip.film_chain_bwd_film(desc, packs[1][0], packs[1][1], M, d_res, hs[-1], zs, None, dfp, rowmax, gmax[:n_film + 1], d_x), reps)
+        t_bm = timeit(lambda: hip.film_chain_bwd_map(desc, packs[2][0], packs[2][1], M, dfp, rowmax, hs, dpres_f, d_cond, gmax[n_film + 1:]), reps)
+        print(f"{name}: M={M} H={H} frozen   fwd {t_fwd*1e3:7.1f} us   bwd_film {t_bf*1e3:7.1f} us   bwd_map {t_bm*1e3:7.1f} us   sum {(t_fwd+t_bf+t_bm)*1e3:7.1f} us", flush=True)
 
 
 if __name__ == "__main__":
