@@ -182,7 +182,7 @@ int nsky_film_chain_bwd_map(const nsky_film_net* net, const void* stream_buf, co
                             int32_t ldcond, float* gmax, nsky_stream_t stream);
 /* SDF value chain: SDFAlbedoField.get_sdf_at_pos (neusky/fields/sdf_albedo_field.py:169-174; nerfstudio SDFField geometry network:
  * Linear + Softplus(beta) twice, then the sdf row of the last Linear) for M encode rows, forward and backward as one kernel each
- * (same weight-stream machinery as the FiLM-SIREN chain: nsky_sdf_stream_layout / nsky_sdf_pack once per optimizer step and
+ * (csrc/sdf_chain.hip; the weight-stream machinery of the FiLM-SIREN chain, csrc/chain.h: nsky_sdf_stream_layout / nsky_sdf_pack once per optimizer step and
  * direction, 0 = forward, 1 = backward).  a0_save / a1_save: the two softplus outputs, tile-native [ceil32(M), hidden] (scratch in
  * inference).  _bwd: g_sdf [M] -> dz1 / dz0 (tile-native pre-activation gradients: the operands of the weight gradients,
  * nsky_wgrad_native), dE [M, ldE] (optional), dw2 [hidden] += sum_rows g a1 and db2 [1] += sum_rows g (optional), gmax [2] = max |dz1|, max |dz0| (caller

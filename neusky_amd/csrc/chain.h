@@ -1,8 +1,8 @@
-// Shared machinery of the chain kernels (film_chain.hip: FiLM-SIREN and the sdf value chain; field_chain.hip: the SDF / albedo
-// field): packed weight stream (one tile = 32 output features x K as fp16 hi + residual planes in MFMA-fragment order),
+// Shared machinery of the chain kernels (film_chain.hip: FiLM-SIREN; sdf_chain.hip: the sdf value chain; field_chain.hip: the
+// SDF / albedo field): packed weight stream (one tile = 32 output features x K as fp16 hi + residual planes in MFMA-fragment order),
 // the LDS ring it is streamed through by global_load_lds_dwordx4, the register-resident product, the fp16 split helpers and
 // the tile-native activation layout.  Everything here is device-inline code in an anonymous namespace: each translation unit
-// gets its own copy.
+// gets its own copy (so does the host side: device_cus() caches the CU count once per translation unit).
 #pragma once
 #include "common.h"
 #include "../../include/neusky_hip.h"
@@ -107,27 +107,17 @@ struct WStream {
 };
 
 // PW = 1 KB pieces of a 16 KB group this wave moves: 4 with four waves per workgroup, 2 with eight
+// WRAP: the stream is walked cyclically: the ring slot follows the running group count, the source wraps
 // RG: groups in the LDS ring (a power of two; 8 = 128 KB with one workgroup per CU, 4 = 64 KB with two)
-template <int PW = 4, int RG = RING_GROUPS>
-__device__ __forceinline__ void ws_issue(const WStream& w, int group) {
-  const unsigned char* s = w.src + (long)group * GROUP;
+template <int PW = 4, bool WRAP = false, int RG = RING_GROUPS>
+__device__ __forceinline__ void ws_issue(WStream& w, int group) {
+  const unsigned char* s = w.src + (long)(WRAP ? w.sg : group) * GROUP;
   const uint32_t d = w.dst + (uint32_t)(group & (RG - 1)) * GROUP;
 #pragma unroll
   for (int p = 0; p < PW; ++p) {
     glds16(s + p * 1024, d + p * 1024);
   }
-}
-
-// the same for a stream that is walked cyclically: the ring slot follows the running group count, the source wraps
-template <int PW = 4, int RG = RING_GROUPS>
-__device__ __forceinline__ void ws_issue_wrap(WStream& w, int group) {
-  const unsigned char* s = w.src + (long)w.sg * GROUP;
-  const uint32_t d = w.dst + (uint32_t)(group & (RG - 1)) * GROUP;
-#pragma unroll
-  for (int p = 0; p < PW; ++p) {
-    glds16(s + p * 1024, d + p * 1024);
-  }
-  w.sg = w.sg + 1 == w.total ? 0 : w.sg + 1;
+  if (WRAP) w.sg = w.sg + 1 == w.total ? 0 : w.sg + 1;
 }
 
 // The two fragment registers are read-write operands of BOTH the request and the wait: the compiler sees one value that is
@@ -162,24 +152,12 @@ __device__ __forceinline__ uint32_t ws_addr(const WStream& w, int group, int sla
   return w.lds_lane + (uint32_t)(group & (RG - 1)) * GROUP + slab * SLAB;
 }
 
-template <int PW = 4>
-__device__ __forceinline__ void ws_begin(WStream& w) {
-#pragma unroll
-  for (int g = 0; g < RING_GROUPS; ++g) ws_issue<PW>(w, g);
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PW * (RING_GROUPS - 2)) : "memory");  // groups 0 and 1 landed
-  w.g = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { w.ch[j] = (_Float16)0.0f; w.cl[j] = (_Float16)0.0f; }
-  frag_read(w.ch, w.cl, ws_addr(w, 0, 0));
-  frag_wait<0>(w.ch, w.cl);
-}
-
-template <int PW = 4, int RG = RING_GROUPS>
-__device__ __forceinline__ void ws_begin_wrap(WStream& w, int total_groups) {
+template <int PW = 4, bool WRAP = false, int RG = RING_GROUPS>
+__device__ __forceinline__ void ws_begin(WStream& w, int total_groups) {  // total_groups: read by WRAP streams only
   w.total = total_groups;
   w.sg = 0;
 #pragma unroll
-  for (int g = 0; g < RG; ++g) ws_issue_wrap<PW, RG>(w, g);
+  for (int g = 0; g < RG; ++g) ws_issue<PW, WRAP, RG>(w, g);
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PW * (RG - 2)) : "memory");  // groups 0 and 1 landed
   w.g = 0;
 #pragma unroll
@@ -188,11 +166,30 @@ __device__ __forceinline__ void ws_begin_wrap(WStream& w, int total_groups) {
   frag_wait<0>(w.ch, w.cl);
 }
 
+// A kernel's stream from its first DMA issue to its last: ws_open behind the __syncthreads() that publishes the kernel's LDS tables,
+// ws_close as its last statement.  ws_open first waits until every memory operation the compiler knows about is done: the DMA pieces
+// are hidden from its bookkeeping and counted by hand on the one in-order vector-memory counter, so the counted waits of the stream
+// hold only if nothing but pieces (and hidden loads counted with them) is in flight from the first issue on.
+// stream: the packed groups; smem: the ring (RG groups, first in the kernel's LDS); total_groups: length of a WRAP stream -- a WRAP
+// caller MUST pass it (the default serves the streams that are walked once and never read it; with 0 the source would never wrap).
+// DRAINED: the caller vouches that nothing is pending and the wait is left out (film_fwd_kernel: the table copy, its only loads, has
+// been consumed by the LDS stores in front of the barrier; with the wait its time fell outside the spread of two parent runs).
+template <int PW = 4, bool WRAP = false, int RG = RING_GROUPS, bool DRAINED = false>
+__device__ __forceinline__ void ws_open(WStream& w, const unsigned char* stream, unsigned char* smem, int wave, int lane, int total_groups = 0) {
+  if (!DRAINED) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  w.src = stream + wave * (PW * 1024) + lane * 16;
+  w.dst = (uint32_t)(uintptr_t)smem + wave * (PW * 1024);
+  w.lds_lane = (uint32_t)(uintptr_t)smem + lane * 16;
+  ws_begin<PW, WRAP, RG>(w, total_groups);
+}
+__device__ __forceinline__ void ws_close() {
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the tail groups of the ring are still landing
+}
+
 template <int PW = 4, bool WRAP = false, int RG = RING_GROUPS>
 __device__ __forceinline__ void ws_transition(WStream& w, int from_group) {
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PW * (RG - 3)) : "memory");
-  if (WRAP) ws_issue_wrap<PW, RG>(w, from_group + RG);
-  else ws_issue<PW, RG>(w, from_group + RG);
+  ws_issue<PW, WRAP, RG>(w, from_group + RG);
 }
 
 // what a wave WITHOUT a row tile does in place of a product (the last round of a persistent workgroup): its share of the group
@@ -288,6 +285,20 @@ __device__ __forceinline__ void product_pair(WStream& w, const f16x8 (&bh)[4], c
   step(4, a1); step(5, a1); step(6, a1); step(7, a1);
   frag_settle(w.ch, w.cl, fh[KS % 3], fl[KS % 3]);
   w.g = g0 + 1;
+}
+
+// A tile's product for a wave WITH a row tile, or (active false) its share of the ring's hand-shakes: a wave that runs one barrier
+// fewer than its workgroup hangs the CU, so the two are paired here and nowhere else.  active is wave-uniform: a constant (the
+// ACTIVE instantiations of the tile functions) or a run-time value (the sdf chain's tail workgroups).  ZERO: the accumulator starts
+// at zero (false: the product adds to what it holds).
+template <int KS, int PW = 4, bool WRAP = false, int RG = RING_GROUPS, bool ZERO = true>
+__device__ __forceinline__ void prod(WStream& w, bool active, const f16x8 (&bh)[KS], const f16x8 (&bl)[KS], f32x16& acc) {
+  if (ZERO) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+  }
+  if (active) product<KS, PW, WRAP, RG>(w, bh, bl, acc);
+  else product_skip<KS, PW, WRAP, RG>(w);
 }
 
 // the same over the first ksn (wave-uniform, run time; >= 1) of KS k-steps: the mapping network's first layer.  No read-ahead
@@ -473,11 +484,14 @@ __device__ __forceinline__ void hidden_load4_nt(f32x4& q, const float* p) {
   asm volatile("global_load_dwordx4 %0, %1, off nt" : "+v"(q) : "v"(p) : "memory");
 }
 
-// planes of KS k-steps from NT tiles this wave stored (scaled by the row maximum m): the lane that stored a piece loads it
-template <int NT>
-__device__ __forceinline__ float planes_from_tiles(const float* blk, int lane, float m, f16x8 (&ph)[2 * NT], f16x8 (&pl)[2 * NT]) {
-  float inv;
-  const float s = row_scale(m, inv);
+// planes of 2 NT k-steps from NT tiles this wave stored (the lane that stored a piece loads it).  x is the row maximum: the tiles are
+// scaled by the power of two that suits it (row_scale) and 1 / scale is returned.  SCALED (planes_scaled below, the only user of the
+// flag): x is the scale itself, a power of two the caller formed, and the return value (1) means nothing.  One body with a flag, not
+// row_scale followed by a call of planes_scaled: that form schedules the loads of every caller differently.
+template <int NT, bool SCALED = false>
+__device__ __forceinline__ float planes_from_tiles(const float* blk, int lane, float x, f16x8 (&ph)[2 * NT], f16x8 (&pl)[2 * NT]) {
+  float inv = 1.0f;
+  const float s = SCALED ? x : row_scale(x, inv);
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     float v[16];
@@ -496,13 +510,75 @@ __device__ __forceinline__ float planes_from_tiles(const float* blk, int lane, f
   }
   return inv;
 }
+template <int NT>
+__device__ __forceinline__ void planes_scaled(const float* blk, int lane, float s, f16x8 (&ph)[2 * NT], f16x8 (&pl)[2 * NT]) {
+  planes_from_tiles<NT, true>(blk, lane, s, ph, pl);
+}
 
-__device__ __forceinline__ float softplus_b(float v, float beta, float inv_beta) {  // torch.nn.functional.softplus(beta, threshold 20)
+// softplus(beta; threshold 20: torch.nn.functional.softplus) and sigmoid(beta v) from one exp / rcp / log
+__device__ __forceinline__ void softplus_sig(float v, float beta, float inv_beta, float& sp, float& sg) {
   const float bv = beta * v;
   const float t = __expf(-fabsf(bv));
   const float u = 1.0f + t, um1 = u - 1.0f;
+  const float r = __builtin_amdgcn_rcpf(u);
   const float l = um1 == 0.0f ? t : __logf(u) * (t * __builtin_amdgcn_rcpf(um1));
-  return bv > 20.0f ? v : (fmaxf(bv, 0.0f) + l) * inv_beta;
+  sp = bv > 20.0f ? v : (fmaxf(bv, 0.0f) + l) * inv_beta;
+  sg = bv >= 0.0f ? r : t * r;
+}
+__device__ __forceinline__ float softplus_b(float v, float beta, float inv_beta) {  // the softplus alone
+  float sp, sg;
+  softplus_sig(v, beta, inv_beta, sp, sg);
+  return sp;
+}
+
+// A kernel's table of N4 float4 (film_pack_kernel's biases + tile scales) -> LDS by THREADS threads, all loads in flight at once.
+// A macro, not a function: through a function's parameters (the two pointers, a reference to the kernel argument, the LDS offset as
+// a template parameter: all tried) the first loads lose their scalar-base + 32-bit-offset form to 64-bit adds per lane.
+#define NSKY_STAGE_TABLE(N4, THREADS, table, lds, tid)                                                                  \
+  {                                                                                                                    \
+    float4 q[((N4) + (THREADS) - 1) / (THREADS)];                                                                      \
+    _Pragma("unroll") for (int i = 0; i < ((N4) + (THREADS) - 1) / (THREADS); ++i)                                     \
+      if (i * (THREADS) + (tid) < (N4)) q[i] = ldg4((table) + 4 * (i * (THREADS) + (tid)));                             \
+    _Pragma("unroll") for (int i = 0; i < ((N4) + (THREADS) - 1) / (THREADS); ++i)                                     \
+      if (i * (THREADS) + (tid) < (N4)) *reinterpret_cast<float4*>((lds) + 4 * (i * (THREADS) + (tid))) = q[i];         \
+  }
+
+// Tail workgroups of the EIGHT-wave kernels (the mapping backward, the sdf chain: two waves per SIMD, 256 batch rows share one weight
+// stream).  A launch of n wave tiles (32 rows each) on C CUs runs F = floor(n / (8 C)) C full workgroups of eight tiles; the
+// remaining R = n - 8 F tiles (less than one workgroup round) do not get a round of full workgroups on a few CUs: they are dealt k =
+// ceil(R / C) to a workgroup (T = ceil(R / k) "tail" workgroups, FIRST in the grid), whose other waves only take part in the ring's
+// hand-shakes (product_skip).  A tail workgroup is done sooner than a full one and the dispatcher hands its CU the next workgroup, so
+// the remainder costs its share of a round instead of a whole one (263 456 DDF rows = 8233 tiles: 1024 full + 41 one-tile workgroups
+// instead of 1030 full ones = five rounds of time for 4.02 of work).
+struct TailPlan { int full_wgs, tail_wgs, tail_k; };
+inline TailPlan tail_plan(long n_tiles, int cus) {
+  TailPlan p;
+  p.full_wgs = (int)(n_tiles / (8L * cus)) * cus;
+  const long rem = n_tiles - 8L * p.full_wgs;
+  if (rem >= 8L * cus - cus) {  // nearly a whole round: full workgroups
+    p.full_wgs += (int)((rem + 7) / 8); p.tail_wgs = 0; p.tail_k = 0;
+    return p;
+  }
+  p.tail_k = (int)((rem + cus - 1) / cus);
+  p.tail_wgs = p.tail_k ? (int)((rem + p.tail_k - 1) / p.tail_k) : 0;
+  return p;
+}
+// wave tile of this wave, or -1 (a wave of a tail workgroup without one)
+__device__ __forceinline__ long tail_tile(int full_wgs, int tail_wgs, int tail_k, long n_tiles, int wave) {
+  const int b = blockIdx.x;
+  if (b >= tail_wgs) return (long)(b - tail_wgs) * 8 + wave;
+  const long t = 8L * full_wgs + (long)b * tail_k + wave;
+  return (wave < tail_k && t < n_tiles) ? t : -1;
+}
+
+inline int device_cus() {
+  static int cus = [] {
+    hipDeviceProp_t p;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 256;
+    return p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+  }();
+  return cus;
 }
 
 }  // namespace

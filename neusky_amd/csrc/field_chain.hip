@@ -103,55 +103,6 @@ __device__ __forceinline__ void quad_gather_all(const float (&mine)[4], float (&
   }
 }
 
-// softplus(beta; threshold 20) and sigmoid(beta v) from one exp / rcp / log
-__device__ __forceinline__ void softplus_sig(float v, float beta, float inv_beta, float& sp, float& sg) {
-  const float bv = beta * v;
-  const float t = __expf(-fabsf(bv));
-  const float u = 1.0f + t, um1 = u - 1.0f;
-  const float r = __builtin_amdgcn_rcpf(u);
-  const float l = um1 == 0.0f ? t : __logf(u) * (t * __builtin_amdgcn_rcpf(um1));
-  sp = bv > 20.0f ? v : (fmaxf(bv, 0.0f) + l) * inv_beta;
-  sg = bv >= 0.0f ? r : t * r;
-}
-
-// planes of 2 NT k-steps from NT tiles this wave stored, scaled by s (the caller's power of two)
-template <int NTT>
-__device__ __forceinline__ void planes_scaled(const float* blk, int lane, float s, f16x8 (&ph)[2 * NTT], f16x8 (&pl)[2 * NTT]) {
-#pragma unroll
-  for (int t = 0; t < NTT; ++t) {
-    float v[16];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 q = ldg4_nt(blk + t * 1024 + g * 256 + lane * 4);
-      v[4 * g] = q.x; v[4 * g + 1] = q.y; v[4 * g + 2] = q.z; v[4 * g + 3] = q.w;
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      float x8[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x8[j] = v[8 * u + j] * s;
-      split8(x8, ph[2 * t + u], pl[2 * t + u]);
-    }
-  }
-}
-
-template <int KSN, bool ACTIVE, bool ZERO = true>
-__device__ __forceinline__ void prod(WStream& ws, const f16x8 (&bh)[KSN], const f16x8 (&bl)[KSN], f32x16& acc) {
-  if (ZERO) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-  }
-  if (ACTIVE) product<KSN, PW, true, RG>(ws, bh, bl, acc);
-  else product_skip<KSN, PW, true, RG>(ws);
-}
-
-__device__ __forceinline__ void ws_setup(WStream& ws, const unsigned char* stream, unsigned char* smem, int wave, int lane, int total_groups) {
-  ws.src = stream + wave * (PW * 1024) + lane * 16;
-  ws.dst = (uint32_t)(uintptr_t)smem + wave * (PW * 1024);
-  ws.lds_lane = (uint32_t)(uintptr_t)smem + lane * 16;
-  ws_begin_wrap<PW, RG>(ws, total_groups);
-}
-
 // =====================================================================================================================
 // geometry network forward, quad layout.  Stream: W0 (NT tiles, K = in_dim), W1 (NT tiles, K = H).
 struct GeoFwdArgs {
@@ -265,7 +216,7 @@ __device__ __forceinline__ void geo_fwd_tile(const GeoFwdArgs& a, WStream& ws, c
   float m = 0.0f, part_v = 0.0f, part_t = 0.0f;
   for (int t = 0; t < NT; ++t) {
     f32x16 acc;
-    prod<KS0, ACTIVE>(ws, eh, el, acc);
+    prod<KS0, PW, true, RG>(ws, ACTIVE, eh, el, acc);
     if (ACTIVE) geo_fwd_epilogue<false>(acc, e_inv * sl[t], bl + 32 * t, nullptr, beta, inv_beta, lane, a0blk + t * 1024, m, part_v, part_t);
   }
   f16x8 ah[KS], al[KS];
@@ -280,7 +231,7 @@ __device__ __forceinline__ void geo_fwd_tile(const GeoFwdArgs& a, WStream& ws, c
   m = 0.0f;
   for (int t = 0; t < NT; ++t) {
     f32x16 acc;
-    prod<KS, ACTIVE>(ws, ah, al, acc);
+    prod<KS, PW, true, RG>(ws, ACTIVE, ah, al, acc);
     if (ACTIVE) geo_fwd_epilogue<true>(acc, a_inv * sl[NT + t], bl + H + 32 * t, bl + 2 * H + 32 * t, beta, inv_beta, lane, a1blk + t * 1024, m, part_v, part_t);
   }
   if (ACTIVE) {
@@ -310,16 +261,15 @@ __global__ __launch_bounds__(THREADS, 2) void field_geo_fwd_kernel(const GeoFwdA
   if (tid == 0) bl[3 * H] = a.net.b_sdf ? a.net.b_sdf[0] : 0.0f;
   for (int i = tid; i < 2 * NT; i += THREADS) sl[i] = a.scales[i];
   __syncthreads();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   WStream ws;
-  ws_setup(ws, a.stream, smem, wave, lane, a.total_groups);
+  ws_open<PW, true, RG>(ws, a.stream, smem, wave, lane, a.total_groups);
   const long G = gridDim.x;
   for (long base = 0; base < a.n_tiles; base += WAVES * G) {
     const long tile = base + wave * G + blockIdx.x;
     if (tile < a.n_tiles) geo_fwd_tile<KS0, true>(a, ws, bl, sl, tile, lane);
     else geo_fwd_tile<KS0, false>(a, ws, bl, sl, 0, lane);
   }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  ws_close();
 }
 
 // =====================================================================================================================
@@ -378,7 +328,7 @@ __device__ __forceinline__ void col_fwd_tile(const ColFwdArgs& a, WStream& ws, c
   float m = 0.0f;
   for (int t = 0; t < NT; ++t) {
     f32x16 acc;
-    prod<KS, ACTIVE>(ws, ph, pl, acc);
+    prod<KS, PW, true, RG>(ws, ACTIVE, ph, pl, acc);
     if (ACTIVE) {
       const float inv = p_inv * sl[t];
       float v[16];
@@ -433,8 +383,8 @@ __device__ __forceinline__ void col_fwd_tile(const ColFwdArgs& a, WStream& ws, c
   m = 0.0f;
   for (int t = 0; t < NT; ++t) {
     f32x16 acc;
-    prod<KS, ACTIVE>(ws, ph, pl, acc);            // the tile's first two groups: the 256 feature columns
-    prod<KSX, ACTIVE, false>(ws, xh, xl, acc);    // its third group: columns 256 .. 303 (same row scale, same accumulator)
+    prod<KS, PW, true, RG>(ws, ACTIVE, ph, pl, acc);            // the tile's first two groups: the 256 feature columns
+    prod<KSX, PW, true, RG, false>(ws, ACTIVE, xh, xl, acc);    // its third group: columns 256 .. 303 (same row scale, same accumulator)
     if (ACTIVE) {
       const float inv = p_inv * sl[NT + t];
       float v[16];
@@ -460,7 +410,7 @@ __device__ __forceinline__ void col_fwd_tile(const ColFwdArgs& a, WStream& ws, c
   float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
   for (int t = 0; t < NT; ++t) {
     f32x16 acc;
-    prod<KS, ACTIVE>(ws, ph, pl, acc);
+    prod<KS, PW, true, RG>(ws, ACTIVE, ph, pl, acc);
     if (ACTIVE) {
       const float inv = p_inv * sl[2 * NT + t];
       float v[16];
@@ -504,16 +454,15 @@ __global__ __launch_bounds__(THREADS, 2) void field_colour_fwd_kernel(const ColF
   if (tid < 3) bl[6 * H + tid] = a.net.bc2[tid];
   for (int i = tid; i < 3 * NT; i += THREADS) sl[i] = a.scales[i];
   __syncthreads();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   WStream ws;
-  ws_setup(ws, a.stream, smem, wave, lane, a.total_groups);
+  ws_open<PW, true, RG>(ws, a.stream, smem, wave, lane, a.total_groups);
   const long G = gridDim.x;
   for (long base = 0; base < a.n_tiles; base += WAVES * G) {
     const long tile = base + wave * G + blockIdx.x;
     if (tile < a.n_tiles) col_fwd_tile<true>(a, ws, bl, sl, tile, lane);
     else col_fwd_tile<false>(a, ws, bl, sl, 0, lane);
   }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  ws_close();
 }
 
 // =====================================================================================================================
@@ -595,7 +544,7 @@ __device__ __forceinline__ void col_bwd_tile(const ColBwdArgs& a, WStream& ws, c
 #pragma unroll
       for (int g = 0; g < 4; ++g) hidden_load4(cq[g], a.c0 + (tile * NT + u) * 1024 + g * 256 + lane * 4);
     }
-    prod<KS, ACTIVE>(ws, ph, pl, acc);
+    prod<KS, PW, true, RG>(ws, ACTIVE, ph, pl, acc);
     if (ACTIVE) {
       hidden_wait<((KS + GSLABS - 1) / GSLABS) * PW>(cq);
       const float inv = p_inv * sl[u];
@@ -618,7 +567,7 @@ __device__ __forceinline__ void col_bwd_tile(const ColBwdArgs& a, WStream& ws, c
   m = 0.0f;
   for (int u = 0; u < NT + 2; ++u) {
     f32x16 acc;
-    prod<KS, ACTIVE>(ws, ph, pl, acc);
+    prod<KS, PW, true, RG>(ws, ACTIVE, ph, pl, acc);
     if (ACTIVE) {
       const float inv = p_inv * sl[NT + u];
       if (u < NT) {
@@ -647,7 +596,7 @@ __device__ __forceinline__ void col_bwd_tile(const ColBwdArgs& a, WStream& ws, c
   // ---- d a1 (value rows) = W2f^T dfeat
   for (int u = 0; u < NT; ++u) {
     f32x16 acc;
-    prod<KS, ACTIVE>(ws, ph, pl, acc);
+    prod<KS, PW, true, RG>(ws, ACTIVE, ph, pl, acc);
     if (ACTIVE) {
       const float inv = p_inv * sl[2 * NT + 2 + u];
       float dv[16];
@@ -668,16 +617,15 @@ __global__ __launch_bounds__(THREADS, 2) void field_colour_bwd_kernel(const ColB
     for (int k = 0; k < 3; ++k) wl[k * H + i] = a.net.wc2[(long)k * a.net.ldc2 + i];
   for (int i = tid; i < 3 * NT + 2; i += THREADS) sl[i] = a.scales[i];
   __syncthreads();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   WStream ws;
-  ws_setup(ws, a.stream, smem, wave, lane, a.total_groups);
+  ws_open<PW, true, RG>(ws, a.stream, smem, wave, lane, a.total_groups);
   const long G = gridDim.x;
   for (long base = 0; base < a.n_tiles; base += WAVES * G) {
     const long tile = base + wave * G + blockIdx.x;
     if (tile < a.n_tiles) col_bwd_tile<true>(a, ws, wl, sl, tile, lane);
     else col_bwd_tile<false>(a, ws, wl, sl, 0, lane);
   }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  ws_close();
 }
 
 // =====================================================================================================================
@@ -780,7 +728,7 @@ __device__ __forceinline__ void geo_bwd_tile(const GeoBwdArgs& a, WStream& ws, c
 #pragma unroll
       for (int g = 0; g < 4; ++g) hidden_load4(aq[g], a.a0q + (tile * NT + u) * 1024 + g * 256 + lane * 4);
     }
-    prod<KS, ACTIVE>(ws, ph, pl, acc);
+    prod<KS, PW, true, RG>(ws, ACTIVE, ph, pl, acc);
     if (ACTIVE) {
       hidden_wait<((KS + GSLABS - 1) / GSLABS) * PW>(aq);
       const float inv = p_inv * sl[u];
@@ -805,7 +753,7 @@ __device__ __forceinline__ void geo_bwd_tile(const GeoBwdArgs& a, WStream& ws, c
   // ---- d(encode rows) = W0^T D0, stacked layout
   for (int u = 0; u < ct; ++u) {
     f32x16 acc;
-    prod<KS, ACTIVE>(ws, ph, pl, acc);
+    prod<KS, PW, true, RG>(ws, ACTIVE, ph, pl, acc);
     if (ACTIVE && live && a.dET) {
       const float inv = p_inv * sl[NT + u];
       float* out = a.dET + ((long)j * a.N + n) * a.ldE;
@@ -836,16 +784,15 @@ __global__ __launch_bounds__(THREADS, 2) void field_geo_bwd_kernel(const GeoBwdA
   for (int i = tid; i < H; i += THREADS) wl[i] = a.net.w_sdf[i];
   for (int i = tid; i < NT + ct; i += THREADS) sl[i] = a.scales[i];
   __syncthreads();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   WStream ws;
-  ws_setup(ws, a.stream, smem, wave, lane, a.total_groups);
+  ws_open<PW, true, RG>(ws, a.stream, smem, wave, lane, a.total_groups);
   const long G = gridDim.x;
   for (long base = 0; base < a.n_tiles; base += WAVES * G) {
     const long tile = base + wave * G + blockIdx.x;
     if (tile < a.n_tiles) geo_bwd_tile<true>(a, ws, wl, sl, tile, lane, ct);
     else geo_bwd_tile<false>(a, ws, wl, sl, 0, lane, ct);
   }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  ws_close();
 }
 
 // =====================================================================================================================
@@ -939,13 +886,7 @@ int check_field_net(const nsky_field_net* n, const char* who) {
 }
 
 int persistent_grid(int n_tiles) {
-  static int cus = [] {
-    hipDeviceProp_t p;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 256;
-    return p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-  }();
-  const int wgs = (n_tiles + WAVES - 1) / WAVES;
+  const int cus = device_cus(), wgs = (n_tiles + WAVES - 1) / WAVES;
   return wgs < cus * WGS_PER_CU ? wgs : cus * WGS_PER_CU;
 }
 
