@@ -9,7 +9,12 @@ pids=""
 for f in $SRCS; do
   o="build/$(basename $f).o"
   OBJS="$OBJS $o"
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ include/neusky_hip.h -nt "$o" ] || [ neusky_amd/csrc/common.h -nt "$o" ] || [ neusky_amd/csrc/chain.h -nt "$o" ]; then
+  stale=""
+  # any header may reach any object: every csrc/*.h and the public header count
+  for h in "$f" include/neusky_hip.h neusky_amd/csrc/*.h; do
+    if [ ! -f "$o" ] || [ "$h" -nt "$o" ]; then stale=1; break; fi
+  done
+  if [ -n "$stale" ]; then
     EXTRA=""
     # attention.hip: scalar (SGPR) operands feed plain v_fmac; the SLP vectoriser's v_pk_fma_f32 needs them copied into VGPR pairs first
     case "$f" in *attention.hip) EXTRA="-fno-slp-vectorize";; esac

@@ -134,9 +134,8 @@ int nsky_weighted_colsum_f32(const float* X, int32_t M, int32_t N, int32_t ldx, 
  *        reads a layer's tiles back before it stores the next layer's).  A mix of NULL and non-NULL entries is an error.
  *        Products are fp32-grade (three fp16 MFMAs on power-of-two pre-scaled hi / residual planes, fp32 accumulate).
  *   Tile-native layout of a [rows, width] fp32 matrix (rows padded to a multiple of 32, width % 32 == 0): 32 x 32 blocks of
- *        4 KB, block (R, t) at float offset (R * (width / 32) + t) * 1024; inside a block element (row c, feature f) at
- *        (f / 8) * 256 + (c + 32 * ((f / 4) & 1)) * 4 + (f & 3) -- the accumulator layout of v_mfma_f32_32x32x16, so the
- *        chain kernels move a tile with four 1 KB-contiguous wave instructions.  nsky_gemm_f32 reads such operands with
+ *        4 KB in the accumulator order of v_mfma_f32_32x32x16; the element offsets are defined in
+ *        neusky_amd/csrc/numerics.h (native_offset).  nsky_gemm_f32 reads such operands with
  *        a_native_nt / b_native_nt = width / 32 (weight gradients).
  */
 #define NSKY_FILM_MAX_LAYERS 12

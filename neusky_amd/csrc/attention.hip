@@ -16,7 +16,7 @@
 //   backward, rows : ds_n = p_n (dp_n - D), D = dO . O (the flash-attention identity, with the combined output), dq~ = sum_n ds_n K~_n
 //   backward, tokens: thread = token of one (camera, head), K~_n, V~_n and their gradients in registers; the camera's rows are staged
 //                    64 at a time in LDS by coalesced loads: dV~_n = sum_rows p_n dO~, dK~_n = sum_rows ds_n q~ -- no cross-lane reduction
-#include "common.h"
+#include "numerics.h"
 #include "../../include/neusky_hip.h"
 
 namespace {
@@ -114,35 +114,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_core_fwd_kernel(const AttnAr
 // the k-step: the A fragments are packed with the same slot order), so the probabilities never leave the registers.  A row's maximum
 // and sum are register reductions plus one exchange with lane c + 32.  A head's fragments are packed by the whole workgroup from the
 // fp32 K~ / V~ (loaded one head ahead, into registers, under the previous head's products).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int MF_WAVES = 4, MF_THREADS = 64 * MF_WAVES, MF_ROWS = 32 * MF_WAVES;
 constexpr int MF_KF = 4 * 3, MF_VF = 2 * 8;  // fragments (hi + lo pairs) of K~ and of V~^T per head
-
-__device__ __forceinline__ void split8h(const float (&x)[8], f16x8& hi, f16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const _Float16 xh = (_Float16)x[j];
-    hi[j] = xh;
-    lo[j] = (_Float16)(x[j] - (float)xh);
-  }
-}
-
-// power-of-two scale s with m s in [2^14, 2^15) (the fp16 residual of every element within 2^-13 of the largest stays a normal
-// number: the matrix cores flush fp16 subnormals), inv = 1 / s
-__device__ __forceinline__ float pow2_scale(float m, float& inv) {
-  if (!(m > 0.0f) || !(m < 3.0e38f)) { inv = 1.0f; return 1.0f; }
-  int e;
-  (void)frexpf(m, &e);
-  e = max(-100, min(100, e));
-  inv = ldexpf(1.0f, e - 15);
-  return ldexpf(1.0f, 15 - e);
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 __global__ __launch_bounds__(MF_THREADS, 2) void attn_core_fwd_mfma_kernel(const AttnArgs a) {
   __shared__ f16x8 sK[MF_KF * 2 * 64];  // 24 KB: [token tile][k-step][hi, lo][lane]
@@ -202,7 +175,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void attn_core_fwd_mfma_kernel(const
       const int item = tid + MF_THREADS * i, f = item >> 6, l = item & 63;
       const float x[8] = {rk[i][0].x * k_s, rk[i][0].y * k_s, rk[i][0].z * k_s, rk[i][0].w * k_s, rk[i][1].x * k_s, rk[i][1].y * k_s, rk[i][1].z * k_s, rk[i][1].w * k_s};
       f16x8 hi, lo;
-      split8h(x, hi, lo);
+      split8(x, hi, lo);
       sK[(2 * f) * 64 + l] = hi;
       sK[(2 * f + 1) * 64 + l] = lo;
     }
@@ -223,7 +196,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void attn_core_fwd_mfma_kernel(const
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[j] = (dim < E && (f & 7) < n_ks) ? sR[(t0 + 8 * (j >> 2) + (j & 3)) * E + dim] : 0.0f;
       f16x8 hi, lo;
-      split8h(x, hi, lo);
+      split8(x, hi, lo);
       sV[(2 * f) * 64 + l] = hi;
       sV[(2 * f + 1) * 64 + l] = lo;
     }
@@ -252,7 +225,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void attn_core_fwd_mfma_kernel(const
           x[j] = q8[j] * coef[p];
           asm volatile("" : "+v"(x[j]));
         }
-        split8h(x, qh[p], ql[p]);
+        split8(x, qh[p], ql[p]);
       }
     }
     // ---- scores (token tiles without a token are skipped: wave-uniform branches)
@@ -310,7 +283,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void attn_core_fwd_mfma_kernel(const
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = s[ks >> 1][8 * (ks & 1) + j];
         f16x8 ph, pl;
-        split8h(x, ph, pl);
+        split8(x, ph, pl);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
           const f16x8 ah = sV[(2 * (dt * 8 + ks)) * 64 + lane], al = sV[(2 * (dt * 8 + ks) + 1) * 64 + lane];
@@ -412,9 +385,9 @@ __global__ __launch_bounds__(MB_THREADS, 1) void attn_core_bwd_rows_mfma_kernel(
         const float xk[8] = {rk[i][0].x * k_s, rk[i][0].y * k_s, rk[i][0].z * k_s, rk[i][0].w * k_s, rk[i][1].x * k_s, rk[i][1].y * k_s, rk[i][1].z * k_s, rk[i][1].w * k_s};
         const float xv[8] = {rv[i][0].x * v_s, rv[i][0].y * v_s, rv[i][0].z * v_s, rv[i][0].w * v_s, rv[i][1].x * v_s, rv[i][1].y * v_s, rv[i][1].z * v_s, rv[i][1].w * v_s};
         f16x8 hi, lo;
-        split8h(xk, hi, lo);
+        split8(xk, hi, lo);
         sKt[(2 * f) * 64 + l] = hi; sKt[(2 * f + 1) * 64 + l] = lo;
-        split8h(xv, hi, lo);
+        split8(xv, hi, lo);
         sVt[(2 * f) * 64 + l] = hi; sVt[(2 * f + 1) * 64 + l] = lo;
       }
     }
@@ -434,7 +407,7 @@ __global__ __launch_bounds__(MB_THREADS, 1) void attn_core_bwd_rows_mfma_kernel(
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[j] = (dim < E && (f & 7) < n_ks) ? sR[(t0 + 8 * (j >> 2) + (j & 3)) * E + dim] : 0.0f;
       f16x8 hi, lo;
-      split8h(x, hi, lo);
+      split8(x, hi, lo);
       sKd[(2 * f) * 64 + l] = hi; sKd[(2 * f + 1) * 64 + l] = lo;
     }
     __syncthreads();
@@ -466,8 +439,8 @@ __global__ __launch_bounds__(MB_THREADS, 1) void attn_core_bwd_rows_mfma_kernel(
           x[j] = q8[j] * cq[p]; y[j] = g8[j] * cg[p];
           asm volatile("" : "+v"(x[j]), "+v"(y[j]));
         }
-        split8h(x, qh[p], ql[p]);
-        split8h(y, gh[p], gl[p]);
+        split8(x, qh[p], ql[p]);
+        split8(y, gh[p], gl[p]);
       }
     }
     const long st = ((long)u * a.nh + h) * a.D + (live ? d : a.D - 1);
@@ -523,7 +496,7 @@ __global__ __launch_bounds__(MB_THREADS, 1) void attn_core_bwd_rows_mfma_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = ds[ks >> 1][8 * (ks & 1) + j] * ds_s;
         f16x8 ph, pl;
-        split8h(x, ph, pl);
+        split8(x, ph, pl);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
           const f16x8 ah = sKd[(2 * (dt * 8 + ks)) * 64 + lane], al = sKd[(2 * (dt * 8 + ks) + 1) * 64 + lane];
@@ -595,8 +568,8 @@ __global__ __launch_bounds__(MT_THREADS, 2) void attn_core_bwd_tokens_mfma_kerne
     for (int p = 0; p < 3; ++p) {
       const float xk[8] = {kr[p][0].x * k_s, kr[p][0].y * k_s, kr[p][0].z * k_s, kr[p][0].w * k_s, kr[p][1].x * k_s, kr[p][1].y * k_s, kr[p][1].z * k_s, kr[p][1].w * k_s};
       const float xv[8] = {vr[p][0].x * v_s, vr[p][0].y * v_s, vr[p][0].z * v_s, vr[p][0].w * v_s, vr[p][1].x * v_s, vr[p][1].y * v_s, vr[p][1].z * v_s, vr[p][1].w * v_s};
-      split8h(xk, kh[p], kl[p]);
-      split8h(xv, vh[p], vl[p]);
+      split8(xk, kh[p], kl[p]);
+      split8(xv, vh[p], vl[p]);
     }
   }
   const float s_inv = k_inv * q_inv * a.scale, dp_inv = v_inv * g_inv;
@@ -661,7 +634,7 @@ __global__ __launch_bounds__(MT_THREADS, 2) void attn_core_bwd_tokens_mfma_kerne
 #pragma unroll
       for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(x[j]));  // the rounded product is what gets split (see the forward)
       f16x8 hi, lo;
-      split8h(x, hi, lo);
+      split8(x, hi, lo);
       dst[lane] = hi;
       dst[64 + lane] = lo;
     }
@@ -705,8 +678,8 @@ __global__ __launch_bounds__(MT_THREADS, 2) void attn_core_bwd_tokens_mfma_kerne
 #pragma unroll
         for (int j = 0; j < 8; ++j) { xp[j] = s[8 * kr + j]; xs[j] = dp[8 * kr + j]; }
         f16x8 ph, pl, dh_, dl_;
-        split8h(xp, ph, pl);
-        split8h(xs, dh_, dl_);
+        split8(xp, ph, pl);
+        split8(xs, dh_, dl_);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
           const f16x8 bh = sGB[(2 * (2 * dt + kr)) * 64 + lane], bl = sGB[(2 * (2 * dt + kr) + 1) * 64 + lane];
@@ -1057,12 +1030,6 @@ __device__ __forceinline__ void ln_store(float* p, const float (&v)[V]) {
     for (int i = 0; i < V / 4; ++i) reinterpret_cast<float4*>(p)[i] = make_float4(v[4 * i], v[V > 1 ? 4 * i + 1 : 0], v[V > 2 ? 4 * i + 2 : 0], v[V > 3 ? 4 * i + 3 : 0]);
   }
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 template <int V, bool BWD>
 __global__ __launch_bounds__(256) void add_layer_norm_kernel(const LnArgs a) {
   constexpr int W = 64 * V;

@@ -1,16 +1,15 @@
 // Shared machinery of the chain kernels (film_chain.hip: FiLM-SIREN; sdf_chain.hip: the sdf value chain; field_chain.hip: the
 // SDF / albedo field): packed weight stream (one tile = 32 output features x K as fp16 hi + residual planes in MFMA-fragment order),
-// the LDS ring it is streamed through by global_load_lds_dwordx4, the register-resident product, the fp16 split helpers and
-// the tile-native activation layout.  Everything here is device-inline code in an anonymous namespace: each translation unit
-// gets its own copy (so does the host side: device_cus() caches the CU count once per translation unit).
+// the LDS ring it is streamed through by global_load_lds_dwordx4 (common.h glds16), the register-resident product and the movers of
+// tile-native activations.  The arithmetic itself -- power-of-two scales, the fp16 hi / residual split, the sine / cosine and softplus
+// forms, the layout's definition -- is numerics.h, shared with the per-layer kernels.  Everything here is device-inline code in an
+// anonymous namespace: each translation unit gets its own copy (so does the host side: device_cus() caches the CU count once per
+// translation unit).
 #pragma once
-#include "common.h"
+#include "numerics.h"
 #include "../../include/neusky_hip.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int SLAB = 2048;
 constexpr int GSLABS = 8;
@@ -53,14 +52,9 @@ __device__ __forceinline__ void pack_tile(const TileDesc& d, unsigned char* __re
     __syncthreads();
   }
   m = red[0];
-  float sc = 1.0f;
-  if (m > 0.0f && m < 3.0e38f) {
-    int e;
-    (void)frexpf(m, &e);  // m < 2^e
-    e = max(-100, min(100, e));
-    sc = ldexpf(1.0f, 15 - e);  // m sc < 2^15
-  }
-  if (tid == 0) scales[blockIdx.x] = 1.0f / sc;
+  float inv;
+  const float sc = pow2_scale(m, inv);
+  if (tid == 0) scales[blockIdx.x] = 1.0f / sc;  // == inv (a power of two); the division is what the pack kernels have always run
   unsigned char* base = stream + d.group * GROUP + (long)d.slab0 * SLAB;
   const int KS = ksteps_of(d.K);
   for (int idx = tid; idx < KS * 64; idx += 256) {
@@ -80,13 +74,6 @@ __device__ __forceinline__ void pack_tile(const TileDesc& d, unsigned char* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
-  // LDS-DMA hidden from hipcc's waitcnt bookkeeping; M0 saved and restored inside the statement; completion counted by hand
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
 // Weight stream consumer.  Invariant while slabs of group g are being consumed: every piece of groups <= g + 1 has landed and
 // all four waves know it (barrier).  Fragment reads run TWO k-steps ahead of the MFMAs (three register buffers, rotated at
 // compile time inside a product) and one k-step ahead across a tile boundary, so an LDS round trip (~150-200 cycles under
@@ -328,36 +315,15 @@ __device__ __forceinline__ void product_dyn(WStream& w, int ksn, const f16x8 (&b
   w.g = g0 + ng;
 }
 
-__device__ __forceinline__ void split8(const float (&x)[8], f16x8& hi, f16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const _Float16 xh = (_Float16)x[j];
-    hi[j] = xh;
-    lo[j] = (_Float16)(x[j] - (float)xh);
-  }
-}
-
-// power-of-two scale s with m s < 2^15 (m = largest magnitude of the row); returns s, inv = 1 / s
+// pow2_scale of a batch row's largest magnitude (lanes l and l ^ 32 hold the two halves of the row)
 __device__ __forceinline__ float row_scale(float m, float& inv) {
-  m = fmaxf(m, __shfl_xor(m, 32, 64));  // lanes l and l ^ 32 hold the two halves of one batch row
-  if (!(m > 0.0f) || !(m < 3.0e38f)) {
-    inv = 1.0f;
-    return 1.0f;
-  }
-  int e;
-  (void)frexpf(m, &e);
-  e = max(-100, min(100, e));
-  inv = ldexpf(1.0f, e - 15);
-  return ldexpf(1.0f, 15 - e);
+  return pow2_scale(fmaxf(m, __shfl_xor(m, 32, 64)), inv);
 }
 
-__device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ldg4_nt(const float* p) {  // bypasses this CU's vector L1 (served by the XCD's L2)
   const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
   return make_float4(v[0], v[1], v[2], v[3]);
 }
-__device__ __forceinline__ void stg4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 // B planes of KS k-steps from an fp32 row [dim] (dim % 4 == 0, columns >= dim read as 0): returns 1 / scale
 template <int KS>
@@ -386,61 +352,7 @@ __device__ __forceinline__ float load_planes(const float* __restrict__ rowp, int
   return inv;
 }
 
-// sin with Cody-Waite reduction to [-pi/4, pi/4] + minimax polynomials (|err| < 2e-7 for |x| < 1e4), cos alongside
-__device__ __forceinline__ void sincos_cw(float x, float& s, float& c) {
-  const float k = rintf(x * 0.6366197723675814f);
-  float r = fmaf(-k, 1.5707962513e+00f, x);
-  r = fmaf(-k, 7.5497894159e-08f, r);
-  r = fmaf(-k, 5.3903029534e-15f, r);
-  const float r2 = r * r;
-  float sp = fmaf(r2, 2.7183114939e-06f, -1.9839334836e-04f);
-  sp = fmaf(sp, r2, 8.3333293855e-03f);
-  sp = fmaf(sp, r2, -1.6666666567e-01f);
-  sp = fmaf(sp * r2, r, r);
-  float cp = fmaf(r2, 2.4433157117e-05f, -1.3887316255e-03f);
-  cp = fmaf(cp, r2, 4.1666645683e-02f);
-  cp = fmaf(cp, r2, -0.5f);
-  cp = fmaf(cp, r2, 1.0f);
-  const int q = (int)k;
-  const float ss = (q & 1) ? cp : sp;
-  const float cc = (q & 1) ? sp : cp;
-  s = (q & 2) ? -ss : ss;
-  c = ((q + 1) & 2) ? -cc : cc;
-}
-
-// One of the two alone (the chain forward needs the sine, the FiLM backward the cosine): reduction by multiples of pi to
-// [-pi/2, pi/2] (two-term Cody-Waite: the fused multiply-adds keep the products exact, the third term of pi is k 1e-15), ONE
-// polynomial, the sign from the parity of k.  14 instructions instead of 23; |err| < 1.4e-7 on the reduced range (fitted and
-// checked in float32 arithmetic), the reduction adds |k| 1e-15.
-__device__ __forceinline__ float sin_cw(float x) {
-  const float k = rintf(x * 0.31830988618379067f);
-  float r = fmaf(-k, 3.14159274101257324f, x);
-  r = fmaf(-k, -8.74227766e-08f, r);
-  const float r2 = r * r;
-  float p = fmaf(r2, 2.6348141091e-06f, -1.9822760078e-04f);
-  p = fmaf(p, r2, 8.3332424983e-03f);
-  p = fmaf(p, r2, -1.6666665673e-01f);
-  const float s = fmaf(p * r2, r, r);
-  return __int_as_float(__float_as_int(s) ^ ((int)k << 31));
-}
-__device__ __forceinline__ float cos_cw(float x) {
-  const float k = rintf(x * 0.31830988618379067f);
-  float r = fmaf(-k, 3.14159274101257324f, x);
-  r = fmaf(-k, -8.74227766e-08f, r);
-  const float r2 = r * r;
-  float p = fmaf(r2, -2.6297973932e-07f, 2.4774602934e-05f);
-  p = fmaf(p, r2, -1.3888651738e-03f);
-  p = fmaf(p, r2, 4.1666660458e-02f);
-  p = fmaf(p, r2, -0.5f);
-  const float c = fmaf(p, r2, 1.0f);
-  return __int_as_float(__float_as_int(c) ^ ((int)k << 31));
-}
-
-// Tile-native activation layout ("native"): the [rows, width] matrix is cut into 32-row x 32-feature blocks of 4 KB, block
-// (R, t) at float offset (R * (width / 32) + t) * 1024, and inside a block element (row c, feature f) sits at
-// (f / 8) * 256 + (c + 32 * ((f / 4) & 1)) * 4 + (f & 3): exactly the accumulator layout of v_mfma_f32_32x32x16 (register
-// 4 g + q of lane (c, h) = feature 8 g + 4 h + q of batch row c), so a wave stores / loads a tile with four 1 KB-contiguous
-// float4 instructions and the lane that stored a piece is the lane that reads it back.  Rows are padded to a multiple of 32.
+// a wave's 32 x 32 tile of a tile-native matrix (numerics.h) <-> its accumulator registers: four 1 KB-contiguous float4 instructions
 __device__ __forceinline__ void store_tile(float* blk, int lane, const float (&v)[16]) {
 #pragma unroll
   for (int g = 0; g < 4; ++g) stg4(blk + g * 256 + lane * 4, make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]));
@@ -461,9 +373,7 @@ __device__ __forceinline__ void load_tile(const float* blk, int lane, float (&v)
 
 // largest magnitude of a gradient matrix -> device scalar (the weight-gradient GEMM pre-scales its fp16 split with it)
 __device__ __forceinline__ void publish_max(float* slot, float v, bool live_row, bool wave_live, int lane) {
-  v = live_row ? v : 0.0f;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  v = wave_max(live_row ? v : 0.0f);
   if (wave_live && lane == 0 && v > 0.0f) atomicMax(reinterpret_cast<unsigned int*>(slot), __float_as_uint(v));
 }
 
@@ -513,22 +423,6 @@ __device__ __forceinline__ float planes_from_tiles(const float* blk, int lane, f
 template <int NT>
 __device__ __forceinline__ void planes_scaled(const float* blk, int lane, float s, f16x8 (&ph)[2 * NT], f16x8 (&pl)[2 * NT]) {
   planes_from_tiles<NT, true>(blk, lane, s, ph, pl);
-}
-
-// softplus(beta; threshold 20: torch.nn.functional.softplus) and sigmoid(beta v) from one exp / rcp / log
-__device__ __forceinline__ void softplus_sig(float v, float beta, float inv_beta, float& sp, float& sg) {
-  const float bv = beta * v;
-  const float t = __expf(-fabsf(bv));
-  const float u = 1.0f + t, um1 = u - 1.0f;
-  const float r = __builtin_amdgcn_rcpf(u);
-  const float l = um1 == 0.0f ? t : __logf(u) * (t * __builtin_amdgcn_rcpf(um1));
-  sp = bv > 20.0f ? v : (fmaxf(bv, 0.0f) + l) * inv_beta;
-  sg = bv >= 0.0f ? r : t * r;
-}
-__device__ __forceinline__ float softplus_b(float v, float beta, float inv_beta) {  // the softplus alone
-  float sp, sg;
-  softplus_sig(v, beta, inv_beta, sp, sg);
-  return sp;
 }
 
 // A kernel's table of N4 float4 (film_pack_kernel's biases + tile scales) -> LDS by THREADS threads, all loads in flight at once.

@@ -12,10 +12,8 @@
 // t and written to the other LDS buffer after them, one barrier per tile.
 #include <stdlib.h>
 
-#include "common.h"
+#include "numerics.h"
 #include "../../include/neusky_hip.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -37,58 +35,6 @@ struct EpiCtx {
   const float* a_scale_max;    // device scalar: largest |A| (A is multiplied by a power of two that brings it to ~2^14; undone on C)
 };
 
-// float offset of element (row k, feature t), t % 4 == 0, of a tile-native matrix with nnt 32-feature tiles per row
-// (include/neusky_hip.h: 32 x 32 blocks in v_mfma_f32_32x32x16 accumulator order)
-__device__ __forceinline__ long native_offset(int k, int t, int nnt) {
-  return ((long)(k >> 5) * nnt + (t >> 5)) * 1024 + ((t & 31) >> 3) * 256 + ((k & 31) + 32 * ((t >> 2) & 1)) * 4;
-}
-__device__ __forceinline__ float pow2_scale_for(float m, float& inv) {  // m s < 2^15
-  if (!(m > 0.0f) || !(m < 3.0e38f)) { inv = 1.0f; return 1.0f; }
-  int e;
-  (void)frexpf(m, &e);
-  e = max(-100, min(100, e));
-  inv = ldexpf(1.0f, e - 15);
-  return ldexpf(1.0f, 15 - e);
-}
-
-// sin/cos with Cody-Waite reduction to [-pi/4, pi/4] and minimax polynomials (|err| < 2e-7 for |x| < 1e4):
-// ~20 VALU ops instead of the ocml slow path; used by the FiLM epilogues where |x| = |freq * z + phase| ~ 1e2.
-__device__ __forceinline__ void sincos_cw(float x, float& s, float& c) {
-  const float k = rintf(x * 0.6366197723675814f);  // x * 2/pi
-  float r = fmaf(-k, 1.5707962513e+00f, x);
-  r = fmaf(-k, 7.5497894159e-08f, r);
-  r = fmaf(-k, 5.3903029534e-15f, r);
-  const float r2 = r * r;
-  float sp = fmaf(r2, 2.7183114939e-06f, -1.9839334836e-04f);
-  sp = fmaf(sp, r2, 8.3333293855e-03f);
-  sp = fmaf(sp, r2, -1.6666666567e-01f);
-  sp = fmaf(sp * r2, r, r);
-  float cp = fmaf(r2, 2.4433157117e-05f, -1.3887316255e-03f);
-  cp = fmaf(cp, r2, 4.1666645683e-02f);
-  cp = fmaf(cp, r2, -0.5f);
-  cp = fmaf(cp, r2, 1.0f);
-  const int q = (int)k;
-  const float ss = (q & 1) ? cp : sp;
-  const float cc = (q & 1) ? sp : cp;
-  s = (q & 2) ? -ss : ss;
-  c = ((q + 1) & 2) ? -cc : cc;
-}
-
-// softplus_beta(v) and sigmoid(beta v) from ONE exponential: t = exp(-|beta v|) in (0, 1];
-// softplus = (max(beta v, 0) + log1p(t)) / beta, sigmoid = 1/(1+t) or t/(1+t).  log1p(t) = log(u) * t / (u - 1) with
-// u = fl(1 + t) cancels the rounding of 1 + t (few-ulp result for every t); hardware exp2/log2/rcp based.
-// torch.nn.functional.softplus semantics: beta v > 20 returns v itself (sdf_albedo_field.py geo network, beta = 100).
-__device__ __forceinline__ void softplus_sigmoid(float v, float beta, float inv_beta, float& sp, float& sg) {
-  const float bv = beta * v;
-  const float t = __expf(-fabsf(bv));
-  const float u = 1.0f + t;
-  const float rc = __builtin_amdgcn_rcpf(u);
-  const float um1 = u - 1.0f;
-  const float l = um1 == 0.0f ? t : __logf(u) * (t * __builtin_amdgcn_rcpf(um1));
-  sp = bv > 20.0f ? v : (fmaxf(bv, 0.0f) + l) * inv_beta;
-  sg = bv >= 0.0f ? rc : t * rc;
-}
-
 __device__ __forceinline__ void epilogue_store(const EpiCtx& e, float* C, int ldc, int row, int col, float acc) {
   float v = acc + (e.bias ? e.bias[col] : 0.0f);
   float r;
@@ -100,7 +46,7 @@ __device__ __forceinline__ void epilogue_store(const EpiCtx& e, float* C, int ld
     case NSKY_EPI_SIGMOID: r = e.p0 * sigmoidf_(v); break;
     case NSKY_EPI_SOFTPLUS: {
       float sg;
-      softplus_sigmoid(v, e.p0, 1.0f / e.p0, r, sg);
+      softplus_sig(v, e.p0, 1.0f / e.p0, r, sg);
       if (e.out1) e.out1[(long)row * e.ldout1 + col] = sg;
     } break;
     case NSKY_EPI_FILM: {
@@ -132,14 +78,11 @@ __device__ __forceinline__ void epilogue_store(const EpiCtx& e, float* C, int ld
   *dst = r;
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 // float4 epilogue: 4 consecutive columns of one row (all operands 16-byte aligned, ld % 4 == 0)
 __device__ __forceinline__ void epilogue_store4(const EpiCtx& e, float* C, int ldc, int row, int col, float4 a) {
   float v[4] = {a.x, a.y, a.z, a.w};
   if (e.bias) {
-    const float4 b = ld4(e.bias + col);
+    const float4 b = ldg4(e.bias + col);
     v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
   }
   float r[4];
@@ -165,12 +108,12 @@ __device__ __forceinline__ void epilogue_store4(const EpiCtx& e, float* C, int l
       float sg[4];
       const float inv_beta = 1.0f / e.p0;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) softplus_sigmoid(v[i], e.p0, inv_beta, r[i], sg[i]);
-      if (e.out1) st4(e.out1 + (long)row * e.ldout1 + col, make_float4(sg[0], sg[1], sg[2], sg[3]));
+      for (int i = 0; i < 4; ++i) softplus_sig(v[i], e.p0, inv_beta, r[i], sg[i]);
+      if (e.out1) stg4(e.out1 + (long)row * e.ldout1 + col, make_float4(sg[0], sg[1], sg[2], sg[3]));
     } break;
     case NSKY_EPI_FILM: {
-      const float4 F = ld4(e.aux0 + (long)row * e.ldaux0 + col);
-      const float4 P = ld4(e.aux1 + (long)row * e.ldaux1 + col);
+      const float4 F = ldg4(e.aux0 + (long)row * e.ldaux0 + col);
+      const float4 P = ldg4(e.aux1 + (long)row * e.ldaux1 + col);
       const float f[4] = {F.x, F.y, F.z, F.w}, ph[4] = {P.x, P.y, P.z, P.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -178,25 +121,25 @@ __device__ __forceinline__ void epilogue_store4(const EpiCtx& e, float* C, int l
         sincos_cw(fmaf(fmaf(e.p0, f[i], e.p1), v[i], ph[i]), sn, cs);
         r[i] = sn;
       }
-      if (e.out1) st4(e.out1 + (long)row * e.ldout1 + col, make_float4(v[0], v[1], v[2], v[3]));
+      if (e.out1) stg4(e.out1 + (long)row * e.ldout1 + col, make_float4(v[0], v[1], v[2], v[3]));
     } break;
     case NSKY_EPI_MUL_AUX: {
-      const float4 A = ld4(e.aux0 + (long)(row % e.row_mod) * e.ldaux0 + col);
+      const float4 A = ldg4(e.aux0 + (long)(row % e.row_mod) * e.ldaux0 + col);
       r[0] = v[0] * A.x; r[1] = v[1] * A.y; r[2] = v[2] * A.z; r[3] = v[3] * A.w;
     } break;
     case NSKY_EPI_BWD_RELU: {
-      const float4 A = ld4(e.aux0 + (long)row * e.ldaux0 + col);
+      const float4 A = ldg4(e.aux0 + (long)row * e.ldaux0 + col);
       r[0] = A.x > 0.f ? v[0] : 0.f; r[1] = A.y > 0.f ? v[1] : 0.f; r[2] = A.z > 0.f ? v[2] : 0.f; r[3] = A.w > 0.f ? v[3] : 0.f;
     } break;
     case NSKY_EPI_BWD_LEAKY: {
-      const float4 A = ld4(e.aux0 + (long)row * e.ldaux0 + col);
+      const float4 A = ldg4(e.aux0 + (long)row * e.ldaux0 + col);
       r[0] = A.x > 0.f ? v[0] : e.p0 * v[0]; r[1] = A.y > 0.f ? v[1] : e.p0 * v[1];
       r[2] = A.z > 0.f ? v[2] : e.p0 * v[2]; r[3] = A.w > 0.f ? v[3] : e.p0 * v[3];
     } break;
     case NSKY_EPI_BWD_FILM: {
-      const float4 Z = ld4(e.aux0 + (long)row * e.ldaux0 + col);
-      const float4 F = ld4(e.aux1 + (long)row * e.ldaux1 + col);
-      const float4 P = ld4(e.aux2 + (long)row * e.ldaux2 + col);
+      const float4 Z = ldg4(e.aux0 + (long)row * e.ldaux0 + col);
+      const float4 F = ldg4(e.aux1 + (long)row * e.ldaux1 + col);
+      const float4 P = ldg4(e.aux2 + (long)row * e.ldaux2 + col);
       const float z[4] = {Z.x, Z.y, Z.z, Z.w}, fr[4] = {F.x, F.y, F.z, F.w}, ph[4] = {P.x, P.y, P.z, P.w};
       float o1[4], o2[4];
 #pragma unroll
@@ -207,8 +150,8 @@ __device__ __forceinline__ void epilogue_store4(const EpiCtx& e, float* C, int l
         const float gc = v[i] * cs;
         r[i] = gc * f; o1[i] = gc * z[i] * e.p0; o2[i] = gc;
       }
-      st4(e.out1 + (long)row * e.ldout1 + col, make_float4(o1[0], o1[1], o1[2], o1[3]));
-      st4(e.out2 + (long)row * e.ldout2 + col, make_float4(o2[0], o2[1], o2[2], o2[3]));
+      stg4(e.out1 + (long)row * e.ldout1 + col, make_float4(o1[0], o1[1], o1[2], o1[3]));
+      stg4(e.out2 + (long)row * e.ldout2 + col, make_float4(o2[0], o2[1], o2[2], o2[3]));
     } break;
     case NSKY_EPI_EXP:
 #pragma unroll
@@ -217,10 +160,10 @@ __device__ __forceinline__ void epilogue_store4(const EpiCtx& e, float* C, int l
   }
   float* dst = C + (long)row * ldc + col;
   if (e.beta != 0.0f) {
-    const float4 o = ld4(dst);
+    const float4 o = ldg4(dst);
     r[0] += e.beta * o.x; r[1] += e.beta * o.y; r[2] += e.beta * o.z; r[3] += e.beta * o.w;
   }
-  st4(dst, make_float4(r[0], r[1], r[2], r[3]));
+  stg4(dst, make_float4(r[0], r[1], r[2], r[3]));
 }
 
 template <int BT, bool KCONTIG, int BK>
@@ -272,17 +215,8 @@ struct TileLoader {
 // label a contiguous run of logical tiles, and the logical order is column-tile fastest: the column tiles of one row
 // tile (which all re-read the same A rows) run back to back on ONE L2 instead of streaming A from HBM once per
 // column tile, while the (small) B operand stays L2-resident for every row tile.
-__device__ __forceinline__ int xcd_contiguous_id() {
-  const int nwg = gridDim.x;
-  int id = blockIdx.x;
-  if (nwg >= 16) {
-    const int q = nwg >> 3, r = nwg & 7, x = id & 7;
-    id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (id >> 3);
-  }
-  return id;
-}
 __device__ __forceinline__ void tile_of_block(int tiles_n, int& m_tile, int& n_tile) {
-  const int id = xcd_contiguous_id();
+  const int id = (int)gridDim.x >= 16 ? xcd_contiguous(blockIdx.x, gridDim.x) : blockIdx.x;  // small grids keep the hardware order
   n_tile = id % tiles_n;
   m_tile = id / tiles_n;
 }
@@ -291,7 +225,7 @@ __device__ __forceinline__ void tile_of_block(int tiles_n, int& m_tile, int& n_t
 // ids, i.e. the same XCD and neighbouring dispatch slots, so the re-reads hit that XCD's L2 instead of going out to HBM once
 // per tile (PMC: the weight-gradient kernel fetched 2.1x its operand bytes with the split on grid.z).
 __device__ __forceinline__ void tile_split_of_block(int tiles_m, int tiles_n, int& m_tile, int& n_tile, int& split) {
-  const int id = xcd_contiguous_id();
+  const int id = (int)gridDim.x >= 16 ? xcd_contiguous(blockIdx.x, gridDim.x) : blockIdx.x;  // small grids keep the hardware order
   const int tiles = tiles_m * tiles_n;
   split = id / tiles;
   const int t = id - split * tiles;
@@ -465,7 +399,6 @@ __device__ __forceinline__ float bf16_lo_as_f32(uint32_t p) { return __builtin_b
 // second one that is folded in with 2^-11 in the epilogue; only l l' (2^-22) is dropped.  fp32-grade products at the
 // cost of the 2-term bf16 form -- valid for operands inside fp16's range (|x| <= 65504; larger magnitudes saturate),
 // i.e. the forward layers' bounded activations and weights, not gradients.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 constexpr float F16_RES_SCALE = 2048.0f;
 
@@ -658,7 +591,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16s_kernel(
   la.nnt = e.a_nnt;
   lb.nnt = e.b_nnt;
   float a_inv = 1.0f;
-  if (e.a_scale_max) la.scale = pow2_scale_for(*e.a_scale_max, a_inv);
+  if (e.a_scale_max) la.scale = pow2_scale(*e.a_scale_max, a_inv);
   const int frow = lane & 31, fh = lane >> 5;
 
   auto compute = [&](const __bf16* As, const __bf16* Bs) {
@@ -741,18 +674,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16s_kernel(
 // Requires K % 4 == 0 and planes zero padded to whole 256-row x 32-k tiles; a partial last k-tile re-reads column 0 of A for
 // the missing chunks (multiplied by the planes' zero padding), M tails re-read row M-1.
 // =================================================================================================
-__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
-  // LDS-DMA hidden from hipcc's waitcnt bookkeeping (it would drain vmcnt(0) before every ds_read otherwise); M0 is saved
-  // and restored inside the statement.  Completion is counted by hand: vmcnt_wait<N>().
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void vmcnt_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <bool H>
 __global__ __launch_bounds__(256, 2) void gemm_planes_kernel(const float* __restrict__ A, const uint16_t* __restrict__ Bhi,
                                                              const uint16_t* __restrict__ Blo, float* __restrict__ C, int M, int N,

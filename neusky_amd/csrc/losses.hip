@@ -4,7 +4,7 @@
 // first backward dense layer).  Every formula keeps the torch semantics the reference gets from autograd: sgn(0) = 0 for |.|,
 // clamp gradients pass inside the closed interval, nan_to_num passes where the input is a number, BCE's log is clamped at
 // -100 and its gradient denominator at 1e-12, F.normalize / cosine_similarity clamp their norms at eps.
-#include "common.h"
+#include "numerics.h"
 #include "../../include/neusky_hip.h"
 
 namespace {
@@ -28,10 +28,6 @@ __device__ __forceinline__ void block_accumulate(float (&loc)[NT], float* __rest
 }
 
 __device__ __forceinline__ float sgnf(float x) { return (x > 0.0f) - (x < 0.0f); }
-
-__device__ __forceinline__ float srgb_raw(float c) {  // utils.py:25-30 before the clamp
-  return c <= 0.0031308f ? 12.92f * c : 1.055f * powf(fabsf(c), 1.0f / 2.4f) - 0.055f;
-}
 
 struct SkyRow {  // masked sRGB background vs masked image of one ray (losses.py:44-58)
   float a[3], b[3], yraw[3], na, nb, an[3], bn[3], sim;

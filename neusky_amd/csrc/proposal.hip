@@ -54,8 +54,6 @@ __global__ __launch_bounds__(256) void proposal_mlp_fwd_kernel(const float* __re
 // dW0 += dh^T f is then ONE v_mfma_f32_16x16x4_f32 per step with both operands already where the instruction wants them (A: unit i of
 // point k in lane i + 16 k, B: feature j of point k in lane j + 16 k), exact fp32; d_feat = W0^T dh by four more of them.  The sums of a
 // block meet in LDS and leave as one atomic per value and block.
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(256) void proposal_mlp_bwd_kernel(const float* __restrict__ feat, int ldf, long P, ProposalMlp m,
                                                                const float* __restrict__ d_raw, float* __restrict__ d_feat, float* __restrict__ dw0,
                                                                float* __restrict__ db0, float* __restrict__ dw1, float* __restrict__ db1) {
@@ -71,7 +69,7 @@ __global__ __launch_bounds__(256) void proposal_mlp_bwd_kernel(const float* __re
 #pragma unroll
   for (int mm = 0; mm < 4; ++mm) w0t[mm] = i < m.in_dim ? m.w0[(long)(4 * mm + k) * m.ldw0 + i] : 0.0f;
   __syncthreads();
-  f32x4_t acc = {0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
   float ab0 = 0.0f, aw1 = 0.0f, ab1 = 0.0f;
   const long wave = (long)blockIdx.x * 4 + (tid >> 6), n_waves = (long)gridDim.x * 4;
   const long steps = (P + 3) / 4;
@@ -103,7 +101,7 @@ __global__ __launch_bounds__(256) void proposal_mlp_bwd_kernel(const float* __re
       if (d_feat) {
         // d_feat^T [feature j][point n] = sum over units of W0[unit][j] dh_unit(point n): four more MFMAs (K = 4 units each), A = W0^T from
         // registers, B = the step's dh values moved to (lane % 16 = point, lane / 16 = unit within the K slice) by one permute each
-        f32x4_t df = {0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 df = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int mm = 0; mm < 4; ++mm) {
           const float b = __shfl(dh, (4 * mm + k) + 16 * (i & 3), 64);

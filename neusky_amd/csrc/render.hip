@@ -6,24 +6,13 @@
 // None of the broadcast tensors of the reference ([R*S,D,3] directions / colours, [R*S,D,1] visibility)
 // is ever materialised: directions [D,3], per-camera colours [U,D,3] and visibility [R,D] are read once
 // per ray into LDS and reduced over the hemisphere with wavefront shuffles.
-#include "common.h"
+#include "numerics.h"
 #include "../../include/neusky_hip.h"
 
 namespace {
 
 constexpr int MAXD = 1024;  // max illumination directions
 constexpr int JPL = MAXD / 64;
-
-__device__ __forceinline__ float srgb_fwd(float x) {
-  float y = x <= 0.0031308f ? 12.92f * x : 1.055f * powf(fabsf(x), 1.0f / 2.4f) - 0.055f;
-  return fminf(fmaxf(y, 0.0f), 1.0f);
-}
-__device__ __forceinline__ float srgb_bwd(float x) {
-  float y = x <= 0.0031308f ? 12.92f * x : 1.055f * powf(fabsf(x), 1.0f / 2.4f) - 0.055f;
-  if (y < 0.0f || y > 1.0f) return 0.0f;
-  if (x <= 0.0031308f) return 12.92f;
-  return 1.055f / 2.4f * powf(fabsf(x), 1.0f / 2.4f - 1.0f);
-}
 
 // one workgroup (4 waves) per ray; wave w takes samples w, w+4, ...; lanes stride the D directions
 __global__ __launch_bounds__(256) void hemi_fwd_kernel(const float* __restrict__ albedo, const float* __restrict__ normals,

@@ -63,6 +63,7 @@ __global__ __launch_bounds__(kThreads) void texel_points_kernel(const float* __r
 
 // (linear_to_sRGB(x) * 255).round().clamp(0, 255) of the exporter's vertex colours: every product and sum rounded on its own
 __device__ __forceinline__ uint8_t srgb_level(float x) {
+  // the curve of numerics.h srgb_fwd written out: that one contracts 1.055 pow - 0.055 into an fma, this file (FP_CONTRACT OFF) must not
   float y = x <= 0.0031308f ? 12.92f * x : 1.055f * powf(fabsf(x), (float)(1.0 / 2.4)) - 0.055f;
   y = fminf(fmaxf(y, 0.0f), 1.0f);
   return (uint8_t)fminf(fmaxf(rintf(y * 255.0f), 0.0f), 255.0f);

@@ -15,7 +15,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "numerics.h"
 #include "../../include/neusky_hip.h"
 
 namespace {
@@ -24,11 +24,6 @@ constexpr int kMaxDirs = NSKY_TRANSFER_MAX_DIRECTIONS;
 constexpr int kMaxLightsPerPass = 8;
 constexpr int kRowsPerWave = 4;
 constexpr int kLdsBudget = 64 * 1024;  // bytes of light colours per workgroup
-
-__device__ __forceinline__ float srgb_fwd(float x) {
-  float y = x <= 0.0031308f ? 12.92f * x : 1.055f * powf(fabsf(x), 1.0f / 2.4f) - 0.055f;
-  return fminf(fmaxf(y, 0.0f), 1.0f);
-}
 
 // ------------------------------------------------------------------------------------------ bake
 // NQ = ceil(D / 64) rounded up to a power of two: the directions a lane owns are j = lane + 64 q, q < NQ.

@@ -22,14 +22,11 @@
 // The batch is split over the grid (split-K) and reduced with contiguous float atomics into dW / db (the callers'
 // accumulators: zero-filled slabs or the parameters' own .grad).  One barrier per 32 rows; the loads of the
 // next two row blocks are in flight while a block is multiplied (see the pipeline comment in the kernel).
-#include "common.h"
+#include "numerics.h"
 #include "../../include/neusky_hip.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
@@ -53,19 +50,9 @@ struct WgradArgs {
   int n_problems, rows, row_blocks, blocks_per_split, n_tiles;  // n_tiles: output blocks of all problems together
 };
 
-__device__ __forceinline__ float pow2_scale(float m, float& inv) {  // m s < 2^15
-  if (!(m > 0.0f) || !(m < 3.0e38f)) { inv = 1.0f; return 1.0f; }
-  int e;
-  (void)frexpf(m, &e);
-  e = max(-100, min(100, e));
-  inv = ldexpf(1.0f, e - 15);
-  return ldexpf(1.0f, 15 - e);
-}
-
-// consecutive hardware workgroup ids go round-robin over the 8 XCDs: hand every XCD one contiguous run of logical ids, so
-// the workgroups of one batch split (which read the same rows of X, and of dZ where the layer is wider than one block)
-// share an L2
-__device__ __forceinline__ int xcd_contiguous(int id, int total) {
+// common.h's xcd_contiguous without its branch (x q + min(x, r) is the same bijection).  Not folded into that one: either spelling
+// costs the kernels of the other file their instruction sequence (here 10 scalar instructions and a branch in the prologue).
+__device__ __forceinline__ int xcd_contiguous_branchless(int id, int total) {
   const int xcd = id & 7, idx = id >> 3, per = total >> 3, rem = total & 7;
   return xcd * per + min(xcd, rem) + idx;
 }
@@ -91,7 +78,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void wgrad_nati
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int logical = xcd_contiguous(blockIdx.x, gridDim.x);
+  const int logical = xcd_contiguous_branchless(blockIdx.x, gridDim.x);
   const int gtile = logical % a.n_tiles, split = logical / a.n_tiles;
   int pi = 0;
   while (pi + 1 < a.n_problems && gtile >= a.p[pi + 1].tile0) ++pi;
