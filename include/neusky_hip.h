@@ -885,6 +885,32 @@ int nsky_transfer_bake(const float* albedo, const float* normals, const float* w
 int nsky_transfer_relight(const void* T, int32_t storage, const int32_t* exponents, const float* acc, const float* lights, const float* bg,
                           int64_t R, int32_t D, int32_t K, float* rgb, float* lin, nsky_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A directional sun on top of the hemisphere render (neusky_amd/relight/sun.py, csrc/sun.hip).  The frame render sees light as its D
+ * directions, one cell of which covers 4 pi / D sr; a sun (6.8e-5 sr) is one direction of its own, with one DDF shadow query per ray.
+ *   direction:  the unit vector TOWARDS the sun, z up: s = (cos az cos el, sin az cos el, sin el), azimuth and elevation in degrees.
+ *   colour:     C [3] in the renderer's irradiance units.  The hemisphere term of nsky_hemi_composite_fwd is the mean of
+ *               clamp(<n,d>, 0, 1) L_d over the directions of the normal's hemisphere, an estimate of (1 / 2 pi) int L cos; a source of
+ *               radiance L and solid angle Omega therefore has C = L Omega / (2 pi).
+ *   transfer:   t[k,r,c] = sum_s weights[r,s] albedo[r,s,c] clamp(<normals[r,s], s_k>, 0, 1)
+ *   shadow:     V[k,r] = vis[k,r] (1 when vis is NULL) if s_k.z > 0 and acc[r] > acc_threshold[0], else 0.  vis is the DDF visibility of
+ *               the K sun directions (compute_visibility_compact with sel = 0..K-1).  A sun that has set adds no light and no shadow,
+ *               whatever vis holds; the rule is applied on the device.
+ *   composite:  lin[k,r,c] = lin_sky[r,c] + C[k,c] V[k,r] t[k,r,c];   rgb = clamp(linear_to_sRGB(lin), 0, 1)
+ *               lin_sky is the `lin` output of nsky_hemi_composite_fwd (sky, visibility, background).  The sun's disc is not drawn.
+ * nsky_sun_transfer:  albedo, normals [R,S,3]; weights [R,S]; suns [K,3]  ->  out [K,R,3].  One wave per ray, the samples read once
+ *                     per pass of up to 8 suns; any S >= 1, any K.  The cosine is taken in fp64 and the sums in fp32: an entry is within
+ *                     (3 + S / 64 + 6) 2^-24 sum_s |weights albedo| of its definition.
+ * nsky_sun_composite: lin_sky [R,3]; t [K,R,3]; vis [K,R] or NULL; acc [R]; acc_threshold [1] (device memory: a captured graph
+ *                     reads a new threshold on replay); suns, colours [K,3]  ->  rgb [K,R,3] and, unless NULL, lin [K,R,3] (the sum in
+ *                     fp64, rounded once) and shadow [K,R] (= V).
+ * Flat indices are int64.  No atomics and a fixed reduction order: every output is bitwise repeatable.  Nothing is read on the host. */
+int nsky_sun_transfer(const float* albedo, const float* normals, const float* weights, const float* suns, int64_t R, int32_t S, int32_t K,
+                      float* out, nsky_stream_t stream);
+int nsky_sun_composite(const float* lin_sky, const float* t, const float* vis, const float* acc, const float* acc_threshold,
+                       const float* suns, const float* colours, int64_t R, int32_t K, float* rgb, float* lin, float* shadow,
+                       nsky_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

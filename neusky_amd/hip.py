@@ -1327,3 +1327,31 @@ def transfer_relight(T, exponents, acc, lights, bg, rgb, lin=None):
     assert exponents is None or exponents.shape[0] == R
     check(_transfer_relight(_c(T), _transfer_storage(T, exponents), _c(exponents), _c(acc), _c(lights), _c(bg), R, D, K, _c(rgb), _c(lin),
                             stream_ptr()), "nsky_transfer_relight")
+
+
+# ---- a directional sun on top of the hemisphere render (relight/sun.py, csrc/sun.hip)
+_sun_transfer = _sig("nsky_sun_transfer", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                     C.c_void_p)
+_sun_composite = _sig("nsky_sun_composite", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def sun_transfer(albedo, normals, weights, suns, out):
+    """albedo, normals: fp32 [R, S, 3]; weights [R, S]; suns [K, 3] -> out [K, R, 3]"""
+    R, S, _ = albedo.shape
+    K = suns.shape[0]
+    assert normals.shape == (R, S, 3) and weights.shape == (R, S) and suns.shape == (K, 3) and out.shape == (K, R, 3)
+    assert all(t.dtype == torch.float32 for t in (albedo, normals, weights, suns, out))
+    check(_sun_transfer(_c(albedo), _c(normals), _c(weights), _c(suns), R, S, K, _c(out), stream_ptr()), "nsky_sun_transfer")
+
+
+def sun_composite(lin_sky, t, vis, acc, acc_threshold, suns, colours, rgb, lin=None, shadow=None):
+    """lin_sky: fp32 [R, 3]; t [K, R, 3]; vis [K, R] or None; acc [R]; acc_threshold [1] (device); suns, colours [K, 3] -> rgb [K, R, 3]
+    (sRGB, clamped) and, if given, lin [K, R, 3] and shadow [K, R]"""
+    K, R, _ = t.shape
+    assert lin_sky.shape == (R, 3) and acc.numel() == R and acc_threshold.numel() == 1 and suns.shape == (K, 3) and colours.shape == (K, 3)
+    assert rgb.shape == (K, R, 3) and (vis is None or vis.shape == (K, R)) and (lin is None or lin.shape == (K, R, 3))
+    assert shadow is None or shadow.shape == (K, R)
+    assert all(x is None or x.dtype == torch.float32 for x in (lin_sky, t, vis, acc, acc_threshold, suns, colours, rgb, lin, shadow))
+    check(_sun_composite(_c(lin_sky), _c(t), _c(vis), _c(acc), _c(acc_threshold), _c(suns), _c(colours), R, K, _c(rgb), _c(lin), _c(shadow),
+                         stream_ptr()), "nsky_sun_composite")

@@ -572,12 +572,16 @@ class NeuSkyFactoModel(ModelBase):
         visibility = so["visibility_dict"]["visibility"] if self.config.use_visibility else None
         sdf_at_termination = so["visibility_dict"].get("sdf_at_termination") if self.config.use_visibility else None
         bake = None if self.training else getattr(self, "_transfer_storage", None)
+        sun = None if self.training else getattr(self, "_frame_sun", None)
         if bake is not None:
             # relight.bake_transfer: the renderer's inputs go to the radiance-transfer bake instead (no light enters; no rgb comes out)
             from ..relight.transfer import bake_rows
             rgb = None
             transfer = bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], weights[..., 0],
                                  so["illumination_directions"], visibility, bake)
+        elif sun is not None:
+            rgb = None
+            sun_out = self._sun_outputs(so, ray_bundle, sun)
         else:
             rgb = self.lambertian_renderer.forward_compact(
                 albedos=fo[NeuSkyFieldHeadNames.ALBEDO], normals=fo[FieldHeadNames.NORMALS],
@@ -595,6 +599,8 @@ class NeuSkyFactoModel(ModelBase):
         if bake is not None:
             del outputs["rgb"]
             outputs.update(transfer)
+        elif sun is not None:
+            outputs.update(sun_out)
         if self.training:
             outputs["eik_grad"] = fo[FieldHeadNames.GRADIENT]  # :903-904
             outputs.update(so)
@@ -604,6 +610,34 @@ class NeuSkyFactoModel(ModelBase):
         if "visibility_dict" in so:
             outputs["visibility_batch"] = so["visibility_dict"]["visibility_batch"]
         return outputs
+
+    def _sun_outputs(self, so: Dict[str, Any], ray_bundle: RayBundle, sun) -> Dict[str, torch.Tensor]:
+        """a chunk lit by its sky and the frame's K suns (include/neusky_hip.h; begin_frame): the hemisphere kernel's linear image, one
+        DDF query per (ray, sun), the sun transfer and the composite.  Ray-major views of the [K, R, ...] results: rgb, lin [R, K, 3],
+        shadow_map, shadow_difference [R, K]."""
+        sun_dirs, colours, threshold, acc_threshold, sel, scale = sun
+        fo = so["field_outputs"]
+        a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
+        w = so["weights"][..., 0].contiguous()
+        R, K, dev = a.shape[0], sun_dirs.shape[0], a.device
+        vis_sky = so["visibility_dict"]["visibility"].contiguous() if self.config.use_visibility else None
+        lin_sky = torch.empty(R, 3, device=dev)
+        hip.hemi_composite_fwd(a, n, w, so["illumination_directions"].contiguous(), so["hdr_illumination_colours"].contiguous(),
+                               so["cam_of_ray"], vis_sky, so["hdr_background_colours"].contiguous(), torch.empty(R, 3, device=dev), lin_sky)
+        acc = so["accumulation"].reshape(-1).contiguous()
+        vis = diff = None
+        if self.config.use_visibility:
+            vd = self.compute_visibility_compact(ray_bundle.origins, ray_bundle.directions, so["p2p_dist"].detach(), sun_dirs, threshold,
+                                                 scale, compute_shadow_map=True, sel=sel)
+            vis = vd["visibility"].t().contiguous()  # [K, R]
+            diff = vd["difference"].view(R, K)
+        t = torch.empty(K, R, 3, device=dev)
+        hip.sun_transfer(a, n, w, sun_dirs, t)
+        rgb, lin, shadow = torch.empty(K, R, 3, device=dev), torch.empty(K, R, 3, device=dev), torch.empty(K, R, device=dev)
+        hip.sun_composite(lin_sky, t, vis, acc, acc_threshold, sun_dirs, colours, rgb, lin, shadow)
+        on = (acc > acc_threshold)[:, None] & (sun_dirs[:, 2] > 0)[None]
+        diff = torch.where(on, diff, torch.zeros((), device=dev)) if diff is not None else torch.zeros(R, K, device=dev)
+        return {"rgb": rgb.permute(1, 0, 2), "lin": lin.permute(1, 0, 2), "shadow_map": shadow.t(), "shadow_difference": diff}
 
     def get_loss_dict(self, outputs: Dict[str, Any], batch: Dict[str, Any], metrics_dict=None) -> Dict[str, torch.Tensor]:
         """neusky_model.py:933-1062, both branches, through ONE fused kernel each way (ops.MainLossesFn): the train branch's eight
@@ -881,11 +915,45 @@ class NeuSkyFactoModel(ModelBase):
             return graph.outputs
         return graph, replay
 
-    def begin_frame(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None) -> None:
+    def begin_frame(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None, sun=None,
+                    shadow_threshold: Optional[float] = None, shadow_sigmoid_scale: Optional[float] = None,
+                    accumulation_mask_threshold: float = 0.0) -> None:
         """decode the illumination of ONE camera for a whole frame (the reference re-decodes it in each of the
         8100 chunks of a 1080p frame, neusky_model.py:1413-1432; the result is the same).
         envmap: a relight.EnvironmentMap lighting the frame instead of the camera's latent: the light colours are the map's cell
-        averages at the frame's directions (relight.project_envmap), the rays' background its bilinear lookup."""
+        averages at the frame's directions (relight.project_envmap), the rays' background its bilinear lookup.
+        sun: a relight.SunLight or a sequence of K of them on top of that sky (_begin_frame_sun)."""
+        self._begin_frame(camera_index, rotation, envmap)
+        self._begin_frame_sun(sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold)
+
+    def _begin_frame_sun(self, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold) -> None:
+        """the K suns of a frame (include/neusky_hip.h): directions, colours, the shadow threshold and the accumulation threshold go to
+        static device buffers (one set per K) that a chunk graph reads through their pointers, so the graph is keyed on K and a new
+        position, colour or threshold replays it.  The sigmoid scale is a by-value argument of nsky_visibility_finish_fwd: a scale
+        other than the model's own joins the key."""
+        self._frame_sun = None
+        if sun is None:
+            return
+        from ..relight.sun import as_suns
+        suns, _ = as_suns(sun)
+        K, dev = len(suns), self.device
+        cache = self.__dict__.setdefault("_frame_sun_static", {})
+        st = cache.get((K, str(dev)))
+        if st is None:
+            st = cache[(K, str(dev))] = (torch.empty(K, 3, device=dev), torch.empty(K, 3, device=dev), torch.empty(1, device=dev),
+                                         torch.empty(1, device=dev), torch.arange(K, device=dev, dtype=torch.int32))
+        st[0].copy_(torch.tensor([s.direction for s in suns], dtype=torch.float64).to(torch.float32))
+        st[1].copy_(torch.tensor([s.colour for s in suns], dtype=torch.float32))
+        if shadow_threshold is None:
+            st[2].copy_(self.visibility_threshold.detach() if self.config.use_visibility else torch.zeros(1))
+        else:
+            st[2].copy_(torch.tensor([float(shadow_threshold)]))
+        st[3].copy_(torch.tensor([float(accumulation_mask_threshold)]))
+        scale = float(self.sigmoid_scale if shadow_sigmoid_scale is None else shadow_sigmoid_scale) if self.config.use_visibility else 0.0
+        self._frame_sun = st + (scale,)
+        self._frame_key = (self._frame_key, "sun", K, scale)
+
+    def _begin_frame(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None) -> None:
         latents, scales = self.get_illumination_field()
         fixed = self.config.fix_test_illumination_directions
         dirs, sel = self.illumination_sampler.on_device(self.device, apply_random_rotation=False if fixed else None)
@@ -933,16 +1001,24 @@ class NeuSkyFactoModel(ModelBase):
     def end_frame(self) -> None:
         self._frame_illumination = None
         self._frame_envmap = None
+        self._frame_sun = None
 
     @torch.no_grad()
     def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle: RayBundle, show_progress=False, rotation=None, to_cpu=False,
                                           step=None, camera_index: Optional[int] = None, chunk: Optional[int] = None,
-                                          use_graph: bool = True, envmap=None) -> Dict[str, torch.Tensor]:
+                                          use_graph: bool = True, envmap=None, sun=None, shadow_threshold: Optional[float] = None,
+                                          shadow_sigmoid_scale: Optional[float] = None,
+                                          accumulation_mask_threshold: float = 0.0) -> Dict[str, torch.Tensor]:
         """neusky_model.py:1369-1501: chunked full-frame render.  The reference chunks at eval_num_rays_per_chunk = 256
         (8100 python iterations per 1080p frame); any chunk size gives the same image, so a larger static chunk is used
         and its forward is captured once in a HIP graph and replayed per chunk (BASELINE config 5).
         envmap: a relight.EnvironmentMap to light the frame with instead of the camera's illumination latent (begin_frame);
-        `rotation` then turns the map (direction d is lit by the map at R d)."""
+        `rotation` then turns the map (direction d is lit by the map at R d).
+        sun: a relight.SunLight, or a sequence of K of them, on top of either sky (include/neusky_hip.h: a directional sun).  `rgb` is
+        then the frame lit by sky and sun, and `lin` (its linear image), `shadow_map` and `shadow_difference` [*shape, 1] join the outputs;
+        a sequence puts a leading K on those four.  The field, the sampler and the sky pass of a chunk run once for all K suns.
+        shadow_threshold / shadow_sigmoid_scale default to the model's trained visibility threshold and sigmoid scale; the shadow is
+        masked by accumulation > accumulation_mask_threshold.  A sun with elevation <= 0 has set: it adds no light and no shadow."""
         assert not self.training, "call model.eval() first"
         chunk = chunk or max(self.config.eval_num_rays_per_chunk, 4096)
         shape = camera_ray_bundle.origins.shape[:-1]
@@ -950,8 +1026,11 @@ class NeuSkyFactoModel(ModelBase):
         num_rays = flat.origins.shape[0]
         if camera_index is None:
             camera_index = int(flat.camera_indices.reshape(-1)[0]) if flat.camera_indices is not None else 0
-        self.begin_frame(camera_index, rotation, envmap)
-        keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"]
+        if sun is not None and not hasattr(sun, "direction"):
+            sun = list(sun)
+        self.begin_frame(camera_index, rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold)
+        sun_keys = ["rgb", "lin", "shadow_map", "shadow_difference"] if sun is not None else []
+        keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
         out = {k: [] for k in keys}
         try:
             # the background term depends on (camera, rotation) through python values baked into a capture, so graphs
@@ -969,7 +1048,14 @@ class NeuSkyFactoModel(ModelBase):
                     out[k].append(res[k].cpu() if to_cpu else res[k])
         finally:
             self.end_frame()
-        return {k: torch.cat(v).view(*shape, -1) for k, v in out.items()}
+        if sun is not None:  # chunks are ray-major [n, K, ...]: K leads, and a single SunLight drops it
+            from ..relight.sun import SunLight
+            K = 1 if isinstance(sun, SunLight) else len(sun)
+            lead = () if isinstance(sun, SunLight) else (K,)
+            for k in sun_keys:
+                full = torch.cat(out.pop(k))
+                out[k] = [full.reshape(num_rays, K, -1).transpose(0, 1).reshape(*lead, *shape, -1)]
+        return {k: torch.cat(v).view(*shape, -1) if k not in sun_keys else v[0] for k, v in out.items()}
 
 
 class _ChunkRunner:

@@ -5,11 +5,16 @@ light directions and the bilinear sky lookup on the GPU (csrc/envmap.hip), and t
 
 `bake_transfer` / `RadianceTransfer` (transfer.py, csrc/transfer.hip): a camera's frame baked once into its radiance transfer, then relit
 under any number of lights at one streaming pass over the transfer each (`--transfer fp32|fp16` on the command line).
+
+`SunLight` / `sun_path` (sun.py, csrc/sun.hip): a directional sun on top of either sky, with one DDF shadow query per ray; the frame
+render with `sun=` returns the lit frame, its `shadow_map` and `shadow_difference` (`--sun-azimuth/--sun-elevation`, `--sun-path`).
 """
 from .cameras import CameraPath, camera_rays, load_camera_path
 from .envmap import EnvironmentMap, envmap_labels, envmap_lookup, project_envmap, z_rotation
 from .io import read_envmap, srgb_to_linear
+from .sun import SunLight, sun_direction, sun_path, sun_solid_angle
 from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
 
-__all__ = ["CameraPath", "EnvironmentMap", "RadianceTransfer", "bake_transfer", "camera_rays", "envmap_labels", "envmap_lookup",
-           "load_camera_path", "pack_fp16", "project_envmap", "read_envmap", "srgb_to_linear", "unpack_fp16", "z_rotation"]
+__all__ = ["CameraPath", "EnvironmentMap", "RadianceTransfer", "SunLight", "bake_transfer", "camera_rays", "envmap_labels", "envmap_lookup",
+           "load_camera_path", "pack_fp16", "project_envmap", "read_envmap", "srgb_to_linear", "sun_direction", "sun_path",
+           "sun_solid_angle", "unpack_fp16", "z_rotation"]

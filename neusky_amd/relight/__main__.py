@@ -11,6 +11,8 @@ import os
 import sys
 import time
 
+from .sun import SUN_ANGULAR_DIAMETER_DEG
+
 
 def build_pipeline(state, device):
     """the `neusky` method's pipeline sized from a checkpoint's state dict, on a stand-in datamanager (no dataset)"""
@@ -57,8 +59,57 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--chunk", type=int, default=4096)
     ap.add_argument("--transfer", default="off", choices=("off", "fp32", "fp16"),
                     help="bake each camera's radiance transfer once (stored as fp32 or scaled fp16) and relight its frames from it")
+    sun = ap.add_argument_group("sun", "a directional sun on top of the sky, with its DDF shadow (relight.SunLight)")
+    sun.add_argument("--sun-azimuth", type=float, help="degrees, counter-clockwise from +x about +z")
+    sun.add_argument("--sun-elevation", type=float, help="degrees above the horizon; a sun at or below it has set")
+    sun.add_argument("--sun-colour", type=float, nargs=3, metavar=("R", "G", "B"), help="in the renderer's irradiance units (default 1 1 1)")
+    sun.add_argument("--sun-radiance", type=float, nargs=3, metavar=("R", "G", "B"), help="the disc's radiance instead: colour = L Omega / 2 pi")
+    sun.add_argument("--sun-angular-diameter", type=float, default=SUN_ANGULAR_DIAMETER_DEG, help="degrees, with --sun-radiance")
+    sun.add_argument("--sun-path", type=float, nargs=4, metavar=("AZ0", "EL0", "AZ1", "EL1"),
+                     help="sweep the sun between two positions: --sun-steps frames per camera from one field pass per chunk")
+    sun.add_argument("--sun-steps", type=int, help="frames of --sun-path")
+    sun.add_argument("--shadow-map", action="store_true", help="also write the sun's shadow map of each frame as shadow_CCCC_FFF.png")
+    sun.add_argument("--shadow-threshold", type=float, help="default: the model's trained visibility threshold")
+    sun.add_argument("--shadow-sigmoid-scale", type=float, help="default: the model's sigmoid scale")
     ap.add_argument("--device", default="cuda:0")
     return ap
+
+
+def parse_suns(ap: argparse.ArgumentParser, args):
+    """the frame's suns from the command line: None, or a list of relight.SunLight (one per frame of a --sun-path)"""
+    from .sun import SunLight, sun_path, sun_solid_angle
+
+    fixed = args.sun_azimuth is not None or args.sun_elevation is not None
+    any_sun = fixed or args.sun_path is not None
+    for flag, given in (("--sun-colour", args.sun_colour), ("--sun-radiance", args.sun_radiance), ("--sun-steps", args.sun_steps),
+                        ("--shadow-map", args.shadow_map or None), ("--shadow-threshold", args.shadow_threshold),
+                        ("--shadow-sigmoid-scale", args.shadow_sigmoid_scale)):
+        if given is not None and not any_sun:
+            ap.error(f"{flag} needs a sun: --sun-azimuth and --sun-elevation, or --sun-path")
+    if not any_sun:
+        return None
+    if args.transfer != "off":
+        ap.error("a sun needs the per-sample normals the baked transfer does not keep: sun flags go with --transfer off")
+    if fixed and args.sun_path is not None:
+        ap.error("--sun-path replaces --sun-azimuth / --sun-elevation")
+    if fixed and (args.sun_azimuth is None or args.sun_elevation is None):
+        ap.error("--sun-azimuth and --sun-elevation go together")
+    if args.sun_colour is not None and args.sun_radiance is not None:
+        ap.error("--sun-colour or --sun-radiance, not both")
+    if args.sun_steps is not None and args.sun_path is None:
+        ap.error("--sun-steps needs --sun-path")
+    if args.sun_path is not None:
+        if args.sun_steps is None or args.sun_steps < 1:
+            ap.error("--sun-path needs --sun-steps N >= 1")
+        if args.turntable > 1:
+            ap.error("--sun-path sweeps the sun: it excludes --turntable > 1")
+    colour = tuple(args.sun_colour) if args.sun_colour is not None else (1.0, 1.0, 1.0)
+    if args.sun_radiance is not None:
+        k = sun_solid_angle(args.sun_angular_diameter) / (2.0 * math.pi)
+        colour = tuple(x * k for x in args.sun_radiance)
+    if args.sun_path is not None:
+        return sun_path(*args.sun_path, args.sun_steps, colour)
+    return [SunLight(args.sun_azimuth, args.sun_elevation, colour)]
 
 
 def main(argv=None) -> int:
@@ -66,6 +117,7 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.turntable < 1:
         ap.error("--turntable must be >= 1")
+    suns = parse_suns(ap, args)
 
     import numpy as np
     import torch
@@ -115,8 +167,23 @@ def main(argv=None) -> int:
             baked = bake_transfer(model, rb, storage=args.transfer, chunk=args.chunk, camera_index=0)
             torch.cuda.synchronize()
             t_bake += time.perf_counter() - tb
-        for f in range(args.turntable):
-            if args.transfer == "off":
+        sweep = None
+        if args.sun_path is not None:  # every frame of the sweep from one field pass per chunk
+            sweep = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[0], envmap=envmap, sun=suns,
+                                                            shadow_threshold=args.shadow_threshold,
+                                                            shadow_sigmoid_scale=args.shadow_sigmoid_scale)
+        for f in range(len(suns) if sweep is not None else args.turntable):
+            shadow = None
+            if sweep is not None:
+                rgb = sweep["rgb"][f].clamp(0.0, 1.0).cpu().numpy()
+                shadow = sweep["shadow_map"][f]
+            elif suns is not None:
+                out = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[f], envmap=envmap,
+                                                              sun=suns[0], shadow_threshold=args.shadow_threshold,
+                                                              shadow_sigmoid_scale=args.shadow_sigmoid_scale)
+                rgb = out["rgb"].clamp(0.0, 1.0).cpu().numpy()
+                shadow = out["shadow_map"]
+            elif args.transfer == "off":
                 out = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[f], envmap=envmap)
                 rgb = out["rgb"].clamp(0.0, 1.0).cpu().numpy()
             else:
@@ -130,6 +197,9 @@ def main(argv=None) -> int:
             Image.fromarray(np.round(rgb * 255.0).astype(np.uint8)).save(stem + ".png")
             if args.save_hdr:
                 np.save(stem + ".npy", srgb_to_linear(rgb).astype(np.float32))
+            if args.shadow_map:
+                grey = np.round(shadow[..., 0].clamp(0.0, 1.0).cpu().numpy() * 255.0).astype(np.uint8)
+                Image.fromarray(grey, mode="L").save(os.path.join(args.output_dir, f"shadow_{c:04d}_{f:03d}.png"))
             frames += 1
     torch.cuda.synchronize()
     t_render = time.perf_counter() - t1
