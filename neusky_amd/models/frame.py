@@ -1,0 +1,297 @@
+"""The chunked full-frame render: the state of a frame and its one owner.
+
+A frame is rendered in static-shape chunks whose forward is captured once in a HIP graph and replayed (`_ChunkRunner`).  What is decided
+once per frame is a `FrameLight`; the model's `FrameRenderer` (`model.frames`) builds it in `begin`, holds it as `active` until `end`, and
+owns what outlives a frame: the static device buffers, the rotations pinned per value and the cache of chunk runners.
+
+A captured chunk reads a tensor through the pointer it was captured with.  So a value that may change between two frames served by one
+graph lives in a static buffer allocated here once and overwritten by `begin`; a value the capture holds as a Python number or through a
+pointer of its own is part of `FrameLight.key`, under which the runner is cached."""
+from __future__ import annotations
+
+from collections import namedtuple
+from dataclasses import InitVar, dataclass, field
+from typing import Any, Dict, Optional, Tuple
+
+import torch
+
+from .. import hip, ops
+from ..cameras.rays import RayBundle
+from ..field_components.neusky_fieldheadnames import FieldHeadNames, NeuSkyFieldHeadNames
+from ..relight.envmap import project_envmap
+from ..relight.sun import as_suns
+from ..relight.transfer import bake_rows
+
+SUN_KEYS = ("rgb", "lin", "shadow_map", "shadow_difference")
+
+
+# all tensors but the map are static buffers: rotation [3, 3], exposure [1]; dirs, colours [K, 3], the thresholds [1], sel = int32 arange(K)
+# (every sun direction is queried).  `scale` is a float, a by-value argument of nsky_visibility_finish_fwd
+FrameEnvmap = namedtuple("FrameEnvmap", "data convention rotation exposure")
+FrameSuns = namedtuple("FrameSuns", "dirs colours threshold acc_threshold sel scale")
+
+
+@dataclass
+class FrameLight:
+    """the light of the active frame: directions [D, 3], the frame camera's colours at them [1, D, 3] and the upper-hemisphere subset, in
+    static buffers; the camera and the (pinned) rotation of its latent; optionally an environment map, suns, a transfer-bake storage"""
+    dirs: torch.Tensor
+    cols: torch.Tensor
+    sel: torch.Tensor
+    cam: int
+    rotation: Optional[torch.Tensor]
+    rotation_values: InitVar[Optional[tuple]] = None  # of a latent's rotation, for the key (an envmap's is read from its static buffer)
+    envmap: Optional[FrameEnvmap] = None
+    sun: Optional[FrameSuns] = None
+    bake: Optional[str] = None
+    key: tuple = field(init=False)
+
+    def __post_init__(self, rotation_values):
+        """what a captured chunk holds by value or by a pointer that is not a static buffer's.  An envmap frame is keyed on the map's
+        storage, shape and convention only, so a new rotation or exposure replays the chunk; a sun frame adds K and the sigmoid scale,
+        so a new position, colour or threshold does."""
+        env = self.envmap
+        key = (self.cam, rotation_values) if env is None else ("envmap", env.data.data_ptr(), tuple(env.data.shape), env.convention)
+        if self.sun is not None:
+            key = (key, "sun", self.sun.dirs.shape[0], self.sun.scale)
+        if self.bake is not None:
+            key = (key, "bake", self.bake)
+        self.key = key
+
+    @property
+    def shading(self) -> str:
+        return "bake" if self.bake is not None else "sun" if self.sun is not None else "sky"
+
+
+def light_colours(model, dirs: torch.Tensor, cam: int, rotation: Optional[torch.Tensor] = None, envmap=None) -> torch.Tensor:
+    """[D, 3]: the light at the frame's directions, of camera `cam`'s latent (turned by `rotation`) or of a relight.EnvironmentMap: the
+    map's cell averages (relight.project_envmap)"""
+    if envmap is not None:
+        return project_envmap(envmap, dirs, rotation)[0]
+    latents, scales = model.get_illumination_field()
+    if rotation is None:
+        return model.illumination_field.forward_grid(dirs, latents[cam][None], scales[cam][None])[0]
+    return model.illumination_field.forward_camera(dirs, latents[cam], scales[cam], rotation)
+
+
+def ray_background(model, ray_directions: torch.Tensor, cam: int, rotation: Optional[torch.Tensor] = None,
+                   envmap: Optional[FrameEnvmap] = None) -> torch.Tensor:
+    """[R, 3]: the sky behind the rays, of camera `cam`'s latent (turned by `rotation`) or of the frame's environment map (its bilinear
+    lookup, read through the static buffers)"""
+    if envmap is not None:
+        bg = torch.empty(ray_directions.shape[0], 3, dtype=torch.float32, device=ray_directions.device)
+        hip.envmap_lookup(envmap.data, envmap.convention, ray_directions.contiguous(), envmap.rotation, envmap.exposure, bg)
+        return bg
+    latents, scales = model.get_illumination_field()
+    return model.illumination_field.forward_camera(ray_directions, latents[cam], scales[cam], rotation)
+
+
+def shade(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -> Dict[str, torch.Tensor]:
+    """what the active frame's shading mode adds to a chunk's outputs: `rgb` under the sky alone; `rgb`, `lin`, `shadow_map` and
+    `shadow_difference` with suns; the transfer keys and no `rgb` for a bake (no light enters)"""
+    if light.shading == "sky":
+        return {"rgb": model.render_lambertian(so)}
+    if light.shading == "sun":
+        return _sun_outputs(model, light.sun, so, ray_bundle)
+    fo = so["field_outputs"]
+    visibility = so["visibility_dict"]["visibility"] if model.config.use_visibility else None
+    return bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], so["weights"][..., 0], so["illumination_directions"],
+                     visibility, light.bake)
+
+
+def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundle) -> Dict[str, torch.Tensor]:
+    """a chunk lit by its sky and the frame's K suns (include/neusky_hip.h): the hemisphere kernel's linear image, one DDF query per
+    (ray, sun), the sun transfer and the composite.  Ray-major views of the [K, R, ...] results: rgb, lin [R, K, 3], shadow_map,
+    shadow_difference [R, K]."""
+    fo = so["field_outputs"]
+    a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
+    w = so["weights"][..., 0].contiguous()
+    R, K, dev = a.shape[0], sun.dirs.shape[0], a.device
+    use_visibility = model.config.use_visibility
+    vis_sky = so["visibility_dict"]["visibility"].contiguous() if use_visibility else None
+    lin_sky = torch.empty(R, 3, device=dev)
+    hip.hemi_composite_fwd(a, n, w, so["illumination_directions"].contiguous(), so["hdr_illumination_colours"].contiguous(),
+                           so["cam_of_ray"], vis_sky, so["hdr_background_colours"].contiguous(), torch.empty(R, 3, device=dev), lin_sky)
+    acc = so["accumulation"].reshape(-1).contiguous()
+    vis = diff = None
+    if use_visibility:
+        vd = model.compute_visibility_compact(ray_bundle.origins, ray_bundle.directions, so["p2p_dist"].detach(), sun.dirs, sun.threshold,
+                                              sun.scale, compute_shadow_map=True, sel=sun.sel)
+        vis = vd["visibility"].t().contiguous()  # [K, R]
+        diff = vd["difference"].view(R, K)
+    t = torch.empty(K, R, 3, device=dev)
+    hip.sun_transfer(a, n, w, sun.dirs, t)
+    rgb, lin, shadow = torch.empty(K, R, 3, device=dev), torch.empty(K, R, 3, device=dev), torch.empty(K, R, device=dev)
+    hip.sun_composite(lin_sky, t, vis, acc, sun.acc_threshold, sun.dirs, sun.colours, rgb, lin, shadow)
+    on = (acc > sun.acc_threshold)[:, None] & (sun.dirs[:, 2] > 0)[None]
+    diff = torch.where(on, diff, torch.zeros((), device=dev)) if diff is not None else torch.zeros(R, K, device=dev)
+    return {"rgb": rgb.permute(1, 0, 2), "lin": lin.permute(1, 0, 2), "shadow_map": shadow.t(), "shadow_difference": diff}
+
+
+class FrameRenderer:
+    """one per model (`model.frames`); plain Python, nothing of it is in the model's state_dict"""
+
+    def __init__(self, model):
+        self.model = model
+        self.active: Optional[FrameLight] = None
+        self.sky_static: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None  # dirs [D, 3], cols [1, D, 3], sel
+        self.envmap_static: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # rotation [3, 3], exposure [1]
+        self.sun_static: Dict[tuple, tuple] = {}  # (K, device) -> dirs, colours, threshold, acc_threshold, sel
+        # a chunk graph cached under a rotation's values reads the rotation through the pointer it was captured with: the first tensor
+        # seen with these values is kept, and serves every later frame that asks for them (one entry per value ever seen)
+        self.rotations: Dict[tuple, torch.Tensor] = {}
+        self.runners: Dict[tuple, "_ChunkRunner"] = {}  # (chunk, use_graph, key if use_graph else None) -> runner
+
+    # ------------------------------------------------------------------ the frame's light
+    def begin(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None, sun=None,
+              shadow_threshold: Optional[float] = None, shadow_sigmoid_scale: Optional[float] = None,
+              accumulation_mask_threshold: float = 0.0, bake: Optional[str] = None) -> None:
+        """model.begin_frame, and `bake`: the storage of a radiance-transfer bake (relight.bake_transfer), which takes the place of
+        the shading"""
+        model = self.model
+        fixed = model.config.fix_test_illumination_directions
+        dirs, sel = model.illumination_sampler.on_device(model.device, apply_random_rotation=False if fixed else None)
+        cam = int(camera_index)
+        values = None if (rotation is None or envmap is not None) else tuple(rotation.reshape(-1).tolist())
+        if values is not None:
+            rotation = self.rotations.setdefault(values, rotation)
+        cols = light_colours(model, dirs, cam, rotation, envmap)[None]
+        # static per-model buffers: a chunk graph captured for one frame stays valid for the next (animation frames
+        # only change the camera / rotation, render_animation.py:196-207)
+        st = self.sky_static
+        if st is None or st[0].shape != dirs.shape or st[0].device != dirs.device:
+            st = self.sky_static = (torch.empty_like(dirs), torch.empty_like(cols), torch.empty_like(sel))
+            self.runners = {}  # (the dropped runners' graphs retire themselves: ops.CapturedGraph)
+        st[0].copy_(dirs); st[1].copy_(cols); st[2].copy_(sel)
+        self.active = FrameLight(st[0], st[1], st[2], cam, rotation, values, self._envmap(envmap, rotation),
+                                 self._suns(sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold), bake)
+
+    def _envmap(self, envmap, rotation) -> Optional[FrameEnvmap]:
+        if envmap is None:
+            return None
+        st = self.envmap_static
+        if st is None or st[0].device != envmap.device:
+            st = self.envmap_static = (torch.empty(3, 3, dtype=torch.float32, device=envmap.device),
+                                       torch.empty(1, dtype=torch.float32, device=envmap.device))
+        if rotation is None:
+            st[0].copy_(torch.eye(3, dtype=torch.float32))
+        else:
+            st[0].copy_(torch.as_tensor(rotation).reshape(3, 3))
+        st[1].copy_(envmap.exposure_tensor)
+        return FrameEnvmap(envmap.data, envmap.convention_id, st[0], st[1])
+
+    def _suns(self, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold) -> Optional[FrameSuns]:
+        if sun is None:
+            return None
+        model = self.model
+        suns, _ = as_suns(sun)
+        K, dev = len(suns), model.device
+        st = self.sun_static.get((K, str(dev)))
+        if st is None:
+            st = self.sun_static[(K, str(dev))] = (torch.empty(K, 3, device=dev), torch.empty(K, 3, device=dev), torch.empty(1, device=dev),
+                                                   torch.empty(1, device=dev), torch.arange(K, device=dev, dtype=torch.int32))
+        st[0].copy_(torch.tensor([s.direction for s in suns], dtype=torch.float64).to(torch.float32))
+        st[1].copy_(torch.tensor([s.colour for s in suns], dtype=torch.float32))
+        if shadow_threshold is None:
+            st[2].copy_(model.visibility_threshold.detach() if model.config.use_visibility else torch.zeros(1))
+        else:
+            st[2].copy_(torch.tensor([float(shadow_threshold)]))
+        st[3].copy_(torch.tensor([float(accumulation_mask_threshold)]))
+        scale = float(model.sigmoid_scale if shadow_sigmoid_scale is None else shadow_sigmoid_scale) if model.config.use_visibility else 0.0
+        return FrameSuns(*st, scale)
+
+    def end(self) -> None:
+        self.active = None
+
+    # ------------------------------------------------------------------ chunks
+    def runner(self, chunk: int, flat: RayBundle, use_graph: bool, cached: bool = True) -> "_ChunkRunner":
+        """the chunk runner of the active frame.  The background term depends on (camera, rotation) through python values baked into a
+        capture, so graphs are cached per (chunk, frame key); eager runners are free to share.  cached=False: a runner of the caller's
+        own, which the caller retires."""
+        if not cached:
+            return _ChunkRunner(self.model, chunk, flat, use_graph)
+        key = (chunk, use_graph, self.active.key if use_graph else None)
+        runner = self.runners.get(key)
+        if runner is None:
+            runner = _ChunkRunner(self.model, chunk, flat, use_graph)
+            if len(self.runners) >= 4:
+                self.runners.clear()
+            self.runners[key] = runner
+        return runner
+
+    def render(self, camera_ray_bundle: RayBundle, rotation, to_cpu: bool, camera_index: Optional[int], chunk: Optional[int],
+               use_graph: bool, envmap, sun, *thresholds) -> Dict[str, torch.Tensor]:
+        """model.get_outputs_for_camera_ray_bundle, which names and documents the arguments (`thresholds`: begin's last three)"""
+        model = self.model
+        assert not model.training, "call model.eval() first"
+        chunk = chunk or max(model.config.eval_num_rays_per_chunk, 4096)
+        shape = camera_ray_bundle.origins.shape[:-1]
+        flat = camera_ray_bundle.slice(0, 1 << 62)
+        num_rays = flat.origins.shape[0]
+        if camera_index is None:
+            camera_index = int(flat.camera_indices.reshape(-1)[0]) if flat.camera_indices is not None else 0
+        single = True
+        if sun is not None:
+            sun, single = as_suns(sun)
+        self.begin(camera_index, rotation, envmap, sun, *thresholds)
+        sun_keys = list(SUN_KEYS) if sun is not None else []
+        keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
+        out = {k: [] for k in keys}
+        try:
+            runner = self.runner(chunk, flat, use_graph)
+            for i in range(0, num_rays, chunk):
+                res = runner.run(flat, i, min(i + chunk, num_rays))
+                for k in keys:
+                    out[k].append(res[k].cpu() if to_cpu else res[k])
+        finally:
+            self.end()
+        if sun is not None:  # chunks are ray-major [n, K, ...]: K leads, and a single SunLight drops it
+            K = len(sun)
+            lead = () if single else (K,)
+            for k in sun_keys:
+                full = torch.cat(out.pop(k))
+                out[k] = [full.reshape(num_rays, K, -1).transpose(0, 1).reshape(*lead, *shape, -1)]
+        return {k: torch.cat(v).view(*shape, -1) if k not in sun_keys else v[0] for k, v in out.items()}
+
+
+class _ChunkRunner:
+    """static-shape forward of one render chunk, optionally captured in a HIP graph and replayed"""
+
+    def __init__(self, model, chunk: int, flat: RayBundle, use_graph: bool):
+        self.model, self.chunk, self.graph = model, chunk, None
+        dev = flat.origins.device
+        self.rb = RayBundle(origins=torch.zeros(chunk, 3, device=dev), directions=torch.zeros(chunk, 3, device=dev),
+                            pixel_area=torch.ones(chunk, 1, device=dev), camera_indices=torch.zeros(chunk, 1, dtype=torch.long, device=dev),
+                            metadata={"directions_norm": torch.ones(chunk, 1, device=dev)})
+        self.rb.directions[:, 2] = 1.0
+        if use_graph:
+            self._load(flat, 0, min(chunk, flat.origins.shape[0]))
+            self.graph = ops.CapturedGraph(dev, 2, lambda i: model.forward(self.rb))  # (retires itself when this runner is dropped)
+
+    def _load(self, flat: RayBundle, a: int, b: int) -> None:
+        n = b - a
+        self.rb.origins[:n].copy_(flat.origins[a:b])
+        self.rb.directions[:n].copy_(flat.directions[a:b])
+        if "directions_norm" in flat.metadata:
+            self.rb.metadata["directions_norm"][:n].copy_(flat.metadata["directions_norm"][a:b])
+        if n < self.chunk:  # pad the last chunk with copies of its first ray (results discarded)
+            self.rb.origins[n:].copy_(self.rb.origins[:1].expand(self.chunk - n, 3))
+            self.rb.directions[n:].copy_(self.rb.directions[:1].expand(self.chunk - n, 3))
+
+    def forward_rows(self, flat: RayBundle, a: int, b: int) -> Dict:
+        """rows a:b of `flat` through the model: the chunk's whole output dictionary, NOT cloned (under a graph: its static outputs,
+        overwritten by the next call), rows past b - a being padding"""
+        self._load(flat, a, b)
+        if self.graph is None:
+            return self.model.forward(self.rb)
+        self.graph.replay()
+        return self.graph.outputs
+
+    def retire(self) -> None:
+        """for an owner that is done with the runner at a known point (bake_transfer), rather than when its last reference goes"""
+        if self.graph is not None:
+            self.graph.retire()
+
+    def run(self, flat: RayBundle, a: int, b: int) -> Dict[str, torch.Tensor]:
+        out = self.forward_rows(flat, a, b)
+        return {k: v[:b - a].clone() for k, v in out.items() if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == self.chunk}

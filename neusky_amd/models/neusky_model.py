@@ -36,6 +36,7 @@ from ..model_components.ray_samplers import HashMLPDensityField, ProposalNetwork
 from ..model_components.renderers import RGBLambertianRendererWithVisibility
 from ..utils.utils import device_rng, device_rng_seed, linear_to_sRGB, to_device_async
 from ..plugin import ConfigBase, ModelBase
+from .frame import FrameRenderer, ray_background, shade
 
 
 def _default_loss_inclusions() -> Dict[str, Any]:  # neusky/configs/neusky_config.py:102-126
@@ -117,6 +118,7 @@ class NeuSkyFactoModel(ModelBase):
         self.fitting_eval_latents = False
         self.train_metadata = kwargs.get("train_metadata", None)
         self.eval_metadata = kwargs.get("eval_metadata", None)
+        self.frames = FrameRenderer(self)  # the chunked full-frame render: its light, static buffers and chunk graphs (frame.py)
         if config.collider_shape != "sphere":
             raise NotImplementedError("the neusky config uses the unit-sphere collider (neusky_config.py:159)")
         self.populate_modules()
@@ -248,7 +250,7 @@ class NeuSkyFactoModel(ModelBase):
         only, for callers written against the reference; the step itself runs sample_illumination_compact."""
         cam = ray_samples.camera_indices[:, 0, 0] if ray_samples.camera_indices.dim() == 3 else ray_samples.camera_indices.reshape(-1)
         R, S = ray_samples.frustums.origins.shape[:2]
-        dirs, cols, cam_of_ray, bg = self.sample_illumination_compact(cam, ray_samples.frustums.directions[:, 0].contiguous(), rotation)
+        dirs, cols, cam_of_ray, bg, _ = self.sample_illumination_compact(cam, ray_samples.frustums.directions[:, 0].contiguous(), rotation)
         D = dirs.shape[0]
         colours = cols[cam_of_ray.long()][:, None].expand(R, S, D, 3).reshape(R * S, D, 3)
         return colours, dirs[None].expand(R * S, D, 3), bg
@@ -256,29 +258,21 @@ class NeuSkyFactoModel(ModelBase):
     def sample_illumination_compact(self, camera_indices: torch.Tensor, ray_directions: torch.Tensor,
                                     rotation: Optional[torch.Tensor] = None, randoms: Optional[Dict] = None):
         """neusky_model.py:445-551 on compact data: camera_indices [R], ray_directions [R,3] ->
-        directions [D,3], cam_colours [U,D,3], cam_of_ray [R] (int32 row of cam_colours), hdr_background [R,3]."""
+        directions [D,3], cam_colours [U,D,3], cam_of_ray [R] (int32 row of cam_colours), hdr_background [R,3], and the
+        upper-hemisphere subset of the directions (:1650-1657; int32, static size D/2 for the antipodal direction set)."""
         latents, scales = self.get_illumination_field()
-        frame = getattr(self, "_frame_illumination", None)
-        if frame is not None and not self.training:
+        frame = None if self.training else self.frames.active
+        if frame is not None:
             # chunked full-frame render: directions and the frame camera's colours were decoded once per frame
-            dirs, cols, sel, cam, rot_f = frame
-            self._upper_sel = sel
-            R = camera_indices.shape[0]
-            env = getattr(self, "_frame_envmap", None)
-            if env is not None:  # the sky of the rays is the environment map itself (relight.envmap_lookup), read through static buffers
-                data, conv, rot_s, exposure = env
-                bg = torch.empty(R, 3, dtype=torch.float32, device=dirs.device)
-                hip.envmap_lookup(data, conv, ray_directions.contiguous(), rot_s, exposure, bg)
-            else:
-                bg = self.illumination_field.forward_camera(ray_directions, latents[cam], scales[cam], rot_f)
-            return dirs, cols, torch.zeros(R, dtype=torch.int32, device=dirs.device), bg
+            bg = ray_background(self, ray_directions, frame.cam, frame.rotation, frame.envmap)
+            cam_of_ray = torch.zeros(camera_indices.shape[0], dtype=torch.int32, device=frame.dirs.device)
+            return frame.dirs, frame.cols, cam_of_ray, bg, frame.sel
         if not self.training and self.config.fix_test_illumination_directions:
             dirs, sel = self.illumination_sampler.on_device(self.device, apply_random_rotation=False)  # :451-454
         elif randoms is not None and "light_rotation" in randoms:
             dirs, sel = self.illumination_sampler.on_device(self.device, rotation=randoms["light_rotation"])
         else:
             dirs, sel = self.illumination_sampler.on_device(self.device)  # :456-458, drawn on the device
-        self._upper_sel = sel  # upper-hemisphere subset (:1650-1657): static size D/2 for the antipodal direction set
         D = dirs.shape[0]
         if (self.training or self.fitting_eval_latents) and latents.shape[0] <= max(1024, camera_indices.shape[0]):
             # every camera of the active latent set is decoded (U = num_train_data, or num_eval_data while the eval latents
@@ -294,10 +288,10 @@ class NeuSkyFactoModel(ModelBase):
                 own = self.illumination_field.forward_grid(dirs, latents[r::n].contiguous(), scales[r::n].contiguous())
                 cols = CameraAllGather.apply(own, latents.shape[0], r, n)
                 bg = self.illumination_field(ray_directions, latents[camera_indices], scales[camera_indices], None)
-                return dirs, cols, inverse.to(torch.int32), bg
+                return dirs, cols, inverse.to(torch.int32), bg, sel
             if rotation is None:  # the rays' own background rows (:535-549) ride in the same decoder pass
                 cols, bg = self.illumination_field.forward_grid_and_rays(dirs, latents, scales, ray_directions, camera_indices)
-                return dirs, cols, inverse.to(torch.int32), bg
+                return dirs, cols, inverse.to(torch.int32), bg, sel
             cols = None
             unique = torch.arange(latents.shape[0], device=dirs.device)
         else:
@@ -315,7 +309,7 @@ class NeuSkyFactoModel(ModelBase):
             cols = self.illumination_field(dd, latents[ci], scales[ci], rot).reshape(U, D, 3)
         rot_r = rotation if (rotation is None or rotation.dim() == 2) else rotation[camera_indices]
         bg = self.illumination_field(ray_directions, latents[camera_indices], scales[camera_indices], rot_r)  # :535-549
-        return dirs, cols, inverse.to(torch.int32), bg
+        return dirs, cols, inverse.to(torch.int32), bg, sel
 
     def start_illumination(self, ray_bundle: RayBundle, rotation=None, randoms=None) -> None:
         """Launch the step's illumination decode on the second stream NOW (it depends on nothing but the batch's camera
@@ -487,7 +481,7 @@ class NeuSkyFactoModel(ModelBase):
         self._illumination_pending = None
         if fork and pending is not None:  # started by start_illumination (the pipeline, before the DDF-fit ground truth pass)
             main, side = torch.cuda.current_stream(), self._illumination_stream()
-            dirs, cam_colours, cam_of_ray, hdr_bg = pending
+            dirs, cam_colours, cam_of_ray, hdr_bg, sel = pending
         elif fork and self._illumination_stream() == torch.cuda.current_stream():
             fork = False  # (the caller's stream IS the illumination pool stream: in line, below)
         elif fork:
@@ -495,7 +489,7 @@ class NeuSkyFactoModel(ModelBase):
             side = self._illumination_stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                dirs, cam_colours, cam_of_ray, hdr_bg = self.sample_illumination_compact(cam, ray_bundle.directions, rotation, randoms)
+                dirs, cam_colours, cam_of_ray, hdr_bg, sel = self.sample_illumination_compact(cam, ray_bundle.directions, rotation, randoms)
         ray_samples, weights_list, sbins_list, sbins, inds_list = self._sample(ray_bundle, randoms, want_inds=randoms is not None)
         probe = self._grid_probe_points(ray_bundle.origins.device, randoms)
         field_outputs = self.field(ray_samples, return_alphas=True, extra_points=None if probe is None else probe[0])
@@ -504,11 +498,11 @@ class NeuSkyFactoModel(ModelBase):
         sbins_list = sbins_list + [sbins]
         if fork:
             main.wait_stream(side)
-            for t in (dirs, cam_colours, cam_of_ray, hdr_bg, getattr(self, "_upper_sel", None)):
+            for t in (dirs, cam_colours, cam_of_ray, hdr_bg, sel):
                 if isinstance(t, torch.Tensor):
                     t.record_stream(main)  # allocated on the side stream, consumed on this one from here on
         else:
-            dirs, cam_colours, cam_of_ray, hdr_bg = self.sample_illumination_compact(cam, ray_bundle.directions, rotation, randoms)
+            dirs, cam_colours, cam_of_ray, hdr_bg, sel = self.sample_illumination_compact(cam, ray_bundle.directions, rotation, randoms)
         out: Dict[str, Any] = {
             "ray_samples": ray_samples, "field_outputs": field_outputs, "weights": weights,
             "bg_transmittance": field_outputs["bg_transmittance"], "weights_list": weights_list, "sbins_list": sbins_list,
@@ -525,8 +519,7 @@ class NeuSkyFactoModel(ModelBase):
             if p2p_vis.requires_grad:
                 raise NotImplementedError("visibility geometry is differentiated only in 'depth'/'both' mode (neusky_config.py:156)")
             out["visibility_dict"] = self.compute_visibility_compact(ray_bundle.origins, ray_bundle.directions, p2p_vis, dirs,
-                                                             self.visibility_threshold, self.sigmoid_scale,
-                                                             sel=getattr(self, "_upper_sel", None))
+                                                             self.visibility_threshold, self.sigmoid_scale, sel=sel)
             out["depth"] = depth
         if probe is not None:
             # (sic) the reference hands `deltas=gap` ([3]) to get_alpha, which broadcasts [P,1]*[3] -> three alphas
@@ -569,38 +562,17 @@ class NeuSkyFactoModel(ModelBase):
         so = self.sample_and_forward_field(ray_bundle, batch=batch, rotation=rotation, step=step, randoms=randoms)
         fo = so["field_outputs"]
         weights, ray_samples = so["weights"], so["ray_samples"]
-        visibility = so["visibility_dict"]["visibility"] if self.config.use_visibility else None
         sdf_at_termination = so["visibility_dict"].get("sdf_at_termination") if self.config.use_visibility else None
-        bake = None if self.training else getattr(self, "_transfer_storage", None)
-        sun = None if self.training else getattr(self, "_frame_sun", None)
-        if bake is not None:
-            # relight.bake_transfer: the renderer's inputs go to the radiance-transfer bake instead (no light enters; no rgb comes out)
-            from ..relight.transfer import bake_rows
-            rgb = None
-            transfer = bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], weights[..., 0],
-                                 so["illumination_directions"], visibility, bake)
-        elif sun is not None:
-            rgb = None
-            sun_out = self._sun_outputs(so, ray_bundle, sun)
-        else:
-            rgb = self.lambertian_renderer.forward_compact(
-                albedos=fo[NeuSkyFieldHeadNames.ALBEDO], normals=fo[FieldHeadNames.NORMALS],
-                light_directions=so["illumination_directions"], cam_colours=so["hdr_illumination_colours"],
-                cam_of_ray=so["cam_of_ray"], visibility=visibility, background_illumination=so["hdr_background_colours"],
-                weights=weights)  # :797-805
+        frame = None if self.training else self.frames.active
+        lit = {"rgb": self.render_lambertian(so)} if frame is None else shade(self, frame, so, ray_bundle)
         accumulation, p2p_dist = so["accumulation"], so["p2p_dist"]
         depth = p2p_dist / ray_bundle.metadata["directions_norm"]
         normal, albedo = so["normal"], so["albedo_on_white"]  # :812-813 (white background), from the same reduction pass
         outputs: Dict[str, Any] = {
-            "rgb": rgb, "albedo": albedo, "accumulation": accumulation, "depth": depth, "p2p_dist": p2p_dist, "normal": normal,
+            **lit, "albedo": albedo, "accumulation": accumulation, "depth": depth, "p2p_dist": p2p_dist, "normal": normal,
             "weights": weights, "hdr_background_colours": so["hdr_background_colours"],
             "directions_norm": ray_bundle.metadata["directions_norm"], "sdf_at_termination": sdf_at_termination,
         }
-        if bake is not None:
-            del outputs["rgb"]
-            outputs.update(transfer)
-        elif sun is not None:
-            outputs.update(sun_out)
         if self.training:
             outputs["eik_grad"] = fo[FieldHeadNames.GRADIENT]  # :903-904
             outputs.update(so)
@@ -611,33 +583,14 @@ class NeuSkyFactoModel(ModelBase):
             outputs["visibility_batch"] = so["visibility_dict"]["visibility_batch"]
         return outputs
 
-    def _sun_outputs(self, so: Dict[str, Any], ray_bundle: RayBundle, sun) -> Dict[str, torch.Tensor]:
-        """a chunk lit by its sky and the frame's K suns (include/neusky_hip.h; begin_frame): the hemisphere kernel's linear image, one
-        DDF query per (ray, sun), the sun transfer and the composite.  Ray-major views of the [K, R, ...] results: rgb, lin [R, K, 3],
-        shadow_map, shadow_difference [R, K]."""
-        sun_dirs, colours, threshold, acc_threshold, sel, scale = sun
+    def render_lambertian(self, so: Dict[str, Any]) -> torch.Tensor:
+        """:797-805 on the compact tensors of sample_and_forward_field"""
         fo = so["field_outputs"]
-        a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
-        w = so["weights"][..., 0].contiguous()
-        R, K, dev = a.shape[0], sun_dirs.shape[0], a.device
-        vis_sky = so["visibility_dict"]["visibility"].contiguous() if self.config.use_visibility else None
-        lin_sky = torch.empty(R, 3, device=dev)
-        hip.hemi_composite_fwd(a, n, w, so["illumination_directions"].contiguous(), so["hdr_illumination_colours"].contiguous(),
-                               so["cam_of_ray"], vis_sky, so["hdr_background_colours"].contiguous(), torch.empty(R, 3, device=dev), lin_sky)
-        acc = so["accumulation"].reshape(-1).contiguous()
-        vis = diff = None
-        if self.config.use_visibility:
-            vd = self.compute_visibility_compact(ray_bundle.origins, ray_bundle.directions, so["p2p_dist"].detach(), sun_dirs, threshold,
-                                                 scale, compute_shadow_map=True, sel=sel)
-            vis = vd["visibility"].t().contiguous()  # [K, R]
-            diff = vd["difference"].view(R, K)
-        t = torch.empty(K, R, 3, device=dev)
-        hip.sun_transfer(a, n, w, sun_dirs, t)
-        rgb, lin, shadow = torch.empty(K, R, 3, device=dev), torch.empty(K, R, 3, device=dev), torch.empty(K, R, device=dev)
-        hip.sun_composite(lin_sky, t, vis, acc, acc_threshold, sun_dirs, colours, rgb, lin, shadow)
-        on = (acc > acc_threshold)[:, None] & (sun_dirs[:, 2] > 0)[None]
-        diff = torch.where(on, diff, torch.zeros((), device=dev)) if diff is not None else torch.zeros(R, K, device=dev)
-        return {"rgb": rgb.permute(1, 0, 2), "lin": lin.permute(1, 0, 2), "shadow_map": shadow.t(), "shadow_difference": diff}
+        return self.lambertian_renderer.forward_compact(
+            albedos=fo[NeuSkyFieldHeadNames.ALBEDO], normals=fo[FieldHeadNames.NORMALS],
+            light_directions=so["illumination_directions"], cam_colours=so["hdr_illumination_colours"],
+            cam_of_ray=so["cam_of_ray"], visibility=so["visibility_dict"]["visibility"] if self.config.use_visibility else None,
+            background_illumination=so["hdr_background_colours"], weights=so["weights"])
 
     def get_loss_dict(self, outputs: Dict[str, Any], batch: Dict[str, Any], metrics_dict=None) -> Dict[str, torch.Tensor]:
         """neusky_model.py:933-1062, both branches, through ONE fused kernel each way (ops.MainLossesFn): the train branch's eight
@@ -922,86 +875,11 @@ class NeuSkyFactoModel(ModelBase):
         8100 chunks of a 1080p frame, neusky_model.py:1413-1432; the result is the same).
         envmap: a relight.EnvironmentMap lighting the frame instead of the camera's latent: the light colours are the map's cell
         averages at the frame's directions (relight.project_envmap), the rays' background its bilinear lookup.
-        sun: a relight.SunLight or a sequence of K of them on top of that sky (_begin_frame_sun)."""
-        self._begin_frame(camera_index, rotation, envmap)
-        self._begin_frame_sun(sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold)
-
-    def _begin_frame_sun(self, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold) -> None:
-        """the K suns of a frame (include/neusky_hip.h): directions, colours, the shadow threshold and the accumulation threshold go to
-        static device buffers (one set per K) that a chunk graph reads through their pointers, so the graph is keyed on K and a new
-        position, colour or threshold replays it.  The sigmoid scale is a by-value argument of nsky_visibility_finish_fwd: a scale
-        other than the model's own joins the key."""
-        self._frame_sun = None
-        if sun is None:
-            return
-        from ..relight.sun import as_suns
-        suns, _ = as_suns(sun)
-        K, dev = len(suns), self.device
-        cache = self.__dict__.setdefault("_frame_sun_static", {})
-        st = cache.get((K, str(dev)))
-        if st is None:
-            st = cache[(K, str(dev))] = (torch.empty(K, 3, device=dev), torch.empty(K, 3, device=dev), torch.empty(1, device=dev),
-                                         torch.empty(1, device=dev), torch.arange(K, device=dev, dtype=torch.int32))
-        st[0].copy_(torch.tensor([s.direction for s in suns], dtype=torch.float64).to(torch.float32))
-        st[1].copy_(torch.tensor([s.colour for s in suns], dtype=torch.float32))
-        if shadow_threshold is None:
-            st[2].copy_(self.visibility_threshold.detach() if self.config.use_visibility else torch.zeros(1))
-        else:
-            st[2].copy_(torch.tensor([float(shadow_threshold)]))
-        st[3].copy_(torch.tensor([float(accumulation_mask_threshold)]))
-        scale = float(self.sigmoid_scale if shadow_sigmoid_scale is None else shadow_sigmoid_scale) if self.config.use_visibility else 0.0
-        self._frame_sun = st + (scale,)
-        self._frame_key = (self._frame_key, "sun", K, scale)
-
-    def _begin_frame(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None) -> None:
-        latents, scales = self.get_illumination_field()
-        fixed = self.config.fix_test_illumination_directions
-        dirs, sel = self.illumination_sampler.on_device(self.device, apply_random_rotation=False if fixed else None)
-        cam = int(camera_index)
-        D = dirs.shape[0]
-        rot_key = None if (rotation is None or envmap is not None) else tuple(rotation.reshape(-1).tolist())
-        if rot_key is not None:
-            # a chunk graph cached under this rotation's values reads the rotation through the pointer it was captured with: the
-            # first tensor seen with these values is kept, and serves every later frame that asks for them
-            rotation = self.__dict__.setdefault("_frame_rotations", {}).setdefault(rot_key, rotation)
-        if envmap is not None:
-            from ..relight import project_envmap
-            cols = project_envmap(envmap, dirs, rotation)[0][None]
-        elif rotation is None:
-            cols = self.illumination_field.forward_grid(dirs, latents[cam][None], scales[cam][None])
-        else:
-            cols = self.illumination_field.forward_camera(dirs, latents[cam], scales[cam], rotation)[None]
-        # static per-model buffers: a chunk graph captured for one frame stays valid for the next (animation frames
-        # only change the camera / rotation, render_animation.py:196-207)
-        st = getattr(self, "_frame_static", None)
-        if st is None or st[0].shape != dirs.shape or st[0].device != dirs.device:
-            st = (torch.empty_like(dirs), torch.empty_like(cols), torch.empty_like(sel))
-            self._frame_static = st
-            self._chunk_runners = {}  # (the dropped runners' graphs retire themselves: ops.CapturedGraph)
-        st[0].copy_(dirs); st[1].copy_(cols); st[2].copy_(sel)
-        self._frame_illumination = (st[0], st[1], st[2], cam, rotation)
-        if envmap is None:
-            self._frame_envmap = None
-            self._frame_key = (cam, rot_key)
-            return
-        # a chunk graph reads the map through its pointer and the rotation / exposure through static buffers: it is keyed on the
-        # map's storage, shape and convention only, so a new rotation or exposure replays it without a new capture
-        env_st = getattr(self, "_frame_envmap_static", None)
-        if env_st is None or env_st[0].device != envmap.device:
-            env_st = (torch.empty(3, 3, dtype=torch.float32, device=envmap.device), torch.empty(1, dtype=torch.float32, device=envmap.device))
-            self._frame_envmap_static = env_st
-        if rotation is None:
-            env_st[0].copy_(torch.eye(3, dtype=torch.float32))
-        else:
-            env_st[0].copy_(torch.as_tensor(rotation).reshape(3, 3))
-        env_st[1].copy_(envmap.exposure_tensor)
-        self._frame_envmap = (envmap.data, envmap.convention_id, env_st[0], env_st[1])
-        self._frame_key = ("envmap", envmap.data.data_ptr(), tuple(envmap.data.shape), envmap.convention_id)
+        sun: a relight.SunLight or a sequence of K of them on top of that sky (frame.FrameSuns)."""
+        self.frames.begin(camera_index, rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold)
 
     def end_frame(self) -> None:
-        self._frame_illumination = None
-        self._frame_envmap = None
-        self._frame_sun = None
+        self.frames.end()
 
     @torch.no_grad()
     def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle: RayBundle, show_progress=False, rotation=None, to_cpu=False,
@@ -1019,83 +897,5 @@ class NeuSkyFactoModel(ModelBase):
         a sequence puts a leading K on those four.  The field, the sampler and the sky pass of a chunk run once for all K suns.
         shadow_threshold / shadow_sigmoid_scale default to the model's trained visibility threshold and sigmoid scale; the shadow is
         masked by accumulation > accumulation_mask_threshold.  A sun with elevation <= 0 has set: it adds no light and no shadow."""
-        assert not self.training, "call model.eval() first"
-        chunk = chunk or max(self.config.eval_num_rays_per_chunk, 4096)
-        shape = camera_ray_bundle.origins.shape[:-1]
-        flat = camera_ray_bundle.slice(0, 1 << 62)
-        num_rays = flat.origins.shape[0]
-        if camera_index is None:
-            camera_index = int(flat.camera_indices.reshape(-1)[0]) if flat.camera_indices is not None else 0
-        if sun is not None and not hasattr(sun, "direction"):
-            sun = list(sun)
-        self.begin_frame(camera_index, rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold)
-        sun_keys = ["rgb", "lin", "shadow_map", "shadow_difference"] if sun is not None else []
-        keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
-        out = {k: [] for k in keys}
-        try:
-            # the background term depends on (camera, rotation) through python values baked into a capture, so graphs
-            # are cached per (chunk, camera, rotation); eager runners are free to share
-            key = (chunk, use_graph, self._frame_key if use_graph else None)
-            runner = self._chunk_runners.get(key)
-            if runner is None:
-                runner = _ChunkRunner(self, chunk, flat, use_graph)
-                if len(self._chunk_runners) >= 4:
-                    self._chunk_runners.clear()
-                self._chunk_runners[key] = runner
-            for i in range(0, num_rays, chunk):
-                res = runner.run(flat, i, min(i + chunk, num_rays))
-                for k in keys:
-                    out[k].append(res[k].cpu() if to_cpu else res[k])
-        finally:
-            self.end_frame()
-        if sun is not None:  # chunks are ray-major [n, K, ...]: K leads, and a single SunLight drops it
-            from ..relight.sun import SunLight
-            K = 1 if isinstance(sun, SunLight) else len(sun)
-            lead = () if isinstance(sun, SunLight) else (K,)
-            for k in sun_keys:
-                full = torch.cat(out.pop(k))
-                out[k] = [full.reshape(num_rays, K, -1).transpose(0, 1).reshape(*lead, *shape, -1)]
-        return {k: torch.cat(v).view(*shape, -1) if k not in sun_keys else v[0] for k, v in out.items()}
-
-
-class _ChunkRunner:
-    """static-shape forward of one render chunk, optionally captured in a HIP graph and replayed"""
-
-    def __init__(self, model: "NeuSkyFactoModel", chunk: int, flat: RayBundle, use_graph: bool):
-        self.model, self.chunk, self.graph = model, chunk, None
-        dev = flat.origins.device
-        self.rb = RayBundle(origins=torch.zeros(chunk, 3, device=dev), directions=torch.zeros(chunk, 3, device=dev),
-                            pixel_area=torch.ones(chunk, 1, device=dev), camera_indices=torch.zeros(chunk, 1, dtype=torch.long, device=dev),
-                            metadata={"directions_norm": torch.ones(chunk, 1, device=dev)})
-        self.rb.directions[:, 2] = 1.0
-        if use_graph:
-            self._load(flat, 0, min(chunk, flat.origins.shape[0]))
-            self.graph = ops.CapturedGraph(dev, 2, lambda i: model.forward(self.rb))  # (retires itself when this runner is dropped)
-
-    def _load(self, flat: RayBundle, a: int, b: int) -> None:
-        n = b - a
-        self.rb.origins[:n].copy_(flat.origins[a:b])
-        self.rb.directions[:n].copy_(flat.directions[a:b])
-        if "directions_norm" in flat.metadata:
-            self.rb.metadata["directions_norm"][:n].copy_(flat.metadata["directions_norm"][a:b])
-        if n < self.chunk:  # pad the last chunk with copies of its first ray (results discarded)
-            self.rb.origins[n:].copy_(self.rb.origins[:1].expand(self.chunk - n, 3))
-            self.rb.directions[n:].copy_(self.rb.directions[:1].expand(self.chunk - n, 3))
-
-    def forward_rows(self, flat: RayBundle, a: int, b: int) -> Dict:
-        """rows a:b of `flat` through the model: the chunk's whole output dictionary, NOT cloned (under a graph: its static outputs,
-        overwritten by the next call), rows past b - a being padding"""
-        self._load(flat, a, b)
-        if self.graph is None:
-            return self.model.forward(self.rb)
-        self.graph.replay()
-        return self.graph.outputs
-
-    def retire(self) -> None:
-        """for an owner that is done with the runner at a known point (bake_transfer), rather than when its last reference goes"""
-        if self.graph is not None:
-            self.graph.retire()
-
-    def run(self, flat: RayBundle, a: int, b: int) -> Dict[str, torch.Tensor]:
-        out = self.forward_rows(flat, a, b)
-        return {k: v[:b - a].clone() for k, v in out.items() if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == self.chunk}
+        return self.frames.render(camera_ray_bundle, rotation, to_cpu, camera_index, chunk, use_graph, envmap, sun, shadow_threshold,
+                                  shadow_sigmoid_scale, accumulation_mask_threshold)

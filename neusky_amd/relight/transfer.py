@@ -115,20 +115,17 @@ class RadianceTransfer:
 
     # ------------------------------------------------------------------ relighting
     def _light(self, model, envmap, cam: int, rotation: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(L [D, 3], bg [R, 3]) of one light, built as the frame render builds them (begin_frame, sample_illumination_compact)"""
+        """(L [D, 3], bg [R, 3]) of one light: the frame render's own constructions (models/frame.py), the latent background in blocks
+        of _BG_ROWS rays"""
+        from ..models.frame import light_colours, ray_background  # here, not at the top: models.frame imports this module
+        L = light_colours(model, self.dirs, cam, rotation, envmap)
         if envmap is not None:
-            from .envmap import envmap_lookup, project_envmap
-            return project_envmap(envmap, self.dirs, rotation)[0], envmap_lookup(envmap, self.ray_directions, rotation)
-        latents, scales = model.get_illumination_field()
-        field = model.illumination_field
-        if rotation is None:
-            L = field.forward_grid(self.dirs, latents[cam][None], scales[cam][None])[0]
-        else:
-            L = field.forward_camera(self.dirs, latents[cam], scales[cam], rotation)
+            from .envmap import envmap_lookup
+            return L, envmap_lookup(envmap, self.ray_directions, rotation)
         R = self.ray_directions.shape[0]
         bg = torch.empty(R, 3, dtype=torch.float32, device=self.device)
         for a in range(0, R, _BG_ROWS):
-            bg[a:a + _BG_ROWS] = field.forward_camera(self.ray_directions[a:a + _BG_ROWS], latents[cam], scales[cam], rotation)
+            bg[a:a + _BG_ROWS] = ray_background(model, self.ray_directions[a:a + _BG_ROWS], cam, rotation)
         return L, bg
 
     @torch.no_grad()
@@ -172,8 +169,7 @@ class RadianceTransfer:
 def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Optional[int] = None, use_graph: bool = True,
                   camera_index: Optional[int] = None) -> RadianceTransfer:
     """Run the chunked eval forward of get_outputs_for_camera_ray_bundle once, with the renderer's inputs routed into the transfer bake
-    (a mode flag on the model, off outside this call: the plain frame render and its captured chunk graphs are untouched)."""
-    from ..models.neusky_model import _ChunkRunner
+    (the shading mode of this call's frame, models/frame.py: the plain frame render and its captured chunk graphs are untouched)."""
     dtype = _storage_dtype(storage)
     assert not model.training, "call model.eval() first"
     if not model.config.fix_test_illumination_directions:
@@ -186,17 +182,16 @@ def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Option
     if camera_index is None:
         camera_index = int(flat.camera_indices.reshape(-1)[0]) if flat.camera_indices is not None else 0
     dev = flat.origins.device
-    model.begin_frame(camera_index)
-    model._transfer_storage = storage
     runner = None
     try:
-        dirs = model._frame_illumination[0].clone()
+        model.frames.begin(camera_index, bake=storage)
+        dirs = model.frames.active.dirs.clone()
         D = dirs.shape[0]
         T = torch.empty(R, D, 3, dtype=dtype, device=dev)
         acc = torch.empty(R, dtype=torch.float32, device=dev)
         exps = torch.empty(R, dtype=torch.int32, device=dev) if storage == "fp16" else None
         outs = {k: [] for k in FRAME_KEYS}
-        runner = _ChunkRunner(model, chunk, flat, use_graph)  # its own runner: a captured graph of this mode is never cached on the model
+        runner = model.frames.runner(chunk, flat, use_graph, cached=False)  # its own: a captured graph of this mode is never cached
         for a in range(0, R, chunk):
             b = min(a + chunk, R)
             res = runner.forward_rows(flat, a, b)
@@ -207,8 +202,7 @@ def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Option
             for k in FRAME_KEYS:
                 outs[k].append(res[k][:b - a].clone())
     finally:
-        model._transfer_storage = None
-        model.end_frame()
+        model.frames.end()
         if runner is not None:
             runner.retire()
     outputs = {k: torch.cat(v).view(*shape, -1) for k, v in outs.items()}

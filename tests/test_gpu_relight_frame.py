@@ -87,12 +87,12 @@ def test_rotation_replays_the_captured_graph(scene):
                                                                [0.0, math.sin(0.3), math.cos(0.3)]])
     got = m.get_outputs_for_camera_ray_bundle(rb, camera_index=1, chunk=64, rotation=r1.to(DEV), use_graph=True, envmap=env)
     assert _rel(got, _oracle(pipe, rb, envmap, "blender", r1)) < 1e-4
-    runners = dict(m._chunk_runners)
+    runners = dict(m.frames.runners)
     graphs = {k: r.graph for k, r in runners.items()}
     got = m.get_outputs_for_camera_ray_bundle(rb, camera_index=1, chunk=64, rotation=r2.to(DEV), use_graph=True, envmap=env)
     assert _rel(got, _oracle(pipe, rb, envmap, "blender", r2)) < 1e-4
-    assert m._chunk_runners.keys() == runners.keys()  # no new capture: the same runner and graph served the second rotation
-    assert all(m._chunk_runners[k] is r and r.graph is graphs[k] for k, r in runners.items())
+    assert m.frames.runners.keys() == runners.keys()  # no new capture: the same runner and graph served the second rotation
+    assert all(m.frames.runners[k] is r and r.graph is graphs[k] for k, r in runners.items())
 
 
 def test_latent_path_unchanged_after_envmap_frames(scene):

@@ -124,16 +124,16 @@ def test_shadow_map_is_the_ddf_query_of_the_sun_direction(scene):
 def test_overrides_reach_the_shadow(scene):
     pipe, _, render, _, lit, _ = scene
     m = pipe.model
-    n = len(m._chunk_runners)
+    n = len(m.frames.runners)
     d = _f64(lit["shadow_difference"])
     thr = float(np.median(d))  # a threshold inside the frame's own range of differences
     got = render(use_graph=True, sun=SUN, shadow_threshold=thr)
-    assert len(m._chunk_runners) == n  # a threshold replays the chunk graph
+    assert len(m.frames.runners) == n  # a threshold replays the chunk graph
     ref = 1.0 - 1.0 / (1.0 + np.exp(-m.sigmoid_scale * (d - thr)))
     on = _f64(lit["accumulation"]) > 0.0
     assert np.abs(_f64(got["shadow_map"]) - ref * on).max() < 1e-5
     masked = render(use_graph=True, sun=SUN, accumulation_mask_threshold=2.0)  # no ray accumulates more than 1
-    assert len(m._chunk_runners) == n
+    assert len(m.frames.runners) == n
     assert masked["shadow_map"].abs().max().item() == 0.0 and masked["shadow_difference"].abs().max().item() == 0.0
     assert torch.equal(masked["rgb"], render(use_graph=True)["rgb"])
 
@@ -156,9 +156,9 @@ def test_a_new_sun_replays_the_captured_chunk(scene):
     m = pipe.model
     a, b = SunLight(20.0, 60.0, (1.0, 1.0, 1.0)), SunLight(250.0, 15.0, (3.0, 2.0, 0.5))
     got_a = render(use_graph=True, sun=a)
-    runners = dict(m._chunk_runners)
+    runners = dict(m.frames.runners)
     got_b = render(use_graph=True, sun=b)
-    assert len(m._chunk_runners) == len(runners) and all(m._chunk_runners[k] is r for k, r in runners.items())
+    assert len(m.frames.runners) == len(runners) and all(m.frames.runners[k] is r for k, r in runners.items())
     assert not torch.equal(got_a["rgb"], got_b["rgb"])
     for got, s in ((got_a, a), (got_b, b)):
         eager = render(use_graph=False, sun=s)

@@ -131,10 +131,10 @@ def test_a_bake_leaves_the_frame_render_untouched(scene):
     m = pipe.model
     before = m.get_outputs_for_camera_ray_bundle(rb, camera_index=1, chunk=32, use_graph=True)
     before = {k: v.clone() for k, v in before.items()}
-    runners = dict(m._chunk_runners)
+    runners = dict(m.frames.runners)
     bake_transfer(m, rb, storage="fp16", chunk=32, camera_index=1)
-    assert getattr(m, "_transfer_storage", None) is None
-    assert m._chunk_runners.keys() == runners.keys() and all(m._chunk_runners[k] is r for k, r in runners.items())
+    assert m.frames.active is None
+    assert m.frames.runners.keys() == runners.keys() and all(m.frames.runners[k] is r for k, r in runners.items())
     after = m.get_outputs_for_camera_ray_bundle(rb, camera_index=1, chunk=32, use_graph=True)
     assert after.keys() == before.keys()
     for k, v in before.items():
