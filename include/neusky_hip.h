@@ -862,6 +862,49 @@ int nsky_envmap_lookup(const float* map, int64_t H, int64_t W, int32_t conventio
                        const float* exposure, float* out, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The sun of an environment map, lifted out of it into a SunLight (neusky_amd/relight/envmap_sun.py, csrc/envmap_sun.hip).  The D cell
+ * averages above smear a sun over a cell hundreds of times its size, so it casts no shadow edge; these kernels find it, take its
+ * excess over the surrounding sky out of the map and return that energy as the colour of a directional sun (the section after the
+ * transfer's).  Everything is in the MAP frame: texel directions e_t (per convention), solid angles omega_t, row 0 at the top and z up
+ * as above.  All arithmetic is fp64 on the fp32 map values, sums run in a fixed order without atomics (two runs agree bit for bit),
+ * flat texel indices are int64.
+ *   luminance:  Y_t = 0.2126 R + 0.7152 G + 0.0722 B.
+ *   excluded:   a texel with a non-finite channel belongs to no set below and is copied to the residual unchanged.
+ *   peak:       p = argmax Y_t over the upper hemisphere (rows with (i + 0.5) / H < 0.5), ties to the lowest flat index; e_p its
+ *               direction.  No finite texel there: index -1, Y_p = 0, nothing is found and e_p reads +z.
+ *   cap, ring:  cap = {t : <e_t, e_p> >= cos rho};  ring = {t : cos 2 rho <= <e_t, e_p> < cos rho}; over all rows: a dot product, not
+ *               an index range, so both wrap across the column seam and close over the pole.
+ *   sky level:  tau = sum_ring omega Y / sum_ring omega.
+ *   found:      the ring is not empty, Y_p > 0 and Y_p >= min_peak_ratio tau (a black sky, tau = 0, with a bright peak counts).
+ *   residual:   t in cap with Y_t > tau: L'_t = fp32(L_t tau / Y_t) (the chromaticity kept, the luminance clamped to the sky level,
+ *               rounded once); every other texel, and every texel when nothing is found: L'_t = L_t bit for bit.
+ *   excess:     x_t = L_t - L'_t in fp64 from the stored fp32 values.
+ *   sun:        colour C = (1 / 2 pi) sum_t omega_t x_t (the sun section's unit, C = L Omega / (2 pi));  direction
+ *               m = normalize(sum_t omega_t Y(x_t) e_t);  solid angle Omega_sun = sum of omega_t over the texels with an excess.
+ *               Nothing found: C = 0, m = e_p, Omega_sun = 0.
+ *   conserved:  sum_t omega_t L_t = sum_t omega_t L'_t + 2 pi C, up to fp64 summation.
+ *   scene:      the renderer lights direction d with the map at R d, so the sun's scene direction is R^T m; the map's exposure
+ *               multiplies C.
+ * scratch: NSKY_ENVMAP_SUN_SCRATCH_BYTES of device memory (8-byte aligned) for the workgroups' partials (at most
+ *          NSKY_ENVMAP_SUN_MAX_BLOCKS workgroups of up to 7 fp64 each); the three calls may share one buffer on one stream.
+ * nsky_envmap_peak:      map [H,W,3], H >= 2  ->  peak: 16 bytes, the int64 texel index then the fp64 Y_p.
+ * nsky_envmap_sun_ring:  map, peak, rho (radians, in (0, pi / 4))  ->  ring [2] = sum_ring omega, sum_ring omega Y.  Visits the rows
+ *                        within 2 rho of the peak's polar angle only.
+ * nsky_envmap_sun_split: map, peak, ring, rho, min_peak_ratio >= 0  ->  residual [H,W,3] (always written completely: a copy when
+ *                        nothing is found; must not be the map) and stats [12] = m (3), C (3), Y_p, tau, Omega_sun, found (0 / 1),
+ *                        peak row, peak column (-1, -1 without a peak).  The copy streams 16 bytes per lane when map and residual are
+ *                        16-byte aligned; only the rows within rho of the peak's polar angle take the angle test.
+ * Each call reads what the previous one wrote to device memory and nothing on the host: the three run on one stream without a
+ * synchronisation. */
+#define NSKY_ENVMAP_SUN_MAX_BLOCKS 1024
+#define NSKY_ENVMAP_SUN_SCRATCH_BYTES (NSKY_ENVMAP_SUN_MAX_BLOCKS * 7 * 8)
+int nsky_envmap_peak(const float* map, int64_t H, int64_t W, int32_t convention, void* scratch, void* peak, nsky_stream_t stream);
+int nsky_envmap_sun_ring(const float* map, int64_t H, int64_t W, int32_t convention, const void* peak, double rho, void* scratch,
+                         double* ring, nsky_stream_t stream);
+int nsky_envmap_sun_split(const float* map, int64_t H, int64_t W, int32_t convention, const void* peak, const double* ring, double rho,
+                          double min_peak_ratio, void* scratch, float* residual, double* stats, nsky_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Precomputed radiance transfer of one frame (neusky_amd/relight/transfer.py, csrc/transfer.hip).  nsky_hemi_composite_fwd is linear in
  * the light colours; with its two sums swapped,
  *   T[r,d,c] = vis[r,d] sum_s weights[r,s] albedo[r,s,c] clamp(<normals[r,s], dirs[d]>, 0, 1) / cnt[r,s]

@@ -1284,6 +1284,44 @@ def envmap_lookup(data, convention: int, directions, rotation, exposure, out):
                          stream_ptr()), "nsky_envmap_lookup")
 
 
+# ---- the sun of an environment map (relight/envmap_sun.py, csrc/envmap_sun.hip): peak -> ring -> split on one stream, no host reads
+ENVMAP_SUN_SCRATCH_BYTES = 1024 * 7 * 8  # NSKY_ENVMAP_SUN_SCRATCH_BYTES
+_envmap_peak = _sig("nsky_envmap_peak", C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
+_envmap_sun_ring = _sig("nsky_envmap_sun_ring", C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                        C.c_void_p)
+_envmap_sun_split = _sig("nsky_envmap_sun_split", C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def _envmap_sun_map(data, scratch):
+    H, W = data.shape[:2]
+    _typed(data, torch.float32, H, W, 3)
+    _typed(scratch, torch.float64, ENVMAP_SUN_SCRATCH_BYTES // 8)
+    return H, W
+
+
+def envmap_peak(data, convention: int, scratch, peak):
+    """data: fp32 [H, W, 3]; scratch: fp64 [ENVMAP_SUN_SCRATCH_BYTES / 8]; peak: int64 [2] <- the texel index, then the bits of the fp64
+    luminance (peak.view(torch.float64)[1])"""
+    H, W = _envmap_sun_map(data, scratch)
+    check(_envmap_peak(ptr(data), H, W, convention, ptr(scratch), ptr(_typed(peak, torch.int64, 2)), stream_ptr()), "nsky_envmap_peak")
+
+
+def envmap_sun_ring(data, convention: int, peak, rho: float, scratch, ring):
+    """peak: as envmap_peak left it; rho: radians; ring: fp64 [2] <- sum omega, sum omega Y over the annulus [rho, 2 rho) about the peak"""
+    H, W = _envmap_sun_map(data, scratch)
+    check(_envmap_sun_ring(ptr(data), H, W, convention, ptr(_typed(peak, torch.int64, 2)), float(rho), ptr(scratch),
+                           ptr(_typed(ring, torch.float64, 2)), stream_ptr()), "nsky_envmap_sun_ring")
+
+
+def envmap_sun_split(data, convention: int, peak, ring, rho: float, min_peak_ratio: float, scratch, residual, stats):
+    """residual: fp32 [H, W, 3] <- the map without its sun; stats: fp64 [12] <- m (3), C (3), Y_p, tau, Omega_sun, found, peak row, column"""
+    H, W = _envmap_sun_map(data, scratch)
+    check(_envmap_sun_split(ptr(data), H, W, convention, ptr(_typed(peak, torch.int64, 2)), ptr(_typed(ring, torch.float64, 2)), float(rho),
+                            float(min_peak_ratio), ptr(scratch), ptr(_typed(residual, torch.float32, H, W, 3)),
+                            ptr(_typed(stats, torch.float64, 12)), stream_ptr()), "nsky_envmap_sun_split")
+
+
 # ---- precomputed radiance transfer (relight/transfer.py): bake a frame's light-independent part once, relight it per light
 TRANSFER_FP32, TRANSFER_FP16 = 0, 1  # NSKY_TRANSFER_FP32 / _FP16
 TRANSFER_MAX_DIRECTIONS = 1024  # NSKY_TRANSFER_MAX_DIRECTIONS

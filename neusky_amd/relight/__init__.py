@@ -8,13 +8,17 @@ under any number of lights at one streaming pass over the transfer each (`--tran
 
 `SunLight` / `sun_path` (sun.py, csrc/sun.hip): a directional sun on top of either sky, with one DDF shadow query per ray; the frame
 render with `sun=` returns the lit frame, its `shadow_map` and `shadow_difference` (`--sun-azimuth/--sun-elevation`, `--sun-path`).
+
+`extract_sun` / `SunExtraction` (envmap_sun.py, csrc/envmap_sun.hip): the sun of an HDR map found, taken out of the map and handed to the
+`SunLight` path with its energy conserved, so that a sunny HDRI casts shadows (`--extract-sun`).
 """
 from .cameras import CameraPath, camera_rays, load_camera_path
 from .envmap import EnvironmentMap, envmap_labels, envmap_lookup, project_envmap, z_rotation
+from .envmap_sun import SunExtraction, extract_sun
 from .io import read_envmap, srgb_to_linear
 from .sun import SunLight, sun_direction, sun_path, sun_solid_angle
 from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
 
-__all__ = ["CameraPath", "EnvironmentMap", "RadianceTransfer", "SunLight", "bake_transfer", "camera_rays", "envmap_labels", "envmap_lookup",
-           "load_camera_path", "pack_fp16", "project_envmap", "read_envmap", "srgb_to_linear", "sun_direction", "sun_path",
-           "sun_solid_angle", "unpack_fp16", "z_rotation"]
+__all__ = ["CameraPath", "EnvironmentMap", "RadianceTransfer", "SunExtraction", "SunLight", "bake_transfer", "camera_rays", "envmap_labels",
+           "envmap_lookup", "extract_sun", "load_camera_path", "pack_fp16", "project_envmap", "read_envmap", "srgb_to_linear", "sun_direction",
+           "sun_path", "sun_solid_angle", "unpack_fp16", "z_rotation"]

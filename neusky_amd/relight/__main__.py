@@ -71,21 +71,46 @@ def build_parser() -> argparse.ArgumentParser:
     sun.add_argument("--shadow-map", action="store_true", help="also write the sun's shadow map of each frame as shadow_CCCC_FFF.png")
     sun.add_argument("--shadow-threshold", type=float, help="default: the model's trained visibility threshold")
     sun.add_argument("--shadow-sigmoid-scale", type=float, help="default: the model's sigmoid scale")
+    sun.add_argument("--extract-sun", action="store_true",
+                     help="find the sun in --envmap, take its excess over the sky out of the map and light with it as the sun (relight.extract_sun)")
+    sun.add_argument("--sun-search-radius", type=float, metavar="DEG", help="with --extract-sun: the cap about the peak (default 2.5)")
+    sun.add_argument("--sun-min-peak-ratio", type=float, metavar="X",
+                     help="with --extract-sun: the peak must be X times the sky around the cap (default 10)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
 
 def parse_suns(ap: argparse.ArgumentParser, args):
-    """the frame's suns from the command line: None, or a list of relight.SunLight (one per frame of a --sun-path)"""
+    """the frame's suns from the command line: None, or a list of relight.SunLight (one per frame of a --sun-path).  With --extract-sun
+    the sun comes out of the map at run time: None, after the checks."""
     from .sun import SunLight, sun_path, sun_solid_angle
 
     fixed = args.sun_azimuth is not None or args.sun_elevation is not None
     any_sun = fixed or args.sun_path is not None
+    for flag, given in (("--sun-search-radius", args.sun_search_radius), ("--sun-min-peak-ratio", args.sun_min_peak_ratio)):
+        if given is not None and not args.extract_sun:
+            ap.error(f"{flag} needs --extract-sun")
+    if args.extract_sun:
+        if args.envmap is None:
+            ap.error("--extract-sun finds the sun in a map: it needs --envmap")
+        if args.transfer != "off":
+            ap.error("a sun needs the per-sample normals the baked transfer does not keep: --extract-sun goes with --transfer off")
+        diameter = None if args.sun_angular_diameter == SUN_ANGULAR_DIAMETER_DEG else args.sun_angular_diameter
+        for flag, given in (("--sun-azimuth", args.sun_azimuth), ("--sun-elevation", args.sun_elevation), ("--sun-path", args.sun_path),
+                            ("--sun-steps", args.sun_steps), ("--sun-colour", args.sun_colour), ("--sun-radiance", args.sun_radiance),
+                            ("--sun-angular-diameter", diameter)):
+            if given is not None:
+                ap.error(f"--extract-sun takes the sun's position and colour from the map: it excludes {flag}")
+        if args.sun_search_radius is not None and not 0.0 < args.sun_search_radius < 45.0:
+            ap.error("--sun-search-radius must lie in (0, 45) degrees")
+        if args.sun_min_peak_ratio is not None and not args.sun_min_peak_ratio >= 0.0:
+            ap.error("--sun-min-peak-ratio must be >= 0")
+        return None
     for flag, given in (("--sun-colour", args.sun_colour), ("--sun-radiance", args.sun_radiance), ("--sun-steps", args.sun_steps),
                         ("--shadow-map", args.shadow_map or None), ("--shadow-threshold", args.shadow_threshold),
                         ("--shadow-sigmoid-scale", args.shadow_sigmoid_scale)):
         if given is not None and not any_sun:
-            ap.error(f"{flag} needs a sun: --sun-azimuth and --sun-elevation, or --sun-path")
+            ap.error(f"{flag} needs a sun: --sun-azimuth and --sun-elevation, --sun-path, or --extract-sun")
     if not any_sun:
         return None
     if args.transfer != "off":
@@ -138,9 +163,26 @@ def main(argv=None) -> int:
         print(f"warning: {len(unmapped)} checkpoint entries not mapped: {unmapped[:4]}", file=sys.stderr)
     pipe.eval()
     model = pipe.model
-    envmap = None
+    envmap = extraction = None
     if args.envmap is not None:
         envmap = EnvironmentMap.from_file(args.envmap, convention=args.convention, exposure=args.exposure, device=args.device)
+        if args.extract_sun:
+            from . import extract_sun
+            from .sun import SunLight
+            given = {k: v for k, v in (("radius_deg", args.sun_search_radius), ("min_peak_ratio", args.sun_min_peak_ratio)) if v is not None}
+            try:
+                found = extract_sun(envmap, **given)
+            except ValueError as e:
+                raise SystemExit(str(e))
+            if found.found:
+                at = SunLight.from_direction(found.direction)
+                print(f"sun found: azimuth {at.azimuth_deg:.2f} elevation {at.elevation_deg:.2f} degrees (map frame) | colour "
+                      f"{found.colour[0]:.4g} {found.colour[1]:.4g} {found.colour[2]:.4g} | {100.0 * found.flux_fraction:.1f}% of the map's flux | "
+                      f"apparent diameter {found.angular_diameter_deg:.2f} degrees")
+                extraction, envmap = found, found.envmap
+            else:
+                print(f"warning: --extract-sun: no sun stands out in {args.envmap} (peak luminance {found.peak_luminance:.4g}, sky around it "
+                      f"{found.sky_luminance:.4g}): rendering with the map as it is", file=sys.stderr)
     else:
         n = model.train_illumination_latents.shape[0]
         if not 0 <= args.latent_index < n:
@@ -177,9 +219,10 @@ def main(argv=None) -> int:
             if sweep is not None:
                 rgb = sweep["rgb"][f].clamp(0.0, 1.0).cpu().numpy()
                 shadow = sweep["shadow_map"][f]
-            elif suns is not None:
+            elif suns is not None or extraction is not None:  # an extracted sun turns with its sky
                 out = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[f], envmap=envmap,
-                                                              sun=suns[0], shadow_threshold=args.shadow_threshold,
+                                                              sun=suns[0] if extraction is None else extraction.sun(rots[f]),
+                                                              shadow_threshold=args.shadow_threshold,
                                                               shadow_sigmoid_scale=args.shadow_sigmoid_scale)
                 rgb = out["rgb"].clamp(0.0, 1.0).cpu().numpy()
                 shadow = out["shadow_map"]
@@ -197,7 +240,7 @@ def main(argv=None) -> int:
             Image.fromarray(np.round(rgb * 255.0).astype(np.uint8)).save(stem + ".png")
             if args.save_hdr:
                 np.save(stem + ".npy", srgb_to_linear(rgb).astype(np.float32))
-            if args.shadow_map:
+            if args.shadow_map and shadow is not None:  # (--extract-sun that found nothing has no shadow to write)
                 grey = np.round(shadow[..., 0].clamp(0.0, 1.0).cpu().numpy() * 255.0).astype(np.uint8)
                 Image.fromarray(grey, mode="L").save(os.path.join(args.output_dir, f"shadow_{c:04d}_{f:03d}.png"))
             frames += 1

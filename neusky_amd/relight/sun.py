@@ -51,6 +51,15 @@ class SunLight:
         k = sun_solid_angle(angular_diameter_deg) / (2.0 * math.pi)
         return cls(azimuth_deg, elevation_deg, tuple(float(x) * k for x in radiance))
 
+    @classmethod
+    def from_direction(cls, direction: Sequence[float], colour: Sequence[float] = (1.0, 1.0, 1.0)) -> "SunLight":
+        """the sun towards `direction` (any length > 0), the inverse of sun_direction: az = atan2(y, x), el = asin(z / |d|), in degrees"""
+        x, y, z = (float(v) for v in direction)
+        n = math.sqrt(x * x + y * y + z * z)
+        if not (n > 0.0 and math.isfinite(n)):
+            raise ValueError(f"a sun's direction has a finite length above zero, got {direction!r}")
+        return cls(math.degrees(math.atan2(y, x)), math.degrees(math.asin(max(-1.0, min(1.0, z / n)))), colour)
+
 
 def sun_path(az0: float, el0: float, az1: float, el1: float, steps: int, colour=(1.0, 1.0, 1.0)) -> List[SunLight]:
     """`steps` suns from (az0, el0) to (az1, el1), linear in both angles, endpoints included"""
