@@ -954,6 +954,46 @@ int nsky_sun_composite(const float* lin_sky, const float* t, const float* vis, c
                        const float* suns, const float* colours, int64_t R, int32_t K, float* rgb, float* lin, float* shadow,
                        nsky_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A clear-sky daylight model whose sky follows the sun (neusky_amd/relight/daylight.py, csrc/daylight.hip): Preetham, Shirley, Smits,
+ * "A Practical Analytic Model for Daylight", 1999.  The constants are the paper's tables.
+ *   inputs:     turbidity T in [2, 10]; the sun direction s, a unit vector with z up (as above), ts = acos(s.z); a view direction d of any
+ *               length, which is normalised; a direction of zero, infinite or NaN length has no sky: its result is 0.
+ *   angles:     a direction with d.z < 0 is replaced by its horizon point (z = 0, xy renormalised) and its result multiplied by
+ *               ground [3]; a direction straight down takes ground times the zenith value.  ct = d.z after that.
+ *               g = atan2(|d x s|, <d, s>)  (not acos of the dot product, which loses half the digits at the sun).
+ *   Perez:      F(ct, g) = (1 + A a)(1 + C exp(D g) + E cos^2 g),  a = exp(B / ct) for ct > 0 and 0 for ct = 0;   F0 = F(1, ts)
+ *   (A..E) of Y: ( 0.1787 T - 1.4630, -0.3554 T + 0.4275, -0.0227 T + 5.3251,  0.1206 T - 2.5771, -0.0670 T + 0.3703)
+ *          of x: (-0.0193 T - 0.2592, -0.0665 T + 0.0008, -0.0004 T + 0.2125, -0.0641 T - 0.8989, -0.0033 T + 0.0452)
+ *          of y: (-0.0167 T - 0.2608, -0.0950 T + 0.0092, -0.0079 T + 0.2102, -0.0441 T - 1.6537, -0.0109 T + 0.0529)
+ *   zenith:     chi = (4/9 - T/120)(pi - 2 ts);   Yz = (4.0453 T - 4.9710) tan(chi) - 0.2155 T + 2.4192  (kcd / m^2)
+ *               xz = [T^2, T, 1] Mx [ts^3, ts^2, ts, 1]^T,  Mx = [[ 0.00166, -0.00375,  0.00209, 0      ],
+ *                                                                 [-0.02903,  0.06377, -0.03202, 0.00394],
+ *                                                                 [ 0.11693, -0.21196,  0.06052, 0.25886]]
+ *               yz likewise,                                My = [[ 0.00275, -0.00610,  0.00317, 0      ],
+ *                                                                 [-0.04214,  0.08970, -0.04153, 0.00516],
+ *                                                                 [ 0.15346, -0.26756,  0.06670, 0.26688]]
+ *   radiance:   Y = Yz F_Y / F0_Y,  x = xz F_x / F0_x,  y = yz F_y / F0_y;   X = x Y / y,  Z = (1 - x - y) Y / y
+ *               linear sRGB = M (X, Y, Z),  M = [[ 3.2404542, -1.5371385, -0.4985314],
+ *                                                [-0.9692660,  1.8760108,  0.0415560],
+ *                                                [ 0.0556434, -0.2040259,  1.0572252]]   (D65)
+ *               clamped to >= 0, then multiplied by exposure (and by ground below the horizon).  A sun with s.z <= 0 has set: its
+ *               whole sky is 0.
+ * nsky_daylight_eval: directions [N,3]; suns [K,3]; turbidity [1], exposure [1], ground [3]  ->  out [K,N,3].  suns and the last three
+ *                     are device memory: a captured graph replays with new values.  Any N >= 1, any K >= 1.  The constants of a sun
+ *                     (zenith values over F0) are worked out once per sun and workgroup in fp64 and kept in LDS, up to 256 suns per
+ *                     launch; a thread owns a direction, reads it once, forms 1 + A a in fp64 and walks the suns in fp32; each
+ *                     sun's row is written with coalesced stores.
+ * nsky_sun_composite_skies: nsky_sun_composite with lin_skies [K,R,3], a sky of each sun's own:
+ *                     lin[k,r,c] = lin_skies[k,r,c] + C[k,c] V[k,r] t[k,r,c].  The same device code with a stride between the skies;
+ *                     K copies of one sky give nsky_sun_composite's results bit for bit.
+ * Flat indices are int64.  No atomics: every output is bitwise repeatable.  Nothing is read on the host. */
+int nsky_daylight_eval(const float* directions, const float* suns, const float* turbidity, const float* exposure, const float* ground,
+                       int64_t N, int32_t K, float* out, nsky_stream_t stream);
+int nsky_sun_composite_skies(const float* lin_skies, const float* t, const float* vis, const float* acc, const float* acc_threshold,
+                             const float* suns, const float* colours, int64_t R, int32_t K, float* rgb, float* lin, float* shadow,
+                             nsky_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

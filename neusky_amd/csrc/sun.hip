@@ -7,6 +7,7 @@
 //              scalar registers; a lane keeps 24 fp32 sums; the cosine itself is taken in fp64 (one rounding instead of three: a term
 //              is then within 3 2^-24 of its definition), the 24 sums of the wave are finished with wave_sum.
 //   composite  one thread per output element: mask, set-sun rule, the sum in fp64 rounded once, the sRGB curve of numerics.h.
+//              nsky_sun_composite_skies: the same kernel, lin_sky[k,r,c] a sky of each sun's own (relight/daylight.py).
 // No atomics, a fixed reduction order: two runs agree bit for bit.  Flat indices are 64-bit.  Nothing here synchronises with the host.
 #include <algorithm>
 
@@ -71,8 +72,9 @@ void launch_transfer(hipStream_t st, const float* albedo, const float* normals, 
   hipLaunchKernelGGL((sun_transfer_kernel<KB>), dim3(grid), dim3(256), 0, st, albedo, normals, weights, suns, R, S, out);
 }
 
-// element i of [K][R][3]: a sun that has set (s_z <= 0) and a ray under the accumulation threshold have V = 0 whatever `vis` holds
-__global__ __launch_bounds__(256) void sun_composite_kernel(const float* __restrict__ lin_sky, const float* __restrict__ t,
+// element i of [K][R][3]: a sun that has set (s_z <= 0) and a ray under the accumulation threshold have V = 0 whatever `vis` holds.
+// sky_stride: floats between the skies of two suns: 0 for one sky [R][3] under all K, R 3 for a sky of each sun's own [K][R][3]
+__global__ __launch_bounds__(256) void sun_composite_kernel(const float* __restrict__ lin_sky, int64_t sky_stride, const float* __restrict__ t,
                                                             const float* __restrict__ vis, const float* __restrict__ acc,
                                                             const float* __restrict__ acc_threshold, const float* __restrict__ suns,
                                                             const float* __restrict__ colours, int64_t R, int K, float* __restrict__ rgb,
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256) void sun_composite_kernel(const float* __restr
     const int64_t r = kr - (int64_t)k * R;
     const bool on = suns[3 * k + 2] > 0.0f && acc[r] > thr;
     const float v = on ? (vis ? vis[kr] : 1.0f) : 0.0f;
-    const float sky = lin_sky[r * 3 + c];
+    const float sky = lin_sky[(int64_t)k * sky_stride + r * 3 + c];
     const float x = on ? (float)((double)sky + (double)colours[3 * k + c] * (double)v * (double)t[i]) : sky;
     if (lin) lin[i] = x;
     rgb[i] = srgb_fwd(x);
@@ -120,17 +122,30 @@ extern "C" int nsky_sun_transfer(const float* albedo, const float* normals, cons
   return NSKY_OK;
 }
 
+// both composites: one sky under all K suns (sky_stride 0) or a sky of each sun's own
+static int launch_composite(const char* name, const float* lin_sky, int64_t sky_stride, const float* t, const float* vis, const float* acc,
+                            const float* acc_threshold, const float* suns, const float* colours, int64_t R, int32_t K, float* rgb,
+                            float* lin, float* shadow, nsky_stream_t stream) {
+  NSKY_CHECK_ARG(R >= 0 && K >= 0, "%s: R %ld, K %d", name, (long)R, (int)K);
+  if (R == 0 || K == 0) return NSKY_OK;
+  NSKY_CHECK_ARG(lin_sky && t && acc && acc_threshold && suns && colours && rgb,
+                 "%s: NULL lin_sky / t / acc / acc_threshold / suns / colours / rgb", name);
+  const int64_t n = (int64_t)K * R * 3;
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16));
+  hipLaunchKernelGGL(sun_composite_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, lin_sky, sky_stride, t, vis, acc, acc_threshold, suns,
+                     colours, R, (int)K, rgb, lin, shadow);
+  NSKY_CHECK_LAUNCH(name);
+  return NSKY_OK;
+}
+
 extern "C" int nsky_sun_composite(const float* lin_sky, const float* t, const float* vis, const float* acc, const float* acc_threshold,
                                   const float* suns, const float* colours, int64_t R, int32_t K, float* rgb, float* lin, float* shadow,
                                   nsky_stream_t stream) {
-  NSKY_CHECK_ARG(R >= 0 && K >= 0, "nsky_sun_composite: R %ld, K %d", (long)R, (int)K);
-  if (R == 0 || K == 0) return NSKY_OK;
-  NSKY_CHECK_ARG(lin_sky && t && acc && acc_threshold && suns && colours && rgb,
-                 "nsky_sun_composite: NULL lin_sky / t / acc / acc_threshold / suns / colours / rgb");
-  const int64_t n = (int64_t)K * R * 3;
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 16));
-  hipLaunchKernelGGL(sun_composite_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, lin_sky, t, vis, acc, acc_threshold, suns, colours,
-                     R, (int)K, rgb, lin, shadow);
-  NSKY_CHECK_LAUNCH("nsky_sun_composite");
-  return NSKY_OK;
+  return launch_composite("nsky_sun_composite", lin_sky, 0, t, vis, acc, acc_threshold, suns, colours, R, K, rgb, lin, shadow, stream);
+}
+
+extern "C" int nsky_sun_composite_skies(const float* lin_skies, const float* t, const float* vis, const float* acc, const float* acc_threshold,
+                                        const float* suns, const float* colours, int64_t R, int32_t K, float* rgb, float* lin, float* shadow,
+                                        nsky_stream_t stream) {
+  return launch_composite("nsky_sun_composite_skies", lin_skies, R * 3, t, vis, acc, acc_threshold, suns, colours, R, K, rgb, lin, shadow, stream);
 }

@@ -1393,3 +1393,32 @@ def sun_composite(lin_sky, t, vis, acc, acc_threshold, suns, colours, rgb, lin=N
     assert all(x is None or x.dtype == torch.float32 for x in (lin_sky, t, vis, acc, acc_threshold, suns, colours, rgb, lin, shadow))
     check(_sun_composite(_c(lin_sky), _c(t), _c(vis), _c(acc), _c(acc_threshold), _c(suns), _c(colours), R, K, _c(rgb), _c(lin), _c(shadow),
                          stream_ptr()), "nsky_sun_composite")
+
+
+_sun_composite_skies = _sig("nsky_sun_composite_skies", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def sun_composite_skies(lin_skies, t, vis, acc, acc_threshold, suns, colours, rgb, lin=None, shadow=None):
+    """sun_composite with lin_skies: fp32 [K, R, 3], a sky of each sun's own"""
+    K, R, _ = t.shape
+    assert lin_skies.shape == (K, R, 3) and acc.numel() == R and acc_threshold.numel() == 1 and suns.shape == (K, 3) and colours.shape == (K, 3)
+    assert rgb.shape == (K, R, 3) and (vis is None or vis.shape == (K, R)) and (lin is None or lin.shape == (K, R, 3))
+    assert shadow is None or shadow.shape == (K, R)
+    assert all(x is None or x.dtype == torch.float32 for x in (lin_skies, t, vis, acc, acc_threshold, suns, colours, rgb, lin, shadow))
+    check(_sun_composite_skies(_c(lin_skies), _c(t), _c(vis), _c(acc), _c(acc_threshold), _c(suns), _c(colours), R, K, _c(rgb), _c(lin),
+                               _c(shadow), stream_ptr()), "nsky_sun_composite_skies")
+
+
+# ---- a clear-sky daylight model whose sky follows the sun (relight/daylight.py, csrc/daylight.hip)
+_daylight_eval = _sig("nsky_daylight_eval", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                      C.c_void_p)
+
+
+def daylight_eval(directions, suns, turbidity, exposure, ground, out):
+    """directions: fp32 [N, 3]; suns [K, 3]; turbidity, exposure [1], ground [3] (device) -> out [K, N, 3]"""
+    N, K = directions.shape[0], suns.shape[0]
+    assert directions.shape == (N, 3) and suns.shape == (K, 3) and out.shape == (K, N, 3) and N >= 1 and K >= 1
+    assert turbidity.numel() == 1 and exposure.numel() == 1 and ground.numel() == 3
+    assert all(x.dtype == torch.float32 for x in (directions, suns, turbidity, exposure, ground, out))
+    check(_daylight_eval(_c(directions), _c(suns), _c(turbidity), _c(exposure), _c(ground), N, K, _c(out), stream_ptr()), "nsky_daylight_eval")

@@ -29,12 +29,16 @@ SUN_KEYS = ("rgb", "lin", "shadow_map", "shadow_difference")
 # (every sun direction is queried).  `scale` is a float, a by-value argument of nsky_visibility_finish_fwd
 FrameEnvmap = namedtuple("FrameEnvmap", "data convention rotation exposure")
 FrameSuns = namedtuple("FrameSuns", "dirs colours threshold acc_threshold sel scale")
+# a relight.DaylightSky under the frame's K suns, all static buffers: lights [K, D, 3], the sky of each sun at the frame's D directions
+# (nsky_daylight_eval there: point samples of the model, not cell averages); turbidity, exposure [1], ground [3]; suns = FrameSuns.dirs
+FrameDaylight = namedtuple("FrameDaylight", "lights turbidity exposure ground suns")
 
 
 @dataclass
 class FrameLight:
     """the light of the active frame: directions [D, 3], the frame camera's colours at them [1, D, 3] and the upper-hemisphere subset, in
-    static buffers; the camera and the (pinned) rotation of its latent; optionally an environment map, suns, a transfer-bake storage"""
+    static buffers; the camera and the (pinned) rotation of its latent; optionally an environment map, suns, a transfer-bake storage, a
+    daylight sky (which takes the place of the latent's: `cols` is then not decoded and not read)"""
     dirs: torch.Tensor
     cols: torch.Tensor
     sel: torch.Tensor
@@ -44,23 +48,29 @@ class FrameLight:
     envmap: Optional[FrameEnvmap] = None
     sun: Optional[FrameSuns] = None
     bake: Optional[str] = None
+    daylight: Optional[FrameDaylight] = None
     key: tuple = field(init=False)
 
     def __post_init__(self, rotation_values):
         """what a captured chunk holds by value or by a pointer that is not a static buffer's.  An envmap frame is keyed on the map's
         storage, shape and convention only, so a new rotation or exposure replays the chunk; a sun frame adds K and the sigmoid scale,
-        so a new position, colour or threshold does."""
+        so a new position, colour or threshold does; a daylight frame adds K once more and drops the camera, so a new turbidity,
+        exposure, ground or camera does."""
         env = self.envmap
         key = (self.cam, rotation_values) if env is None else ("envmap", env.data.data_ptr(), tuple(env.data.shape), env.convention)
+        if self.daylight is not None:  # no latent is read: one chunk graph serves every camera
+            key = "daylight sky"
         if self.sun is not None:
             key = (key, "sun", self.sun.dirs.shape[0], self.sun.scale)
         if self.bake is not None:
             key = (key, "bake", self.bake)
+        if self.daylight is not None:
+            key = (key, "daylight", self.daylight.lights.shape[0])
         self.key = key
 
     @property
     def shading(self) -> str:
-        return "bake" if self.bake is not None else "sun" if self.sun is not None else "sky"
+        return "bake" if self.bake is not None else "daylight" if self.daylight is not None else "sun" if self.sun is not None else "sky"
 
 
 def light_colours(model, dirs: torch.Tensor, cam: int, rotation: Optional[torch.Tensor] = None, envmap=None) -> torch.Tensor:
@@ -75,9 +85,13 @@ def light_colours(model, dirs: torch.Tensor, cam: int, rotation: Optional[torch.
 
 
 def ray_background(model, ray_directions: torch.Tensor, cam: int, rotation: Optional[torch.Tensor] = None,
-                   envmap: Optional[FrameEnvmap] = None) -> torch.Tensor:
+                   envmap: Optional[FrameEnvmap] = None, daylight: Optional[FrameDaylight] = None) -> torch.Tensor:
     """[R, 3]: the sky behind the rays, of camera `cam`'s latent (turned by `rotation`) or of the frame's environment map (its bilinear
-    lookup, read through the static buffers)"""
+    lookup, read through the static buffers); under a daylight sky [K, R, 3]: the sky of each of the frame's suns"""
+    if daylight is not None:
+        bg = torch.empty(daylight.suns.shape[0], ray_directions.shape[0], 3, dtype=torch.float32, device=ray_directions.device)
+        hip.daylight_eval(ray_directions.contiguous(), daylight.suns, daylight.turbidity, daylight.exposure, daylight.ground, bg)
+        return bg
     if envmap is not None:
         bg = torch.empty(ray_directions.shape[0], 3, dtype=torch.float32, device=ray_directions.device)
         hip.envmap_lookup(envmap.data, envmap.convention, ray_directions.contiguous(), envmap.rotation, envmap.exposure, bg)
@@ -88,30 +102,41 @@ def ray_background(model, ray_directions: torch.Tensor, cam: int, rotation: Opti
 
 def shade(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -> Dict[str, torch.Tensor]:
     """what the active frame's shading mode adds to a chunk's outputs: `rgb` under the sky alone; `rgb`, `lin`, `shadow_map` and
-    `shadow_difference` with suns; the transfer keys and no `rgb` for a bake (no light enters)"""
+    `shadow_difference` with suns, under the frame's sky or a daylight sky of each sun's own; the transfer keys and no `rgb` for a bake
+    (no light enters)"""
     if light.shading == "sky":
         return {"rgb": model.render_lambertian(so)}
-    if light.shading == "sun":
-        return _sun_outputs(model, light.sun, so, ray_bundle)
+    if light.shading in ("sun", "daylight"):
+        return _sun_outputs(model, light.sun, so, ray_bundle, light.daylight)
     fo = so["field_outputs"]
     visibility = so["visibility_dict"]["visibility"] if model.config.use_visibility else None
     return bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], so["weights"][..., 0], so["illumination_directions"],
                      visibility, light.bake)
 
 
-def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundle) -> Dict[str, torch.Tensor]:
+def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundle,
+                 daylight: Optional[FrameDaylight] = None) -> Dict[str, torch.Tensor]:
     """a chunk lit by its sky and the frame's K suns (include/neusky_hip.h): the hemisphere kernel's linear image, one DDF query per
     (ray, sun), the sun transfer and the composite.  Ray-major views of the [K, R, ...] results: rgb, lin [R, K, 3], shadow_map,
-    shadow_difference [R, K]."""
+    shadow_difference [R, K].
+    Under a daylight sky the linear image is one per sun [K, R, 3]: the chunk's radiance transfer (fp32, in a scratch) relit by the K
+    skies at the frame's directions, over the K backgrounds sample_illumination_compact evaluated at the rays."""
     fo = so["field_outputs"]
     a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
     w = so["weights"][..., 0].contiguous()
     R, K, dev = a.shape[0], sun.dirs.shape[0], a.device
     use_visibility = model.config.use_visibility
     vis_sky = so["visibility_dict"]["visibility"].contiguous() if use_visibility else None
-    lin_sky = torch.empty(R, 3, device=dev)
-    hip.hemi_composite_fwd(a, n, w, so["illumination_directions"].contiguous(), so["hdr_illumination_colours"].contiguous(),
-                           so["cam_of_ray"], vis_sky, so["hdr_background_colours"].contiguous(), torch.empty(R, 3, device=dev), lin_sky)
+    if daylight is None:
+        lin_sky = torch.empty(R, 3, device=dev)
+        hip.hemi_composite_fwd(a, n, w, so["illumination_directions"].contiguous(), so["hdr_illumination_colours"].contiguous(),
+                               so["cam_of_ray"], vis_sky, so["hdr_background_colours"].contiguous(), torch.empty(R, 3, device=dev), lin_sky)
+    else:
+        dirs = so["illumination_directions"].contiguous()
+        T, t_acc = torch.empty(R, dirs.shape[0], 3, device=dev), torch.empty(R, device=dev)
+        hip.transfer_bake(a, n, w, dirs, vis_sky, T, 0, None, t_acc)
+        lin_sky = torch.empty(K, R, 3, device=dev)
+        hip.transfer_relight(T, None, t_acc, daylight.lights, so["hdr_background_colours"], torch.empty(K, R, 3, device=dev), lin_sky)
     acc = so["accumulation"].reshape(-1).contiguous()
     vis = diff = None
     if use_visibility:
@@ -122,7 +147,8 @@ def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundl
     t = torch.empty(K, R, 3, device=dev)
     hip.sun_transfer(a, n, w, sun.dirs, t)
     rgb, lin, shadow = torch.empty(K, R, 3, device=dev), torch.empty(K, R, 3, device=dev), torch.empty(K, R, device=dev)
-    hip.sun_composite(lin_sky, t, vis, acc, sun.acc_threshold, sun.dirs, sun.colours, rgb, lin, shadow)
+    composite = hip.sun_composite if daylight is None else hip.sun_composite_skies
+    composite(lin_sky, t, vis, acc, sun.acc_threshold, sun.dirs, sun.colours, rgb, lin, shadow)
     on = (acc > sun.acc_threshold)[:, None] & (sun.dirs[:, 2] > 0)[None]
     diff = torch.where(on, diff, torch.zeros((), device=dev)) if diff is not None else torch.zeros(R, K, device=dev)
     return {"rgb": rgb.permute(1, 0, 2), "lin": lin.permute(1, 0, 2), "shadow_map": shadow.t(), "shadow_difference": diff}
@@ -137,6 +163,9 @@ class FrameRenderer:
         self.sky_static: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None  # dirs [D, 3], cols [1, D, 3], sel
         self.envmap_static: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # rotation [3, 3], exposure [1]
         self.sun_static: Dict[tuple, tuple] = {}  # (K, device) -> dirs, colours, threshold, acc_threshold, sel
+        # (K, D, device) -> lights, turbidity, exposure, ground (the last three views of one [5] buffer).  Like sun_static, one small
+        # set per K ever used, kept for the model's lifetime: a captured chunk holds their pointers
+        self.daylight_static: Dict[tuple, tuple] = {}
         # a chunk graph cached under a rotation's values reads the rotation through the pointer it was captured with: the first tensor
         # seen with these values is kept, and serves every later frame that asks for them (one entry per value ever seen)
         self.rotations: Dict[tuple, torch.Tensor] = {}
@@ -145,26 +174,36 @@ class FrameRenderer:
     # ------------------------------------------------------------------ the frame's light
     def begin(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None, sun=None,
               shadow_threshold: Optional[float] = None, shadow_sigmoid_scale: Optional[float] = None,
-              accumulation_mask_threshold: float = 0.0, bake: Optional[str] = None) -> None:
+              accumulation_mask_threshold: float = 0.0, bake: Optional[str] = None, daylight=None) -> None:
         """model.begin_frame, and `bake`: the storage of a radiance-transfer bake (relight.bake_transfer), which takes the place of
         the shading"""
         model = self.model
+        if daylight is not None:
+            if sun is None:
+                raise ValueError("daylight: the sky follows a sun: give `sun`, one SunLight or K (DaylightSky.sun, DaylightSky.sun_path)")
+            if envmap is not None or rotation is not None or bake is not None:
+                raise ValueError("daylight takes the place of the latent's or the map's sky: it excludes envmap, rotation and a bake")
         fixed = model.config.fix_test_illumination_directions
         dirs, sel = model.illumination_sampler.on_device(model.device, apply_random_rotation=False if fixed else None)
         cam = int(camera_index)
         values = None if (rotation is None or envmap is not None) else tuple(rotation.reshape(-1).tolist())
         if values is not None:
             rotation = self.rotations.setdefault(values, rotation)
-        cols = light_colours(model, dirs, cam, rotation, envmap)[None]
+        # (a daylight frame reads no `cols`: the camera's latent is not decoded, the buffer keeps what it held)
+        cols = light_colours(model, dirs, cam, rotation, envmap)[None] if daylight is None else None
         # static per-model buffers: a chunk graph captured for one frame stays valid for the next (animation frames
         # only change the camera / rotation, render_animation.py:196-207)
         st = self.sky_static
         if st is None or st[0].shape != dirs.shape or st[0].device != dirs.device:
-            st = self.sky_static = (torch.empty_like(dirs), torch.empty_like(cols), torch.empty_like(sel))
+            st = self.sky_static = (torch.empty_like(dirs), torch.zeros(1, *dirs.shape, dtype=dirs.dtype, device=dirs.device),
+                                    torch.empty_like(sel))
             self.runners = {}  # (the dropped runners' graphs retire themselves: ops.CapturedGraph)
-        st[0].copy_(dirs); st[1].copy_(cols); st[2].copy_(sel)
-        self.active = FrameLight(st[0], st[1], st[2], cam, rotation, values, self._envmap(envmap, rotation),
-                                 self._suns(sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold), bake)
+        st[0].copy_(dirs); st[2].copy_(sel)
+        if cols is not None:
+            st[1].copy_(cols)
+        suns = self._suns(sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold)
+        self.active = FrameLight(st[0], st[1], st[2], cam, rotation, values, self._envmap(envmap, rotation), suns, bake,
+                                 self._daylight(daylight, st[0], suns))
 
     def _envmap(self, envmap, rotation) -> Optional[FrameEnvmap]:
         if envmap is None:
@@ -200,6 +239,18 @@ class FrameRenderer:
         scale = float(model.sigmoid_scale if shadow_sigmoid_scale is None else shadow_sigmoid_scale) if model.config.use_visibility else 0.0
         return FrameSuns(*st, scale)
 
+    def _daylight(self, daylight, dirs: torch.Tensor, suns: Optional[FrameSuns]) -> Optional[FrameDaylight]:
+        if daylight is None:
+            return None
+        K, D, dev = suns.dirs.shape[0], dirs.shape[0], dirs.device
+        st = self.daylight_static.get((K, D, str(dev)))
+        if st is None:
+            packed = torch.empty(5, device=dev)
+            st = self.daylight_static[(K, D, str(dev))] = (torch.empty(K, D, 3, device=dev), packed[0:1], packed[1:2], packed[2:5], packed)
+        st[4].copy_(torch.tensor([daylight.turbidity, daylight.exposure, *daylight.ground], dtype=torch.float32))
+        hip.daylight_eval(dirs, suns.dirs, st[1], st[2], st[3], st[0])
+        return FrameDaylight(*st[:4], suns.dirs)
+
     def end(self) -> None:
         self.active = None
 
@@ -220,8 +271,8 @@ class FrameRenderer:
         return runner
 
     def render(self, camera_ray_bundle: RayBundle, rotation, to_cpu: bool, camera_index: Optional[int], chunk: Optional[int],
-               use_graph: bool, envmap, sun, *thresholds) -> Dict[str, torch.Tensor]:
-        """model.get_outputs_for_camera_ray_bundle, which names and documents the arguments (`thresholds`: begin's last three)"""
+               use_graph: bool, envmap, sun, *thresholds, daylight=None) -> Dict[str, torch.Tensor]:
+        """model.get_outputs_for_camera_ray_bundle, which names and documents the arguments (`thresholds`: begin's three)"""
         model = self.model
         assert not model.training, "call model.eval() first"
         chunk = chunk or max(model.config.eval_num_rays_per_chunk, 4096)
@@ -233,7 +284,7 @@ class FrameRenderer:
         single = True
         if sun is not None:
             sun, single = as_suns(sun)
-        self.begin(camera_index, rotation, envmap, sun, *thresholds)
+        self.begin(camera_index, rotation, envmap, sun, *thresholds, daylight=daylight)
         sun_keys = list(SUN_KEYS) if sun is not None else []
         keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
         out = {k: [] for k in keys}

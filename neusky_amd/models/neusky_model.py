@@ -264,7 +264,7 @@ class NeuSkyFactoModel(ModelBase):
         frame = None if self.training else self.frames.active
         if frame is not None:
             # chunked full-frame render: directions and the frame camera's colours were decoded once per frame
-            bg = ray_background(self, ray_directions, frame.cam, frame.rotation, frame.envmap)
+            bg = ray_background(self, ray_directions, frame.cam, frame.rotation, frame.envmap, frame.daylight)
             cam_of_ray = torch.zeros(camera_indices.shape[0], dtype=torch.int32, device=frame.dirs.device)
             return frame.dirs, frame.cols, cam_of_ray, bg, frame.sel
         if not self.training and self.config.fix_test_illumination_directions:
@@ -870,13 +870,16 @@ class NeuSkyFactoModel(ModelBase):
 
     def begin_frame(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None, sun=None,
                     shadow_threshold: Optional[float] = None, shadow_sigmoid_scale: Optional[float] = None,
-                    accumulation_mask_threshold: float = 0.0) -> None:
+                    accumulation_mask_threshold: float = 0.0, daylight=None) -> None:
         """decode the illumination of ONE camera for a whole frame (the reference re-decodes it in each of the
         8100 chunks of a 1080p frame, neusky_model.py:1413-1432; the result is the same).
         envmap: a relight.EnvironmentMap lighting the frame instead of the camera's latent: the light colours are the map's cell
         averages at the frame's directions (relight.project_envmap), the rays' background its bilinear lookup.
-        sun: a relight.SunLight or a sequence of K of them on top of that sky (frame.FrameSuns)."""
-        self.frames.begin(camera_index, rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold)
+        sun: a relight.SunLight or a sequence of K of them on top of that sky (frame.FrameSuns).
+        daylight: a relight.DaylightSky in place of either sky, one sky per sun (frame.FrameDaylight); needs `sun`, excludes `envmap`
+        and `rotation`; the camera's latent is not decoded."""
+        self.frames.begin(camera_index, rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold,
+                          daylight=daylight)
 
     def end_frame(self) -> None:
         self.frames.end()
@@ -886,7 +889,7 @@ class NeuSkyFactoModel(ModelBase):
                                           step=None, camera_index: Optional[int] = None, chunk: Optional[int] = None,
                                           use_graph: bool = True, envmap=None, sun=None, shadow_threshold: Optional[float] = None,
                                           shadow_sigmoid_scale: Optional[float] = None,
-                                          accumulation_mask_threshold: float = 0.0) -> Dict[str, torch.Tensor]:
+                                          accumulation_mask_threshold: float = 0.0, daylight=None) -> Dict[str, torch.Tensor]:
         """neusky_model.py:1369-1501: chunked full-frame render.  The reference chunks at eval_num_rays_per_chunk = 256
         (8100 python iterations per 1080p frame); any chunk size gives the same image, so a larger static chunk is used
         and its forward is captured once in a HIP graph and replayed per chunk (BASELINE config 5).
@@ -896,6 +899,10 @@ class NeuSkyFactoModel(ModelBase):
         then the frame lit by sky and sun, and `lin` (its linear image), `shadow_map` and `shadow_difference` [*shape, 1] join the outputs;
         a sequence puts a leading K on those four.  The field, the sampler and the sky pass of a chunk run once for all K suns.
         shadow_threshold / shadow_sigmoid_scale default to the model's trained visibility threshold and sigmoid scale; the shadow is
-        masked by accumulation > accumulation_mask_threshold.  A sun with elevation <= 0 has set: it adds no light and no shadow."""
+        masked by accumulation > accumulation_mask_threshold.  A sun with elevation <= 0 has set: it adds no light and no shadow.
+        daylight: a relight.DaylightSky: a clear sky that follows the sun, in place of the latent's or a map's (needs `sun`, excludes
+        `envmap` and `rotation`).  Each of the K suns then has its own sky at the frame's light directions (point samples of the model),
+        its own background behind the rays and, from DaylightSky.sun / sun_path, its own colour; the outputs are those of a sun frame,
+        and a set sun's frame is black.  The field, the sampler and the visibility pass of a chunk still run once for all K."""
         return self.frames.render(camera_ray_bundle, rotation, to_cpu, camera_index, chunk, use_graph, envmap, sun, shadow_threshold,
-                                  shadow_sigmoid_scale, accumulation_mask_threshold)
+                                  shadow_sigmoid_scale, accumulation_mask_threshold, daylight=daylight)

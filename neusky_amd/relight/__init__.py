@@ -11,14 +11,18 @@ render with `sun=` returns the lit frame, its `shadow_map` and `shadow_differenc
 
 `extract_sun` / `SunExtraction` (envmap_sun.py, csrc/envmap_sun.hip): the sun of an HDR map found, taken out of the map and handed to the
 `SunLight` path with its energy conserved, so that a sunny HDRI casts shadows (`--extract-sun`).
+
+`DaylightSky` (daylight.py, csrc/daylight.hip): a clear-sky daylight model whose sky, sun colour and background follow the sun; the
+frame render with `daylight=` gives each of K suns its own sky from one field pass per chunk (`--daylight`, `--turbidity`).
 """
 from .cameras import CameraPath, camera_rays, load_camera_path
+from .daylight import DaylightSky
 from .envmap import EnvironmentMap, envmap_labels, envmap_lookup, project_envmap, z_rotation
 from .envmap_sun import SunExtraction, extract_sun
 from .io import read_envmap, srgb_to_linear
 from .sun import SunLight, sun_direction, sun_path, sun_solid_angle
 from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
 
-__all__ = ["CameraPath", "EnvironmentMap", "RadianceTransfer", "SunExtraction", "SunLight", "bake_transfer", "camera_rays", "envmap_labels",
+__all__ = ["CameraPath", "DaylightSky", "EnvironmentMap", "RadianceTransfer", "SunExtraction", "SunLight", "bake_transfer", "camera_rays", "envmap_labels",
            "envmap_lookup", "extract_sun", "load_camera_path", "pack_fp16", "project_envmap", "read_envmap", "srgb_to_linear", "sun_direction",
            "sun_path", "sun_solid_angle", "unpack_fp16", "z_rotation"]

@@ -1,5 +1,5 @@
 """python -m neusky_amd.relight: render a checkpoint's scene along a nerfstudio camera path, lit by an HDR environment map (or by one of
-its training illumination latents), as 8-bit sRGB PNG frames.
+its training illumination latents, or by a clear-sky daylight model that follows the sun), as 8-bit sRGB PNG frames.
 
 The pipeline is built from the `neusky` method's config with no dataset: the scene box comes from the checkpoint's `_model.field.aabb`,
 the numbers of train / eval latent rows and the latent dimension from its latent tables."""
@@ -51,6 +51,8 @@ def build_parser() -> argparse.ArgumentParser:
     light = ap.add_mutually_exclusive_group(required=True)
     light.add_argument("--envmap", help="equirectangular map: .hdr/.pic, .pfm, .npy, .png/.jpg (sRGB), .exr (with pyexr)")
     light.add_argument("--latent-index", type=int, help="light with this training illumination latent instead")
+    light.add_argument("--daylight", action="store_true",
+                       help="light with a clear-sky daylight model instead: sky, sun colour and background follow the sun (relight.DaylightSky)")
     ap.add_argument("--convention", default="blender", choices=("blender", "neusky"), help="the map's azimuth convention")
     ap.add_argument("--exposure", type=float, default=1.0)
     ap.add_argument("--rotation-deg", type=float, default=0.0, help="turn the illumination about +z")
@@ -59,6 +61,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--chunk", type=int, default=4096)
     ap.add_argument("--transfer", default="off", choices=("off", "fp32", "fp16"),
                     help="bake each camera's radiance transfer once (stored as fp32 or scaled fp16) and relight its frames from it")
+    day = ap.add_argument_group("daylight", "with --daylight (Preetham, Shirley, Smits 1999)")
+    day.add_argument("--turbidity", type=float, help="2 (very clear) .. 10 (hazy), default 3")
+    day.add_argument("--sky-exposure", type=float, help="multiplies the model's sky (kcd / m^2) and its sun, default 0.1")
+    day.add_argument("--ground", type=float, nargs=3, metavar=("R", "G", "B"),
+                     help="factor on the horizon's sky for what lies below it (default 0.25 0.25 0.25)")
     sun = ap.add_argument_group("sun", "a directional sun on top of the sky, with its DDF shadow (relight.SunLight)")
     sun.add_argument("--sun-azimuth", type=float, help="degrees, counter-clockwise from +x about +z")
     sun.add_argument("--sun-elevation", type=float, help="degrees above the horizon; a sun at or below it has set")
@@ -80,9 +87,38 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
-def parse_suns(ap: argparse.ArgumentParser, args):
+def parse_daylight(ap: argparse.ArgumentParser, args):
+    """the relight.DaylightSky of --daylight, or None; what the flag excludes is an error here"""
+    from .daylight import DaylightSky
+
+    if not args.daylight:
+        for flag, given in (("--turbidity", args.turbidity), ("--sky-exposure", args.sky_exposure), ("--ground", args.ground)):
+            if given is not None:
+                ap.error(f"{flag} needs --daylight")
+        return None
+    if args.extract_sun:
+        ap.error("--extract-sun finds the sun in a map: it excludes --daylight")
+    if args.transfer != "off":
+        ap.error("--daylight needs the per-sample normals the baked transfer does not keep: it goes with --transfer off")
+    if args.rotation_deg != 0.0:
+        ap.error("--daylight: the sky follows the sun: move the sun instead of --rotation-deg")
+    if args.turntable > 1:
+        ap.error("--daylight: the sky follows the sun: sweep the sun with --sun-path instead of --turntable > 1")
+    if args.exposure != 1.0:
+        ap.error("--exposure scales a map or a latent: the daylight model's exposure is --sky-exposure")
+    if args.sun_path is None and (args.sun_azimuth is None or args.sun_elevation is None):
+        ap.error("--daylight needs a sun: --sun-azimuth with --sun-elevation, or --sun-path with --sun-steps")
+    try:
+        given = {"turbidity": args.turbidity, "exposure": args.sky_exposure, "ground": args.ground}
+        return DaylightSky(**{k: v for k, v in given.items() if v is not None})
+    except ValueError as e:
+        ap.error(str(e))
+
+
+def parse_suns(ap: argparse.ArgumentParser, args, daylight=None):
     """the frame's suns from the command line: None, or a list of relight.SunLight (one per frame of a --sun-path).  With --extract-sun
-    the sun comes out of the map at run time: None, after the checks."""
+    the sun comes out of the map at run time: None, after the checks.  Under a daylight sky a sun takes the model's colour unless
+    --sun-colour or --sun-radiance names one."""
     from .sun import SunLight, sun_path, sun_solid_angle
 
     fixed = args.sun_azimuth is not None or args.sun_elevation is not None
@@ -132,6 +168,10 @@ def parse_suns(ap: argparse.ArgumentParser, args):
     if args.sun_radiance is not None:
         k = sun_solid_angle(args.sun_angular_diameter) / (2.0 * math.pi)
         colour = tuple(x * k for x in args.sun_radiance)
+    if daylight is not None and args.sun_colour is None and args.sun_radiance is None:
+        if args.sun_path is not None:
+            return daylight.sun_path(*args.sun_path, args.sun_steps)
+        return [daylight.sun(args.sun_azimuth, args.sun_elevation)]
     if args.sun_path is not None:
         return sun_path(*args.sun_path, args.sun_steps, colour)
     return [SunLight(args.sun_azimuth, args.sun_elevation, colour)]
@@ -142,7 +182,8 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.turntable < 1:
         ap.error("--turntable must be >= 1")
-    suns = parse_suns(ap, args)
+    daylight = parse_daylight(ap, args)
+    suns = parse_suns(ap, args, daylight)
 
     import numpy as np
     import torch
@@ -183,6 +224,11 @@ def main(argv=None) -> int:
             else:
                 print(f"warning: --extract-sun: no sun stands out in {args.envmap} (peak luminance {found.peak_luminance:.4g}, sky around it "
                       f"{found.sky_luminance:.4g}): rendering with the map as it is", file=sys.stderr)
+    elif daylight is not None:
+        first, last = suns[0], suns[-1]
+        print(f"daylight: turbidity {daylight.turbidity:g} sky exposure {daylight.exposure:g} | {len(suns)} sun{'s' if len(suns) > 1 else ''}: "
+              f"elevation {first.elevation_deg:.2f} colour {first.colour[0]:.4g} {first.colour[1]:.4g} {first.colour[2]:.4g} -> "
+              f"elevation {last.elevation_deg:.2f} colour {last.colour[0]:.4g} {last.colour[1]:.4g} {last.colour[2]:.4g}")
     else:
         n = model.train_illumination_latents.shape[0]
         if not 0 <= args.latent_index < n:
@@ -213,7 +259,7 @@ def main(argv=None) -> int:
         if args.sun_path is not None:  # every frame of the sweep from one field pass per chunk
             sweep = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[0], envmap=envmap, sun=suns,
                                                             shadow_threshold=args.shadow_threshold,
-                                                            shadow_sigmoid_scale=args.shadow_sigmoid_scale)
+                                                            shadow_sigmoid_scale=args.shadow_sigmoid_scale, daylight=daylight)
         for f in range(len(suns) if sweep is not None else args.turntable):
             shadow = None
             if sweep is not None:
@@ -223,7 +269,7 @@ def main(argv=None) -> int:
                 out = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[f], envmap=envmap,
                                                               sun=suns[0] if extraction is None else extraction.sun(rots[f]),
                                                               shadow_threshold=args.shadow_threshold,
-                                                              shadow_sigmoid_scale=args.shadow_sigmoid_scale)
+                                                              shadow_sigmoid_scale=args.shadow_sigmoid_scale, daylight=daylight)
                 rgb = out["rgb"].clamp(0.0, 1.0).cpu().numpy()
                 shadow = out["shadow_map"]
             elif args.transfer == "off":
