@@ -994,6 +994,61 @@ int nsky_sun_composite_skies(const float* lin_skies, const float* t, const float
                              const float* suns, const float* colours, int64_t R, int32_t K, float* rgb, float* lin, float* shadow,
                              nsky_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sphere-traced shadow rays through the SDF, with penumbrae (neusky_amd/relight/shadows.py, csrc/sphere_trace.hip): the sun's shadow
+ * from the surface the SDF field holds instead of one DDF query.  The march is a loop on the host: the field's sdf at every ray's point
+ * (the non-tangent hash encode and nsky_sdf_chain_fwd, or any function of the points), then nsky_sphere_trace_step.
+ *
+ * The march rule.  A shadow ray has a start point x, a unit direction s and parameters:
+ *   N         96     iterations
+ *   eps       1e-3   hit threshold
+ *   relax     1.0    step scale
+ *   min_step  1e-3   smallest step
+ *   grace     16     leaving phase, iterations
+ *   radius    the model's sphere-collider radius    scene bound
+ *   tan_half  tan(angular_diameter / 2); 0 = hard shadow    penumbra width
+ * State per ray: t = 0, m = 1, status = ALIVE, outside = false.
+ * Iteration i = 0 .. N-1, on ALIVE rays only, in this order:
+ *   1. p = x + t s.  If |p| >= radius: status = ESCAPED.
+ *   2. f = sdf(p).
+ *   3. If f >= eps: outside = true.
+ *   4. If f < eps and (outside or i >= grace): status = HIT, m = 0.
+ *   5. If still ALIVE, outside, tan_half > 0 and t > 0: m = min(m, clamp(f / (t tan_half), 0, 1)).
+ *   6. If still ALIVE: t += max(|f| relax, min_step).
+ * Result: visibility = m.  That is 0 for HIT.  For a hard shadow it is 1 otherwise.  A ray still ALIVE after N iterations keeps its m
+ * and is reported as EXHAUSTED.  status is int8.  t is the last parameter.
+ * The leaving phase (steps 3-4) lets a start point that lies up to a few eps inside the surface climb out instead of shadowing itself.
+ * Step 5 is the usual closest-approach penumbra estimate: an approximation of a disc light, not an integral over it.  Every default
+ * is a design choice, not a measurement.  A ray that starts outside the radius escapes at once.
+ *
+ *   rays:    T rays; ray i has direction row i / dir_div (dir_div = R for K suns over R start points: i = k R + r; 1 for a direction
+ *            of each ray's own) and start row i % R.
+ *   params:  fp32 [6] in device memory = eps, relax, min_step, tan_half, radius, bias: a captured graph replays with new values.
+ *            N (`steps`), grace and the iteration index are by value.
+ *   state:   fp32 [6][T], one plane each: x (3), t, m, a flag word (int32 bits: status in the low byte, 0x100 = outside).
+ * nsky_sphere_trace_begin:        origins, directions [R,3]; depth [R]; normals [R,3] (the rendered normals, any length); suns [K,3]
+ *                                 -> state and points [K R,3]:  x = o + depth d + bias n^ (each product and sum one fma); a normal of
+ *                                 zero (or non-finite) length is replaced by s_k.  Rule step 1 of iteration 0 is applied here.
+ * nsky_sphere_trace_begin_points: starts [M,3]; directions [T / dir_div, 3]  ->  the same from explicit start points (T a multiple of M).
+ * nsky_sphere_trace_step:         state, sdf [T] at `points`, directions, params, iteration  ->  state, points [T,3].  Rule steps 3-6 of
+ *                                 this iteration, then p = fma(t, s, x) and rule step 1 of the next (none after iteration steps - 1).
+ *                                 Dead rays keep their point to the bit (their t no longer moves).  16-byte accesses when T % 4 == 0
+ *                                 and state, sdf and points are 16-byte aligned, else 4-byte ones; the results are the same.
+ * nsky_sphere_trace_finish:       state  ->  vis [T] (= m), status [T] (int8, ALIVE reported as EXHAUSTED), t [T].
+ * Flat indices are int64.  No atomics: every output is bitwise repeatable.  Nothing is read on the host. */
+#define NSKY_TRACE_ALIVE 0
+#define NSKY_TRACE_HIT 1
+#define NSKY_TRACE_ESCAPED 2
+#define NSKY_TRACE_EXHAUSTED 3
+#define NSKY_TRACE_PARAMS 6
+int nsky_sphere_trace_begin(const float* origins, const float* directions, const float* depth, const float* normals, const float* suns,
+                            int64_t R, int32_t K, const float* params, float* state, float* points, nsky_stream_t stream);
+int nsky_sphere_trace_begin_points(const float* starts, const float* directions, int64_t M, int64_t T, int64_t dir_div, const float* params,
+                                   float* state, float* points, nsky_stream_t stream);
+int nsky_sphere_trace_step(float* state, const float* sdf, const float* directions, int64_t T, int64_t dir_div, const float* params,
+                           int32_t iteration, int32_t steps, int32_t grace, float* points, nsky_stream_t stream);
+int nsky_sphere_trace_finish(const float* state, int64_t T, float* vis, int8_t* status, float* t, nsky_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1422,3 +1422,69 @@ def daylight_eval(directions, suns, turbidity, exposure, ground, out):
     assert turbidity.numel() == 1 and exposure.numel() == 1 and ground.numel() == 3
     assert all(x.dtype == torch.float32 for x in (directions, suns, turbidity, exposure, ground, out))
     check(_daylight_eval(_c(directions), _c(suns), _c(turbidity), _c(exposure), _c(ground), N, K, _c(out), stream_ptr()), "nsky_daylight_eval")
+
+
+# ---- sphere-traced shadow rays through the SDF (relight/shadows.py, csrc/sphere_trace.hip)
+TRACE_ALIVE, TRACE_HIT, TRACE_ESCAPED, TRACE_EXHAUSTED = 0, 1, 2, 3
+TRACE_PARAMS = 6  # eps, relax, min_step, tan_half, radius, bias
+_sphere_trace_begin = _sig("nsky_sphere_trace_begin", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sphere_trace_begin_points = _sig("nsky_sphere_trace_begin_points", C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p)
+_sphere_trace_step = _sig("nsky_sphere_trace_step", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                          C.c_int32, C.c_int32, C.c_void_p, C.c_void_p)
+_sphere_trace_finish = _sig("nsky_sphere_trace_finish", C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def _trace_buffers(T, params, state, points):
+    assert params.shape == (TRACE_PARAMS,) and state.shape == (6, T) and points.shape == (T, 3)
+    assert all(x.dtype == torch.float32 and x.is_contiguous() for x in (params, state, points))
+
+
+def sphere_trace_begin(origins, directions, depth, normals, suns, params, state, points):
+    """origins, directions, normals: fp32 [R, 3]; depth [R]; suns [K, 3]; params [6] (device) -> state [6, K R], points [K R, 3]"""
+    R, K = origins.shape[0], suns.shape[0]
+    assert origins.shape == (R, 3) and directions.shape == (R, 3) and normals.shape == (R, 3) and depth.numel() == R and suns.shape == (K, 3)
+    assert all(x.dtype == torch.float32 for x in (origins, directions, depth, normals, suns))
+    _trace_buffers(K * R, params, state, points)
+    check(_sphere_trace_begin(_c(origins), _c(directions), _c(depth), _c(normals), _c(suns), R, K, ptr(params), ptr(state), ptr(points),
+                              stream_ptr()), "nsky_sphere_trace_begin")
+
+
+def sphere_trace_begin_points(starts, directions, params, state, points):
+    """starts: fp32 [M, 3]; directions [M, 3] (one per ray) or [K, 3] (every start under every direction, ray k M + r) -> state, points"""
+    M, T = starts.shape[0], points.shape[0]
+    assert starts.shape == (M, 3) and directions.dim() == 2 and directions.shape[1] == 3 and M >= 1
+    assert starts.dtype == torch.float32 and directions.dtype == torch.float32
+    dir_div = trace_dir_div(directions, M, T)
+    _trace_buffers(T, params, state, points)
+    check(_sphere_trace_begin_points(_c(starts), _c(directions), M, T, dir_div, ptr(params), ptr(state), ptr(points), stream_ptr()),
+          "nsky_sphere_trace_begin_points")
+
+
+def trace_dir_div(directions, M: int, T: int) -> int:
+    """rays per direction row: 1 for a direction of each ray's own ([T, 3]), M for K directions over M starts (T = K M)"""
+    if T == M and directions.shape[0] == M:
+        return 1
+    if directions.shape[0] * M != T:
+        raise ValueError(f"{T} rays from {M} start points and {directions.shape[0]} directions")
+    return M
+
+
+def sphere_trace_step(state, sdf, directions, dir_div: int, params, iteration: int, steps: int, grace: int, points):
+    """one round of the march: state [6, T], sdf fp32 [T] at `points`, directions [T / dir_div, 3] -> state, points [T, 3]"""
+    T = points.shape[0]
+    _trace_buffers(T, params, state, points)
+    assert sdf.dtype == torch.float32 and sdf.numel() == T and directions.dtype == torch.float32
+    assert dir_div >= 1 and directions.shape == (-(-T // dir_div), 3) and 0 <= iteration < steps
+    check(_sphere_trace_step(ptr(state), _c(sdf), _c(directions), T, dir_div, ptr(params), iteration, steps, grace, ptr(points), stream_ptr()),
+          "nsky_sphere_trace_step")
+
+
+def sphere_trace_finish(state, vis, status, t):
+    """state [6, T] -> vis, t: fp32 [T]; status: int8 [T]"""
+    T = state.shape[1]
+    assert state.shape == (6, T) and state.dtype == torch.float32 and state.is_contiguous()
+    assert vis.numel() == T and t.numel() == T and status.numel() == T and status.dtype == torch.int8
+    assert vis.dtype == torch.float32 and t.dtype == torch.float32 and all(x.is_contiguous() for x in (vis, status, t))
+    check(_sphere_trace_finish(ptr(state), T, ptr(vis), ptr(status), ptr(t), stream_ptr()), "nsky_sphere_trace_finish")

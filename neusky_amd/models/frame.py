@@ -19,10 +19,13 @@ from .. import hip, ops
 from ..cameras.rays import RayBundle
 from ..field_components.neusky_fieldheadnames import FieldHeadNames, NeuSkyFieldHeadNames
 from ..relight.envmap import project_envmap
+from ..relight.shadows import SHADOW_DEFAULTS, trace_params, trace_settings, trace_sun_shadows
 from ..relight.sun import as_suns
 from ..relight.transfer import bake_rows
 
 SUN_KEYS = ("rgb", "lin", "shadow_map", "shadow_difference")
+SDF_SHADOW_KEYS = ("shadow_status",)  # joins them under sun_shadows="sdf"
+COLLIDER_RADIUS = 1.0  # of NeuSkyModel.collider: the scene bound of a shadow march
 
 
 # all tensors but the map are static buffers: rotation [3, 3], exposure [1]; dirs, colours [K, 3], the thresholds [1], sel = int32 arange(K)
@@ -32,13 +35,17 @@ FrameSuns = namedtuple("FrameSuns", "dirs colours threshold acc_threshold sel sc
 # a relight.DaylightSky under the frame's K suns, all static buffers: lights [K, D, 3], the sky of each sun at the frame's D directions
 # (nsky_daylight_eval there: point samples of the model, not cell averages); turbidity, exposure [1], ground [3]; suns = FrameSuns.dirs
 FrameDaylight = namedtuple("FrameDaylight", "lights turbidity exposure ground suns")
+# sun_shadows="sdf": the suns' shadows are marched through the SDF (relight/shadows.py).  params: the kernels' parameter block [6] (eps,
+# relax, min_step, tan_half, radius, bias), a static buffer; steps and grace are Python numbers, by-value arguments of the step kernel
+FrameTrace = namedtuple("FrameTrace", "params steps grace")
 
 
 @dataclass
 class FrameLight:
     """the light of the active frame: directions [D, 3], the frame camera's colours at them [1, D, 3] and the upper-hemisphere subset, in
     static buffers; the camera and the (pinned) rotation of its latent; optionally an environment map, suns, a transfer-bake storage, a
-    daylight sky (which takes the place of the latent's: `cols` is then not decoded and not read)"""
+    daylight sky (which takes the place of the latent's: `cols` is then not decoded and not read), a shadow march in place of the suns'
+    DDF queries"""
     dirs: torch.Tensor
     cols: torch.Tensor
     sel: torch.Tensor
@@ -49,13 +56,15 @@ class FrameLight:
     sun: Optional[FrameSuns] = None
     bake: Optional[str] = None
     daylight: Optional[FrameDaylight] = None
+    trace: Optional[FrameTrace] = None
     key: tuple = field(init=False)
 
     def __post_init__(self, rotation_values):
         """what a captured chunk holds by value or by a pointer that is not a static buffer's.  An envmap frame is keyed on the map's
         storage, shape and convention only, so a new rotation or exposure replays the chunk; a sun frame adds K and the sigmoid scale,
         so a new position, colour or threshold does; a daylight frame adds K once more and drops the camera, so a new turbidity,
-        exposure, ground or camera does."""
+        exposure, ground or camera does; a frame with marched shadows adds the march's length and leaving phase, so a new eps, bias or
+        angular diameter does."""
         env = self.envmap
         key = (self.cam, rotation_values) if env is None else ("envmap", env.data.data_ptr(), tuple(env.data.shape), env.convention)
         if self.daylight is not None:  # no latent is read: one chunk graph serves every camera
@@ -66,6 +75,8 @@ class FrameLight:
             key = (key, "bake", self.bake)
         if self.daylight is not None:
             key = (key, "daylight", self.daylight.lights.shape[0])
+        if self.trace is not None:
+            key = (key, "sdf shadows", self.trace.steps, self.trace.grace)
         self.key = key
 
     @property
@@ -107,20 +118,24 @@ def shade(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -
     if light.shading == "sky":
         return {"rgb": model.render_lambertian(so)}
     if light.shading in ("sun", "daylight"):
-        return _sun_outputs(model, light.sun, so, ray_bundle, light.daylight)
+        return _sun_outputs(model, light.sun, so, ray_bundle, light.daylight, light.trace)
     fo = so["field_outputs"]
     visibility = so["visibility_dict"]["visibility"] if model.config.use_visibility else None
     return bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], so["weights"][..., 0], so["illumination_directions"],
                      visibility, light.bake)
 
 
-def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundle,
-                 daylight: Optional[FrameDaylight] = None) -> Dict[str, torch.Tensor]:
+def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundle, daylight: Optional[FrameDaylight] = None,
+                 trace: Optional[FrameTrace] = None) -> Dict[str, torch.Tensor]:
     """a chunk lit by its sky and the frame's K suns (include/neusky_hip.h): the hemisphere kernel's linear image, one DDF query per
     (ray, sun), the sun transfer and the composite.  Ray-major views of the [K, R, ...] results: rgb, lin [R, K, 3], shadow_map,
     shadow_difference [R, K].
     Under a daylight sky the linear image is one per sun [K, R, 3]: the chunk's radiance transfer (fp32, in a scratch) relit by the K
-    skies at the frame's directions, over the K backgrounds sample_illumination_compact evaluated at the rays."""
+    skies at the frame's directions, over the K backgrounds sample_illumination_compact evaluated at the rays.
+    With `trace` the K visibilities come from a march through the SDF instead of the DDF (whether or not the model has one), from the
+    chunk's rendered depth along the ray and its rendered normal; `shadow_difference`, a DDF quantity, is then zero, and `shadow_status`
+    [R, K] (int8) is the march's own verdict on each shadow ray (relight.shadows: HIT, ESCAPED, EXHAUSTED), before the set-sun and
+    accumulation rules."""
     fo = so["field_outputs"]
     a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
     w = so["weights"][..., 0].contiguous()
@@ -138,8 +153,12 @@ def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundl
         lin_sky = torch.empty(K, R, 3, device=dev)
         hip.transfer_relight(T, None, t_acc, daylight.lights, so["hdr_background_colours"], torch.empty(K, R, 3, device=dev), lin_sky)
     acc = so["accumulation"].reshape(-1).contiguous()
-    vis = diff = None
-    if use_visibility:
+    vis = diff = status = None
+    if trace is not None:
+        march = trace_sun_shadows(model.field, ray_bundle.origins, ray_bundle.directions, so["p2p_dist"], so["normal"], sun.dirs, trace.params,
+                                  trace.steps, trace.grace)
+        vis, status = march.visibility, march.status
+    elif use_visibility:
         vd = model.compute_visibility_compact(ray_bundle.origins, ray_bundle.directions, so["p2p_dist"].detach(), sun.dirs, sun.threshold,
                                               sun.scale, compute_shadow_map=True, sel=sun.sel)
         vis = vd["visibility"].t().contiguous()  # [K, R]
@@ -151,7 +170,10 @@ def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundl
     composite(lin_sky, t, vis, acc, sun.acc_threshold, sun.dirs, sun.colours, rgb, lin, shadow)
     on = (acc > sun.acc_threshold)[:, None] & (sun.dirs[:, 2] > 0)[None]
     diff = torch.where(on, diff, torch.zeros((), device=dev)) if diff is not None else torch.zeros(R, K, device=dev)
-    return {"rgb": rgb.permute(1, 0, 2), "lin": lin.permute(1, 0, 2), "shadow_map": shadow.t(), "shadow_difference": diff}
+    out = {"rgb": rgb.permute(1, 0, 2), "lin": lin.permute(1, 0, 2), "shadow_map": shadow.t(), "shadow_difference": diff}
+    if status is not None:
+        out["shadow_status"] = status.t()
+    return out
 
 
 class FrameRenderer:
@@ -166,6 +188,7 @@ class FrameRenderer:
         # (K, D, device) -> lights, turbidity, exposure, ground (the last three views of one [5] buffer).  Like sun_static, one small
         # set per K ever used, kept for the model's lifetime: a captured chunk holds their pointers
         self.daylight_static: Dict[tuple, tuple] = {}
+        self.trace_static: Dict[str, torch.Tensor] = {}  # device -> the shadow march's parameter block [6]
         # a chunk graph cached under a rotation's values reads the rotation through the pointer it was captured with: the first tensor
         # seen with these values is kept, and serves every later frame that asks for them (one entry per value ever seen)
         self.rotations: Dict[tuple, torch.Tensor] = {}
@@ -174,10 +197,20 @@ class FrameRenderer:
     # ------------------------------------------------------------------ the frame's light
     def begin(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None, sun=None,
               shadow_threshold: Optional[float] = None, shadow_sigmoid_scale: Optional[float] = None,
-              accumulation_mask_threshold: float = 0.0, bake: Optional[str] = None, daylight=None) -> None:
+              accumulation_mask_threshold: float = 0.0, bake: Optional[str] = None, daylight=None, sun_shadows: str = "ddf",
+              shadow_trace: Optional[dict] = None) -> None:
         """model.begin_frame, and `bake`: the storage of a radiance-transfer bake (relight.bake_transfer), which takes the place of
         the shading"""
         model = self.model
+        if sun_shadows not in ("ddf", "sdf"):
+            raise ValueError(f"sun_shadows: 'ddf' or 'sdf', got {sun_shadows!r}")
+        if sun_shadows == "sdf":
+            if sun is None or bake is not None:
+                raise ValueError("sun_shadows='sdf' marches the shadow rays of a sun: give `sun` (and no bake)")
+            if shadow_threshold is not None or shadow_sigmoid_scale is not None:
+                raise ValueError("shadow_threshold and shadow_sigmoid_scale shape the DDF shadow: they exclude sun_shadows='sdf'")
+        elif shadow_trace is not None:
+            raise ValueError("shadow_trace holds the parameters of the march: it needs sun_shadows='sdf'")
         if daylight is not None:
             if sun is None:
                 raise ValueError("daylight: the sky follows a sun: give `sun`, one SunLight or K (DaylightSky.sun, DaylightSky.sun_path)")
@@ -203,7 +236,7 @@ class FrameRenderer:
             st[1].copy_(cols)
         suns = self._suns(sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold)
         self.active = FrameLight(st[0], st[1], st[2], cam, rotation, values, self._envmap(envmap, rotation), suns, bake,
-                                 self._daylight(daylight, st[0], suns))
+                                 self._daylight(daylight, st[0], suns), self._trace(shadow_trace) if sun_shadows == "sdf" else None)
 
     def _envmap(self, envmap, rotation) -> Optional[FrameEnvmap]:
         if envmap is None:
@@ -251,6 +284,16 @@ class FrameRenderer:
         hip.daylight_eval(dirs, suns.dirs, st[1], st[2], st[3], st[0])
         return FrameDaylight(*st[:4], suns.dirs)
 
+    def _trace(self, shadow_trace: Optional[dict]) -> FrameTrace:
+        """shadow_trace: any of relight.shadows.SHADOW_DEFAULTS' keys; `radius` defaults to the sphere collider's"""
+        p = trace_settings(shadow_trace, {**SHADOW_DEFAULTS, "radius": COLLIDER_RADIUS})
+        dev = str(self.model.device)
+        st = self.trace_static.get(dev)
+        if st is None:
+            st = self.trace_static[dev] = torch.empty(hip.TRACE_PARAMS, device=self.model.device)
+        st.copy_(trace_params(p))
+        return FrameTrace(st, p["steps"], p["grace"])
+
     def end(self) -> None:
         self.active = None
 
@@ -271,7 +314,8 @@ class FrameRenderer:
         return runner
 
     def render(self, camera_ray_bundle: RayBundle, rotation, to_cpu: bool, camera_index: Optional[int], chunk: Optional[int],
-               use_graph: bool, envmap, sun, *thresholds, daylight=None) -> Dict[str, torch.Tensor]:
+               use_graph: bool, envmap, sun, *thresholds, daylight=None, sun_shadows: str = "ddf",
+               shadow_trace: Optional[dict] = None) -> Dict[str, torch.Tensor]:
         """model.get_outputs_for_camera_ray_bundle, which names and documents the arguments (`thresholds`: begin's three)"""
         model = self.model
         assert not model.training, "call model.eval() first"
@@ -284,8 +328,8 @@ class FrameRenderer:
         single = True
         if sun is not None:
             sun, single = as_suns(sun)
-        self.begin(camera_index, rotation, envmap, sun, *thresholds, daylight=daylight)
-        sun_keys = list(SUN_KEYS) if sun is not None else []
+        self.begin(camera_index, rotation, envmap, sun, *thresholds, daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace)
+        sun_keys = list(SUN_KEYS + (SDF_SHADOW_KEYS if sun_shadows == "sdf" else ())) if sun is not None else []
         keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
         out = {k: [] for k in keys}
         try:

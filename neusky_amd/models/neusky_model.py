@@ -870,16 +870,18 @@ class NeuSkyFactoModel(ModelBase):
 
     def begin_frame(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None, sun=None,
                     shadow_threshold: Optional[float] = None, shadow_sigmoid_scale: Optional[float] = None,
-                    accumulation_mask_threshold: float = 0.0, daylight=None) -> None:
+                    accumulation_mask_threshold: float = 0.0, daylight=None, sun_shadows: str = "ddf",
+                    shadow_trace: Optional[dict] = None) -> None:
         """decode the illumination of ONE camera for a whole frame (the reference re-decodes it in each of the
         8100 chunks of a 1080p frame, neusky_model.py:1413-1432; the result is the same).
         envmap: a relight.EnvironmentMap lighting the frame instead of the camera's latent: the light colours are the map's cell
         averages at the frame's directions (relight.project_envmap), the rays' background its bilinear lookup.
         sun: a relight.SunLight or a sequence of K of them on top of that sky (frame.FrameSuns).
         daylight: a relight.DaylightSky in place of either sky, one sky per sun (frame.FrameDaylight); needs `sun`, excludes `envmap`
-        and `rotation`; the camera's latent is not decoded."""
+        and `rotation`; the camera's latent is not decoded.
+        sun_shadows, shadow_trace: get_outputs_for_camera_ray_bundle's (frame.FrameTrace)."""
         self.frames.begin(camera_index, rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold,
-                          daylight=daylight)
+                          daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace)
 
     def end_frame(self) -> None:
         self.frames.end()
@@ -889,7 +891,8 @@ class NeuSkyFactoModel(ModelBase):
                                           step=None, camera_index: Optional[int] = None, chunk: Optional[int] = None,
                                           use_graph: bool = True, envmap=None, sun=None, shadow_threshold: Optional[float] = None,
                                           shadow_sigmoid_scale: Optional[float] = None,
-                                          accumulation_mask_threshold: float = 0.0, daylight=None) -> Dict[str, torch.Tensor]:
+                                          accumulation_mask_threshold: float = 0.0, daylight=None, sun_shadows: str = "ddf",
+                                          shadow_trace: Optional[dict] = None) -> Dict[str, torch.Tensor]:
         """neusky_model.py:1369-1501: chunked full-frame render.  The reference chunks at eval_num_rays_per_chunk = 256
         (8100 python iterations per 1080p frame); any chunk size gives the same image, so a larger static chunk is used
         and its forward is captured once in a HIP graph and replayed per chunk (BASELINE config 5).
@@ -903,6 +906,16 @@ class NeuSkyFactoModel(ModelBase):
         daylight: a relight.DaylightSky: a clear sky that follows the sun, in place of the latent's or a map's (needs `sun`, excludes
         `envmap` and `rotation`).  Each of the K suns then has its own sky at the frame's light directions (point samples of the model),
         its own background behind the rays and, from DaylightSky.sun / sun_path, its own colour; the outputs are those of a sun frame,
-        and a set sun's frame is black.  The field, the sampler and the visibility pass of a chunk still run once for all K."""
+        and a set sun's frame is black.  The field, the sampler and the visibility pass of a chunk still run once for all K.
+        sun_shadows: "ddf" (the default: one DDF query per ray and sun) or "sdf": the suns' shadow rays are sphere-traced through the SDF
+        field (relight.shadows, include/neusky_hip.h), from each ray's rendered depth and normal; this needs no visibility network
+        (use_visibility = False renders too).  The shadow then follows the surface the mesh export writes and has a penumbra of the
+        sun's angular diameter.  `shadow_difference`, a DDF quantity, is all zeros in this mode, and `shadow_status` [*shape, 1] (int8:
+        relight.shadows.HIT / ESCAPED / EXHAUSTED, the march's verdict before the set-sun and accumulation rules) joins the outputs.
+        shadow_threshold and shadow_sigmoid_scale are errors with it.
+        shadow_trace: with "sdf", a dictionary of any of the march's parameters (relight.shadows.SHADOW_DEFAULTS): steps, eps, relax,
+        min_step, grace, radius, angular_diameter_deg (0 gives a hard edge) and bias (the lift of the start point off the rendered
+        surface along its normal, scene units).  Only steps and grace are held by a captured chunk: the others replay it."""
         return self.frames.render(camera_ray_bundle, rotation, to_cpu, camera_index, chunk, use_graph, envmap, sun, shadow_threshold,
-                                  shadow_sigmoid_scale, accumulation_mask_threshold, daylight=daylight)
+                                  shadow_sigmoid_scale, accumulation_mask_threshold, daylight=daylight, sun_shadows=sun_shadows,
+                                  shadow_trace=shadow_trace)

@@ -66,7 +66,7 @@ def build_parser() -> argparse.ArgumentParser:
     day.add_argument("--sky-exposure", type=float, help="multiplies the model's sky (kcd / m^2) and its sun, default 0.1")
     day.add_argument("--ground", type=float, nargs=3, metavar=("R", "G", "B"),
                      help="factor on the horizon's sky for what lies below it (default 0.25 0.25 0.25)")
-    sun = ap.add_argument_group("sun", "a directional sun on top of the sky, with its DDF shadow (relight.SunLight)")
+    sun = ap.add_argument_group("sun", "a directional sun on top of the sky, with its DDF or sphere-traced shadow (relight.SunLight)")
     sun.add_argument("--sun-azimuth", type=float, help="degrees, counter-clockwise from +x about +z")
     sun.add_argument("--sun-elevation", type=float, help="degrees above the horizon; a sun at or below it has set")
     sun.add_argument("--sun-colour", type=float, nargs=3, metavar=("R", "G", "B"), help="in the renderer's irradiance units (default 1 1 1)")
@@ -78,6 +78,14 @@ def build_parser() -> argparse.ArgumentParser:
     sun.add_argument("--shadow-map", action="store_true", help="also write the sun's shadow map of each frame as shadow_CCCC_FFF.png")
     sun.add_argument("--shadow-threshold", type=float, help="default: the model's trained visibility threshold")
     sun.add_argument("--shadow-sigmoid-scale", type=float, help="default: the model's sigmoid scale")
+    sun.add_argument("--sun-shadows", default="ddf", choices=("ddf", "sdf"),
+                     help="the sun's shadow from one DDF query per ray (default), or sphere-traced through the SDF with a penumbra "
+                          "(relight.trace_visibility): it follows the exported surface and needs no visibility network")
+    sun.add_argument("--shadow-steps", type=int, metavar="N", help="with --sun-shadows sdf: rounds of the march (default 96)")
+    sun.add_argument("--shadow-bias", type=float, metavar="B",
+                     help="with --sun-shadows sdf: lift of the start point off the rendered surface along its normal, scene units (default 1e-2)")
+    sun.add_argument("--shadow-angular-diameter", type=float, metavar="DEG",
+                     help=f"with --sun-shadows sdf: the disc the penumbra is as wide as (default {SUN_ANGULAR_DIAMETER_DEG}, the sun; 0: a hard edge)")
     sun.add_argument("--extract-sun", action="store_true",
                      help="find the sun in --envmap, take its excess over the sky out of the map and light with it as the sun (relight.extract_sun)")
     sun.add_argument("--sun-search-radius", type=float, metavar="DEG", help="with --extract-sun: the cap about the peak (default 2.5)")
@@ -177,6 +185,32 @@ def parse_suns(ap: argparse.ArgumentParser, args, daylight=None):
     return [SunLight(args.sun_azimuth, args.sun_elevation, colour)]
 
 
+def parse_shadows(ap: argparse.ArgumentParser, args):
+    """(sun_shadows, shadow_trace) of the frame render from --sun-shadows and its flags: ("ddf", None), or "sdf" and the march's
+    parameters the command line names, defaults filled in"""
+    from .shadows import SHADOW_DEFAULTS, trace_settings
+
+    marched = (("--shadow-steps", args.shadow_steps), ("--shadow-bias", args.shadow_bias),
+               ("--shadow-angular-diameter", args.shadow_angular_diameter))
+    if args.sun_shadows == "ddf":
+        for flag, given in marched:
+            if given is not None:
+                ap.error(f"{flag} needs --sun-shadows sdf")
+        return "ddf", None
+    for flag, given in (("--shadow-threshold", args.shadow_threshold), ("--shadow-sigmoid-scale", args.shadow_sigmoid_scale)):
+        if given is not None:
+            ap.error(f"{flag} shapes the DDF shadow: it excludes --sun-shadows sdf")
+    if args.sun_azimuth is None and args.sun_path is None and not args.extract_sun:
+        ap.error("--sun-shadows sdf needs a sun: --sun-azimuth and --sun-elevation, --sun-path, or --extract-sun")
+    trace = {"steps": args.shadow_steps, "bias": args.shadow_bias, "angular_diameter_deg": args.shadow_angular_diameter}
+    trace = {k: SHADOW_DEFAULTS[k] if v is None else v for k, v in trace.items()}
+    try:
+        trace_settings(trace, SHADOW_DEFAULTS)
+    except ValueError as e:
+        ap.error(str(e))
+    return "sdf", trace
+
+
 def main(argv=None) -> int:
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -184,6 +218,7 @@ def main(argv=None) -> int:
         ap.error("--turntable must be >= 1")
     daylight = parse_daylight(ap, args)
     suns = parse_suns(ap, args, daylight)
+    sun_shadows, shadow_trace = parse_shadows(ap, args)
 
     import numpy as np
     import torch
@@ -242,6 +277,8 @@ def main(argv=None) -> int:
     os.makedirs(args.output_dir, exist_ok=True)
     frames = 0
     t_bake = t_relight = 0.0
+    shadow_rays = exhausted = 0  # of --sun-shadows sdf
+    marched = {"sun_shadows": sun_shadows, "shadow_trace": shadow_trace}
     t1 = time.perf_counter()
     for c in range(len(cams)):
         rb = camera_rays(cams, c, args.device)
@@ -259,7 +296,8 @@ def main(argv=None) -> int:
         if args.sun_path is not None:  # every frame of the sweep from one field pass per chunk
             sweep = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[0], envmap=envmap, sun=suns,
                                                             shadow_threshold=args.shadow_threshold,
-                                                            shadow_sigmoid_scale=args.shadow_sigmoid_scale, daylight=daylight)
+                                                            shadow_sigmoid_scale=args.shadow_sigmoid_scale, daylight=daylight, **marched)
+            out = sweep
         for f in range(len(suns) if sweep is not None else args.turntable):
             shadow = None
             if sweep is not None:
@@ -269,7 +307,7 @@ def main(argv=None) -> int:
                 out = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[f], envmap=envmap,
                                                               sun=suns[0] if extraction is None else extraction.sun(rots[f]),
                                                               shadow_threshold=args.shadow_threshold,
-                                                              shadow_sigmoid_scale=args.shadow_sigmoid_scale, daylight=daylight)
+                                                              shadow_sigmoid_scale=args.shadow_sigmoid_scale, daylight=daylight, **marched)
                 rgb = out["rgb"].clamp(0.0, 1.0).cpu().numpy()
                 shadow = out["shadow_map"]
             elif args.transfer == "off":
@@ -282,6 +320,10 @@ def main(argv=None) -> int:
                     batch = batch.clamp(0.0, 1.0).cpu().numpy()
                     t_relight += time.perf_counter() - tr
                 rgb = batch[f % LIGHTS_PER_PASS]
+            if shadow is not None and sun_shadows == "sdf" and (sweep is None or f == 0):  # (a sweep's status holds all its frames)
+                from .shadows import EXHAUSTED
+                shadow_rays += out["shadow_status"].numel()
+                exhausted += int((out["shadow_status"] == EXHAUSTED).sum())
             stem = os.path.join(args.output_dir, f"frame_{c:04d}_{f:03d}")
             Image.fromarray(np.round(rgb * 255.0).astype(np.uint8)).save(stem + ".png")
             if args.save_hdr:
@@ -295,6 +337,9 @@ def main(argv=None) -> int:
     transfer = "" if args.transfer == "off" else f" | transfer {args.transfer}: bake {t_bake:.3f}s relight {t_relight:.3f}s"
     print(f"{args.output_dir}: {frames} frames {cams.width}x{cams.height} | load {t_load:.3f}s render {t_render:.3f}s "
           f"({t_render / max(frames, 1):.3f}s/frame){transfer}")
+    if sun_shadows == "sdf":
+        print(f"sdf shadows: {exhausted} of {shadow_rays} shadow rays ({100.0 * exhausted / max(shadow_rays, 1):.3f}%) were still marching after "
+              f"{shadow_trace['steps']} steps (raise --shadow-steps if that is too many)")
     return 0
 
 
