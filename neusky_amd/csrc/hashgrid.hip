@@ -72,14 +72,18 @@ __device__ __forceinline__ void grid_position(const float x[3], int mode, float 
       }
     }
   } else {  // L2 contraction
-    float m = sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    // The contracted position decides the CELL, so it is formed with the roundings of the oracle's fp32 restatement, one by one:
+    // the norm as torch's CPU reduction accumulates it (fma, left to right), then (2 - 1/m) (x / m) -- not k x, which differs by
+    // an ulp at a quarter of the points and, at a cell boundary, by a cell.  The _rn intrinsics keep the compiler from contracting
+    // a product into the next sum.  (The Jacobian below has no such tie to break: k and dk as before.)
+    float m = __fsqrt_rn(fmaf(x[2], x[2], fmaf(x[1], x[1], __fmul_rn(x[0], x[0]))));
     if (!(m < 1.0f)) {
-      float inv = 1.0f / m;
+      float inv = __fdiv_rn(1.0f, m);
       float k = (2.0f - inv) * inv;
       float dk = (-2.0f + 2.0f * inv) * inv * inv;
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
-        c[a] = k * x[a];
+        c[a] = __fmul_rn(2.0f - inv, __fdiv_rn(x[a], m));
 #pragma unroll
         for (int b = 0; b < 3; ++b) J[a][b] = (a == b ? k : 0.0f) + x[a] * dk * x[b] * inv;
       }
@@ -334,6 +338,15 @@ __global__ __launch_bounds__(256) void encode_bwd_kernel(Grid g, const float* __
 // for lines-scattered requests is ~17x below the contiguous rate.  So the scatter is laid out to (a) put
 // the two features of a corner on adjacent lanes (one line, one request), and (b) keep the small dense
 // levels, where thousands of points collide on a few KB, in LDS and flush them once per workgroup.
+// The two interpolation factors of an axis (w0: the corner at the cell's origin, w1: its +1 neighbour) and d w1 / d pos.
+// Smoothstep: w0 = 1 - S(t) is formed as S(1 - t) -- the same polynomial.  `1 - S(t)` keeps 2^-24 ABSOLUTE in fp32, and a corner
+// at t -> 1 has a weight of that size: measured against float64, table entries fed by such corners alone were off by up to 1 %.
+__device__ __forceinline__ void axis_weights(float t, bool smooth, float scale, float& w0, float& w1, float& dw) {
+  const float u = 1.0f - t;
+  if (smooth) { w1 = t * t * (3.0f - 2.0f * t); w0 = u * u * (3.0f - 2.0f * u); dw = 6.0f * t * u * scale; }
+  else { w1 = t; w0 = u; dw = scale; }
+}
+
 struct CornerTerm {
   uint32_t idx;
   float a;  // value to add to table[idx][f]
@@ -347,21 +360,19 @@ __device__ __forceinline__ CornerTerm corner_term(const Grid& g, int level, int 
   const uint32_t res = (uint32_t)g.resolution[level];
   const uint32_t size = g.offset[level + 1] - g.offset[level];
   uint32_t pg[3];
-  float w[3], dw[3];
+  float w0[3], w[3], dw[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const float q = fmaf(scale, pos[a], 0.5f);
     const float fl = floorf(q);
     pg[a] = (uint32_t)(int)fl;
-    const float t = q - fl;
-    if (g.smoothstep) { w[a] = t * t * (3.0f - 2.0f * t); dw[a] = 6.0f * t * (1.0f - t) * scale; }
-    else { w[a] = t; dw[a] = scale; }
+    axis_weights(q - fl, g.smoothstep != 0, scale, w0[a], w[a], dw[a]);
   }
   CornerTerm ct;
   ct.idx = g.offset[level] + grid_index(size, res, pg[0] + (k & 1), pg[1] + ((k >> 1) & 1), pg[2] + ((k >> 2) & 1));
-  const float wx = (k & 1) ? w[0] : 1.0f - w[0];
-  const float wy = (k & 2) ? w[1] : 1.0f - w[1];
-  const float wz = (k & 4) ? w[2] : 1.0f - w[2];
+  const float wx = (k & 1) ? w[0] : w0[0];
+  const float wy = (k & 2) ? w[1] : w0[1];
+  const float wz = (k & 4) ? w[2] : w0[2];
   const int col = feat0 + 2 * level + f;
   float a = wx * wy * wz * dY[(long)p * lddy + col];
   if (TANGENTS) {
@@ -549,15 +560,13 @@ __device__ __forceinline__ void owner_point(const OwnerArgs& a, float* acc, cons
   float pos[3], J[3][3];
   grid_position(xv, a.mode, pos, J);
   uint32_t pg[3];
-  float w[3], dw[3];
+  float w0[3], w[3], dw[3];
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
     const float q = fmaf(scale, pos[d], 0.5f);
     const float fl = floorf(q);
     pg[d] = (uint32_t)(int)fl;
-    const float td = q - fl;
-    w[d] = smooth ? td * td * (3.0f - 2.0f * td) : td;
-    dw[d] = smooth ? 6.0f * td * (1.0f - td) * scale : scale;
+    axis_weights(q - fl, smooth, scale, w0[d], w[d], dw[d]);
   }
   float2 gpa[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};  // gradient w.r.t. d feat / d pos_a, pulled back through J
   if (TANGENTS)
@@ -584,13 +593,13 @@ __device__ __forceinline__ void owner_point(const OwnerArgs& a, float* acc, cons
         const int q = __ffs(pairs) - 1;
         pairs &= pairs - 1;
         const uint32_t yz = (Y0 + ((q & 1) ? YM : 0u)) ^ (Z0 + ((q & 2) ? ZM : 0u));
-        const float wy = (q & 1) ? w[1] : 1.0f - w[1];
-        const float wz = (q & 2) ? w[2] : 1.0f - w[2];
+        const float wy = (q & 1) ? w[1] : w0[1];
+        const float wz = (q & 2) ? w[2] : w0[2];
 #pragma unroll
         for (int xb = 0; xb < 2; ++xb) {
           const uint32_t idx = ((pg[0] + (uint32_t)xb) ^ yz) & smask;
           if ((idx >> OWN_SHIFT) != chunk) continue;
-          const float wx = xb ? w[0] : 1.0f - w[0];
+          const float wx = xb ? w[0] : w0[0];
           float a0 = wx * wy * wz * gy.x, a1 = wx * wy * wz * gy.y;
           if (TANGENTS) {
             const float cx = (xb ? dw[0] : -dw[0]) * wy * wz;
@@ -613,9 +622,9 @@ __device__ __forceinline__ void owner_point(const OwnerArgs& a, float* acc, cons
     uint32_t idx = xk + yk + zk;
     if (idx >= size) idx %= size;
     if ((idx >> OWN_SHIFT) != chunk) continue;
-    const float wx = (k & 1) ? w[0] : 1.0f - w[0];
-    const float wy = (k & 2) ? w[1] : 1.0f - w[1];
-    const float wz = (k & 4) ? w[2] : 1.0f - w[2];
+    const float wx = (k & 1) ? w[0] : w0[0];
+    const float wy = (k & 2) ? w[1] : w0[1];
+    const float wz = (k & 4) ? w[2] : w0[2];
     float a0 = wx * wy * wz * gy.x, a1 = wx * wy * wz * gy.y;
     if (TANGENTS) {
       const float cx = ((k & 1) ? dw[0] : -dw[0]) * wy * wz;

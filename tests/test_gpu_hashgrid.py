@@ -19,8 +19,15 @@ def _setup(smooth, n_levels=16, log2T=19, max_res=2048, seed=0, table_scale=0.5)
     return geom, cfg, table
 
 
-@pytest.mark.parametrize("mode", [0, 1])
+def _order(mode):  # the oracle's contraction norm for the kernels' mode 1 / 2
+    return float("inf") if mode == 1 else 2
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
 def test_indices_bit_exact(mode):
+    """mode 2: the kernel forms the L2-contracted position with the oracle's fp32 roundings one by one (torch's norm accumulates with
+    fma, left to right; then (2 - 1/m) (x / m)).  With k x, k = (2 - 1/m) / m, the position differed by an ulp at 1061 of these
+    4099 points, and point 630 fell into the neighbouring cell on level 11 (q = 136.99999 against 137.0000047)."""
     from neusky_amd import hip
     geom, cfg, table = _setup(False)
     g = torch.Generator().manual_seed(1)
@@ -28,21 +35,26 @@ def test_indices_bit_exact(mode):
     x = (torch.rand(P, 3, generator=g) * 2 - 1) * (1.0 if mode == 0 else 1.3)
     x[:3] = torch.tensor([[1.0, -1.0, 0.0], [0.0, 0.0, 0.0], [0.999999, 0.5, -0.25]])
     idx = hip.hash_indices(geom, table.to(DEV), x.to(DEV), mode).cpu().to(torch.int64) & 0xFFFFFFFF
-    pos = x if mode == 0 else (O.scene_contraction(x) + 2.0) / 4.0
+    assert mode == 0 or ((x.norm(dim=-1) < 1).any() and (x.norm(dim=-1) > 1).any())
+    pos = x if mode == 0 else (O.scene_contraction(x, _order(mode)) + 2.0) / 4.0
     ref, _ = O.hash_grid_indices(pos, cfg)
     # cell choice depends on fp32 rounding of (contract(x)+2)/4 * scale + 0.5: identical op order -> bit exact
     mism = (idx != ref).any(-1).any(-1)
     assert mism.sum().item() == 0, f"{mism.sum().item()} points with different corner rows"
 
 
-@pytest.mark.parametrize("smooth,mode", [(True, 1), (False, 0)])
+# mode 2 (L2 contraction), measured on an MI355X: rows max 1.20e-4 / mean 2.3e-6, tangents 1.9e-4 of the largest entry
+# (mode 1: 2.0e-4; mode 0: 6.2e-5 / 2.1e-6 and 9.3e-5)
+@pytest.mark.parametrize("smooth,mode", [(True, 1), (False, 0), (True, 2)])
 def test_forward_rows_and_tangents(smooth, mode):
     from neusky_amd import hip
     geom, cfg, table = _setup(smooth)
     g = torch.Generator().manual_seed(2)
     P = 1000
-    x = (torch.rand(P, 3, generator=g) * 2 - 1) * (1.25 if mode == 1 else 1.0)
-    include_x, pe = (True, 6) if mode == 1 else (True, 0)
+    x = (torch.rand(P, 3, generator=g) * 2 - 1) * (1.25 if mode else 1.0)
+    r = x.norm(dim=-1)  # both sides of the L2 contraction's unit sphere, in the values and in the Jacobian subset; nothing on it
+    assert (r < 1).any() and (r > 1).any() and (r[:40] < 1).any() and (r[:40] > 1).any() and ((r[:40] - 1).abs() > 1e-3).all()
+    include_x, pe = (True, 6) if mode else (True, 0)
     width = 3 + 6 * pe + 32
     ldy = (width + 3) // 4 * 4
     Y = torch.full((P, ldy), float("nan"), device=DEV)
@@ -50,7 +62,7 @@ def test_forward_rows_and_tangents(smooth, mode):
     hip.encode_fwd(geom, table.to(DEV), x.to(DEV), mode, include_x, pe, 5.0, Y, Tn)
 
     xd = x.double().requires_grad_(True)
-    pos = xd if mode == 0 else (O.scene_contraction(xd) + 2.0) / 4.0
+    pos = xd if mode == 0 else (O.scene_contraction(xd, _order(mode)) + 2.0) / 4.0
     feat = O.hash_grid_encode(pos, table.double(), cfg)
     parts = [xd] + ([O.nerf_encoding(xd, 6, 0.0, 5.0, False)] if pe else []) + [feat]
     row = torch.cat(parts, -1)
@@ -58,6 +70,7 @@ def test_forward_rows_and_tangents(smooth, mode):
     # fp32 evaluation of t = frac(pos*scale + 0.5) at scale ~2047 carries ~1e-4 of a cell (1 ulp of pos*scale),
     # so the finest levels differ from exact math by ~1e-4 * |table| (table_scale = 0.5 here; 1e-4 at tcnn init).
     err = (got[:, :width] - row.detach()).abs()
+    print(f"mode {mode}: row max err {err.max().item():.3e}, mean {err.mean().item():.3e}")
     assert err.max().item() < 3e-4 and err.mean().item() < 1e-5, (err.max().item(), err.mean().item())
     assert (got[:, width:] == 0).all()
     # Jacobian rows: d row / d x_k by autograd, column by column (small P subset)
@@ -68,18 +81,23 @@ def test_forward_rows_and_tangents(smooth, mode):
         jac[:, :, c] = gr.T
     tn = Tn.cpu().double()[:, sub, :width]
     scale = jac.abs().max().item()
+    print(f"mode {mode}: tangent max err {(tn - jac).abs().max().item() / scale:.3e} of the largest entry")
     assert (tn - jac).abs().max().item() < 5e-4 * scale, ((tn - jac).abs().max().item(), scale)
 
 
+# mode 2, measured on an MI355X: table gradient 3.5e-5 (P = 777) and 2.4e-5 (P = 33000), input gradient 1.1e-5 and 1.2e-5 of the
+# largest entry (mode 1: 3.7e-5 / 2.3e-5 and 1.1e-5 / 1.2e-5)
 # P = 777: direct scatter of the fine levels; P = 33000: chunk-owner kernel (>= 32768 points; T = 2^15 -> two chunks per hashed level)
 @pytest.mark.parametrize("smooth,mode,with_t,P,log2T", [(True, 1, True, 777, 14), (False, 0, False, 777, 14),
-                                                        (True, 1, True, 33000, 15), (False, 0, False, 33000, 15)])
+                                                        (True, 1, True, 33000, 15), (False, 0, False, 33000, 15),
+                                                        (True, 2, True, 777, 14), (True, 2, True, 33000, 15)])
 def test_backward_table_and_input(smooth, mode, with_t, P, log2T):
     from neusky_amd import hip
     geom, cfg, table = _setup(smooth, n_levels=8, log2T=log2T, max_res=256)
     g = torch.Generator().manual_seed(3)
-    x = (torch.rand(P, 3, generator=g) * 2 - 1) * (1.2 if mode == 1 else 1.0)
-    pe = 6 if mode == 1 else 0
+    x = (torch.rand(P, 3, generator=g) * 2 - 1) * (1.2 if mode else 1.0)
+    assert mode == 0 or ((x.norm(dim=-1) < 1).any() and (x.norm(dim=-1) > 1).any())
+    pe = 6 if mode else 0
     width = 3 + 6 * pe + 2 * geom.n_levels
     ldy = (width + 3) // 4 * 4
     dY = torch.zeros(P, ldy); dY[:, :width] = torch.randn(P, width, generator=g)
@@ -92,7 +110,7 @@ def test_backward_table_and_input(smooth, mode, with_t, P, log2T):
 
     xd = x.double().requires_grad_(True)
     tb = table.double().requires_grad_(True)
-    pos = xd if mode == 0 else (O.scene_contraction(xd) + 2.0) / 4.0
+    pos = xd if mode == 0 else (O.scene_contraction(xd, _order(mode)) + 2.0) / 4.0
     feat = O.hash_grid_encode(pos, tb, cfg)
     parts = [xd] + ([O.nerf_encoding(xd, 6, 0.0, 5.0, False)] if pe else []) + [feat]
     row = torch.cat(parts, -1)
@@ -109,8 +127,10 @@ def test_backward_table_and_input(smooth, mode, with_t, P, log2T):
             loss = loss + (jvp * dT[k, :, :width].double()).sum()
     gt_ref = torch.autograd.grad(loss, tb)[0]
     scale = gt_ref.abs().max().item()
-    assert (dtab.cpu().double() - gt_ref).abs().max().item() < 5e-4 * scale
     sx = gx_ref.abs().max().item()
+    print(f"mode {mode}, P {P}: table gradient max err {(dtab.cpu().double() - gt_ref).abs().max().item() / scale:.3e}, "
+          f"input gradient {(dx.cpu().double() - gx_ref).abs().max().item() / sx:.3e} of the largest entry")
+    assert (dtab.cpu().double() - gt_ref).abs().max().item() < 5e-4 * scale
     assert (dx.cpu().double() - gx_ref).abs().max().item() < 5e-4 * sx
 
 
