@@ -11,32 +11,36 @@ from __future__ import annotations
 
 from collections import namedtuple
 from dataclasses import InitVar, dataclass, field
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Callable, Dict, Optional
 
 import torch
 
 from .. import hip, ops
 from ..cameras.rays import RayBundle
 from ..field_components.neusky_fieldheadnames import FieldHeadNames, NeuSkyFieldHeadNames
-from ..relight.envmap import project_envmap
-from ..relight.shadows import SHADOW_DEFAULTS, trace_params, trace_settings, trace_sun_shadows
-from ..relight.sun import as_suns
+from ..relight.lighting import FrameLighting, light_colours
+from ..relight.shadows import trace_params, trace_sun_shadows
 from ..relight.transfer import bake_rows
 
 SUN_KEYS = ("rgb", "lin", "shadow_map", "shadow_difference")
 SDF_SHADOW_KEYS = ("shadow_status",)  # joins them under sun_shadows="sdf"
-COLLIDER_RADIUS = 1.0  # of NeuSkyModel.collider: the scene bound of a shadow march
 
 
-# all tensors but the map are static buffers: rotation [3, 3], exposure [1]; dirs, colours [K, 3], the thresholds [1], sel = int32 arange(K)
-# (every sun direction is queried).  `scale` is a float, a by-value argument of nsky_visibility_finish_fwd
+# the static buffers of a frame, as FrameRenderer.static keeps them; a member that is none of the entry's own (`data`, `convention`, `scale`,
+# `suns`, `steps`, `grace`: held by a captured chunk by value or by another's pointer) is None there and set per frame with _replace.
+# the sky: dirs [D, 3], the frame camera's colours at them [1, D, 3], sel
+FrameSky = namedtuple("FrameSky", "dirs cols sel")
+# a relight.EnvironmentMap: its data and convention id, and the frame's rotation [3, 3] and the map's exposure [1]
 FrameEnvmap = namedtuple("FrameEnvmap", "data convention rotation exposure")
+# K suns: dirs, colours [K, 3], the thresholds [1], sel = int32 arange(K) (every sun direction is queried).  `scale` is a float, a
+# by-value argument of nsky_visibility_finish_fwd
 FrameSuns = namedtuple("FrameSuns", "dirs colours threshold acc_threshold sel scale")
-# a relight.DaylightSky under the frame's K suns, all static buffers: lights [K, D, 3], the sky of each sun at the frame's D directions
-# (nsky_daylight_eval there: point samples of the model, not cell averages); turbidity, exposure [1], ground [3]; suns = FrameSuns.dirs
-FrameDaylight = namedtuple("FrameDaylight", "lights turbidity exposure ground suns")
+# a relight.DaylightSky under the frame's K suns: lights [K, D, 3], the sky of each sun at the frame's D directions (nsky_daylight_eval
+# there: point samples of the model, not cell averages); turbidity, exposure [1], ground [3]; suns = FrameSuns.dirs.  `packed` [5] is
+# the allocation the three are views of: begin fills them with one copy into it, and nothing else reads it
+FrameDaylight = namedtuple("FrameDaylight", "lights turbidity exposure ground suns packed")
 # sun_shadows="sdf": the suns' shadows are marched through the SDF (relight/shadows.py).  params: the kernels' parameter block [6] (eps,
-# relax, min_step, tan_half, radius, bias), a static buffer; steps and grace are Python numbers, by-value arguments of the step kernel
+# relax, min_step, tan_half, radius, bias); steps and grace are Python numbers, by-value arguments of the step kernel
 FrameTrace = namedtuple("FrameTrace", "params steps grace")
 
 
@@ -82,33 +86,6 @@ class FrameLight:
     @property
     def shading(self) -> str:
         return "bake" if self.bake is not None else "daylight" if self.daylight is not None else "sun" if self.sun is not None else "sky"
-
-
-def light_colours(model, dirs: torch.Tensor, cam: int, rotation: Optional[torch.Tensor] = None, envmap=None) -> torch.Tensor:
-    """[D, 3]: the light at the frame's directions, of camera `cam`'s latent (turned by `rotation`) or of a relight.EnvironmentMap: the
-    map's cell averages (relight.project_envmap)"""
-    if envmap is not None:
-        return project_envmap(envmap, dirs, rotation)[0]
-    latents, scales = model.get_illumination_field()
-    if rotation is None:
-        return model.illumination_field.forward_grid(dirs, latents[cam][None], scales[cam][None])[0]
-    return model.illumination_field.forward_camera(dirs, latents[cam], scales[cam], rotation)
-
-
-def ray_background(model, ray_directions: torch.Tensor, cam: int, rotation: Optional[torch.Tensor] = None,
-                   envmap: Optional[FrameEnvmap] = None, daylight: Optional[FrameDaylight] = None) -> torch.Tensor:
-    """[R, 3]: the sky behind the rays, of camera `cam`'s latent (turned by `rotation`) or of the frame's environment map (its bilinear
-    lookup, read through the static buffers); under a daylight sky [K, R, 3]: the sky of each of the frame's suns"""
-    if daylight is not None:
-        bg = torch.empty(daylight.suns.shape[0], ray_directions.shape[0], 3, dtype=torch.float32, device=ray_directions.device)
-        hip.daylight_eval(ray_directions.contiguous(), daylight.suns, daylight.turbidity, daylight.exposure, daylight.ground, bg)
-        return bg
-    if envmap is not None:
-        bg = torch.empty(ray_directions.shape[0], 3, dtype=torch.float32, device=ray_directions.device)
-        hip.envmap_lookup(envmap.data, envmap.convention, ray_directions.contiguous(), envmap.rotation, envmap.exposure, bg)
-        return bg
-    latents, scales = model.get_illumination_field()
-    return model.illumination_field.forward_camera(ray_directions, latents[cam], scales[cam], rotation)
 
 
 def shade(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -> Dict[str, torch.Tensor]:
@@ -182,40 +159,26 @@ class FrameRenderer:
     def __init__(self, model):
         self.model = model
         self.active: Optional[FrameLight] = None
-        self.sky_static: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None  # dirs [D, 3], cols [1, D, 3], sel
-        self.envmap_static: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # rotation [3, 3], exposure [1]
-        self.sun_static: Dict[tuple, tuple] = {}  # (K, device) -> dirs, colours, threshold, acc_threshold, sel
-        # (K, D, device) -> lights, turbidity, exposure, ground (the last three views of one [5] buffer).  Like sun_static, one small
-        # set per K ever used, kept for the model's lifetime: a captured chunk holds their pointers
-        self.daylight_static: Dict[tuple, tuple] = {}
-        self.trace_static: Dict[str, torch.Tensor] = {}  # device -> the shadow march's parameter block [6]
+        # the static buffers, one named tuple per key, kept for the model's lifetime (a captured chunk holds their pointers): "sky" ->
+        # FrameSky; ("envmap", device) -> FrameEnvmap; ("suns", K, device) -> FrameSuns; ("daylight", K, D, device) -> FrameDaylight;
+        # ("trace", device) -> FrameTrace.  Only "sky" is ever allocated again, on a new D or device, and takes the runners with it
+        self.static: Dict[Any, tuple] = {}
         # a chunk graph cached under a rotation's values reads the rotation through the pointer it was captured with: the first tensor
         # seen with these values is kept, and serves every later frame that asks for them (one entry per value ever seen)
         self.rotations: Dict[tuple, torch.Tensor] = {}
         self.runners: Dict[tuple, "_ChunkRunner"] = {}  # (chunk, use_graph, key if use_graph else None) -> runner
 
     # ------------------------------------------------------------------ the frame's light
-    def begin(self, camera_index: int, rotation: Optional[torch.Tensor] = None, envmap=None, sun=None,
-              shadow_threshold: Optional[float] = None, shadow_sigmoid_scale: Optional[float] = None,
-              accumulation_mask_threshold: float = 0.0, bake: Optional[str] = None, daylight=None, sun_shadows: str = "ddf",
-              shadow_trace: Optional[dict] = None) -> None:
-        """model.begin_frame, and `bake`: the storage of a radiance-transfer bake (relight.bake_transfer), which takes the place of
-        the shading"""
+    def _static(self, key, allocate: Callable[[], tuple]) -> tuple:
+        st = self.static.get(key)
+        if st is None:
+            st = self.static[key] = allocate()
+        return st
+
+    def begin(self, camera_index: int, lighting: FrameLighting) -> None:
+        """the device state of a frame lit by `lighting`, active until `end`: the rotation pinned, the static buffers filled"""
         model = self.model
-        if sun_shadows not in ("ddf", "sdf"):
-            raise ValueError(f"sun_shadows: 'ddf' or 'sdf', got {sun_shadows!r}")
-        if sun_shadows == "sdf":
-            if sun is None or bake is not None:
-                raise ValueError("sun_shadows='sdf' marches the shadow rays of a sun: give `sun` (and no bake)")
-            if shadow_threshold is not None or shadow_sigmoid_scale is not None:
-                raise ValueError("shadow_threshold and shadow_sigmoid_scale shape the DDF shadow: they exclude sun_shadows='sdf'")
-        elif shadow_trace is not None:
-            raise ValueError("shadow_trace holds the parameters of the march: it needs sun_shadows='sdf'")
-        if daylight is not None:
-            if sun is None:
-                raise ValueError("daylight: the sky follows a sun: give `sun`, one SunLight or K (DaylightSky.sun, DaylightSky.sun_path)")
-            if envmap is not None or rotation is not None or bake is not None:
-                raise ValueError("daylight takes the place of the latent's or the map's sky: it excludes envmap, rotation and a bake")
+        rotation, envmap = lighting.rotation, lighting.envmap
         fixed = model.config.fix_test_illumination_directions
         dirs, sel = model.illumination_sampler.on_device(model.device, apply_random_rotation=False if fixed else None)
         cam = int(camera_index)
@@ -223,76 +186,76 @@ class FrameRenderer:
         if values is not None:
             rotation = self.rotations.setdefault(values, rotation)
         # (a daylight frame reads no `cols`: the camera's latent is not decoded, the buffer keeps what it held)
-        cols = light_colours(model, dirs, cam, rotation, envmap)[None] if daylight is None else None
+        cols = light_colours(model, dirs, cam, rotation, envmap)[None] if lighting.daylight is None else None
         # static per-model buffers: a chunk graph captured for one frame stays valid for the next (animation frames
         # only change the camera / rotation, render_animation.py:196-207)
-        st = self.sky_static
-        if st is None or st[0].shape != dirs.shape or st[0].device != dirs.device:
-            st = self.sky_static = (torch.empty_like(dirs), torch.zeros(1, *dirs.shape, dtype=dirs.dtype, device=dirs.device),
-                                    torch.empty_like(sel))
+        sky = self.static.get("sky")
+        if sky is None or sky.dirs.shape != dirs.shape or sky.dirs.device != dirs.device:
+            sky = self.static["sky"] = FrameSky(torch.empty_like(dirs), torch.zeros(1, *dirs.shape, dtype=dirs.dtype, device=dirs.device),
+                                                torch.empty_like(sel))
             self.runners = {}  # (the dropped runners' graphs retire themselves: ops.CapturedGraph)
-        st[0].copy_(dirs); st[2].copy_(sel)
+        sky.dirs.copy_(dirs); sky.sel.copy_(sel)
         if cols is not None:
-            st[1].copy_(cols)
-        suns = self._suns(sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold)
-        self.active = FrameLight(st[0], st[1], st[2], cam, rotation, values, self._envmap(envmap, rotation), suns, bake,
-                                 self._daylight(daylight, st[0], suns), self._trace(shadow_trace) if sun_shadows == "sdf" else None)
+            sky.cols.copy_(cols)
+        suns = self._suns(lighting)
+        self.active = FrameLight(sky.dirs, sky.cols, sky.sel, cam, rotation, values, self._envmap(envmap, rotation), suns, lighting.bake,
+                                 self._daylight(lighting.daylight, sky.dirs, suns), self._trace(lighting.shadow_trace))
 
     def _envmap(self, envmap, rotation) -> Optional[FrameEnvmap]:
         if envmap is None:
             return None
-        st = self.envmap_static
-        if st is None or st[0].device != envmap.device:
-            st = self.envmap_static = (torch.empty(3, 3, dtype=torch.float32, device=envmap.device),
-                                       torch.empty(1, dtype=torch.float32, device=envmap.device))
+        dev = envmap.device
+        st = self._static(("envmap", str(dev)), lambda: FrameEnvmap(None, None, torch.empty(3, 3, dtype=torch.float32, device=dev),
+                                                                    torch.empty(1, dtype=torch.float32, device=dev)))
         if rotation is None:
-            st[0].copy_(torch.eye(3, dtype=torch.float32))
+            st.rotation.copy_(torch.eye(3, dtype=torch.float32))
         else:
-            st[0].copy_(torch.as_tensor(rotation).reshape(3, 3))
-        st[1].copy_(envmap.exposure_tensor)
-        return FrameEnvmap(envmap.data, envmap.convention_id, st[0], st[1])
+            st.rotation.copy_(torch.as_tensor(rotation).reshape(3, 3))
+        st.exposure.copy_(envmap.exposure_tensor)
+        return st._replace(data=envmap.data, convention=envmap.convention_id)
 
-    def _suns(self, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold) -> Optional[FrameSuns]:
-        if sun is None:
+    def _suns(self, lighting: FrameLighting) -> Optional[FrameSuns]:
+        suns = lighting.suns
+        if suns is None:
             return None
         model = self.model
-        suns, _ = as_suns(sun)
         K, dev = len(suns), model.device
-        st = self.sun_static.get((K, str(dev)))
-        if st is None:
-            st = self.sun_static[(K, str(dev))] = (torch.empty(K, 3, device=dev), torch.empty(K, 3, device=dev), torch.empty(1, device=dev),
-                                                   torch.empty(1, device=dev), torch.arange(K, device=dev, dtype=torch.int32))
-        st[0].copy_(torch.tensor([s.direction for s in suns], dtype=torch.float64).to(torch.float32))
-        st[1].copy_(torch.tensor([s.colour for s in suns], dtype=torch.float32))
-        if shadow_threshold is None:
-            st[2].copy_(model.visibility_threshold.detach() if model.config.use_visibility else torch.zeros(1))
+        st = self._static(("suns", K, str(dev)), lambda: FrameSuns(
+            torch.empty(K, 3, device=dev), torch.empty(K, 3, device=dev), torch.empty(1, device=dev), torch.empty(1, device=dev),
+            torch.arange(K, device=dev, dtype=torch.int32), None))
+        st.dirs.copy_(torch.tensor([s.direction for s in suns], dtype=torch.float64).to(torch.float32))
+        st.colours.copy_(torch.tensor([s.colour for s in suns], dtype=torch.float32))
+        if lighting.shadow_threshold is None:
+            st.threshold.copy_(model.visibility_threshold.detach() if model.config.use_visibility else torch.zeros(1))
         else:
-            st[2].copy_(torch.tensor([float(shadow_threshold)]))
-        st[3].copy_(torch.tensor([float(accumulation_mask_threshold)]))
-        scale = float(model.sigmoid_scale if shadow_sigmoid_scale is None else shadow_sigmoid_scale) if model.config.use_visibility else 0.0
-        return FrameSuns(*st, scale)
+            st.threshold.copy_(torch.tensor([float(lighting.shadow_threshold)]))
+        st.acc_threshold.copy_(torch.tensor([float(lighting.accumulation_mask_threshold)]))
+        scale = 0.0  # (a model without a visibility field has no sigmoid_scale: read it under use_visibility only)
+        if model.config.use_visibility:
+            scale = float(model.sigmoid_scale if lighting.shadow_sigmoid_scale is None else lighting.shadow_sigmoid_scale)
+        return st._replace(scale=scale)
 
     def _daylight(self, daylight, dirs: torch.Tensor, suns: Optional[FrameSuns]) -> Optional[FrameDaylight]:
         if daylight is None:
             return None
         K, D, dev = suns.dirs.shape[0], dirs.shape[0], dirs.device
-        st = self.daylight_static.get((K, D, str(dev)))
-        if st is None:
-            packed = torch.empty(5, device=dev)
-            st = self.daylight_static[(K, D, str(dev))] = (torch.empty(K, D, 3, device=dev), packed[0:1], packed[1:2], packed[2:5], packed)
-        st[4].copy_(torch.tensor([daylight.turbidity, daylight.exposure, *daylight.ground], dtype=torch.float32))
-        hip.daylight_eval(dirs, suns.dirs, st[1], st[2], st[3], st[0])
-        return FrameDaylight(*st[:4], suns.dirs)
 
-    def _trace(self, shadow_trace: Optional[dict]) -> FrameTrace:
-        """shadow_trace: any of relight.shadows.SHADOW_DEFAULTS' keys; `radius` defaults to the sphere collider's"""
-        p = trace_settings(shadow_trace, {**SHADOW_DEFAULTS, "radius": COLLIDER_RADIUS})
-        dev = str(self.model.device)
-        st = self.trace_static.get(dev)
-        if st is None:
-            st = self.trace_static[dev] = torch.empty(hip.TRACE_PARAMS, device=self.model.device)
-        st.copy_(trace_params(p))
-        return FrameTrace(st, p["steps"], p["grace"])
+        def allocate():
+            packed = torch.empty(5, device=dev)
+            return FrameDaylight(torch.empty(K, D, 3, device=dev), packed[0:1], packed[1:2], packed[2:5], None, packed)
+        st = self._static(("daylight", K, D, str(dev)), allocate)._replace(suns=suns.dirs)
+        st.packed.copy_(torch.tensor([daylight.turbidity, daylight.exposure, *daylight.ground], dtype=torch.float32))
+        hip.daylight_eval(dirs, st.suns, st.turbidity, st.exposure, st.ground, st.lights)
+        return st
+
+    def _trace(self, shadow_trace: Optional[dict]) -> Optional[FrameTrace]:
+        """shadow_trace: FrameLighting's, every parameter of the march or None"""
+        if shadow_trace is None:
+            return None
+        dev = self.model.device
+        st = self._static(("trace", str(dev)), lambda: FrameTrace(torch.empty(hip.TRACE_PARAMS, device=dev), None, None))
+        st.params.copy_(trace_params(shadow_trace))
+        return st._replace(steps=shadow_trace["steps"], grace=shadow_trace["grace"])
 
     def end(self) -> None:
         self.active = None
@@ -313,10 +276,10 @@ class FrameRenderer:
             self.runners[key] = runner
         return runner
 
-    def render(self, camera_ray_bundle: RayBundle, rotation, to_cpu: bool, camera_index: Optional[int], chunk: Optional[int],
-               use_graph: bool, envmap, sun, *thresholds, daylight=None, sun_shadows: str = "ddf",
-               shadow_trace: Optional[dict] = None) -> Dict[str, torch.Tensor]:
-        """model.get_outputs_for_camera_ray_bundle, which names and documents the arguments (`thresholds`: begin's three)"""
+    @torch.no_grad()
+    def render(self, camera_ray_bundle: RayBundle, lighting: FrameLighting, *, to_cpu: bool = False, camera_index: Optional[int] = None,
+               chunk: Optional[int] = None, use_graph: bool = True) -> Dict[str, torch.Tensor]:
+        """model.get_outputs_for_camera_ray_bundle, which documents the chunking and the outputs"""
         model = self.model
         assert not model.training, "call model.eval() first"
         chunk = chunk or max(model.config.eval_num_rays_per_chunk, 4096)
@@ -325,11 +288,9 @@ class FrameRenderer:
         num_rays = flat.origins.shape[0]
         if camera_index is None:
             camera_index = int(flat.camera_indices.reshape(-1)[0]) if flat.camera_indices is not None else 0
-        single = True
-        if sun is not None:
-            sun, single = as_suns(sun)
-        self.begin(camera_index, rotation, envmap, sun, *thresholds, daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace)
-        sun_keys = list(SUN_KEYS + (SDF_SHADOW_KEYS if sun_shadows == "sdf" else ())) if sun is not None else []
+        self.begin(camera_index, lighting)
+        suns = lighting.suns
+        sun_keys = list(SUN_KEYS + (SDF_SHADOW_KEYS if lighting.sun_shadows == "sdf" else ())) if suns is not None else []
         keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
         out = {k: [] for k in keys}
         try:
@@ -340,9 +301,9 @@ class FrameRenderer:
                     out[k].append(res[k].cpu() if to_cpu else res[k])
         finally:
             self.end()
-        if sun is not None:  # chunks are ray-major [n, K, ...]: K leads, and a single SunLight drops it
-            K = len(sun)
-            lead = () if single else (K,)
+        if suns is not None:  # chunks are ray-major [n, K, ...]: K leads, and a single SunLight drops it
+            K = len(suns)
+            lead = () if lighting.single_sun else (K,)
             for k in sun_keys:
                 full = torch.cat(out.pop(k))
                 out[k] = [full.reshape(num_rays, K, -1).transpose(0, 1).reshape(*lead, *shape, -1)]

@@ -36,7 +36,8 @@ from ..model_components.ray_samplers import HashMLPDensityField, ProposalNetwork
 from ..model_components.renderers import RGBLambertianRendererWithVisibility
 from ..utils.utils import device_rng, device_rng_seed, linear_to_sRGB, to_device_async
 from ..plugin import ConfigBase, ModelBase
-from .frame import FrameRenderer, ray_background, shade
+from ..relight.lighting import FrameLighting, ray_background
+from .frame import FrameRenderer, shade
 
 
 def _default_loss_inclusions() -> Dict[str, Any]:  # neusky/configs/neusky_config.py:102-126
@@ -873,15 +874,10 @@ class NeuSkyFactoModel(ModelBase):
                     accumulation_mask_threshold: float = 0.0, daylight=None, sun_shadows: str = "ddf",
                     shadow_trace: Optional[dict] = None) -> None:
         """decode the illumination of ONE camera for a whole frame (the reference re-decodes it in each of the
-        8100 chunks of a 1080p frame, neusky_model.py:1413-1432; the result is the same).
-        envmap: a relight.EnvironmentMap lighting the frame instead of the camera's latent: the light colours are the map's cell
-        averages at the frame's directions (relight.project_envmap), the rays' background its bilinear lookup.
-        sun: a relight.SunLight or a sequence of K of them on top of that sky (frame.FrameSuns).
-        daylight: a relight.DaylightSky in place of either sky, one sky per sun (frame.FrameDaylight); needs `sun`, excludes `envmap`
-        and `rotation`; the camera's latent is not decoded.
-        sun_shadows, shadow_trace: get_outputs_for_camera_ray_bundle's (frame.FrameTrace)."""
-        self.frames.begin(camera_index, rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold,
-                          daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace)
+        8100 chunks of a 1080p frame, neusky_model.py:1413-1432; the result is the same).  The frame stays active until end_frame.
+        The lighting keywords: relight.FrameLighting, which documents and checks them."""
+        self.frames.begin(camera_index, FrameLighting.of(rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold,
+                                                         daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace))
 
     def end_frame(self) -> None:
         self.frames.end()
@@ -896,26 +892,8 @@ class NeuSkyFactoModel(ModelBase):
         """neusky_model.py:1369-1501: chunked full-frame render.  The reference chunks at eval_num_rays_per_chunk = 256
         (8100 python iterations per 1080p frame); any chunk size gives the same image, so a larger static chunk is used
         and its forward is captured once in a HIP graph and replayed per chunk (BASELINE config 5).
-        envmap: a relight.EnvironmentMap to light the frame with instead of the camera's illumination latent (begin_frame);
-        `rotation` then turns the map (direction d is lit by the map at R d).
-        sun: a relight.SunLight, or a sequence of K of them, on top of either sky (include/neusky_hip.h: a directional sun).  `rgb` is
-        then the frame lit by sky and sun, and `lin` (its linear image), `shadow_map` and `shadow_difference` [*shape, 1] join the outputs;
-        a sequence puts a leading K on those four.  The field, the sampler and the sky pass of a chunk run once for all K suns.
-        shadow_threshold / shadow_sigmoid_scale default to the model's trained visibility threshold and sigmoid scale; the shadow is
-        masked by accumulation > accumulation_mask_threshold.  A sun with elevation <= 0 has set: it adds no light and no shadow.
-        daylight: a relight.DaylightSky: a clear sky that follows the sun, in place of the latent's or a map's (needs `sun`, excludes
-        `envmap` and `rotation`).  Each of the K suns then has its own sky at the frame's light directions (point samples of the model),
-        its own background behind the rays and, from DaylightSky.sun / sun_path, its own colour; the outputs are those of a sun frame,
-        and a set sun's frame is black.  The field, the sampler and the visibility pass of a chunk still run once for all K.
-        sun_shadows: "ddf" (the default: one DDF query per ray and sun) or "sdf": the suns' shadow rays are sphere-traced through the SDF
-        field (relight.shadows, include/neusky_hip.h), from each ray's rendered depth and normal; this needs no visibility network
-        (use_visibility = False renders too).  The shadow then follows the surface the mesh export writes and has a penumbra of the
-        sun's angular diameter.  `shadow_difference`, a DDF quantity, is all zeros in this mode, and `shadow_status` [*shape, 1] (int8:
-        relight.shadows.HIT / ESCAPED / EXHAUSTED, the march's verdict before the set-sun and accumulation rules) joins the outputs.
-        shadow_threshold and shadow_sigmoid_scale are errors with it.
-        shadow_trace: with "sdf", a dictionary of any of the march's parameters (relight.shadows.SHADOW_DEFAULTS): steps, eps, relax,
-        min_step, grace, radius, angular_diameter_deg (0 gives a hard edge) and bias (the lift of the start point off the rendered
-        surface along its normal, scene units).  Only steps and grace are held by a captured chunk: the others replay it."""
-        return self.frames.render(camera_ray_bundle, rotation, to_cpu, camera_index, chunk, use_graph, envmap, sun, shadow_threshold,
-                                  shadow_sigmoid_scale, accumulation_mask_threshold, daylight=daylight, sun_shadows=sun_shadows,
-                                  shadow_trace=shadow_trace)
+        Outputs [*shape, C]: rgb, albedo, accumulation, depth, p2p_dist, normal, and what the lighting adds.  The lighting keywords
+        (rotation, envmap, sun, the thresholds, daylight, sun_shadows, shadow_trace): relight.FrameLighting, which documents and checks them."""
+        lighting = FrameLighting.of(rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold,
+                                    daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace)
+        return self.frames.render(camera_ray_bundle, lighting, to_cpu=to_cpu, camera_index=camera_index, chunk=chunk, use_graph=use_graph)

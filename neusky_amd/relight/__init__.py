@@ -17,17 +17,20 @@ frame render with `daylight=` gives each of K suns its own sky from one field pa
 
 `trace_visibility` / `SphereTrace` (shadows.py, csrc/sphere_trace.hip): shadow rays sphere-traced through the SDF, with penumbrae; the
 frame render with `sun_shadows="sdf"` takes every sun's shadow from it instead of the DDF (`--sun-shadows sdf`).
+
+`FrameLighting` (lighting.py): all of the above as the one value a frame's light is said in, with the rules between its options.
 """
 from .cameras import CameraPath, camera_rays, load_camera_path
 from .daylight import DaylightSky
 from .envmap import EnvironmentMap, envmap_labels, envmap_lookup, project_envmap, z_rotation
 from .envmap_sun import SunExtraction, extract_sun
 from .io import read_envmap, srgb_to_linear
+from .lighting import FrameLighting
 from .shadows import ALIVE, ESCAPED, EXHAUSTED, HIT, SHADOW_DEFAULTS, TRACE_DEFAULTS, SphereTrace, trace_sun_shadows, trace_visibility
 from .sun import SunLight, sun_direction, sun_path, sun_solid_angle
 from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
 
-__all__ = ["ALIVE", "CameraPath", "DaylightSky", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "HIT", "RadianceTransfer", "SHADOW_DEFAULTS", "SphereTrace",
-           "SunExtraction", "SunLight", "TRACE_DEFAULTS", "bake_transfer", "camera_rays", "envmap_labels", "envmap_lookup", "extract_sun",
-           "load_camera_path", "pack_fp16", "project_envmap", "read_envmap", "srgb_to_linear", "sun_direction", "sun_path", "sun_solid_angle",
-           "trace_sun_shadows", "trace_visibility", "unpack_fp16", "z_rotation"]
+__all__ = ["ALIVE", "CameraPath", "DaylightSky", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "FrameLighting", "HIT", "RadianceTransfer",
+           "SHADOW_DEFAULTS", "SphereTrace", "SunExtraction", "SunLight", "TRACE_DEFAULTS", "bake_transfer", "camera_rays", "envmap_labels",
+           "envmap_lookup", "extract_sun", "load_camera_path", "pack_fp16", "project_envmap", "read_envmap", "srgb_to_linear", "sun_direction",
+           "sun_path", "sun_solid_angle", "trace_sun_shadows", "trace_visibility", "unpack_fp16", "z_rotation"]

@@ -6,6 +6,7 @@ the numbers of train / eval latent rows and the latent dimension from its latent
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import math
 import os
 import sys
@@ -225,7 +226,7 @@ def main(argv=None) -> int:
     from PIL import Image
 
     from ..utils.checkpoints import load_reference_pipeline_state
-    from . import EnvironmentMap, camera_rays, load_camera_path, srgb_to_linear, z_rotation
+    from . import EnvironmentMap, FrameLighting, camera_rays, load_camera_path, srgb_to_linear, z_rotation
 
     t0 = time.perf_counter()
     cams = load_camera_path(args.camera_path)
@@ -278,7 +279,15 @@ def main(argv=None) -> int:
     frames = 0
     t_bake = t_relight = 0.0
     shadow_rays = exhausted = 0  # of --sun-shadows sdf
-    marched = {"sun_shadows": sun_shadows, "shadow_trace": shadow_trace}
+    # what every frame shares; a frame then differs by its rotation and, under an extracted sun, its sun: that sun turns with its sky, so
+    # the one given here only stands for "one sun" and every frame replaces it
+    sun = None
+    if extraction is not None:
+        sun = extraction.sun(None)
+    elif suns is not None:
+        sun = suns if args.sun_path is not None else suns[0]
+    marched = {} if sun is None else {"sun_shadows": sun_shadows, "shadow_trace": shadow_trace}  # (--extract-sun may have found none)
+    base = FrameLighting.of(None, envmap, sun, args.shadow_threshold, args.shadow_sigmoid_scale, daylight=daylight, **marched)
     t1 = time.perf_counter()
     for c in range(len(cams)):
         rb = camera_rays(cams, c, args.device)
@@ -292,27 +301,16 @@ def main(argv=None) -> int:
             baked = bake_transfer(model, rb, storage=args.transfer, chunk=args.chunk, camera_index=0)
             torch.cuda.synchronize()
             t_bake += time.perf_counter() - tb
-        sweep = None
-        if args.sun_path is not None:  # every frame of the sweep from one field pass per chunk
-            sweep = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[0], envmap=envmap, sun=suns,
-                                                            shadow_threshold=args.shadow_threshold,
-                                                            shadow_sigmoid_scale=args.shadow_sigmoid_scale, daylight=daylight, **marched)
-            out = sweep
-        for f in range(len(suns) if sweep is not None else args.turntable):
+        sweep = args.sun_path is not None  # every frame of the sweep from one field pass per chunk: rendered at its first frame
+        for f in range(len(suns) if sweep else args.turntable):
             shadow = None
-            if sweep is not None:
-                rgb = sweep["rgb"][f].clamp(0.0, 1.0).cpu().numpy()
-                shadow = sweep["shadow_map"][f]
-            elif suns is not None or extraction is not None:  # an extracted sun turns with its sky
-                out = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[f], envmap=envmap,
-                                                              sun=suns[0] if extraction is None else extraction.sun(rots[f]),
-                                                              shadow_threshold=args.shadow_threshold,
-                                                              shadow_sigmoid_scale=args.shadow_sigmoid_scale, daylight=daylight, **marched)
-                rgb = out["rgb"].clamp(0.0, 1.0).cpu().numpy()
-                shadow = out["shadow_map"]
-            elif args.transfer == "off":
-                out = model.get_outputs_for_camera_ray_bundle(rb, camera_index=0, chunk=args.chunk, rotation=rots[f], envmap=envmap)
-                rgb = out["rgb"].clamp(0.0, 1.0).cpu().numpy()
+            if args.transfer == "off":
+                if f == 0 or not sweep:
+                    turned = {} if extraction is None else {"suns": (extraction.sun(rots[f]),)}
+                    out = model.frames.render(rb, dataclasses.replace(base, rotation=rots[f], **turned), camera_index=0, chunk=args.chunk)
+                rgb = (out["rgb"][f] if sweep else out["rgb"]).clamp(0.0, 1.0).cpu().numpy()
+                if sun is not None:
+                    shadow = out["shadow_map"][f] if sweep else out["shadow_map"]
             else:
                 if f % LIGHTS_PER_PASS == 0:  # one pass over the transfer lights the next 8 frames
                     tr = time.perf_counter()
@@ -320,7 +318,7 @@ def main(argv=None) -> int:
                     batch = batch.clamp(0.0, 1.0).cpu().numpy()
                     t_relight += time.perf_counter() - tr
                 rgb = batch[f % LIGHTS_PER_PASS]
-            if shadow is not None and sun_shadows == "sdf" and (sweep is None or f == 0):  # (a sweep's status holds all its frames)
+            if shadow is not None and sun_shadows == "sdf" and (not sweep or f == 0):  # (a sweep's status holds all its frames)
                 from .shadows import EXHAUSTED
                 shadow_rays += out["shadow_status"].numel()
                 exhausted += int((out["shadow_status"] == EXHAUSTED).sum())

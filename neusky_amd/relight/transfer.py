@@ -12,6 +12,8 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
 
+from .lighting import FrameLighting, light_colours, ray_background
+
 STORAGES = ("fp32", "fp16")
 LIGHTS_PER_PASS = 8
 FRAME_KEYS = ("albedo", "accumulation", "depth", "p2p_dist", "normal")  # the light-independent outputs of the frame render
@@ -115,9 +117,8 @@ class RadianceTransfer:
 
     # ------------------------------------------------------------------ relighting
     def _light(self, model, envmap, cam: int, rotation: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(L [D, 3], bg [R, 3]) of one light: the frame render's own constructions (models/frame.py), the latent background in blocks
+        """(L [D, 3], bg [R, 3]) of one light: the frame render's own constructions (lighting.py), the latent background in blocks
         of _BG_ROWS rays"""
-        from ..models.frame import light_colours, ray_background  # here, not at the top: models.frame imports this module
         L = light_colours(model, self.dirs, cam, rotation, envmap)
         if envmap is not None:
             from .envmap import envmap_lookup
@@ -184,7 +185,7 @@ def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Option
     dev = flat.origins.device
     runner = None
     try:
-        model.frames.begin(camera_index, bake=storage)
+        model.frames.begin(camera_index, FrameLighting.of(bake=storage))
         dirs = model.frames.active.dirs.clone()
         D = dirs.shape[0]
         T = torch.empty(R, D, 3, dtype=dtype, device=dev)

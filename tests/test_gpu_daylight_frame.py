@@ -16,7 +16,8 @@ import torch
 import daylight_cpu as DC
 import sun_cpu as SC
 import transfer_cpu as TC
-from util_step import randomise, small_pipeline_config
+from util_frames import frame_scene
+from util_step import randomise
 from neusky_amd.relight import DaylightSky, EnvironmentMap
 from neusky_amd.relight.sun import SunLight
 
@@ -32,21 +33,8 @@ SUN_KEYS = ("rgb", "lin", "shadow_map", "shadow_difference")
 
 @pytest.fixture(scope="module")
 def scene():
-    torch.manual_seed(0)
-    pipe = small_pipeline_config(R=16, D=32, images=4).setup(device=DEV)
-    randomise(pipe)
+    pipe, rb = frame_scene(H, W, DEV)
     m = pipe.model
-    with torch.no_grad():
-        g = torch.Generator().manual_seed(3)
-        m.eval_illumination_latents.copy_((torch.randn(m.eval_illumination_latents.shape, generator=g) * 0.3).to(DEV))
-        m.eval_scale.copy_((1 + 0.2 * torch.rand(m.eval_scale.shape, generator=g)).to(DEV))
-    pipe.eval()
-    rb, _ = pipe.datamanager._rays(H * W, torch.Generator().manual_seed(5))
-    rb.origins = rb.origins[:1].expand(H * W, 3).contiguous().view(H, W, 3)  # one camera
-    rb.directions = rb.directions.view(H, W, 3)
-    rb.camera_indices = torch.ones(H, W, 1, dtype=torch.long, device=DEV)
-    rb.pixel_area = rb.pixel_area.view(H, W, 1)
-    rb.metadata = {"directions_norm": torch.ones(H, W, 1, device=DEV)}
     render = lambda **kw: m.get_outputs_for_camera_ray_bundle(rb, camera_index=1, chunk=CHUNK, **kw)  # noqa: E731
     env = EnvironmentMap((torch.rand(32, 64, 3, generator=torch.Generator().manual_seed(7)) ** 2 * 3.0).numpy(), "blender", exposure=0.8)
     plain = {"latent": {}, "envmap": {"envmap": env}, "envmap and sun": {"envmap": env, "sun": SunLight(130.0, 35.0, (2.0, 1.7, 1.2))}}

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 import envmap_sun_cpu as EC
-from util_step import randomise, small_pipeline_config
+from util_frames import frame_scene
+from util_step import randomise
 from neusky_amd.relight import EnvironmentMap, SunLight, extract_sun, project_envmap, z_rotation
 
 pytestmark = pytest.mark.gpu
@@ -26,21 +27,8 @@ ROLL = 11
 
 @pytest.fixture(scope="module")
 def scene():
-    torch.manual_seed(0)
-    pipe = small_pipeline_config(R=16, D=32, images=4).setup(device=DEV)
-    randomise(pipe)
+    pipe, rb = frame_scene(H, W, DEV)
     m = pipe.model
-    with torch.no_grad():
-        g = torch.Generator().manual_seed(3)
-        m.eval_illumination_latents.copy_((torch.randn(m.eval_illumination_latents.shape, generator=g) * 0.3).to(DEV))
-        m.eval_scale.copy_((1 + 0.2 * torch.rand(m.eval_scale.shape, generator=g)).to(DEV))
-    pipe.eval()
-    rb, _ = pipe.datamanager._rays(H * W, torch.Generator().manual_seed(5))
-    rb.origins = rb.origins[:1].expand(H * W, 3).contiguous().view(H, W, 3)  # one camera
-    rb.directions = rb.directions.view(H, W, 3)
-    rb.camera_indices = torch.ones(H, W, 1, dtype=torch.long, device=DEV)
-    rb.pixel_area = rb.pixel_area.view(H, W, 1)
-    rb.metadata = {"directions_norm": torch.ones(H, W, 1, device=DEV)}
 
     def render(use_graph=True, **kw):
         return m.get_outputs_for_camera_ray_bundle(rb, camera_index=1, chunk=CHUNK, use_graph=use_graph, **kw)

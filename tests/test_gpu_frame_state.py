@@ -1,11 +1,12 @@
 """The frame render's state (models/frame.py: model.frames): a failure inside a frame leaves none active, the chunk-graph key is a function
-of the frame's parts only, a training forward ignores an active frame, and the runner cache evicts as documented.  The fixture is the one
+of the frame's parts only, a FrameLighting handed to the owner renders the frame of its keywords, a training forward ignores an active
+frame, and the runner cache evicts as documented.  The fixture is the one
 of the frame tests: 13 x 16 rays of one camera at chunk 64, three whole chunks and a padded one."""
 import pytest
 import torch
 
-from util_step import randomise, small_pipeline_config
-from neusky_amd.relight import EnvironmentMap, bake_transfer, z_rotation
+from util_frames import frame_scene
+from neusky_amd.relight import EnvironmentMap, FrameLighting, bake_transfer, z_rotation
 from neusky_amd.relight.sun import SunLight
 
 pytestmark = pytest.mark.gpu
@@ -16,21 +17,8 @@ SUN = SunLight(130.0, 35.0, (2.0, 1.7, 1.2))
 
 @pytest.fixture(scope="module")
 def scene():
-    torch.manual_seed(0)
-    pipe = small_pipeline_config(R=16, D=32, images=4).setup(device=DEV)
-    randomise(pipe)
+    pipe, rb = frame_scene(H, W, DEV)
     m = pipe.model
-    with torch.no_grad():
-        g = torch.Generator().manual_seed(3)
-        m.eval_illumination_latents.copy_((torch.randn(m.eval_illumination_latents.shape, generator=g) * 0.3).to(DEV))
-        m.eval_scale.copy_((1 + 0.2 * torch.rand(m.eval_scale.shape, generator=g)).to(DEV))
-    pipe.eval()
-    rb, _ = pipe.datamanager._rays(H * W, torch.Generator().manual_seed(5))
-    rb.origins = rb.origins[:1].expand(H * W, 3).contiguous().view(H, W, 3)  # one camera
-    rb.directions = rb.directions.view(H, W, 3)
-    rb.camera_indices = torch.ones(H, W, 1, dtype=torch.long, device=DEV)
-    rb.pixel_area = rb.pixel_area.view(H, W, 1)
-    rb.metadata = {"directions_norm": torch.ones(H, W, 1, device=DEV)}
     render = lambda chunk=CHUNK, **kw: m.get_outputs_for_camera_ray_bundle(rb, camera_index=1, chunk=chunk, **kw)  # noqa: E731
     return pipe, rb, render
 
@@ -103,6 +91,21 @@ def test_the_key_is_a_function_of_the_frames_parts_only(scene):
         assert key(1, sun=SUN, shadow_sigmoid_scale=2.0 * m.sigmoid_scale)[0] == (sky_key, "sun", 1, 2.0 * m.sigmoid_scale)
         assert key(1, None, env, SUN)[0] == (e0, "sun", 1, float(m.sigmoid_scale))
     assert f.active is None
+
+
+@pytest.mark.parametrize("keywords", [{}, {"sun": SUN}, {"sun": SUN, "sun_shadows": "sdf", "shadow_trace": {"steps": 16}}],
+                         ids=["plain", "sun", "sdf shadows"])
+def test_a_frame_lighting_renders_the_frame_of_its_keywords(scene, keywords):
+    pipe, rb, render = scene
+    m = pipe.model
+    ref = {k: v.clone() for k, v in render(use_graph=True, **keywords).items()}
+    runners = dict(m.frames.runners)
+    out = m.frames.render(rb, FrameLighting.of(**keywords), camera_index=1, chunk=CHUNK, use_graph=True)
+    assert m.frames.runners.keys() == runners.keys() and all(m.frames.runners[k] is r for k, r in runners.items())
+    assert m.frames.active is None
+    assert out.keys() == ref.keys()
+    for k, v in ref.items():
+        assert out[k].dtype == v.dtype and out[k].shape == v.shape and torch.equal(out[k], v), k
 
 
 def test_training_ignores_an_active_frame(scene):

@@ -13,7 +13,8 @@ import torch
 
 import envmap_cpu as E
 from oracle import neusky_oracle as O
-from util_step import oracle_params, oracle_step_cfg, randomise, small_pipeline_config
+from util_frames import frame_scene
+from util_step import oracle_params, oracle_step_cfg, randomise
 from neusky_amd.relight import EnvironmentMap, z_rotation
 
 pytestmark = pytest.mark.gpu
@@ -23,22 +24,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def scene():
-    torch.manual_seed(0)
-    pipe = small_pipeline_config(R=16, D=32, images=4).setup(device=DEV)
-    randomise(pipe)
-    m = pipe.model
-    with torch.no_grad():
-        g = torch.Generator().manual_seed(3)
-        m.eval_illumination_latents.copy_((torch.randn(m.eval_illumination_latents.shape, generator=g) * 0.3).to(DEV))
-        m.eval_scale.copy_((1 + 0.2 * torch.rand(m.eval_scale.shape, generator=g)).to(DEV))
-    pipe.eval()
     H, W = 9, 13
-    rb, _ = pipe.datamanager._rays(H * W, torch.Generator().manual_seed(5))
-    rb.origins = rb.origins[:1].expand(H * W, 3).contiguous().view(H, W, 3)  # one camera
-    rb.directions = rb.directions.view(H, W, 3)
-    rb.camera_indices = torch.ones(H, W, 1, dtype=torch.long, device=DEV)
-    rb.pixel_area = rb.pixel_area.view(H, W, 1)
-    rb.metadata = {"directions_norm": torch.ones(H, W, 1, device=DEV)}
+    pipe, rb = frame_scene(H, W, DEV)
+    m = pipe.model
     # the latent-lit frame BEFORE any environment-map call
     before = m.get_outputs_for_camera_ray_bundle(rb, camera_index=1, chunk=32, use_graph=True)
     envmap = (torch.rand(32, 64, 3, generator=torch.Generator().manual_seed(7)) ** 2 * 3.0).numpy()

@@ -6,7 +6,8 @@ import pytest
 import torch
 
 from oracle import neusky_oracle as O
-from util_step import oracle_params, oracle_step_cfg, randomise, small_pipeline_config
+from util_frames import frame_scene
+from util_step import oracle_params, oracle_step_cfg
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -14,22 +15,8 @@ DEV = "cuda:0"
 
 @pytest.fixture(scope="module")
 def scene():
-    torch.manual_seed(0)
-    pipe = small_pipeline_config(R=16, D=32, images=4).setup(device=DEV)
-    randomise(pipe)
-    m = pipe.model
-    with torch.no_grad():
-        g = torch.Generator().manual_seed(3)
-        m.eval_illumination_latents.copy_((torch.randn(m.eval_illumination_latents.shape, generator=g) * 0.3).to(DEV))
-        m.eval_scale.copy_((1 + 0.2 * torch.rand(m.eval_scale.shape, generator=g)).to(DEV))
-    pipe.eval()
     H, W = 9, 13
-    rb, _ = pipe.datamanager._rays(H * W, torch.Generator().manual_seed(5))
-    rb.origins = rb.origins[:1].expand(H * W, 3).contiguous().view(H, W, 3)  # one camera
-    rb.directions = rb.directions.view(H, W, 3)
-    rb.camera_indices = torch.ones(H, W, 1, dtype=torch.long, device=DEV)
-    rb.pixel_area = rb.pixel_area.view(H, W, 1)
-    rb.metadata = {"directions_norm": torch.ones(H, W, 1, device=DEV)}
+    pipe, rb = frame_scene(H, W, DEV)
     return pipe, rb, (H, W)
 
 

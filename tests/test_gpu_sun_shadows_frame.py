@@ -217,6 +217,41 @@ def test_a_model_without_a_visibility_network_casts_a_shadow(scene):
     assert sdf["shadow_difference"].abs().max().item() == 0.0 and "shadow_status" in sdf and "shadow_status" not in ddf
 
 
+def test_a_model_built_without_a_visibility_field_renders_its_suns():
+    """not the flag flipped on a model that has a DDF: the pipeline is set up with no visibility field, so the model has neither
+    `sigmoid_scale` nor `visibility_threshold`, and a sun frame must not ask for them (randomise() would: the ball is grown from the
+    geometric initialisation instead)"""
+    torch.manual_seed(0)
+    cfg = small_pipeline_config(R=16, D=32, images=4, S=24)
+    cfg.visibility_field = None
+    cfg.model.use_visibility = False
+    pipe = cfg.setup(device=DEV)
+    grow_the_ball(pipe)
+    m = pipe.model
+    assert m.visibility_field is None and not hasattr(m, "sigmoid_scale") and not hasattr(m, "visibility_threshold")
+    with torch.no_grad():
+        g = torch.Generator().manual_seed(3)
+        m.eval_illumination_latents.copy_((torch.randn(m.eval_illumination_latents.shape, generator=g) * 0.3).to(DEV))
+        m.eval_scale.copy_((1 + 0.2 * torch.rand(m.eval_scale.shape, generator=g)).to(DEV))
+    pipe.eval()
+    rb = camera_grid(8, 12, DEV)  # 96 rays at chunk 64: a whole chunk and a padded one
+    render = lambda **kw: m.get_outputs_for_camera_ray_bundle(rb, camera_index=1, chunk=64, **kw)  # noqa: E731
+    with torch.no_grad():
+        m.begin_frame(1, sun=SUN)
+        key = m.frames.active.key
+        m.end_frame()
+    assert key == ((1, None), "sun", 1, 0.0)
+    ddf = render(sun=SUN)
+    on = ddf["accumulation"] > 0.0
+    assert on.any() and torch.equal(ddf["shadow_map"], on.to(torch.float32))  # no DDF: every accumulating ray sees the sun
+    sdf = render(sun=[SUN, DARK], sun_shadows="sdf", shadow_trace=TRACE)
+    sky = render(sun=SUN, daylight=DaylightSky(), sun_shadows="sdf", shadow_trace=TRACE)
+    for out in (ddf, sdf, sky):
+        assert all(torch.isfinite(out[k]).all() for k in SUN_KEYS if k in out)
+    assert sdf["shadow_status"].shape == (2, 8, 12, 1) and sdf["shadow_difference"].abs().max().item() == 0.0
+    assert torch.equal(sky["shadow_map"], sdf["shadow_map"][0])  # the march does not depend on the sky
+
+
 def test_what_excludes_the_march_is_refused(scene):
     _, _, render, marched, _ = scene
     with pytest.raises(ValueError):
