@@ -929,6 +929,29 @@ int nsky_transfer_relight(const void* T, int32_t storage, const int32_t* exponen
                           int64_t R, int32_t D, int32_t K, float* rgb, float* lin, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A radiance transfer in a basis of the light directions (neusky_amd/relight/transfer_sh.py, csrc/transfer_sh.hip).  The relight above
+ * is linear in the light, so with a basis B [D, J] of the directions
+ *   C[r,j,c] = sum_d T[r,d,c] B[d,j];      sum_d T[r,d,c] L[d,c] = sum_j C[r,j,c] l[j,c]  with  l = B^T L
+ * for every light in the span of an orthonormal B (for any other light: the relight under its projection B B^T L), and a row keeps
+ * 3 J numbers in place of 3 D.  Both entries take any B: the real spherical harmonics are one choice, made in Python.
+ *   storage:  as above, for T and for C alike; C has row exponents of its own, by the same rule (a power of two, the row maximum of
+ *             |C[r]| 2^e in [0.5, 1), a row of zeros takes 0).
+ * nsky_transfer_project:       T [R][D][3] (with exponents [R] for fp16: what nsky_transfer_bake wrote), B [D,J] fp32  ->  rows
+ *                              [row0, row0 + R) of C [rows][J][3] in out_storage and, for fp16, of out_exponents [rows] (both are
+ *                              indexed by the row of C, so a chunk lands in a frame-sized buffer).  1 <= D <= 1024, 1 <= J <= 128.
+ *                              fp32 FMAs in the order of d, per row: an entry is within D 2^-24 sum_d |T B| of its definition (plus the
+ *                              rounding to fp16, 2^-11 of the row maximum), and a row's bits do not depend on the rows around it.
+ * nsky_transfer_relight_short: the contract of nsky_transfer_relight with C, J, lights [K,J,3] in place of T, D, lights [K,D,3], for
+ *                              rows of 3 J numbers: any J in 1..128, any K (passes of up to 8 lights, C read once per pass).  The sums
+ *                              are taken in fp64 and rounded once with the background.  C starts on a 16-byte boundary.
+ * Flat indices are int64.  No atomics and a fixed order: every output is bitwise repeatable.  Nothing is read on the host. */
+#define NSKY_TRANSFER_MAX_COEFFICIENTS 128
+int nsky_transfer_project(const void* T, int32_t storage, const int32_t* exponents, const float* B, int64_t R, int32_t D, int32_t J,
+                          int32_t out_storage, void* C, int64_t row0, int32_t* out_exponents, nsky_stream_t stream);
+int nsky_transfer_relight_short(const void* C, int32_t storage, const int32_t* exponents, const float* acc, const float* lights,
+                                const float* bg, int64_t R, int32_t J, int32_t K, float* rgb, float* lin, nsky_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * A directional sun on top of the hemisphere render (neusky_amd/relight/sun.py, csrc/sun.hip).  The frame render sees light as its D
  * directions, one cell of which covers 4 pi / D sr; a sun (6.8e-5 sr) is one direction of its own, with one DDF shadow query per ray.
  *   direction:  the unit vector TOWARDS the sun, z up: s = (cos az cos el, sin az cos el, sin el), azimuth and elevation in degrees.

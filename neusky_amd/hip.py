@@ -1367,6 +1367,47 @@ def transfer_relight(T, exponents, acc, lights, bg, rgb, lin=None):
                             stream_ptr()), "nsky_transfer_relight")
 
 
+# ---- a radiance transfer in a basis of the light directions (relight/transfer_sh.py, csrc/transfer_sh.hip)
+TRANSFER_MAX_COEFFICIENTS = 128  # NSKY_TRANSFER_MAX_COEFFICIENTS
+_transfer_project = _sig("nsky_transfer_project", C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
+_transfer_relight_short = _sig("nsky_transfer_relight_short", C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                               C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def transfer_project(T, exponents, basis, coeffs, row0: int = 0, coeff_exponents=None):
+    """T: fp32 or fp16 [R, D, 3] (+ exponents int32 [R]); basis: fp32 [D, J] -> rows [row0, row0 + R) of coeffs (fp32 or fp16
+    [rows, J, 3]) and, for fp16, of coeff_exponents (int32 [rows]): coeffs[row0 + r, j, c] = sum_d T[r, d, c] basis[d, j]"""
+    R, D, _ = T.shape
+    J = basis.shape[1]
+    if not 1 <= J <= TRANSFER_MAX_COEFFICIENTS or not 1 <= D <= TRANSFER_MAX_DIRECTIONS:
+        raise ValueError(f"a projection takes 1..{TRANSFER_MAX_DIRECTIONS} directions onto 1..{TRANSFER_MAX_COEFFICIENTS} coefficients, not "
+                         f"{D} onto {J}")
+    if coeffs.dim() != 3 or tuple(coeffs.shape[1:]) != (J, 3) or not 0 <= row0 <= coeffs.shape[0] - R:
+        raise ValueError(f"rows [{row0}, {row0 + R}) of coefficients shaped {tuple(coeffs.shape)} for J = {J}")
+    assert T.shape[2] == 3 and basis.shape == (D, J) and basis.dtype == torch.float32
+    assert exponents is None or exponents.shape[0] == R
+    assert coeff_exponents is None or coeff_exponents.reshape(-1).shape[0] == coeffs.shape[0]
+    check(_transfer_project(_c(T), _transfer_storage(T, exponents), _c(exponents), _c(basis), R, D, J,
+                            _transfer_storage(coeffs, coeff_exponents), _c(coeffs), row0, _c(coeff_exponents), stream_ptr()),
+          "nsky_transfer_project")
+
+
+def transfer_relight_short(coeffs, exponents, acc, lights, bg, rgb, lin=None):
+    """transfer_relight for rows of coefficients: coeffs: fp32 or fp16 [R, J, 3] (+ exponents int32 [R]), any J in 1..128; lights: fp32
+    [K, J, 3]; bg: fp32 [K, R, 3] -> rgb [K, R, 3] (sRGB, clamped) and, if given, lin [K, R, 3]"""
+    R, J, _ = coeffs.shape
+    K = lights.shape[0]
+    if not 1 <= J <= TRANSFER_MAX_COEFFICIENTS:
+        raise ValueError(f"rows of 1..{TRANSFER_MAX_COEFFICIENTS} coefficients, not {J}")
+    assert lights.shape == (K, J, 3) and bg.shape == (K, R, 3) and rgb.shape == (K, R, 3) and acc.shape[0] == R
+    assert lin is None or lin.shape == (K, R, 3)
+    assert all(t.dtype == torch.float32 for t in (acc, lights, bg, rgb)) and (lin is None or lin.dtype == torch.float32)
+    assert exponents is None or exponents.shape[0] == R
+    check(_transfer_relight_short(_c(coeffs), _transfer_storage(coeffs, exponents), _c(exponents), _c(acc), _c(lights), _c(bg), R, J, K,
+                                  _c(rgb), _c(lin), stream_ptr()), "nsky_transfer_relight_short")
+
+
 # ---- a directional sun on top of the hemisphere render (relight/sun.py, csrc/sun.hip)
 _sun_transfer = _sig("nsky_sun_transfer", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                      C.c_void_p)

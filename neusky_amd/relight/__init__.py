@@ -6,6 +6,10 @@ light directions and the bilinear sky lookup on the GPU (csrc/envmap.hip), and t
 `bake_transfer` / `RadianceTransfer` (transfer.py, csrc/transfer.hip): a camera's frame baked once into its radiance transfer, then relit
 under any number of lights at one streaming pass over the transfer each (`--transfer fp32|fp16` on the command line).
 
+`bake_transfer_sh` / `compress_transfer` / `SHRadianceTransfer` (transfer_sh.py, csrc/transfer_sh.hip): the same transfer kept as
+(order + 1)^2 spherical-harmonic coefficients per ray in place of D directions; every relight reports the `light_residual` of its light
+(`--sh-order N` with `--transfer`).
+
 `SunLight` / `sun_path` (sun.py, csrc/sun.hip): a directional sun on top of either sky, with one DDF shadow query per ray; the frame
 render with `sun=` returns the lit frame, its `shadow_map` and `shadow_difference` (`--sun-azimuth/--sun-elevation`, `--sun-path`).
 
@@ -29,8 +33,10 @@ from .lighting import FrameLighting
 from .shadows import ALIVE, ESCAPED, EXHAUSTED, HIT, SHADOW_DEFAULTS, TRACE_DEFAULTS, SphereTrace, trace_sun_shadows, trace_visibility
 from .sun import SunLight, sun_direction, sun_path, sun_solid_angle
 from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
+from .transfer_sh import SHRadianceTransfer, bake_transfer_sh, compress_transfer, light_basis, project_lights, sh_basis
 
 __all__ = ["ALIVE", "CameraPath", "DaylightSky", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "FrameLighting", "HIT", "RadianceTransfer",
-           "SHADOW_DEFAULTS", "SphereTrace", "SunExtraction", "SunLight", "TRACE_DEFAULTS", "bake_transfer", "camera_rays", "envmap_labels",
-           "envmap_lookup", "extract_sun", "load_camera_path", "pack_fp16", "project_envmap", "read_envmap", "srgb_to_linear", "sun_direction",
+           "SHADOW_DEFAULTS", "SHRadianceTransfer", "SphereTrace", "SunExtraction", "SunLight", "TRACE_DEFAULTS", "bake_transfer",
+           "bake_transfer_sh", "camera_rays", "compress_transfer", "envmap_labels", "envmap_lookup", "extract_sun", "light_basis",
+           "load_camera_path", "pack_fp16", "project_envmap", "project_lights", "read_envmap", "sh_basis", "srgb_to_linear", "sun_direction",
            "sun_path", "sun_solid_angle", "trace_sun_shadows", "trace_visibility", "unpack_fp16", "z_rotation"]

@@ -62,6 +62,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--chunk", type=int, default=4096)
     ap.add_argument("--transfer", default="off", choices=("off", "fp32", "fp16"),
                     help="bake each camera's radiance transfer once (stored as fp32 or scaled fp16) and relight its frames from it")
+    ap.add_argument("--sh-order", type=int, metavar="N",
+                    help="with --transfer: keep each camera's transfer as (N + 1)^2 spherical-harmonic coefficients per ray (N in 0..8) and "
+                         "relight from them; the last line reports the largest light_residual, the share of a frame's light the order left out")
     day = ap.add_argument_group("daylight", "with --daylight (Preetham, Shirley, Smits 1999)")
     day.add_argument("--turbidity", type=float, help="2 (very clear) .. 10 (hazy), default 3")
     day.add_argument("--sky-exposure", type=float, help="multiplies the model's sky (kcd / m^2) and its sun, default 0.1")
@@ -217,6 +220,11 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.turntable < 1:
         ap.error("--turntable must be >= 1")
+    if args.sh_order is not None:
+        if args.transfer == "off":
+            ap.error("--sh-order keeps a baked transfer in spherical harmonics: it needs --transfer fp32 or --transfer fp16")
+        if not 0 <= args.sh_order <= 8:
+            ap.error("--sh-order must lie in 0..8")
     daylight = parse_daylight(ap, args)
     suns = parse_suns(ap, args, daylight)
     sun_shadows, shadow_trace = parse_shadows(ap, args)
@@ -279,6 +287,7 @@ def main(argv=None) -> int:
     frames = 0
     t_bake = t_relight = 0.0
     shadow_rays = exhausted = 0  # of --sun-shadows sdf
+    sh_residual = None  # of --sh-order: the largest light_residual so far, a device tensor
     # what every frame shares; a frame then differs by its rotation and, under an extracted sun, its sun: that sun turns with its sky, so
     # the one given here only stands for "one sun" and every frame replaces it
     sun = None
@@ -298,7 +307,11 @@ def main(argv=None) -> int:
         if args.transfer != "off":
             from .transfer import LIGHTS_PER_PASS, bake_transfer
             tb = time.perf_counter()
-            baked = bake_transfer(model, rb, storage=args.transfer, chunk=args.chunk, camera_index=0)
+            if args.sh_order is None:
+                baked = bake_transfer(model, rb, storage=args.transfer, chunk=args.chunk, camera_index=0)
+            else:
+                from .transfer_sh import bake_transfer_sh
+                baked = bake_transfer_sh(model, rb, order=args.sh_order, storage=args.transfer, chunk=args.chunk, camera_index=0)
             torch.cuda.synchronize()
             t_bake += time.perf_counter() - tb
         sweep = args.sun_path is not None  # every frame of the sweep from one field pass per chunk: rendered at its first frame
@@ -314,8 +327,11 @@ def main(argv=None) -> int:
             else:
                 if f % LIGHTS_PER_PASS == 0:  # one pass over the transfer lights the next 8 frames
                     tr = time.perf_counter()
-                    batch = baked.relight(model, envmap=envmap, camera_index=0, rotations=rots[f:f + LIGHTS_PER_PASS])["rgb"]
-                    batch = batch.clamp(0.0, 1.0).cpu().numpy()
+                    relit = baked.relight(model, envmap=envmap, camera_index=0, rotations=rots[f:f + LIGHTS_PER_PASS])
+                    if args.sh_order is not None:  # kept on the device: read once, at the end
+                        worst = relit["light_residual"].max()
+                        sh_residual = worst if sh_residual is None else torch.maximum(sh_residual, worst)
+                    batch = relit["rgb"].clamp(0.0, 1.0).cpu().numpy()
                     t_relight += time.perf_counter() - tr
                 rgb = batch[f % LIGHTS_PER_PASS]
             if shadow is not None and sun_shadows == "sdf" and (not sweep or f == 0):  # (a sweep's status holds all its frames)
@@ -333,6 +349,9 @@ def main(argv=None) -> int:
     torch.cuda.synchronize()
     t_render = time.perf_counter() - t1
     transfer = "" if args.transfer == "off" else f" | transfer {args.transfer}: bake {t_bake:.3f}s relight {t_relight:.3f}s"
+    if args.sh_order is not None and sh_residual is not None:
+        transfer += (f" | sh order {args.sh_order} ({baked.C.shape[1]} coefficients, {baked.nbytes / 1e6:.1f} MB per camera): "
+                     f"largest light_residual {float(sh_residual):.3e}")
     print(f"{args.output_dir}: {frames} frames {cams.width}x{cams.height} | load {t_load:.3f}s render {t_render:.3f}s "
           f"({t_render / max(frames, 1):.3f}s/frame){transfer}")
     if sun_shadows == "sdf":

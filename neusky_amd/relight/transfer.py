@@ -60,6 +60,49 @@ def bake_rows(albedo, normals, weights, dirs, vis, storage: str) -> Dict[str, to
     return out
 
 
+def frame_light(model, envmap, dirs: torch.Tensor, ray_directions: torch.Tensor, cam: int,
+                rotation: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(L [D, 3], bg [R, 3]) of one light of a baked frame: the frame render's own constructions (lighting.py), the latent background
+    in blocks of _BG_ROWS rays"""
+    L = light_colours(model, dirs, cam, rotation, envmap)
+    if envmap is not None:
+        from .envmap import envmap_lookup
+        return L, envmap_lookup(envmap, ray_directions, rotation)
+    R = ray_directions.shape[0]
+    bg = torch.empty(R, 3, dtype=torch.float32, device=ray_directions.device)
+    for a in range(0, R, _BG_ROWS):
+        bg[a:a + _BG_ROWS] = ray_background(model, ray_directions[a:a + _BG_ROWS], cam, rotation)
+    return L, bg
+
+
+def relight_passes(baked, model, envmap, camera_index: Optional[int], rotations, exposure):
+    """What `relight` of a baked frame (a RadianceTransfer or an SHRadianceTransfer) shares: (single, K, passes), `passes` yielding
+    (k0, lights [kb, D, 3], bg [kb, R, 3]) for each pass of up to LIGHTS_PER_PASS lights."""
+    if envmap is None and model is None:
+        raise ValueError("relight needs an environment map, or a model whose illumination latent lights the frame")
+    cam = baked.camera_index if camera_index is None else int(camera_index)
+    single = rotations is None or (torch.is_tensor(rotations) and rotations.dim() == 2)
+    rots = [rotations] if single else list(rotations)
+    dev = baked.device
+    rots = [None if r is None else torch.as_tensor(r, dtype=torch.float32).to(dev).reshape(3, 3) for r in rots]
+    gain = None if exposure is None else torch.as_tensor(exposure, dtype=torch.float32).to(dev)
+    R, D = baked.ray_directions.shape[0], baked.dirs.shape[0]
+    K = len(rots)
+
+    def passes():
+        for k0 in range(0, K, LIGHTS_PER_PASS):
+            kb = min(LIGHTS_PER_PASS, K - k0)
+            lights = torch.empty(kb, D, 3, dtype=torch.float32, device=dev)
+            bg = torch.empty(kb, R, 3, dtype=torch.float32, device=dev)
+            for i in range(kb):
+                L, b = frame_light(model, envmap, baked.dirs, baked.ray_directions, cam, rots[k0 + i])
+                lights[i].copy_(L if gain is None else L * gain)
+                bg[i].copy_(b if gain is None else b * gain)
+            yield k0, lights, bg
+
+    return single, K, passes()
+
+
 class RadianceTransfer:
     """One baked frame: T [R, D, 3] (fp32, or fp16 with int32 row exponents [R]), acc [R], the bake's light directions [D, 3], the rays'
     directions [R, 3] (for the background), the frame shape, and the light-independent outputs of the frame render."""
@@ -117,17 +160,8 @@ class RadianceTransfer:
 
     # ------------------------------------------------------------------ relighting
     def _light(self, model, envmap, cam: int, rotation: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(L [D, 3], bg [R, 3]) of one light: the frame render's own constructions (lighting.py), the latent background in blocks
-        of _BG_ROWS rays"""
-        L = light_colours(model, self.dirs, cam, rotation, envmap)
-        if envmap is not None:
-            from .envmap import envmap_lookup
-            return L, envmap_lookup(envmap, self.ray_directions, rotation)
-        R = self.ray_directions.shape[0]
-        bg = torch.empty(R, 3, dtype=torch.float32, device=self.device)
-        for a in range(0, R, _BG_ROWS):
-            bg[a:a + _BG_ROWS] = ray_background(model, self.ray_directions[a:a + _BG_ROWS], cam, rotation)
-        return L, bg
+        """(L [D, 3], bg [R, 3]) of one light (frame_light)"""
+        return frame_light(model, envmap, self.dirs, self.ray_directions, cam, rotation)
 
     @torch.no_grad()
     def relight(self, model=None, *, envmap=None, camera_index: Optional[int] = None, rotations=None, exposure=None,
@@ -137,26 +171,12 @@ class RadianceTransfer:
         [*shape, 3]; a sequence or a [K, 3, 3] tensor -> rgb [K, *shape, 3], processed in batches of 8 lights per pass over T.
         exposure: a float or a 0-d tensor multiplying the light (on top of the map's own exposure).  Nothing synchronises with the host."""
         from .. import hip
-        if envmap is None and model is None:
-            raise ValueError("relight needs an environment map, or a model whose illumination latent lights the frame")
-        cam = self.camera_index if camera_index is None else int(camera_index)
-        single = rotations is None or (torch.is_tensor(rotations) and rotations.dim() == 2)
-        rots = [rotations] if single else list(rotations)
-        dev = self.device
-        rots = [None if r is None else torch.as_tensor(r, dtype=torch.float32).to(dev).reshape(3, 3) for r in rots]
-        gain = None if exposure is None else torch.as_tensor(exposure, dtype=torch.float32).to(dev)
-        R, D = self.T.shape[0], self.T.shape[1]
-        K = len(rots)
+        single, K, passes = relight_passes(self, model, envmap, camera_index, rotations, exposure)
+        R, dev = self.T.shape[0], self.device
         rgb = torch.empty(K, R, 3, dtype=torch.float32, device=dev)
         lin = torch.empty(K, R, 3, dtype=torch.float32, device=dev) if return_linear else None
-        for k0 in range(0, K, LIGHTS_PER_PASS):
-            kb = min(LIGHTS_PER_PASS, K - k0)
-            lights = torch.empty(kb, D, 3, dtype=torch.float32, device=dev)
-            bg = torch.empty(kb, R, 3, dtype=torch.float32, device=dev)
-            for i in range(kb):
-                L, b = self._light(model, envmap, cam, rots[k0 + i])
-                lights[i].copy_(L if gain is None else L * gain)
-                bg[i].copy_(b if gain is None else b * gain)
+        for k0, lights, bg in passes:
+            kb = lights.shape[0]
             hip.transfer_relight(self.T, self.exponents, self.acc, lights, bg, rgb[k0:k0 + kb], None if lin is None else lin[k0:k0 + kb])
         lead = () if single else (K,)
         out = {"rgb": rgb.view(*lead, *self.shape, 3)}
@@ -166,12 +186,11 @@ class RadianceTransfer:
         return out
 
 
-@torch.no_grad()
-def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Optional[int] = None, use_graph: bool = True,
-                  camera_index: Optional[int] = None) -> RadianceTransfer:
-    """Run the chunked eval forward of get_outputs_for_camera_ray_bundle once, with the renderer's inputs routed into the transfer bake
-    (the shading mode of this call's frame, models/frame.py: the plain frame render and its captured chunk graphs are untouched)."""
-    dtype = _storage_dtype(storage)
+def _bake_chunks(model, camera_ray_bundle, storage: str, chunk: Optional[int], use_graph: bool, camera_index: Optional[int], open_sink):
+    """The chunk loop of a bake (bake_transfer, transfer_sh.bake_transfer_sh): the frame's chunked eval forward with the renderer's inputs
+    routed into the transfer bake in `storage`.  open_sink(R, dirs, device) -> take(a, b, res), called after each chunk's forward with
+    the chunk's result (res["transfer"], res["transfer_exponents"]: rows [a, b) of the frame in their first b - a rows).
+    -> (shape, dirs, acc [R], ray directions [R, 3], outputs, camera_index)"""
     assert not model.training, "call model.eval() first"
     if not model.config.fix_test_illumination_directions:
         raise ValueError("bake_transfer needs fix_test_illumination_directions=True: a transfer is valid for the light directions it was "
@@ -187,19 +206,15 @@ def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Option
     try:
         model.frames.begin(camera_index, FrameLighting.of(bake=storage))
         dirs = model.frames.active.dirs.clone()
-        D = dirs.shape[0]
-        T = torch.empty(R, D, 3, dtype=dtype, device=dev)
+        take = open_sink(R, dirs, dev)
         acc = torch.empty(R, dtype=torch.float32, device=dev)
-        exps = torch.empty(R, dtype=torch.int32, device=dev) if storage == "fp16" else None
         outs = {k: [] for k in FRAME_KEYS}
         runner = model.frames.runner(chunk, flat, use_graph, cached=False)  # its own: a captured graph of this mode is never cached
         for a in range(0, R, chunk):
             b = min(a + chunk, R)
             res = runner.forward_rows(flat, a, b)
-            T[a:b].copy_(res["transfer"][:b - a])
+            take(a, b, res)
             acc[a:b].copy_(res["transfer_acc"][:b - a, 0])
-            if exps is not None:
-                exps[a:b].copy_(res["transfer_exponents"][:b - a, 0])
             for k in FRAME_KEYS:
                 outs[k].append(res[k][:b - a].clone())
     finally:
@@ -207,4 +222,26 @@ def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Option
         if runner is not None:
             runner.retire()
     outputs = {k: torch.cat(v).view(*shape, -1) for k, v in outs.items()}
-    return RadianceTransfer(T, exps, acc, dirs, flat.directions.reshape(R, 3).contiguous().clone(), shape, outputs, camera_index)
+    return shape, dirs, acc, flat.directions.reshape(R, 3).contiguous().clone(), outputs, camera_index
+
+
+@torch.no_grad()
+def bake_transfer(model, camera_ray_bundle, storage: str = "fp32", chunk: Optional[int] = None, use_graph: bool = True,
+                  camera_index: Optional[int] = None) -> RadianceTransfer:
+    """Run the chunked eval forward of get_outputs_for_camera_ray_bundle once, with the renderer's inputs routed into the transfer bake
+    (the shading mode of this call's frame, models/frame.py: the plain frame render and its captured chunk graphs are untouched)."""
+    dtype = _storage_dtype(storage)
+    kept = {}
+
+    def open_sink(R, dirs, dev):
+        T = kept["T"] = torch.empty(R, dirs.shape[0], 3, dtype=dtype, device=dev)
+        exps = kept["exps"] = torch.empty(R, dtype=torch.int32, device=dev) if storage == "fp16" else None
+
+        def take(a, b, res):
+            T[a:b].copy_(res["transfer"][:b - a])
+            if exps is not None:
+                exps[a:b].copy_(res["transfer_exponents"][:b - a, 0])
+        return take
+
+    shape, dirs, acc, rays, outputs, camera_index = _bake_chunks(model, camera_ray_bundle, storage, chunk, use_graph, camera_index, open_sink)
+    return RadianceTransfer(kept["T"], kept["exps"], acc, dirs, rays, shape, outputs, camera_index)
