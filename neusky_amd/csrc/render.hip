@@ -632,7 +632,7 @@ __global__ __launch_bounds__(256) void interlevel_kernel(const float* __restrict
     bins[i] = sb[(long)r * (n + 1) + i];
     if (BWD) { diff[i] = 0.0f; cover[i] = 0; }
   }
-  if (lane == 0) {  // sequential prefix sums (n <= 256), the order torch.cumsum uses on one row
+  if (lane == 0) {  // sequential prefix sums (n <= 1023, the host's LDS limit), the order torch.cumsum uses on one row
     float acc = 0.0f;
     cy[0] = 0.0f;
     for (int i = 0; i < n; ++i) {

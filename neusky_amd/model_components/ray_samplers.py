@@ -74,7 +74,7 @@ def weights_from_density(density: torch.Tensor, deltas: torch.Tensor) -> torch.T
     dd = deltas * density
     alphas = 1 - torch.exp(-dd)
     T = torch.cumsum(dd[..., :-1, :], dim=-2)
-    T = torch.exp(-torch.cat([torch.zeros_like(T[..., :1, :]), T], dim=-2))
+    T = torch.exp(-torch.cat([torch.zeros_like(dd[..., :1, :]), T], dim=-2))  # (dd, not T: with one bin T has no row to copy)
     return torch.nan_to_num(alphas * T)
 
 
