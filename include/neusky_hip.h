@@ -1072,6 +1072,73 @@ int nsky_sphere_trace_step(float* state, const float* sdf, const float* directio
                            int32_t iteration, int32_t steps, int32_t grace, float* points, nsky_stream_t stream);
 int nsky_sphere_trace_finish(const float* state, int64_t T, float* vis, int8_t* status, float* t, nsky_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A display transform: from a linear, high-dynamic-range image to a picture (neusky_amd/relight/display.py, csrc/display.hip):
+ * metered exposure, an optional bloom, a tone curve, the sRGB transfer function and the rounding to 8 bits, all on the device.
+ * Input: lin [K,H,W,3] fp32 (P = H W pixels per image), and optionally mask [K,H,W] fp32 (a frame's accumulation).
+ *
+ *   luminance:  Y = (0.2126f r + 0.7152f g) + 0.0722f b in fp32, every product and sum rounded once (no fused multiply-add): a float32
+ *               restatement has the same bits.
+ *   metered:    a pixel is metered when Y is finite, Y >= 2^-24, and (with a mask) mask > meter_mask_threshold.
+ *   bins:       bin = (bits(Y) >> 17) - 6592, clamped above to 3071: 3072 bins, 48 octaves from 2^-24 to 2^24 with 64 bins each (the 6
+ *               leading bits of the mantissa), values >= 2^24 in the last.  No logarithm decides a bin: the histogram is an
+ *               integer-exact function of the input.  2^-24 -> 0, its predecessor -> none, 1 -> 1536, 1 + 1/64 -> 1537,
+ *               nextafter(2, 0) -> 1599, nextafter(2^24, 0) -> 3071, 2^24 -> 3072, clamped to 3071.
+ *   histogram:  int64 counts [K][3072], or [1][3072] shared by the K images (a sequence metered as one).  Counts are ADDED to what the
+ *               histogram holds: the caller zeroes it, and several calls accumulate.
+ *   exposure:   with n metered pixels in a row of the histogram: a = floor(p_lo n), b = n - floor((1 - p_hi) n), in fp64 from the fp32
+ *               percentiles.  In sorted order bin j holds the positions [sum_{i<j} c_i, sum_{i<=j} c_i); c'_j is its overlap with [a, b);
+ *               m = sum_j c'_j ((j + 0.5) / 64 - 24) / (b - a), the mean over the kept pixels of their bins' centres, a centre being
+ *               exponent + mantissa fraction: the piecewise-linear log2, exact at powers of two and at most 0.0861 below log2;
+ *               E = key 2^(ev - m) in fp64, stored fp32; E = 1 when b <= a (nothing metered among it).  (j + 0.5) / 64 - 24 is a
+ *               multiple of 1 / 128, so the sum is an integer over 128 and exact in any order (the kernel forms it in int64); scaling
+ *               the image by 2^k rolls the histogram by 64 k bins and gives E 2^-k.  key = 0.18, percentiles (0.05, 0.95) and ev = 0
+ *               are the defaults of relight.DisplayTransform: design choices, not measurements.
+ *   bloom:      source s = max(E lin - threshold, 0) per channel (product and difference rounded once each; a NaN gives 0);
+ *               B = G_sigma * s, a separable Gaussian of radius r = ceil(3 sigma) <= 96 (0 < sigma <= 32 pixels) whose 2 r + 1 weights
+ *               exp(-t^2 / (2 sigma^2)) are normalised in fp64 on the host and rounded to fp32.  Outside the frame the source is zero.
+ *               Rows first, then columns, each pass an fp32 fmaf chain in tap order -r..r starting from 0.  Images never mix.
+ *   map:        x = min(max(E lin + strength B, 0), 2^60) (without bloom E lin alone, the product rounded once; with it
+ *               fma(strength, B, E lin); the max turns a NaN into 0; the min keeps the curves' polynomials finite, where every curve has
+ *               long reached its limit);  y = curve(x) per channel;  rgb = clamp(linear_to_sRGB(y), 0, 1), the function every
+ *               renderer here ends with;  rgb8 = rint(255 rgb), ties to even, as uint8.
+ *   curves:     CLAMP     y = x
+ *               REINHARD  y = x (1 + x / w^2) / (1 + x), white point w (default 4)
+ *               ACES      Narkowicz's fit: y = x (2.51 x + 0.03) / (x (2.43 x + 0.59) + 0.14)
+ *               HABLE     the Uncharted-2 operator h(v) = (v (A v + C B) + D E) / (v (A v + B) + D F) - E / F with
+ *                         A, B, C, D, E, F = 0.15, 0.50, 0.10, 0.20, 0.02, 0.30:  y = h(2 x) / h(11.2) (exposure bias 2, white 11.2).
+ *                         It is evaluated as h(v) = v (0.042 v + 0.005) / (0.3 (v (0.15 v + 0.5) + 0.06)), the same function with the
+ *                         constant terms cancelled on paper, whose value at 0 is exactly 0.
+ *               With CLAMP, E = 1 and no bloom, rgb has the bits of the `rgb` the frame's own renderer wrote from the same lin.
+ *   params:     fp32 [8] in device memory = key, ev, p_lo, p_hi, white point, bloom threshold, bloom strength, meter_mask_threshold:
+ *               with E, what may change between two frames; a captured graph replays with new values.  The curve, the blur's radius
+ *               and weights and the shapes are by value or by pointer.
+ * nsky_display_histogram: lin [K,P,3]; mask [K,P] or NULL; params  ->  hist (+=) [K][3072], or [1][3072] when `shared` != 0.  A workgroup
+ *                         counts in LDS (12 KB) over a grid-stride share of one image and adds its non-zero counts with 64-bit integer
+ *                         atomics: exact, and the same bits in every run.  K <= 65535.
+ * nsky_display_exposure:  hist [K][3072]; params  ->  E [K].  One workgroup per row.
+ * nsky_display_blur:      lin [K,H,W,3]; E [KE], KE = K or 1 (one exposure for all); params; weights [2 radius + 1]; 1 <= radius <= 96
+ *                         ->  B [K,H,W,3] through scratch [K,H,W,3].  LDS tiles with a halo of the radius; the radius may exceed the
+ *                         tile and the image.
+ * nsky_display_map:       lin [K,P,3]; B [K,P,3] or NULL (no bloom); E [KE]; params; curve  ->  rgb8 uint8 [K,P,3] and, unless NULL,
+ *                         rgb fp32 [K,P,3].  One pass; 16-byte accesses when P % 4 == 0 and the pointers allow it, the same results
+ *                         otherwise.
+ * Flat indices are int64.  The only atomics are integer adds: every output is bitwise repeatable.  Nothing is read on the host. */
+#define NSKY_DISPLAY_BINS 3072
+#define NSKY_DISPLAY_PARAMS 8
+#define NSKY_DISPLAY_MAX_RADIUS 96
+#define NSKY_DISPLAY_CLAMP 0
+#define NSKY_DISPLAY_REINHARD 1
+#define NSKY_DISPLAY_ACES 2
+#define NSKY_DISPLAY_HABLE 3
+int nsky_display_histogram(const float* lin, const float* mask, const float* params, int64_t P, int32_t K, int32_t shared, int64_t* hist,
+                           nsky_stream_t stream);
+int nsky_display_exposure(const int64_t* hist, const float* params, int32_t K, float* E, nsky_stream_t stream);
+int nsky_display_blur(const float* lin, const float* E, int32_t KE, const float* params, const float* weights, int32_t radius, int32_t K,
+                      int32_t H, int32_t W, float* scratch, float* B, nsky_stream_t stream);
+int nsky_display_map(const float* lin, const float* B, const float* E, int32_t KE, const float* params, int32_t curve, int64_t P, int32_t K,
+                     uint8_t* rgb8, float* rgb, nsky_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1529,3 +1529,69 @@ def sphere_trace_finish(state, vis, status, t):
     assert vis.numel() == T and t.numel() == T and status.numel() == T and status.dtype == torch.int8
     assert vis.dtype == torch.float32 and t.dtype == torch.float32 and all(x.is_contiguous() for x in (vis, status, t))
     check(_sphere_trace_finish(ptr(state), T, ptr(vis), ptr(status), ptr(t), stream_ptr()), "nsky_sphere_trace_finish")
+
+
+# ---- a display transform: metered exposure, bloom, tone curve, sRGB, 8 bits (relight/display.py, csrc/display.hip)
+DISPLAY_BINS, DISPLAY_PARAMS, DISPLAY_MAX_RADIUS = 3072, 8, 96  # NSKY_DISPLAY_BINS / _PARAMS / _MAX_RADIUS
+DISPLAY_CURVES = {"clamp": 0, "reinhard": 1, "aces": 2, "hable": 3}  # NSKY_DISPLAY_CLAMP ..
+_display_histogram = _sig("nsky_display_histogram", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                          C.c_void_p)
+_display_exposure = _sig("nsky_display_exposure", C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
+_display_blur = _sig("nsky_display_blur", C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
+_display_map = _sig("nsky_display_map", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
+                    C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def _display_image(lin):
+    if lin.dim() != 4 or lin.shape[3] != 3 or lin.dtype != torch.float32:
+        raise ValueError(f"a linear image is float32 [K, H, W, 3], got {lin.dtype} {tuple(lin.shape)}")
+    return lin.shape[0], lin.shape[1], lin.shape[2]
+
+
+def _display_params(params):
+    return ptr(_typed(params, torch.float32, DISPLAY_PARAMS))
+
+
+def display_histogram(lin, mask, params, hist):
+    """lin: fp32 [K, H, W, 3]; mask: fp32 [K, H, W] or None; params [8] (device) -> hist int64 [K, 3072], or [1, 3072] shared by the K
+    images; the counts are added to what it holds"""
+    K, H, W = _display_image(lin)
+    rows = hist.shape[0] if hist.dim() == 2 else -1
+    if rows not in (1, K) or hist.dtype != torch.int64 or hist.shape[1] != DISPLAY_BINS:
+        raise ValueError(f"a histogram is int64 [{K}, {DISPLAY_BINS}] or [1, {DISPLAY_BINS}], got {hist.dtype} {tuple(hist.shape)}")
+    check(_display_histogram(_c(lin), ptr(_typed(mask, torch.float32, K, H, W)), _display_params(params), H * W, K, int(rows == 1 and K > 1),
+                             _c(hist), stream_ptr()), "nsky_display_histogram")
+
+
+def display_exposure(hist, params, E):
+    """hist: int64 [K, 3072]; params [8] -> E fp32 [K]"""
+    K = hist.shape[0]
+    check(_display_exposure(ptr(_typed(hist, torch.int64, K, DISPLAY_BINS)), _display_params(params), K, ptr(_typed(E, torch.float32, K)),
+                            stream_ptr()), "nsky_display_exposure")
+
+
+def _display_exposures(E, K):
+    if E.dtype != torch.float32 or E.dim() != 1 or E.shape[0] not in (1, K) or not E.is_contiguous():
+        raise ValueError(f"the exposures are float32 [{K}] or [1], got {E.dtype} {tuple(E.shape)}")
+    return E.shape[0]
+
+
+def display_blur(lin, E, params, weights, scratch, B):
+    """lin: fp32 [K, H, W, 3]; E [K] or [1]; params [8]; weights fp32 [2 r + 1], 1 <= r <= 96 -> B [K, H, W, 3] through scratch (same shape)"""
+    K, H, W = _display_image(lin)
+    n = weights.numel()
+    if weights.dim() != 1 or n % 2 != 1 or not 1 <= n // 2 <= DISPLAY_MAX_RADIUS:
+        raise ValueError(f"2 r + 1 weights with r in 1..{DISPLAY_MAX_RADIUS}, got {tuple(weights.shape)}")
+    check(_display_blur(_c(lin), ptr(E), _display_exposures(E, K), _display_params(params), ptr(_typed(weights, torch.float32, n)), n // 2, K, H,
+                        W, ptr(_typed(scratch, torch.float32, K, H, W, 3)), ptr(_typed(B, torch.float32, K, H, W, 3)), stream_ptr()),
+          "nsky_display_blur")
+
+
+def display_map(lin, B, E, params, curve: str, rgb8, rgb=None):
+    """lin: fp32 [K, H, W, 3]; B: the bloom (same shape) or None; E [K] or [1]; params [8]; curve: a key of DISPLAY_CURVES -> rgb8 uint8
+    [K, H, W, 3] and, if given, rgb fp32 [K, H, W, 3]"""
+    K, H, W = _display_image(lin)
+    check(_display_map(_c(lin), ptr(_typed(B, torch.float32, K, H, W, 3)), ptr(E), _display_exposures(E, K), _display_params(params),
+                       DISPLAY_CURVES[curve], H * W, K, ptr(_typed(rgb8, torch.uint8, K, H, W, 3)), ptr(_typed(rgb, torch.float32, K, H, W, 3)),
+                       stream_ptr()), "nsky_display_map")

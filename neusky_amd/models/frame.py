@@ -49,7 +49,8 @@ class FrameLight:
     """the light of the active frame: directions [D, 3], the frame camera's colours at them [1, D, 3] and the upper-hemisphere subset, in
     static buffers; the camera and the (pinned) rotation of its latent; optionally an environment map, suns, a transfer-bake storage, a
     daylight sky (which takes the place of the latent's: `cols` is then not decoded and not read), a shadow march in place of the suns'
-    DDF queries"""
+    DDF queries; `linear`: a frame under the sky alone also keeps its linear image `lin` (a sun frame always does), for a display
+    transform"""
     dirs: torch.Tensor
     cols: torch.Tensor
     sel: torch.Tensor
@@ -61,6 +62,7 @@ class FrameLight:
     bake: Optional[str] = None
     daylight: Optional[FrameDaylight] = None
     trace: Optional[FrameTrace] = None
+    linear: bool = False
     key: tuple = field(init=False)
 
     def __post_init__(self, rotation_values):
@@ -68,7 +70,7 @@ class FrameLight:
         storage, shape and convention only, so a new rotation or exposure replays the chunk; a sun frame adds K and the sigmoid scale,
         so a new position, colour or threshold does; a daylight frame adds K once more and drops the camera, so a new turbidity,
         exposure, ground or camera does; a frame with marched shadows adds the march's length and leaving phase, so a new eps, bias or
-        angular diameter does."""
+        angular diameter does; a sky frame that keeps its linear image says so (its chunk has one more output)."""
         env = self.envmap
         key = (self.cam, rotation_values) if env is None else ("envmap", env.data.data_ptr(), tuple(env.data.shape), env.convention)
         if self.daylight is not None:  # no latent is read: one chunk graph serves every camera
@@ -81,6 +83,8 @@ class FrameLight:
             key = (key, "daylight", self.daylight.lights.shape[0])
         if self.trace is not None:
             key = (key, "sdf shadows", self.trace.steps, self.trace.grace)
+        if self.linear and self.shading == "sky":
+            key = (key, "linear")
         self.key = key
 
     @property
@@ -91,15 +95,28 @@ class FrameLight:
 def shade(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -> Dict[str, torch.Tensor]:
     """what the active frame's shading mode adds to a chunk's outputs: `rgb` under the sky alone; `rgb`, `lin`, `shadow_map` and
     `shadow_difference` with suns, under the frame's sky or a daylight sky of each sun's own; the transfer keys and no `rgb` for a bake
-    (no light enters)"""
+    (no light enters).  A sky frame asked for its linear image adds `lin`: what the renderer's kernel computes beside `rgb` and drops."""
     if light.shading == "sky":
-        return {"rgb": model.render_lambertian(so)}
+        return _sky_outputs(model, so) if light.linear else {"rgb": model.render_lambertian(so)}
     if light.shading in ("sun", "daylight"):
         return _sun_outputs(model, light.sun, so, ray_bundle, light.daylight, light.trace)
     fo = so["field_outputs"]
     visibility = so["visibility_dict"]["visibility"] if model.config.use_visibility else None
     return bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], so["weights"][..., 0], so["illumination_directions"],
                      visibility, light.bake)
+
+
+def _sky_outputs(model, so: Dict[str, Any]) -> Dict[str, torch.Tensor]:
+    """render_lambertian's kernel on the same inputs, keeping both of its outputs: rgb (the same bits) and lin [R, 3]"""
+    fo = so["field_outputs"]
+    a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
+    R, dev = a.shape[0], a.device
+    rgb, lin = torch.empty(R, 3, device=dev), torch.empty(R, 3, device=dev)
+    hip.hemi_composite_fwd(a, n, so["weights"][..., 0].contiguous(), so["illumination_directions"].contiguous(),
+                           so["hdr_illumination_colours"].contiguous(), so["cam_of_ray"],
+                           so["visibility_dict"]["visibility"].contiguous() if model.config.use_visibility else None,
+                           so["hdr_background_colours"].contiguous(), rgb, lin)
+    return {"rgb": rgb, "lin": lin}
 
 
 def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundle, daylight: Optional[FrameDaylight] = None,
@@ -175,8 +192,9 @@ class FrameRenderer:
             st = self.static[key] = allocate()
         return st
 
-    def begin(self, camera_index: int, lighting: FrameLighting) -> None:
-        """the device state of a frame lit by `lighting`, active until `end`: the rotation pinned, the static buffers filled"""
+    def begin(self, camera_index: int, lighting: FrameLighting, *, linear: bool = False) -> None:
+        """the device state of a frame lit by `lighting`, active until `end`: the rotation pinned, the static buffers filled.  linear: a
+        frame under the sky alone keeps its linear image `lin` too (it joins the chunk runner's key only when set)"""
         model = self.model
         rotation, envmap = lighting.rotation, lighting.envmap
         fixed = model.config.fix_test_illumination_directions
@@ -199,7 +217,7 @@ class FrameRenderer:
             sky.cols.copy_(cols)
         suns = self._suns(lighting)
         self.active = FrameLight(sky.dirs, sky.cols, sky.sel, cam, rotation, values, self._envmap(envmap, rotation), suns, lighting.bake,
-                                 self._daylight(lighting.daylight, sky.dirs, suns), self._trace(lighting.shadow_trace))
+                                 self._daylight(lighting.daylight, sky.dirs, suns), self._trace(lighting.shadow_trace), bool(linear))
 
     def _envmap(self, envmap, rotation) -> Optional[FrameEnvmap]:
         if envmap is None:
@@ -278,8 +296,11 @@ class FrameRenderer:
 
     @torch.no_grad()
     def render(self, camera_ray_bundle: RayBundle, lighting: FrameLighting, *, to_cpu: bool = False, camera_index: Optional[int] = None,
-               chunk: Optional[int] = None, use_graph: bool = True) -> Dict[str, torch.Tensor]:
-        """model.get_outputs_for_camera_ray_bundle, which documents the chunking and the outputs"""
+               chunk: Optional[int] = None, use_graph: bool = True, display=None) -> Dict[str, torch.Tensor]:
+        """model.get_outputs_for_camera_ray_bundle, which documents the chunking and the outputs.  display: a relight.DisplayTransform of
+        the frame's linear image, metered where the accumulation exceeds its meter_mask_threshold: adds display_rgb8, display_rgb and
+        display_exposure (and, to a frame under the sky alone, its `lin`); it runs on the assembled frame, after the chunks, so its
+        parameters touch no chunk graph."""
         model = self.model
         assert not model.training, "call model.eval() first"
         chunk = chunk or max(model.config.eval_num_rays_per_chunk, 4096)
@@ -288,10 +309,14 @@ class FrameRenderer:
         num_rays = flat.origins.shape[0]
         if camera_index is None:
             camera_index = int(flat.camera_indices.reshape(-1)[0]) if flat.camera_indices is not None else 0
-        self.begin(camera_index, lighting)
+        if display is not None and lighting.bake is not None:
+            raise ValueError("a bake takes the place of the shading: it has no image to display")
+        self.begin(camera_index, lighting, linear=display is not None)
         suns = lighting.suns
         sun_keys = list(SUN_KEYS + (SDF_SHADOW_KEYS if lighting.sun_shadows == "sdf" else ())) if suns is not None else []
         keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
+        if display is not None and suns is None:
+            keys.append("lin")
         out = {k: [] for k in keys}
         try:
             runner = self.runner(chunk, flat, use_graph)
@@ -307,7 +332,11 @@ class FrameRenderer:
             for k in sun_keys:
                 full = torch.cat(out.pop(k))
                 out[k] = [full.reshape(num_rays, K, -1).transpose(0, 1).reshape(*lead, *shape, -1)]
-        return {k: torch.cat(v).view(*shape, -1) if k not in sun_keys else v[0] for k, v in out.items()}
+        res = {k: torch.cat(v).view(*shape, -1) if k not in sun_keys else v[0] for k, v in out.items()}
+        if display is not None:
+            from ..relight.display import frame_display
+            res.update(frame_display(display, res["lin"].to(self.model.device), shape, res["accumulation"].to(self.model.device)))
+        return res
 
 
 class _ChunkRunner:

@@ -22,10 +22,14 @@ frame render with `daylight=` gives each of K suns its own sky from one field pa
 `trace_visibility` / `SphereTrace` (shadows.py, csrc/sphere_trace.hip): shadow rays sphere-traced through the SDF, with penumbrae; the
 frame render with `sun_shadows="sdf"` takes every sun's shadow from it instead of the DDF (`--sun-shadows sdf`).
 
+`DisplayTransform` (display.py, csrc/display.hip): from a linear image to a picture on the device: metered exposure, bloom, a tone curve,
+sRGB and 8 bits; the frame render and both transfers' `relight` take one as `display=` (`--tonemap`, `--auto-exposure`).
+
 `FrameLighting` (lighting.py): all of the above as the one value a frame's light is said in, with the rules between its options.
 """
 from .cameras import CameraPath, camera_rays, load_camera_path
 from .daylight import DaylightSky
+from .display import DisplayTransform, bloom_weights, frame_display
 from .envmap import EnvironmentMap, envmap_labels, envmap_lookup, project_envmap, z_rotation
 from .envmap_sun import SunExtraction, extract_sun
 from .io import read_envmap, srgb_to_linear
@@ -35,8 +39,8 @@ from .sun import SunLight, sun_direction, sun_path, sun_solid_angle
 from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
 from .transfer_sh import SHRadianceTransfer, bake_transfer_sh, compress_transfer, light_basis, project_lights, sh_basis
 
-__all__ = ["ALIVE", "CameraPath", "DaylightSky", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "FrameLighting", "HIT", "RadianceTransfer",
+__all__ = ["ALIVE", "CameraPath", "DaylightSky", "DisplayTransform", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "FrameLighting", "HIT", "RadianceTransfer",
            "SHADOW_DEFAULTS", "SHRadianceTransfer", "SphereTrace", "SunExtraction", "SunLight", "TRACE_DEFAULTS", "bake_transfer",
-           "bake_transfer_sh", "camera_rays", "compress_transfer", "envmap_labels", "envmap_lookup", "extract_sun", "light_basis",
+           "bake_transfer_sh", "bloom_weights", "camera_rays", "compress_transfer", "envmap_labels", "envmap_lookup", "extract_sun", "frame_display", "light_basis",
            "load_camera_path", "pack_fp16", "project_envmap", "project_lights", "read_envmap", "sh_basis", "srgb_to_linear", "sun_direction",
            "sun_path", "sun_solid_angle", "trace_sun_shadows", "trace_visibility", "unpack_fp16", "z_rotation"]

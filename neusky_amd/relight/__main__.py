@@ -95,8 +95,54 @@ def build_parser() -> argparse.ArgumentParser:
     sun.add_argument("--sun-search-radius", type=float, metavar="DEG", help="with --extract-sun: the cap about the peak (default 2.5)")
     sun.add_argument("--sun-min-peak-ratio", type=float, metavar="X",
                      help="with --extract-sun: the peak must be X times the sky around the cap (default 10)")
+    show = ap.add_argument_group("display", "from the linear image to the PNG on the device (relight.DisplayTransform): with any of these "
+                                 "the PNG is written from the transform's 8-bit output instead of the renderer's clipped one")
+    show.add_argument("--tonemap", choices=("clamp", "reinhard", "aces", "hable"), help="the tone curve; the flags below but the last need it")
+    show.add_argument("--auto-exposure", choices=("off", "frame", "sequence"),
+                      help="meter the exposure: per frame, or once for all frames of a camera's turntable or sun sweep (default off)")
+    show.add_argument("--exposure-key", type=float, metavar="KEY", help="with a metered exposure: what the mean luminance maps to (default 0.18)")
+    show.add_argument("--exposure-ev", type=float, metavar="EV", help="with a metered exposure: stops on top of it (default 0)")
+    show.add_argument("--meter-percentiles", type=float, nargs=2, metavar=("LO", "HI"),
+                      help="with a metered exposure: the share of the metered pixels, by luminance, whose mean counts (default 0.05 0.95)")
+    show.add_argument("--white-point", type=float, metavar="W", help="with --tonemap reinhard: the value that maps to 1 (default 4)")
+    show.add_argument("--bloom-sigma", type=float, metavar="PIXELS", help="add a Gaussian bloom of this width, at most 32 (default: none)")
+    show.add_argument("--bloom-threshold", type=float, metavar="T", help="with --bloom-sigma: what exceeds T after exposure blooms (default 1)")
+    show.add_argument("--bloom-strength", type=float, metavar="S", help="with --bloom-sigma: the bloom's factor (default 0.1)")
+    show.add_argument("--save-linear", action="store_true",
+                      help="also write frame_*.lin.npy: the unclipped linear image of each frame, before exposure")
     ap.add_argument("--device", default="cuda:0")
     return ap
+
+
+def parse_display(ap: argparse.ArgumentParser, args):
+    """the relight.DisplayTransform of --tonemap and its flags; the default transform (which reproduces the clipped image) for
+    --save-linear alone; None with none of them"""
+    from .display import DisplayTransform
+
+    metered = args.auto_exposure in ("frame", "sequence")
+    dependent = (("--auto-exposure", args.auto_exposure), ("--exposure-key", args.exposure_key), ("--exposure-ev", args.exposure_ev),
+                 ("--meter-percentiles", args.meter_percentiles), ("--white-point", args.white_point), ("--bloom-sigma", args.bloom_sigma),
+                 ("--bloom-threshold", args.bloom_threshold), ("--bloom-strength", args.bloom_strength))
+    if args.tonemap is None:
+        for flag, given in dependent:
+            if given is not None:
+                ap.error(f"{flag} needs --tonemap")
+        return DisplayTransform() if args.save_linear else None
+    for flag, given in dependent[1:4]:
+        if given is not None and not metered:
+            ap.error(f"{flag} shapes the metered exposure: it needs --auto-exposure frame or --auto-exposure sequence")
+    if args.white_point is not None and args.tonemap != "reinhard":
+        ap.error("--white-point is the white point of --tonemap reinhard")
+    for flag, given in dependent[6:]:
+        if given is not None and args.bloom_sigma is None:
+            ap.error(f"{flag} needs --bloom-sigma")
+    given = {"key": args.exposure_key, "ev": args.exposure_ev, "percentiles": args.meter_percentiles, "white": args.white_point,
+             "bloom_sigma": args.bloom_sigma, "bloom_threshold": args.bloom_threshold, "bloom_strength": args.bloom_strength}
+    try:
+        return DisplayTransform(curve=args.tonemap, exposure=args.auto_exposure if metered else 1.0,
+                                **{k: (tuple(v) if k == "percentiles" else v) for k, v in given.items() if v is not None})
+    except ValueError as e:
+        ap.error(str(e))
 
 
 def parse_daylight(ap: argparse.ArgumentParser, args):
@@ -228,6 +274,7 @@ def main(argv=None) -> int:
     daylight = parse_daylight(ap, args)
     suns = parse_suns(ap, args, daylight)
     sun_shadows, shadow_trace = parse_shadows(ap, args)
+    display = parse_display(ap, args)
 
     import numpy as np
     import torch
@@ -297,6 +344,19 @@ def main(argv=None) -> int:
         sun = suns if args.sun_path is not None else suns[0]
     marched = {} if sun is None else {"sun_shadows": sun_shadows, "shadow_trace": shadow_trace}  # (--extract-sun may have found none)
     base = FrameLighting.of(None, envmap, sun, args.shadow_threshold, args.shadow_sigmoid_scale, daylight=daylight, **marched)
+    # with a display transform a frame's PNG comes from its 8-bit output (the bytes are what the host reads).  Under "sequence" the frames of
+    # a camera share one exposure: frames that are not rendered together (a turntable) are metered into one histogram as they come and
+    # wait, as linear images on the device, for the exposure of the whole camera
+    exposures = []  # device tensors: read once, at the end
+    together = display is not None and display.exposure == "sequence" and args.sun_path is None
+    pending, hist = [], None
+    floats = display is None or args.save_hdr  # whether the host reads a frame's float image at all
+
+    def write_display(stem, rgb8, lin):
+        Image.fromarray(rgb8.cpu().numpy()).save(stem + ".png")
+        if args.save_linear:
+            np.save(stem + ".lin.npy", lin.cpu().numpy())
+
     t1 = time.perf_counter()
     for c in range(len(cams)):
         rb = camera_rays(cams, c, args.device)
@@ -320,32 +380,58 @@ def main(argv=None) -> int:
             if args.transfer == "off":
                 if f == 0 or not sweep:
                     turned = {} if extraction is None else {"suns": (extraction.sun(rots[f]),)}
-                    out = model.frames.render(rb, dataclasses.replace(base, rotation=rots[f], **turned), camera_index=0, chunk=args.chunk)
-                rgb = (out["rgb"][f] if sweep else out["rgb"]).clamp(0.0, 1.0).cpu().numpy()
+                    shown = {} if display is None else {"display": display}
+                    out = model.frames.render(rb, dataclasses.replace(base, rotation=rots[f], **turned), camera_index=0, chunk=args.chunk,
+                                              **shown)
+                    if display is not None and not together:
+                        exposures.append(out["display_exposure"])
+                if floats:
+                    rgb = (out["rgb"][f] if sweep else out["rgb"]).clamp(0.0, 1.0).cpu().numpy()
+                if display is not None:
+                    lin, rgb8, mask = (out[k][f] if sweep else out[k] for k in ("lin", "display_rgb8", "accumulation"))
                 if sun is not None:
                     shadow = out["shadow_map"][f] if sweep else out["shadow_map"]
             else:
                 if f % LIGHTS_PER_PASS == 0:  # one pass over the transfer lights the next 8 frames
                     tr = time.perf_counter()
-                    relit = baked.relight(model, envmap=envmap, camera_index=0, rotations=rots[f:f + LIGHTS_PER_PASS])
+                    shown = {} if display is None else {"display": display, "return_linear": True}
+                    relit = baked.relight(model, envmap=envmap, camera_index=0, rotations=rots[f:f + LIGHTS_PER_PASS], **shown)
+                    if display is not None and not together:
+                        exposures.append(relit["display_exposure"])
                     if args.sh_order is not None:  # kept on the device: read once, at the end
                         worst = relit["light_residual"].max()
                         sh_residual = worst if sh_residual is None else torch.maximum(sh_residual, worst)
-                    batch = relit["rgb"].clamp(0.0, 1.0).cpu().numpy()
+                    if floats:
+                        batch = relit["rgb"].clamp(0.0, 1.0).cpu().numpy()
                     t_relight += time.perf_counter() - tr
-                rgb = batch[f % LIGHTS_PER_PASS]
+                if floats:
+                    rgb = batch[f % LIGHTS_PER_PASS]
+                if display is not None:
+                    lin, rgb8, mask = relit["linear"][f % LIGHTS_PER_PASS], relit["display_rgb8"][f % LIGHTS_PER_PASS], baked.acc
             if shadow is not None and sun_shadows == "sdf" and (not sweep or f == 0):  # (a sweep's status holds all its frames)
                 from .shadows import EXHAUSTED
                 shadow_rays += out["shadow_status"].numel()
                 exhausted += int((out["shadow_status"] == EXHAUSTED).sum())
             stem = os.path.join(args.output_dir, f"frame_{c:04d}_{f:03d}")
-            Image.fromarray(np.round(rgb * 255.0).astype(np.uint8)).save(stem + ".png")
+            if display is None:
+                Image.fromarray(np.round(rgb * 255.0).astype(np.uint8)).save(stem + ".png")
+            elif together:
+                hist = display.luminance_histogram(lin, mask, out=hist)  # (one image: the first call makes the [1, 3072] the rest add to)
+                pending.append((stem, lin))
+            else:
+                write_display(stem, rgb8, lin)
             if args.save_hdr:
                 np.save(stem + ".npy", srgb_to_linear(rgb).astype(np.float32))
             if args.shadow_map and shadow is not None:  # (--extract-sun that found nothing has no shadow to write)
                 grey = np.round(shadow[..., 0].clamp(0.0, 1.0).cpu().numpy() * 255.0).astype(np.uint8)
                 Image.fromarray(grey, mode="L").save(os.path.join(args.output_dir, f"shadow_{c:04d}_{f:03d}.png"))
             frames += 1
+        if pending:
+            E = display.exposure_from_histogram(hist)
+            exposures.append(E)
+            for stem, lin in pending:
+                write_display(stem, display.apply(lin, exposure=E)["rgb8"], lin)
+            pending, hist = [], None
     torch.cuda.synchronize()
     t_render = time.perf_counter() - t1
     transfer = "" if args.transfer == "off" else f" | transfer {args.transfer}: bake {t_bake:.3f}s relight {t_relight:.3f}s"
@@ -354,6 +440,10 @@ def main(argv=None) -> int:
                      f"largest light_residual {float(sh_residual):.3e}")
     print(f"{args.output_dir}: {frames} frames {cams.width}x{cams.height} | load {t_load:.3f}s render {t_render:.3f}s "
           f"({t_render / max(frames, 1):.3f}s/frame){transfer}")
+    if display is not None and exposures:
+        E = torch.cat([e.reshape(-1) for e in exposures])
+        how = "set" if not display.metered else "metered per frame" if display.exposure == "frame" else "metered per camera"
+        print(f"display: tonemap {display.curve} | exposure {how}: smallest {float(E.min()):.4g} largest {float(E.max()):.4g}")
     if sun_shadows == "sdf":
         print(f"sdf shadows: {exhausted} of {shadow_rays} shadow rays ({100.0 * exhausted / max(shadow_rays, 1):.3f}%) were still marching after "
               f"{shadow_trace['steps']} steps (raise --shadow-steps if that is too many)")

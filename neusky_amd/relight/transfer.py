@@ -165,24 +165,29 @@ class RadianceTransfer:
 
     @torch.no_grad()
     def relight(self, model=None, *, envmap=None, camera_index: Optional[int] = None, rotations=None, exposure=None,
-                return_linear: bool = False) -> Dict[str, torch.Tensor]:
+                return_linear: bool = False, display=None) -> Dict[str, torch.Tensor]:
         """The frame under new light: the keys of get_outputs_for_camera_ray_bundle.  envmap: a relight.EnvironmentMap, else the
         illumination latent of `camera_index` (default: the bake's camera) of `model`.  rotations: None or one [3, 3] matrix -> rgb
         [*shape, 3]; a sequence or a [K, 3, 3] tensor -> rgb [K, *shape, 3], processed in batches of 8 lights per pass over T.
-        exposure: a float or a 0-d tensor multiplying the light (on top of the map's own exposure).  Nothing synchronises with the host."""
+        exposure: a float or a 0-d tensor multiplying the light (on top of the map's own exposure).  display: a relight.DisplayTransform
+        of the linear image, metered where acc exceeds its meter_mask_threshold: adds display_rgb8, display_rgb and display_exposure.
+        Nothing synchronises with the host."""
         from .. import hip
+        from .display import frame_display
         single, K, passes = relight_passes(self, model, envmap, camera_index, rotations, exposure)
         R, dev = self.T.shape[0], self.device
         rgb = torch.empty(K, R, 3, dtype=torch.float32, device=dev)
-        lin = torch.empty(K, R, 3, dtype=torch.float32, device=dev) if return_linear else None
+        lin = torch.empty(K, R, 3, dtype=torch.float32, device=dev) if return_linear or display is not None else None
         for k0, lights, bg in passes:
             kb = lights.shape[0]
             hip.transfer_relight(self.T, self.exponents, self.acc, lights, bg, rgb[k0:k0 + kb], None if lin is None else lin[k0:k0 + kb])
         lead = () if single else (K,)
         out = {"rgb": rgb.view(*lead, *self.shape, 3)}
-        if lin is not None:
+        if return_linear:
             out["linear"] = lin.view(*lead, *self.shape, 3)
         out.update(self.outputs)
+        if display is not None:
+            out.update(frame_display(display, lin.view(*lead, *self.shape, 3), self.shape, self.acc))
         return out
 
 

@@ -172,23 +172,27 @@ class SHRadianceTransfer:
 
     @torch.no_grad()
     def relight(self, model=None, *, envmap=None, camera_index: Optional[int] = None, rotations=None, exposure=None,
-                return_linear: bool = False) -> Dict[str, torch.Tensor]:
+                return_linear: bool = False, display=None) -> Dict[str, torch.Tensor]:
         """RadianceTransfer.relight for the frame in its basis: the same arguments and keys, the light projected onto the basis, plus
         "light_residual" ([K], or 0-d for a single light): |L - Q Q^T L|_F / |L|_F, a device tensor (nothing synchronises with the
-        host).  The frame is the dense relight under Q Q^T L: exact where the residual is zero."""
+        host).  The frame is the dense relight under Q Q^T L: exact where the residual is zero.  Its linear image may be negative where
+        the basis rings: a `display` transform takes such a value as 0, like a NaN, and does not meter it."""
+        from .display import frame_display
         single, K, passes = relight_passes(self, model, envmap, camera_index, rotations, exposure)
         R, dev = self.C.shape[0], self.device
         rgb = torch.empty(K, R, 3, dtype=torch.float32, device=dev)
-        lin = torch.empty(K, R, 3, dtype=torch.float32, device=dev) if return_linear else None
+        lin = torch.empty(K, R, 3, dtype=torch.float32, device=dev) if return_linear or display is not None else None
         residual = torch.empty(K, dtype=torch.float64, device=dev)
         for k0, lights, bg in passes:
             kb = lights.shape[0]
             residual[k0:k0 + kb] = self._relight_pass(lights, bg, rgb[k0:k0 + kb], None if lin is None else lin[k0:k0 + kb])
         lead = () if single else (K,)
         out = {"rgb": rgb.view(*lead, *self.shape, 3), "light_residual": residual[0] if single else residual}
-        if lin is not None:
+        if return_linear:
             out["linear"] = lin.view(*lead, *self.shape, 3)
         out.update(self.outputs)
+        if display is not None:
+            out.update(frame_display(display, lin.view(*lead, *self.shape, 3), self.shape, self.acc))
         return out
 
 
