@@ -1139,6 +1139,63 @@ int nsky_display_blur(const float* lin, const float* E, int32_t KE, const float*
 int nsky_display_map(const float* lin, const float* B, const float* E, int32_t KE, const float* params, int32_t curve, int64_t P, int32_t K,
                      uint8_t* rgb8, float* rgb, nsky_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Adaptive antialiasing of a frame (neusky_amd/relight/antialias.py, csrc/antialias.hip): the first pass of a frame takes one ray through
+ * every pixel centre; an edge mask marks the pixels whose neighbourhood differs, a second pass traces S - 1 further sub-pixel rays through
+ * each marked pixel, and a resolve averages the S samples in linear light.  A frame is H x W pixels, P = H W, pixel p = y W + x.
+ *
+ *   edge mask:  the neighbours q of pixel p are the up to 4 pixels left, right, above and below it inside the image.  With a the
+ *               accumulation, p is marked when for any q one of these holds, every product, sum and difference in fp32 rounded once (no
+ *               fused multiply-add), so that a float32 restatement in the same order has the same mask to the bit:
+ *                 accumulation  |a_p - a_q| > accumulation
+ *                 depth         a_p > covered, a_q > covered and |depth_p - depth_q| > depth * min(depth_p, depth_q)
+ *                 normal        a_p > covered, a_q > covered, n_p . n_p >= 1e-12f, n_q . n_q >= 1e-12f and, with d = n_p . n_q,
+ *                               d <= 0 or d * d < cos2 * ((n_p . n_p) * (n_q . n_q)): the angle between the rendered normals exceeds
+ *                               normal_deg, without a square root.  cos2 = cos^2(normal_deg), formed in fp64 on the host and rounded to
+ *                               fp32; a dot product is (x x' + y y') + z z'.  A normal shorter than 1e-6 switches the test off for
+ *                               its pairs.
+ *                 colour        for any of the K linear images, |Y_p - Y_q| > colour * max(Y_p, Y_q, 1e-4f), Y the display
+ *                               transform's luminance (0.2126f r + 0.7152f g) + 0.0722f b: a relative test, the same under any
+ *                               exposure.
+ *               Every test is symmetric in p and q: both pixels of a differing pair are marked, and no dilation follows.  A comparison
+ *               with a NaN is false (min and max return their other operand).  The thresholds are by value: nothing here is captured.
+ *               accumulation = 0.1, depth = 0.02, normal_deg = 15, colour = 0.1 and covered = 0.5 are the defaults of
+ *               relight.Antialias: design choices, not measurements.
+ *   rays:       from the frame's own bundle, no camera: D = directions * directions_norm (norm 1 when NULL), g_x = D(y, x + 1) - D(y, x)
+ *               (in the last column D(y, x) - D(y, x - 1); zero when W = 1), g_y the same along rows;
+ *               D' = (D + dx g_x) + dy g_y per component, fp32, every operation rounded once; directions_norm' = |D'| =
+ *               sqrt((x x + y y) + z z), directions' = D' / |D'|.  Origins, pixel_area and camera_indices are the pixel's.  The
+ *               un-normalised pinhole direction is affine in the pixel coordinate, so for a pinhole bundle this is the ray through
+ *               (x + 0.5 + dx, y + 0.5 + dy) up to fp32 rounding (3e-7 on a component at 1080p).  Ray (e, s) of the E pixels and S - 1
+ *               offsets is row e (S - 1) + s: pixel-major.
+ *   resolve:    F[k, pixels[e], c] = (F[k, pixels[e], c] + sum_s X[k, e, s, c]) / S, S = S1 + 1: the sum in fp64 in the order F, s = 0 ..
+ *               S1 - 1, the quotient in fp64, rounded to fp32 once.  With rgb, rgb[k, pixels[e], c] = clamp(linear_to_sRGB(.), 0, 1)
+ *               of the value written, the function every renderer here ends with.  Pixels not listed are not touched.
+ * nsky_aa_edge_mask:      depth [P], normal [P,3], accumulation [P]; lin: channel c of pixel p of image k at lin[k ls_k + p ls_p + c]
+ *                         (strides in floats; K >= 0; K = 0: no colour test, lin may be NULL)  ->  mask uint8 [P], 1 marked, 0 not.
+ *                         One thread per pixel.
+ * nsky_aa_subpixel_rays:  origins, directions [P,3]; norm [P] or NULL; pixel_area [P] or NULL; camera_indices int64 [P] or NULL;
+ *                         pixels int64 [E]; offsets [S1,2] = (dx, dy)  ->  out_origins, out_directions [E S1, 3], out_norm [E S1] and,
+ *                         where the input is given, out_pixel_area [E S1], out_camera_indices int64 [E S1].  One thread per ray.  A pixel
+ *                         index outside [0, P) is clamped into it (no access leaves the frame); the caller checks its own list.
+ * nsky_aa_resolve:        F (in place): element (k, p, c) at F[k fs_k + p fs_p + c]; X: element (k, e, s, c) at
+ *                         X[k xs_k + e xs_e + s xs_s + c]; rgb, or NULL: element (k, p, c) at rgb[k rs_k + p rs_p + c].  All strides are
+ *                         in floats and name the layout as it is: a frame of K suns is assembled from ray-major chunks and K leads only
+ *                         in its shape (a frame [P,K,C] seen as [K,P,C] has fs_k = C, fs_p = K C), and the second pass's chunks arrive
+ *                         ray-major, [E S1, K, C] (xs_k = C, xs_s = K C, xs_e = S1 K C): nothing is transposed for this kernel.
+ *                         pixels int64 [E], pairwise distinct (two entries naming one pixel would race).  One thread per (e, k, c).  An
+ *                         index outside [0, P) is skipped.
+ * Flat indices are int64.  No atomics: every output is bitwise repeatable.  Nothing is read on the host. */
+int nsky_aa_edge_mask(const float* depth, const float* normal, const float* accumulation, const float* lin, int64_t ls_k, int64_t ls_p,
+                      int32_t K, int32_t H, int32_t W, float t_accumulation, float t_depth, float cos2, float t_colour, float covered,
+                      uint8_t* mask, nsky_stream_t stream);
+int nsky_aa_subpixel_rays(const float* origins, const float* directions, const float* norm, const float* pixel_area,
+                          const int64_t* camera_indices, const int64_t* pixels, const float* offsets, int32_t H, int32_t W, int64_t E,
+                          int32_t S1, float* out_origins, float* out_directions, float* out_norm, float* out_pixel_area,
+                          int64_t* out_camera_indices, nsky_stream_t stream);
+int nsky_aa_resolve(float* F, int64_t fs_k, int64_t fs_p, const float* X, int64_t xs_k, int64_t xs_e, int64_t xs_s, const int64_t* pixels,
+                    int32_t K, int64_t P, int64_t E, int32_t S1, int32_t C, float* rgb, int64_t rs_k, int64_t rs_p, nsky_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1595,3 +1595,69 @@ def display_map(lin, B, E, params, curve: str, rgb8, rgb=None):
     check(_display_map(_c(lin), ptr(_typed(B, torch.float32, K, H, W, 3)), ptr(E), _display_exposures(E, K), _display_params(params),
                        DISPLAY_CURVES[curve], H * W, K, ptr(_typed(rgb8, torch.uint8, K, H, W, 3)), ptr(_typed(rgb, torch.float32, K, H, W, 3)),
                        stream_ptr()), "nsky_display_map")
+
+
+# ---- adaptive antialiasing of a frame: edge mask, sub-pixel rays, resolve (relight/antialias.py, csrc/antialias.hip)
+_aa_edge_mask = _sig("nsky_aa_edge_mask", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                     C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p)
+_aa_subpixel_rays = _sig("nsky_aa_subpixel_rays", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                         C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_aa_resolve = _sig("nsky_aa_resolve", C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                   C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
+
+
+def aa_edge_mask(depth, normal, accumulation, lin, t_accumulation: float, t_depth: float, cos2: float, t_colour: float, covered: float, mask):
+    """depth, accumulation: fp32 [H, W]; normal [H, W, 3]; lin: fp32 [K, H W, 3] through its strides (the last one 1), or None (no colour
+    test); the thresholds of the rule by value (cos2 = cos^2 of the normals' angle) -> mask uint8 [H, W]"""
+    if normal.dim() != 3 or normal.shape[2] != 3:
+        raise ValueError(f"the normals of a frame are float32 [H, W, 3], got {tuple(normal.shape)}")
+    H, W = normal.shape[0], normal.shape[1]
+    K = 0 if lin is None else lin.shape[0]
+    ls_k, ls_p = (0, 3) if lin is None else _aa_strided(lin, K, H * W, 3, "the linear images")
+    check(_aa_edge_mask(ptr(_typed(depth, torch.float32, H, W)), ptr(_typed(normal, torch.float32, H, W, 3)),
+                        ptr(_typed(accumulation, torch.float32, H, W)), ptr(lin), ls_k, ls_p, K, H, W, t_accumulation, t_depth, cos2, t_colour,
+                        covered, ptr(_typed(mask, torch.uint8, H, W)), stream_ptr()), "nsky_aa_edge_mask")
+
+
+def _aa_strided(t, K, P, Cn, what):
+    """the strides (k, p) of fp32 [K, P, C] whose channels are contiguous and whose elements are all distinct addresses"""
+    if t.dtype != torch.float32 or tuple(t.shape) != (K, P, Cn) or (Cn > 1 and t.stride(2) != 1):
+        raise ValueError(f"{what} are float32 [{K}, {P}, {Cn}] with contiguous channels, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    sk, sp = t.stride(0), t.stride(1)
+    k_major = (P == 1 or sp >= Cn) and (K == 1 or sk >= P * sp)
+    p_major = (K == 1 or sk >= Cn) and (P == 1 or sp >= K * sk)
+    if t.numel() and not (k_major or p_major):
+        raise ValueError(f"{what}: strides {t.stride()} of {tuple(t.shape)} overlap")
+    return sk, sp
+
+
+def aa_subpixel_rays(origins, directions, norm, pixel_area, camera_indices, H: int, W: int, pixels, offsets, out_origins, out_directions,
+                     out_norm, out_pixel_area=None, out_camera_indices=None):
+    """a frame's flat bundle: origins, directions fp32 [H W, 3]; norm, pixel_area fp32 [H W, 1] or None; camera_indices int64 [H W, 1] or
+    None; pixels int64 [E] (indices in [0, H W): the caller's to check); offsets fp32 [S1, 2] -> the same members for the E S1 rays"""
+    P, E, S1 = H * W, pixels.shape[0], offsets.shape[0]
+    N = E * S1
+    check(_aa_subpixel_rays(ptr(_typed(origins, torch.float32, P, 3)), ptr(_typed(directions, torch.float32, P, 3)),
+                            ptr(_typed(norm, torch.float32, P, 1)), ptr(_typed(pixel_area, torch.float32, P, 1)),
+                            ptr(_typed(camera_indices, torch.int64, P, 1)), ptr(_typed(pixels, torch.int64, E)),
+                            ptr(_typed(offsets, torch.float32, S1, 2)), H, W, E, S1, ptr(_typed(out_origins, torch.float32, N, 3)),
+                            ptr(_typed(out_directions, torch.float32, N, 3)), ptr(_typed(out_norm, torch.float32, N, 1)),
+                            ptr(_typed(out_pixel_area, torch.float32, N, 1)), ptr(_typed(out_camera_indices, torch.int64, N, 1)), stream_ptr()),
+          "nsky_aa_subpixel_rays")
+
+
+def aa_resolve(frame, samples, pixels, rgb=None):
+    """frame: fp32 [K, P, C] through its strides (the last one 1: K may lead in the shape alone), in place; samples: fp32 [K, E, S1, C]
+    through its strides (the last one 1); pixels: int64 [E], pairwise distinct; rgb: fp32 [K, P, C] through its strides, or None"""
+    if frame.dim() != 3 or samples.dim() != 4:
+        raise ValueError(f"a frame is [K, P, C] and its samples [K, E, S1, C], got {tuple(frame.shape)} and {tuple(samples.shape)}")
+    K, P, Cn = frame.shape
+    E, S1 = samples.shape[1], samples.shape[2]
+    if samples.dtype != torch.float32 or tuple(samples.shape) != (K, E, S1, Cn) or (samples.numel() > 0 and Cn > 1 and samples.stride(3) != 1):
+        raise ValueError(f"the samples are float32 [{K}, E, S1, {Cn}] with contiguous channels, got {samples.dtype} {tuple(samples.shape)} "
+                         f"strides {samples.stride()}")
+    xs_k, xs_e, xs_s = samples.stride(0), samples.stride(1), samples.stride(2)
+    fs_k, fs_p = _aa_strided(frame, K, P, Cn, "a frame's values")
+    rs_k, rs_p = (0, 0) if rgb is None else _aa_strided(rgb, K, P, Cn, "a frame's rgb")
+    check(_aa_resolve(ptr(frame), fs_k, fs_p, ptr(samples), xs_k, xs_e, xs_s, ptr(_typed(pixels, torch.int64, E)), K, P, E, S1, Cn, ptr(rgb),
+                      rs_k, rs_p, stream_ptr()), "nsky_aa_resolve")

@@ -296,11 +296,13 @@ class FrameRenderer:
 
     @torch.no_grad()
     def render(self, camera_ray_bundle: RayBundle, lighting: FrameLighting, *, to_cpu: bool = False, camera_index: Optional[int] = None,
-               chunk: Optional[int] = None, use_graph: bool = True, display=None) -> Dict[str, torch.Tensor]:
+               chunk: Optional[int] = None, use_graph: bool = True, display=None, antialias=None) -> Dict[str, torch.Tensor]:
         """model.get_outputs_for_camera_ray_bundle, which documents the chunking and the outputs.  display: a relight.DisplayTransform of
         the frame's linear image, metered where the accumulation exceeds its meter_mask_threshold: adds display_rgb8, display_rgb and
         display_exposure (and, to a frame under the sky alone, its `lin`); it runs on the assembled frame, after the chunks, so its
-        parameters touch no chunk graph."""
+        parameters touch no chunk graph.  antialias: a relight.Antialias: a second pass of sub-pixel rays through the pixels its edge rule
+        marks, through the same runner and inside the same begin / end, resolved into `lin` (and `rgb` from it), `albedo`, `accumulation`
+        and `shadow_map`; adds aa_mask and aa_fraction (and `lin` as `display` does); `display` then sees the resolved frame."""
         model = self.model
         assert not model.training, "call model.eval() first"
         chunk = chunk or max(model.config.eval_num_rays_per_chunk, 4096)
@@ -311,28 +313,42 @@ class FrameRenderer:
             camera_index = int(flat.camera_indices.reshape(-1)[0]) if flat.camera_indices is not None else 0
         if display is not None and lighting.bake is not None:
             raise ValueError("a bake takes the place of the shading: it has no image to display")
-        self.begin(camera_index, lighting, linear=display is not None)
+        if antialias is not None:
+            from ..relight.antialias import Antialias, antialias_frame
+            if not isinstance(antialias, Antialias):
+                raise ValueError(f"antialias: a relight.Antialias, got {antialias!r}")
+            if lighting.bake is not None:
+                raise ValueError("a bake takes the place of the shading: antialias has no image to resolve")
+            if len(shape) != 2:
+                raise ValueError(f"antialias reads a pixel's neighbours: it needs the ray bundle of a frame, [H, W], not {tuple(shape)}")
+        linear = display is not None or antialias is not None
+        self.begin(camera_index, lighting, linear=linear)
         suns = lighting.suns
         sun_keys = list(SUN_KEYS + (SDF_SHADOW_KEYS if lighting.sun_shadows == "sdf" else ())) if suns is not None else []
         keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
-        if display is not None and suns is None:
+        if linear and suns is None:
             keys.append("lin")
         out = {k: [] for k in keys}
+        early = to_cpu and antialias is None  # (the second pass resolves on the device: its frame goes to the host afterwards)
         try:
             runner = self.runner(chunk, flat, use_graph)
             for i in range(0, num_rays, chunk):
                 res = runner.run(flat, i, min(i + chunk, num_rays))
                 for k in keys:
-                    out[k].append(res[k].cpu() if to_cpu else res[k])
+                    out[k].append(res[k].cpu() if early else res[k])
+            if suns is not None:  # chunks are ray-major [n, K, ...]: K leads, and a single SunLight drops it
+                K = len(suns)
+                lead = () if lighting.single_sun else (K,)
+                for k in sun_keys:
+                    full = torch.cat(out.pop(k))
+                    out[k] = [full.reshape(num_rays, K, -1).transpose(0, 1).reshape(*lead, *shape, -1)]
+            res = {k: torch.cat(v).view(*shape, -1) if k not in sun_keys else v[0] for k, v in out.items()}
+            if antialias is not None:
+                res.update(antialias_frame(antialias, runner, flat, shape, res, 0 if suns is None else len(suns)))
+                if to_cpu:
+                    res = {k: v.cpu() if torch.is_tensor(v) else v for k, v in res.items()}
         finally:
             self.end()
-        if suns is not None:  # chunks are ray-major [n, K, ...]: K leads, and a single SunLight drops it
-            K = len(suns)
-            lead = () if lighting.single_sun else (K,)
-            for k in sun_keys:
-                full = torch.cat(out.pop(k))
-                out[k] = [full.reshape(num_rays, K, -1).transpose(0, 1).reshape(*lead, *shape, -1)]
-        res = {k: torch.cat(v).view(*shape, -1) if k not in sun_keys else v[0] for k, v in out.items()}
         if display is not None:
             from ..relight.display import frame_display
             res.update(frame_display(display, res["lin"].to(self.model.device), shape, res["accumulation"].to(self.model.device)))

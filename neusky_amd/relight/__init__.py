@@ -25,8 +25,12 @@ frame render with `sun_shadows="sdf"` takes every sun's shadow from it instead o
 `DisplayTransform` (display.py, csrc/display.hip): from a linear image to a picture on the device: metered exposure, bloom, a tone curve,
 sRGB and 8 bits; the frame render and both transfers' `relight` take one as `display=` (`--tonemap`, `--auto-exposure`).
 
+`Antialias` (antialias.py, csrc/antialias.hip): adaptive supersampling of a frame: an edge mask from the frame's own G-buffer and linear
+image, `subpixel_rays` through the marked pixels, a resolve in linear light; the frame render takes one as `antialias=` (`--antialias`).
+
 `FrameLighting` (lighting.py): all of the above as the one value a frame's light is said in, with the rules between its options.
 """
+from .antialias import Antialias, r2_offsets, subpixel_rays
 from .cameras import CameraPath, camera_rays, load_camera_path
 from .daylight import DaylightSky
 from .display import DisplayTransform, bloom_weights, frame_display
@@ -39,8 +43,8 @@ from .sun import SunLight, sun_direction, sun_path, sun_solid_angle
 from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
 from .transfer_sh import SHRadianceTransfer, bake_transfer_sh, compress_transfer, light_basis, project_lights, sh_basis
 
-__all__ = ["ALIVE", "CameraPath", "DaylightSky", "DisplayTransform", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "FrameLighting", "HIT", "RadianceTransfer",
+__all__ = ["ALIVE", "Antialias", "CameraPath", "DaylightSky", "DisplayTransform", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "FrameLighting", "HIT", "RadianceTransfer",
            "SHADOW_DEFAULTS", "SHRadianceTransfer", "SphereTrace", "SunExtraction", "SunLight", "TRACE_DEFAULTS", "bake_transfer",
            "bake_transfer_sh", "bloom_weights", "camera_rays", "compress_transfer", "envmap_labels", "envmap_lookup", "extract_sun", "frame_display", "light_basis",
-           "load_camera_path", "pack_fp16", "project_envmap", "project_lights", "read_envmap", "sh_basis", "srgb_to_linear", "sun_direction",
-           "sun_path", "sun_solid_angle", "trace_sun_shadows", "trace_visibility", "unpack_fp16", "z_rotation"]
+           "load_camera_path", "pack_fp16", "project_envmap", "project_lights", "r2_offsets", "read_envmap", "sh_basis", "srgb_to_linear", "sun_direction",
+           "subpixel_rays", "sun_path", "sun_solid_angle", "trace_sun_shadows", "trace_visibility", "unpack_fp16", "z_rotation"]

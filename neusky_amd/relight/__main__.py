@@ -110,8 +110,37 @@ def build_parser() -> argparse.ArgumentParser:
     show.add_argument("--bloom-strength", type=float, metavar="S", help="with --bloom-sigma: the bloom's factor (default 0.1)")
     show.add_argument("--save-linear", action="store_true",
                       help="also write frame_*.lin.npy: the unclipped linear image of each frame, before exposure")
+    aa = ap.add_argument_group("antialiasing", "adaptive supersampling (relight.Antialias): the pixels an edge rule marks in the frame's own "
+                               "depth, normals, accumulation and linear image take further sub-pixel rays, averaged in linear light")
+    aa.add_argument("--antialias", type=int, default=1, metavar="S",
+                    help="samples per marked pixel, the centre ray included (2..64); 1 (default): off.  The flags below need it above 1")
+    aa.add_argument("--aa-colour", type=float, metavar="T", help="mark a relative difference of luminance above T (default 0.1)")
+    aa.add_argument("--aa-depth", type=float, metavar="T", help="mark a relative difference of depth above T (default 0.02)")
+    aa.add_argument("--aa-normal-deg", type=float, metavar="DEG", help="mark an angle between normals above DEG (default 15)")
+    aa.add_argument("--aa-accumulation", type=float, metavar="T", help="mark a difference of accumulation above T (default 0.1)")
+    aa.add_argument("--aa-all", action="store_true", help="mark every pixel: plain supersampling")
+    aa.add_argument("--aa-mask", action="store_true", help="also write the marked pixels of each frame as aa_CCCC_FFF.png (0 or 255)")
     ap.add_argument("--device", default="cuda:0")
     return ap
+
+
+def parse_antialias(ap: argparse.ArgumentParser, args):
+    """the relight.Antialias of --antialias S and its flags; None for S = 1"""
+    from .antialias import Antialias
+
+    given = {"colour": args.aa_colour, "depth": args.aa_depth, "normal_deg": args.aa_normal_deg, "accumulation": args.aa_accumulation}
+    if args.antialias == 1:
+        flags = [("--aa-" + k.replace("_", "-"), v) for k, v in given.items()] + [("--aa-all", args.aa_all or None), ("--aa-mask", args.aa_mask or None)]
+        for flag, value in flags:
+            if value is not None:
+                ap.error(f"{flag} needs --antialias S with S > 1")
+        return None
+    if args.transfer != "off":
+        ap.error(f"--antialias {args.antialias} traces further rays through the marked pixels: it goes with --transfer off, not --transfer {args.transfer}")
+    try:
+        return Antialias(samples=args.antialias, every_pixel=args.aa_all, **{k: v for k, v in given.items() if v is not None})
+    except ValueError as e:
+        ap.error(str(e))
 
 
 def parse_display(ap: argparse.ArgumentParser, args):
@@ -275,6 +304,7 @@ def main(argv=None) -> int:
     suns = parse_suns(ap, args, daylight)
     sun_shadows, shadow_trace = parse_shadows(ap, args)
     display = parse_display(ap, args)
+    antialias = parse_antialias(ap, args)
 
     import numpy as np
     import torch
@@ -351,6 +381,7 @@ def main(argv=None) -> int:
     together = display is not None and display.exposure == "sequence" and args.sun_path is None
     pending, hist = [], None
     floats = display is None or args.save_hdr  # whether the host reads a frame's float image at all
+    marked = []  # of --antialias: every frame's share of marked pixels
 
     def write_display(stem, rgb8, lin):
         Image.fromarray(rgb8.cpu().numpy()).save(stem + ".png")
@@ -381,10 +412,14 @@ def main(argv=None) -> int:
                 if f == 0 or not sweep:
                     turned = {} if extraction is None else {"suns": (extraction.sun(rots[f]),)}
                     shown = {} if display is None else {"display": display}
+                    if antialias is not None:
+                        shown["antialias"] = antialias
                     out = model.frames.render(rb, dataclasses.replace(base, rotation=rots[f], **turned), camera_index=0, chunk=args.chunk,
                                               **shown)
                     if display is not None and not together:
                         exposures.append(out["display_exposure"])
+                    if antialias is not None:
+                        marked.append(out["aa_fraction"])
                 if floats:
                     rgb = (out["rgb"][f] if sweep else out["rgb"]).clamp(0.0, 1.0).cpu().numpy()
                 if display is not None:
@@ -425,6 +460,9 @@ def main(argv=None) -> int:
             if args.shadow_map and shadow is not None:  # (--extract-sun that found nothing has no shadow to write)
                 grey = np.round(shadow[..., 0].clamp(0.0, 1.0).cpu().numpy() * 255.0).astype(np.uint8)
                 Image.fromarray(grey, mode="L").save(os.path.join(args.output_dir, f"shadow_{c:04d}_{f:03d}.png"))
+            if args.aa_mask:  # (a sun sweep's frames come from one render: they share its mask)
+                grey = out["aa_mask"][..., 0].cpu().numpy() * np.uint8(255)
+                Image.fromarray(grey, mode="L").save(os.path.join(args.output_dir, f"aa_{c:04d}_{f:03d}.png"))
             frames += 1
         if pending:
             E = display.exposure_from_histogram(hist)
@@ -444,6 +482,9 @@ def main(argv=None) -> int:
         E = torch.cat([e.reshape(-1) for e in exposures])
         how = "set" if not display.metered else "metered per frame" if display.exposure == "frame" else "metered per camera"
         print(f"display: tonemap {display.curve} | exposure {how}: smallest {float(E.min()):.4g} largest {float(E.max()):.4g}")
+    if antialias is not None and marked:
+        how = "every pixel" if antialias.every_pixel else "the pixels its edge rule marks"
+        print(f"antialias: {antialias.samples} samples through {how} | share of marked pixels: smallest {min(marked):.4g} largest {max(marked):.4g}")
     if sun_shadows == "sdf":
         print(f"sdf shadows: {exhausted} of {shadow_rays} shadow rays ({100.0 * exhausted / max(shadow_rays, 1):.3f}%) were still marching after "
               f"{shadow_trace['steps']} steps (raise --shadow-steps if that is too many)")
