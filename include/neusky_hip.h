@@ -1073,6 +1073,68 @@ int nsky_sphere_trace_step(float* state, const float* sdf, const float* directio
 int nsky_sphere_trace_finish(const float* state, int64_t T, float* vis, int8_t* status, float* t, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Point and spot lights inside the scene, with sphere-traced shadows (neusky_amd/relight/lights.py, csrc/lights.hip, and the bounded
+ * step in csrc/sphere_trace.hip).  Every light above is at infinity; a lamp has a direction and a distance of its own at every sample,
+ * and its shadow ray ends at the lamp: geometry behind the lamp does not shadow it.
+ * A light:
+ *   p [3]          position, scene units
+ *   I [3]          intensity: the colour C a directional sun would need to light a facing surface as this lamp does from distance 1
+ *                  (irradiance units times scene units squared)
+ *   rho >= 0       source radius: a spherical source; 0 gives a hard shadow
+ *   clearance >= 0 the shadow ray ends this far in front of p, so a lamp placed in or on reconstructed geometry is not shadowed by its
+ *                  own post
+ *   min_distance > 0   the floor of the inverse-square law
+ *   a [3], cos_inner >= cos_outer   a spot cone: the unit axis (the way the lamp points) and the cosines of its two half-angles; an
+ *                  omnidirectional light has cos_inner = cos_outer = -1
+ * The defaults clearance = max(rho, 0.02), min_distance = max(rho, 0.01) and no cone are design choices, not measurements.
+ *   lights:     fp32 [L,16] in device memory; columns p (0..2), a (3..5), cos_inner, cos_outer, rho, clearance, min_distance, pad,
+ *               I (12..14), pad.  Only L is by value: a captured graph replays under new positions, colours, cones and radii.
+ *   transfer:   x = positions[r,s], the points the field was evaluated at.  v = p - x, q = |v|^2.  If q == 0 the term is 0, otherwise
+ *               u = v / sqrt(q);  cosine = clamp(<normals[r,s], u>, 0, 1) (the normals as given, as the sun takes them);  c = -<u, a>;
+ *               spot = 1 if c >= cos_inner, else 0 if c <= cos_outer, else h^2 (3 - 2 h) with h = (c - cos_outer) / (cos_inner -
+ *               cos_outer) (the tests in this order: the omnidirectional light never divides);  g = spot / max(q, min_distance^2);
+ *               t[l,r,c] = sum_s weights[r,s] albedo[r,s,c] cosine g
+ *   march:      the march rule above with two changes.  Step 1 becomes: if t >= t_end_i or |p| >= radius: status = ESCAPED (the ray
+ *               reached its light, or left the scene towards a light outside the collider).  Step 5 uses a tan_half_i of each ray's
+ *               own.  Ray i = l R + r starts at x = o + depth d + bias n^ (the fmas of nsky_sphere_trace_begin; a zero or non-finite
+ *               normal is replaced by the unit vector from o + depth d to the light).  v = p_l - x, len = |v|, s_i = v / len,
+ *               t_end_i = len - clearance_l, tan_half_i = rho_l / len: the cone from the start point to the source has radius
+ *               rho t / len at parameter t, so this is the closest-approach estimate for a sphere of radius rho.  len == 0 gives
+ *               s = (0,0,1), t_end = 0, tan_half = 0.  s, t_end and tan_half are formed in fp64 and rounded once.
+ *   composite:  V[l,r] = vis[l,r] (1 when vis is NULL) if acc[r] > acc_threshold[0], else 0;  E[r,c] = sum_l I[l,c] V[l,r] t[l,r,c] in
+ *               fp64, l ascending;  light_lin = fl32(E);  lin[k,r,c] = fl32(base[k,r,c] + E[r,c]), one rounding, for each of the Kb
+ *               base images (a frame under each of K suns; E == 0 leaves the base's bits);  rgb = clamp(linear_to_sRGB(lin), 0, 1).
+ *               The L lights add into one frame: they are not alternatives, as K suns are.  A lamp's own disc is not drawn.
+ * nsky_light_transfer:  positions, albedo, normals [R,S,3]; weights [R,S]; lights [L,16]  ->  out [L,R,3].  One wave per ray, the
+ *                       samples read once per pass of up to 8 lights; any S >= 1, any L >= 1.  The factor cosine g is formed in fp64
+ *                       from the fp32 inputs and rounded once, the sums are nsky_sun_transfer's: an entry is within
+ *                       (3 + S / 64 + 6) 2^-24 sum_s |weights albedo| cosine g of its definition.
+ * nsky_light_trace_begin:  origins, directions [R,3]; depth [R]; normals [R,3]; lights; params [6] (the march's block)  ->  state
+ *                       [6][T], points [T,3], ray_dirs [T,3], bounds [2][T] (t_end, tan_half), T = L R.  Rule step 1 of iteration 0
+ *                       is applied here.
+ * nsky_light_trace_begin_points:  starts [M,3]  ->  the same from explicit start points (T = L M).
+ * nsky_sphere_trace_step_bounded:  nsky_sphere_trace_step with a direction row of each ray's own (ray_dirs) and bounds.  16-byte
+ *                       accesses when T % 4 == 0 and state, sdf, ray_dirs, bounds and points are 16-byte aligned, else 4-byte ones;
+ *                       the results are the same.  nsky_sphere_trace_finish ends the march.
+ * nsky_lights_composite:  base [Kb,R,3] with base_stride = 3 R, or [R,3] with base_stride = 0; t [L,R,3]; vis [L,R] or NULL; acc [R];
+ *                       acc_threshold [1] (device memory); lights  ->  rgb, lin [Kb,R,3] (lin may be NULL) and, unless NULL, light_lin
+ *                       [R,3] and visibility [L,R] (= V).
+ * Flat indices are int64.  No atomics and a fixed reduction order: every output is bitwise repeatable.  Nothing is read on the host. */
+#define NSKY_LIGHT_FLOATS 16
+int nsky_light_transfer(const float* positions, const float* albedo, const float* normals, const float* weights, const float* lights,
+                        int64_t R, int32_t S, int32_t L, float* out, nsky_stream_t stream);
+int nsky_light_trace_begin(const float* origins, const float* directions, const float* depth, const float* normals, const float* lights,
+                           int64_t R, int32_t L, const float* params, float* state, float* points, float* ray_dirs, float* bounds,
+                           nsky_stream_t stream);
+int nsky_light_trace_begin_points(const float* starts, const float* lights, int64_t M, int32_t L, const float* params, float* state,
+                                  float* points, float* ray_dirs, float* bounds, nsky_stream_t stream);
+int nsky_sphere_trace_step_bounded(float* state, const float* sdf, const float* ray_dirs, const float* bounds, int64_t T, const float* params,
+                                   int32_t iteration, int32_t steps, int32_t grace, float* points, nsky_stream_t stream);
+int nsky_lights_composite(const float* base, int64_t base_stride, const float* t, const float* vis, const float* acc,
+                          const float* acc_threshold, const float* lights, int64_t R, int32_t L, int32_t Kb, float* rgb, float* lin,
+                          float* light_lin, float* visibility, nsky_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * A display transform: from a linear, high-dynamic-range image to a picture (neusky_amd/relight/display.py, csrc/display.hip):
  * metered exposure, an optional bloom, a tone curve, the sRGB transfer function and the rounding to 8 bits, all on the device.
  * Input: lin [K,H,W,3] fp32 (P = H W pixels per image), and optionally mask [K,H,W] fp32 (a frame's accumulation).

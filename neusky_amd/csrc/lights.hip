@@ -1,0 +1,254 @@
+// Point and spot lights inside the scene (neusky_amd/relight/lights.py).  Definitions: include/neusky_hip.h.
+//
+// A sun is one direction for all samples of all rays; a lamp has a direction and a distance of its own at every sample:
+//   t[l,r,c]   = sum_s w[r,s] alb[r,s,c] clamp(n[r,s].u, 0, 1) spot(-u.a_l) / max(|p_l - x[r,s]|^2, min_distance_l^2),  u = (p_l - x) / |p_l - x|
+//   lin[k,r,c] = base[k,r,c] + sum_l I[l,c] V[l,r] t[l,r,c]
+//   lights     fp32 [L][16] in device memory: p (0..2), a (3..5), cos_inner, cos_outer, rho, clearance, min_distance, -, I (12..14), -
+//   transfer   nsky_sun_transfer's shape: one wave per ray, lanes stride the samples, a sample (40 bytes) is read once per pass and meets
+//              up to 8 lights; the factor cosine spot / max(q, min_distance^2) is formed in fp64 (a square root and two divisions per
+//              sample and light) and rounded once; a lane keeps 24 fp32 sums, finished with wave_sum.
+//   begin      one thread per shadow ray i = l R + r: the start point as nsky_sphere_trace_begin forms it, then the ray's own direction,
+//              end and penumbra width in fp64, rounded once.  The march itself is nsky_sphere_trace_step_bounded (csrc/sphere_trace.hip).
+//   composite  one thread per (ray, channel): the L terms in fp64, l ascending, added to each of the Kb base images with one rounding.
+// No atomics, a fixed reduction order: two runs agree bit for bit.  Flat indices are 64-bit.  Nothing here synchronises with the host.
+#include <algorithm>
+
+#include "numerics.h"
+#include "../../include/neusky_hip.h"
+
+namespace {
+
+constexpr int kMaxLightsPerPass = 8;
+constexpr int kLightStride = NSKY_LIGHT_FLOATS;
+enum { L_P = 0, L_A = 3, L_COS_INNER = 6, L_COS_OUTER = 7, L_RHO = 8, L_CLEARANCE = 9, L_MIN_DISTANCE = 10, L_I = 12 };
+enum { P_RADIUS = 4, P_BIAS = 5 };  // of the march's parameter block (csrc/sphere_trace.hip)
+
+template <int LB>
+__global__ __launch_bounds__(256) void light_transfer_kernel(const float* __restrict__ positions, const float* __restrict__ albedo,
+                                                             const float* __restrict__ normals, const float* __restrict__ weights,
+                                                             const float* __restrict__ lights, int64_t R, int S, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double px[LB], py[LB], pz[LB], ax[LB], ay[LB], az[LB], ci[LB], co[LB], md2[LB];  // (uniform)
+#pragma unroll
+  for (int l = 0; l < LB; ++l) {
+    const float* q = lights + l * kLightStride;
+    px[l] = q[L_P], py[l] = q[L_P + 1], pz[l] = q[L_P + 2];
+    ax[l] = q[L_A], ay[l] = q[L_A + 1], az[l] = q[L_A + 2];
+    ci[l] = q[L_COS_INNER], co[l] = q[L_COS_OUTER];
+    md2[l] = (double)q[L_MIN_DISTANCE] * (double)q[L_MIN_DISTANCE];
+  }
+  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < R; r += (int64_t)gridDim.x * 4) {
+    float a[LB][3];
+#pragma unroll
+    for (int l = 0; l < LB; ++l) a[l][0] = a[l][1] = a[l][2] = 0.0f;
+    for (int s = lane; s < S; s += 64) {
+      const int64_t i = r * S + s, o = i * 3;
+      const float w = weights[i];
+      const float g0 = w * albedo[o], g1 = w * albedo[o + 1], g2 = w * albedo[o + 2];
+      const double nx = normals[o], ny = normals[o + 1], nz = normals[o + 2];
+      const double x = positions[o], y = positions[o + 1], z = positions[o + 2];
+#pragma unroll
+      for (int l = 0; l < LB; ++l) {
+        const double vx = px[l] - x, vy = py[l] - y, vz = pz[l] - z;
+        const double q = fma(vz, vz, fma(vy, vy, vx * vx));
+        float factor = 0.0f;
+        if (q > 0.0) {
+          const double inv = 1.0 / sqrt(q);
+          const double ux = vx * inv, uy = vy * inv, uz = vz * inv;
+          const double cosine = fmin(fmax(fma(nz, uz, fma(ny, uy, nx * ux)), 0.0), 1.0);
+          const double c = -fma(uz, az[l], fma(uy, ay[l], ux * ax[l]));
+          double spot = 1.0;
+          if (!(c >= ci[l])) {
+            if (c <= co[l]) {
+              spot = 0.0;
+            } else {
+              const double h = (c - co[l]) / (ci[l] - co[l]);
+              spot = h * h * (3.0 - 2.0 * h);
+            }
+          }
+          factor = (float)(cosine * spot / fmax(q, md2[l]));
+        }
+        a[l][0] = fmaf(g0, factor, a[l][0]);
+        a[l][1] = fmaf(g1, factor, a[l][1]);
+        a[l][2] = fmaf(g2, factor, a[l][2]);
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < LB; ++l) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) a[l][c] = wave_sum(a[l][c]);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int l = 0; l < LB; ++l) {
+        const int64_t o = ((int64_t)l * R + r) * 3;
+        out[o] = a[l][0];
+        out[o + 1] = a[l][1];
+        out[o + 2] = a[l][2];
+      }
+    }
+  }
+}
+
+template <int LB>
+void launch_transfer(hipStream_t st, const float* positions, const float* albedo, const float* normals, const float* weights,
+                     const float* lights, int64_t R, int S, float* out) {
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((R + 3) / 4, 256 * 8));
+  hipLaunchKernelGGL((light_transfer_kernel<LB>), dim3(grid), dim3(256), 0, st, positions, albedo, normals, weights, lights, R, S, out);
+}
+
+// o, d, n [R][3] and depth [R] (d, depth, n all NULL: o holds the start points); ray i = l R + r
+__global__ __launch_bounds__(256) void light_begin_kernel(const float* __restrict__ o, const float* __restrict__ d,
+                                                          const float* __restrict__ depth, const float* __restrict__ n,
+                                                          const float* __restrict__ lights, int64_t R, int64_t T,
+                                                          const float* __restrict__ params, float* __restrict__ state,
+                                                          float* __restrict__ points, float* __restrict__ ray_dirs,
+                                                          float* __restrict__ bounds) {
+  const float radius2 = params[P_RADIUS] * params[P_RADIUS], bias = params[P_BIAS];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < T; i += (int64_t)gridDim.x * 256) {
+    const int64_t l = i / R, r = (i - l * R) * 3;
+    const float* q = lights + l * kLightStride;
+    const double lx = q[L_P], ly = q[L_P + 1], lz = q[L_P + 2];
+    float x = o[r], y = o[r + 1], z = o[r + 2];
+    if (d) {
+      const float t = depth[i - l * R];
+      x = fmaf(t, d[r], x), y = fmaf(t, d[r + 1], y), z = fmaf(t, d[r + 2], z);
+      float nx = n[r], ny = n[r + 1], nz = n[r + 2];
+      const double nn = (double)nx * nx + (double)ny * ny + (double)nz * nz;
+      if (nn > 0.0 && nn < (double)INFINITY) {
+        const double inv = 1.0 / sqrt(nn);
+        nx = (float)(nx * inv), ny = (float)(ny * inv), nz = (float)(nz * inv);
+      } else {  // no rendered normal: lift the point towards the light
+        const double wx = lx - x, wy = ly - y, wz = lz - z;
+        const double ww = wx * wx + wy * wy + wz * wz;
+        if (ww > 0.0) {
+          const double inv = 1.0 / sqrt(ww);
+          nx = (float)(wx * inv), ny = (float)(wy * inv), nz = (float)(wz * inv);
+        } else {
+          nx = 0.0f, ny = 0.0f, nz = 1.0f;
+        }
+      }
+      x = fmaf(bias, nx, x), y = fmaf(bias, ny, y), z = fmaf(bias, nz, z);
+    }
+    const double vx = lx - x, vy = ly - y, vz = lz - z;
+    const double len = sqrt(vx * vx + vy * vy + vz * vz);
+    float sx = 0.0f, sy = 0.0f, sz = 1.0f, t_end = 0.0f, tan_half = 0.0f;
+    if (len > 0.0) {
+      sx = (float)(vx / len), sy = (float)(vy / len), sz = (float)(vz / len);
+      t_end = (float)(len - (double)q[L_CLEARANCE]);
+      tan_half = (float)((double)q[L_RHO] / len);
+    }
+    state[i] = x;
+    state[T + i] = y;
+    state[2 * T + i] = z;
+    state[3 * T + i] = 0.0f;
+    state[4 * T + i] = 1.0f;
+    // rule step 1 of iteration 0, t = 0: the ray is at its light already, or starts beyond the radius
+    const bool leaves = !(0.0f < t_end) || fmaf(z, z, fmaf(y, y, x * x)) >= radius2;
+    reinterpret_cast<int32_t*>(state)[5 * T + i] = leaves ? NSKY_TRACE_ESCAPED : NSKY_TRACE_ALIVE;
+    points[i * 3] = x, points[i * 3 + 1] = y, points[i * 3 + 2] = z;
+    ray_dirs[i * 3] = sx, ray_dirs[i * 3 + 1] = sy, ray_dirs[i * 3 + 2] = sz;
+    bounds[i] = t_end;
+    bounds[T + i] = tan_half;
+  }
+}
+
+// element j of [R][3]; base_stride: floats between two base images: 0 for one base [R][3] under all Kb outputs, R 3 for [Kb][R][3]
+__global__ __launch_bounds__(256) void lights_composite_kernel(const float* __restrict__ base, int64_t base_stride, const float* __restrict__ t,
+                                                               const float* __restrict__ vis, const float* __restrict__ acc,
+                                                               const float* __restrict__ acc_threshold, const float* __restrict__ lights,
+                                                               int64_t R, int L, int Kb, float* __restrict__ rgb, float* __restrict__ lin,
+                                                               float* __restrict__ light_lin, float* __restrict__ visibility) {
+  const int64_t n = R * 3;
+  const float thr = acc_threshold[0];
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
+    const int64_t r = j / 3;
+    const int c = (int)(j - r * 3);
+    const bool on = acc[r] > thr;
+    double e = 0.0;
+    for (int l = 0; l < L; ++l) {
+      const int64_t lr = (int64_t)l * R + r;
+      const float v = on ? (vis ? vis[lr] : 1.0f) : 0.0f;
+      e += (double)lights[l * kLightStride + L_I + c] * (double)v * (double)t[lr * 3 + c];
+      if (visibility && c == 0) visibility[lr] = v;
+    }
+    if (light_lin) light_lin[j] = (float)e;
+    for (int k = 0; k < Kb; ++k) {
+      const float b = base[(int64_t)k * base_stride + j];
+      const float x = e == 0.0 ? b : (float)((double)b + e);  // (no light: the base's bits, a -0 included)
+      const int64_t i = (int64_t)k * n + j;
+      if (lin) lin[i] = x;
+      rgb[i] = srgb_fwd(x);
+    }
+  }
+}
+
+unsigned grid_for(int64_t threads) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((threads + 255) / 256, 256 * 8)); }
+
+int launch_begin(const char* name, const float* o, const float* d, const float* depth, const float* n, const float* lights, int64_t R, int32_t L,
+                 const float* params, float* state, float* points, float* ray_dirs, float* bounds, nsky_stream_t stream) {
+  NSKY_CHECK_ARG(R >= 0 && L >= 0, "%s: R %ld, L %d", name, (long)R, (int)L);
+  const int64_t T = (int64_t)L * R;
+  if (T == 0) return NSKY_OK;
+  NSKY_CHECK_ARG(o && lights && params && state && points && ray_dirs && bounds,
+                 "%s: NULL origins / lights / params / state / points / ray_dirs / bounds", name);
+  hipLaunchKernelGGL(light_begin_kernel, dim3(grid_for(T)), dim3(256), 0, (hipStream_t)stream, o, d, depth, n, lights, R, T, params, state, points,
+                     ray_dirs, bounds);
+  NSKY_CHECK_LAUNCH(name);
+  return NSKY_OK;
+}
+
+}  // namespace
+
+extern "C" int nsky_light_transfer(const float* positions, const float* albedo, const float* normals, const float* weights,
+                                   const float* lights, int64_t R, int32_t S, int32_t L, float* out, nsky_stream_t stream) {
+  NSKY_CHECK_ARG(R >= 0 && S >= 1 && L >= 0, "nsky_light_transfer: R %ld, S %d, L %d", (long)R, (int)S, (int)L);
+  if (R == 0 || L == 0) return NSKY_OK;
+  NSKY_CHECK_ARG(positions && albedo && normals && weights && lights && out,
+                 "nsky_light_transfer: NULL positions / albedo / normals / weights / lights / out");
+  hipStream_t st = (hipStream_t)stream;
+  for (int l0 = 0; l0 < L; l0 += kMaxLightsPerPass) {
+    const float* q = lights + (int64_t)l0 * kLightStride;
+    float* o = out + (int64_t)l0 * R * 3;
+    switch (std::min(kMaxLightsPerPass, L - l0)) {
+      case 1: launch_transfer<1>(st, positions, albedo, normals, weights, q, R, S, o); break;
+      case 2: launch_transfer<2>(st, positions, albedo, normals, weights, q, R, S, o); break;
+      case 3: launch_transfer<3>(st, positions, albedo, normals, weights, q, R, S, o); break;
+      case 4: launch_transfer<4>(st, positions, albedo, normals, weights, q, R, S, o); break;
+      case 5: launch_transfer<5>(st, positions, albedo, normals, weights, q, R, S, o); break;
+      case 6: launch_transfer<6>(st, positions, albedo, normals, weights, q, R, S, o); break;
+      case 7: launch_transfer<7>(st, positions, albedo, normals, weights, q, R, S, o); break;
+      default: launch_transfer<8>(st, positions, albedo, normals, weights, q, R, S, o); break;
+    }
+    NSKY_CHECK_LAUNCH("nsky_light_transfer");
+  }
+  return NSKY_OK;
+}
+
+extern "C" int nsky_light_trace_begin(const float* origins, const float* directions, const float* depth, const float* normals,
+                                      const float* lights, int64_t R, int32_t L, const float* params, float* state, float* points,
+                                      float* ray_dirs, float* bounds, nsky_stream_t stream) {
+  NSKY_CHECK_ARG(R == 0 || L <= 0 || (directions && depth && normals), "nsky_light_trace_begin: NULL directions / depth / normals");
+  return launch_begin("nsky_light_trace_begin", origins, directions, depth, normals, lights, R, L, params, state, points, ray_dirs, bounds,
+                      stream);
+}
+
+extern "C" int nsky_light_trace_begin_points(const float* starts, const float* lights, int64_t M, int32_t L, const float* params, float* state,
+                                             float* points, float* ray_dirs, float* bounds, nsky_stream_t stream) {
+  return launch_begin("nsky_light_trace_begin_points", starts, nullptr, nullptr, nullptr, lights, M, L, params, state, points, ray_dirs, bounds,
+                      stream);
+}
+
+extern "C" int nsky_lights_composite(const float* base, int64_t base_stride, const float* t, const float* vis, const float* acc,
+                                     const float* acc_threshold, const float* lights, int64_t R, int32_t L, int32_t Kb, float* rgb, float* lin,
+                                     float* light_lin, float* visibility, nsky_stream_t stream) {
+  NSKY_CHECK_ARG(R >= 0 && L >= 0 && Kb >= 0 && (base_stride == 0 || base_stride == R * 3), "nsky_lights_composite: R %ld, L %d, Kb %d, stride %ld",
+                 (long)R, (int)L, (int)Kb, (long)base_stride);
+  if (R == 0 || Kb == 0) return NSKY_OK;
+  NSKY_CHECK_ARG(base && acc && acc_threshold && rgb && (L == 0 || (t && lights)),
+                 "nsky_lights_composite: NULL base / t / acc / acc_threshold / lights / rgb");
+  hipLaunchKernelGGL(lights_composite_kernel, dim3(grid_for(R * 3)), dim3(256), 0, (hipStream_t)stream, base, base_stride, t, vis, acc,
+                     acc_threshold, lights, R, (int)L, (int)Kb, rgb, lin, light_lin, visibility);
+  NSKY_CHECK_LAUNCH("nsky_lights_composite");
+  return NSKY_OK;
+}

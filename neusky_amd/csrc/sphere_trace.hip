@@ -8,6 +8,7 @@
 //   step       one thread per ray, or per 4 consecutive rays with 16-byte accesses when T % 4 == 0 and every pointer is 16-byte aligned
 //              (28 bytes read and 24 written per ray either way).  Every ray's point is rewritten as fma(t, s, x): a dead ray's t no
 //              longer changes, so it keeps its last point to the bit.
+//   step_bounded  the step of rays that end at a light (csrc/lights.hip): a direction, a t_end and a tan_half of each ray's own.
 //   finish     state -> vis = m, status (int8; ALIVE -> EXHAUSTED), t.
 // No atomics, no reductions: every output is bitwise repeatable.  Flat indices are 64-bit.  Nothing here synchronises with the host.
 #include <algorithm>
@@ -72,8 +73,12 @@ __global__ __launch_bounds__(256) void begin_kernel(const float* __restrict__ o,
 
 // rule steps 3-6 of round `it` for the sdf f at the ray's point, then the next point and rule step 1 of round it + 1 (no round follows
 // the last one: a ray alive after it is exhausted, wherever its next point would lie)
+// BOUNDED (a ray towards a light inside the scene, csrc/lights.hip): the ray also ends at t_end, and its penumbra has a width of its own
+template <bool BOUNDED = false>
 __device__ __forceinline__ void march_ray(const Params& P, float f, float x, float y, float z, float sx, float sy, float sz, int it, int steps,
-                                          int grace, float& t, float& m, int& flags, float& px, float& py, float& pz) {
+                                          int grace, float& t, float& m, int& flags, float& px, float& py, float& pz, float t_end = 0.0f,
+                                          float ray_tan_half = 0.0f) {
+  const float tan_half = BOUNDED ? ray_tan_half : P.tan_half;
   if ((flags & kStatusMask) == NSKY_TRACE_ALIVE) {
     if (f >= P.eps) flags |= kOutside;
     const bool outside = (flags & kOutside) != 0;
@@ -81,15 +86,16 @@ __device__ __forceinline__ void march_ray(const Params& P, float f, float x, flo
       flags = (flags & ~kStatusMask) | NSKY_TRACE_HIT;
       m = 0.0f;
     } else {
-      if (outside && P.tan_half > 0.0f && t > 0.0f) m = fminf(m, fminf(fmaxf(f / (t * P.tan_half), 0.0f), 1.0f));
+      if (outside && tan_half > 0.0f && t > 0.0f) m = fminf(m, fminf(fmaxf(f / (t * tan_half), 0.0f), 1.0f));
       t += fmaxf(fabsf(f) * P.relax, P.min_step);
     }
   }
   px = fmaf(t, sx, x);
   py = fmaf(t, sy, y);
   pz = fmaf(t, sz, z);
-  if ((flags & kStatusMask) == NSKY_TRACE_ALIVE && it + 1 < steps && beyond(px, py, pz, P.radius2))
-    flags = (flags & ~kStatusMask) | NSKY_TRACE_ESCAPED;
+  bool leaves = beyond(px, py, pz, P.radius2);
+  if constexpr (BOUNDED) leaves = leaves || t >= t_end;
+  if ((flags & kStatusMask) == NSKY_TRACE_ALIVE && it + 1 < steps && leaves) flags = (flags & ~kStatusMask) | NSKY_TRACE_ESCAPED;
 }
 
 template <int V>
@@ -123,6 +129,58 @@ __global__ __launch_bounds__(256) void step_kernel(float* __restrict__ state, co
       march_ray(P, f[v], x[v], y[v], z[v], dirs[k], dirs[k + 1], dirs[k + 2], it, steps, grace, t[v], m[v], flags[v], p[3 * v], p[3 * v + 1],
                 p[3 * v + 2]);
     }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(state + 3 * T + i) = *reinterpret_cast<const float4*>(t);
+      *reinterpret_cast<float4*>(state + 4 * T + i) = *reinterpret_cast<const float4*>(m);
+      *reinterpret_cast<int4*>(state + 5 * T + i) = *reinterpret_cast<const int4*>(flags);
+      float4* out = reinterpret_cast<float4*>(points + i * 3);
+      out[0] = *reinterpret_cast<const float4*>(p);
+      out[1] = *reinterpret_cast<const float4*>(p + 4);
+      out[2] = *reinterpret_cast<const float4*>(p + 8);
+    } else {
+      state[3 * T + i] = t[0], state[4 * T + i] = m[0];
+      reinterpret_cast<int32_t*>(state)[5 * T + i] = flags[0];
+      points[i * 3] = p[0], points[i * 3 + 1] = p[1], points[i * 3 + 2] = p[2];
+    }
+  }
+}
+
+// the step of rays that end at a light: direction row i of ray i, bounds [2][T] = t_end, tan_half (nsky_light_trace_begin)
+template <int V>
+__global__ __launch_bounds__(256) void step_bounded_kernel(float* __restrict__ state, const float* __restrict__ sdf,
+                                                           const float* __restrict__ dirs, const float* __restrict__ bounds, int64_t T,
+                                                           const float* __restrict__ params, int it, int steps, int grace,
+                                                           float* __restrict__ points) {
+  const Params P = load_params(params);
+  const int64_t groups = T / V;  // (V == 4: T % 4 == 0)
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int64_t i = g * V;
+    alignas(16) float x[V], y[V], z[V], t[V], m[V], f[V], te[V], th[V], s[3 * V], p[3 * V];
+    alignas(16) int flags[V];
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(x) = *reinterpret_cast<const float4*>(state + i);
+      *reinterpret_cast<float4*>(y) = *reinterpret_cast<const float4*>(state + T + i);
+      *reinterpret_cast<float4*>(z) = *reinterpret_cast<const float4*>(state + 2 * T + i);
+      *reinterpret_cast<float4*>(t) = *reinterpret_cast<const float4*>(state + 3 * T + i);
+      *reinterpret_cast<float4*>(m) = *reinterpret_cast<const float4*>(state + 4 * T + i);
+      *reinterpret_cast<int4*>(flags) = *reinterpret_cast<const int4*>(state + 5 * T + i);
+      *reinterpret_cast<float4*>(f) = *reinterpret_cast<const float4*>(sdf + i);
+      *reinterpret_cast<float4*>(te) = *reinterpret_cast<const float4*>(bounds + i);
+      *reinterpret_cast<float4*>(th) = *reinterpret_cast<const float4*>(bounds + T + i);
+      const float4* in = reinterpret_cast<const float4*>(dirs + i * 3);
+      *reinterpret_cast<float4*>(s) = in[0];
+      *reinterpret_cast<float4*>(s + 4) = in[1];
+      *reinterpret_cast<float4*>(s + 8) = in[2];
+    } else {
+      x[0] = state[i], y[0] = state[T + i], z[0] = state[2 * T + i], t[0] = state[3 * T + i], m[0] = state[4 * T + i];
+      flags[0] = reinterpret_cast<const int32_t*>(state)[5 * T + i];
+      f[0] = sdf[i], te[0] = bounds[i], th[0] = bounds[T + i];
+      s[0] = dirs[i * 3], s[1] = dirs[i * 3 + 1], s[2] = dirs[i * 3 + 2];
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v)
+      march_ray<true>(P, f[v], x[v], y[v], z[v], s[3 * v], s[3 * v + 1], s[3 * v + 2], it, steps, grace, t[v], m[v], flags[v], p[3 * v],
+                      p[3 * v + 1], p[3 * v + 2], te[v], th[v]);
     if constexpr (V == 4) {
       *reinterpret_cast<float4*>(state + 3 * T + i) = *reinterpret_cast<const float4*>(t);
       *reinterpret_cast<float4*>(state + 4 * T + i) = *reinterpret_cast<const float4*>(m);
@@ -211,6 +269,25 @@ extern "C" int nsky_sphere_trace_step(float* state, const float* sdf, const floa
     hipLaunchKernelGGL(step_kernel<1>, dim3(grid_for(T)), dim3(256), 0, st, state, sdf, directions, T, dir_div, params, (int)iteration,
                        (int)steps, (int)grace, points);
   NSKY_CHECK_LAUNCH("nsky_sphere_trace_step");
+  return NSKY_OK;
+}
+
+extern "C" int nsky_sphere_trace_step_bounded(float* state, const float* sdf, const float* ray_dirs, const float* bounds, int64_t T,
+                                              const float* params, int32_t iteration, int32_t steps, int32_t grace, float* points,
+                                              nsky_stream_t stream) {
+  NSKY_CHECK_ARG(T >= 0 && iteration >= 0 && iteration < steps && grace >= 0, "nsky_sphere_trace_step_bounded: T %ld, iteration %d of %d, grace %d",
+                 (long)T, (int)iteration, (int)steps, (int)grace);
+  if (T == 0) return NSKY_OK;
+  NSKY_CHECK_ARG(state && sdf && ray_dirs && bounds && params && points,
+                 "nsky_sphere_trace_step_bounded: NULL state / sdf / ray_dirs / bounds / params / points");
+  hipStream_t st = (hipStream_t)stream;
+  if (T % 4 == 0 && aligned16(state) && aligned16(sdf) && aligned16(points) && aligned16(ray_dirs) && aligned16(bounds))
+    hipLaunchKernelGGL(step_bounded_kernel<4>, dim3(grid_for(T / 4)), dim3(256), 0, st, state, sdf, ray_dirs, bounds, T, params, (int)iteration,
+                       (int)steps, (int)grace, points);
+  else
+    hipLaunchKernelGGL(step_bounded_kernel<1>, dim3(grid_for(T)), dim3(256), 0, st, state, sdf, ray_dirs, bounds, T, params, (int)iteration,
+                       (int)steps, (int)grace, points);
+  NSKY_CHECK_LAUNCH("nsky_sphere_trace_step_bounded");
   return NSKY_OK;
 }
 

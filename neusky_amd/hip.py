@@ -1531,6 +1531,86 @@ def sphere_trace_finish(state, vis, status, t):
     check(_sphere_trace_finish(ptr(state), T, ptr(vis), ptr(status), ptr(t), stream_ptr()), "nsky_sphere_trace_finish")
 
 
+# ---- point and spot lights inside the scene (relight/lights.py, csrc/lights.hip; the bounded step: csrc/sphere_trace.hip)
+LIGHT_FLOATS = 16  # NSKY_LIGHT_FLOATS: p (0..2), a (3..5), cos_inner, cos_outer, rho, clearance, min_distance, -, I (12..14), -
+_light_transfer = _sig("nsky_light_transfer", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                       C.c_void_p, C.c_void_p)
+_light_trace_begin = _sig("nsky_light_trace_begin", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_light_trace_begin_points = _sig("nsky_light_trace_begin_points", C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sphere_trace_step_bounded = _sig("nsky_sphere_trace_step_bounded", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p)
+_lights_composite = _sig("nsky_lights_composite", C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                         C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def _lights_block(lights):
+    L = lights.shape[0]
+    assert lights.shape == (L, LIGHT_FLOATS) and L >= 1 and lights.dtype == torch.float32 and lights.is_contiguous()
+    return L
+
+
+def _light_trace_buffers(T, params, state, points, ray_dirs, bounds):
+    _trace_buffers(T, params, state, points)
+    assert ray_dirs.shape == (T, 3) and bounds.shape == (2, T)
+    assert all(x.dtype == torch.float32 and x.is_contiguous() for x in (ray_dirs, bounds))
+
+
+def light_transfer(positions, albedo, normals, weights, lights, out):
+    """positions, albedo, normals: fp32 [R, S, 3]; weights [R, S]; lights [L, 16] -> out [L, R, 3]"""
+    R, S, _ = albedo.shape
+    L = _lights_block(lights)
+    assert positions.shape == (R, S, 3) and normals.shape == (R, S, 3) and weights.shape == (R, S) and out.shape == (L, R, 3)
+    assert all(t.dtype == torch.float32 for t in (positions, albedo, normals, weights, out))
+    check(_light_transfer(_c(positions), _c(albedo), _c(normals), _c(weights), ptr(lights), R, S, L, _c(out), stream_ptr()),
+          "nsky_light_transfer")
+
+
+def light_trace_begin(origins, directions, depth, normals, lights, params, state, points, ray_dirs, bounds):
+    """origins, directions, normals: fp32 [R, 3]; depth [R]; lights [L, 16]; params [6] (device) -> state [6, L R], points, ray_dirs
+    [L R, 3], bounds [2, L R] (t_end, tan_half)"""
+    R, L = origins.shape[0], _lights_block(lights)
+    assert origins.shape == (R, 3) and directions.shape == (R, 3) and normals.shape == (R, 3) and depth.numel() == R
+    assert all(x.dtype == torch.float32 for x in (origins, directions, depth, normals))
+    _light_trace_buffers(L * R, params, state, points, ray_dirs, bounds)
+    check(_light_trace_begin(_c(origins), _c(directions), _c(depth), _c(normals), ptr(lights), R, L, ptr(params), ptr(state), ptr(points),
+                             ptr(ray_dirs), ptr(bounds), stream_ptr()), "nsky_light_trace_begin")
+
+
+def light_trace_begin_points(starts, lights, params, state, points, ray_dirs, bounds):
+    """starts: fp32 [M, 3]; lights [L, 16] (every start under every light, ray l M + r) -> state, points, ray_dirs, bounds"""
+    M, L = starts.shape[0], _lights_block(lights)
+    assert starts.shape == (M, 3) and M >= 1 and starts.dtype == torch.float32
+    _light_trace_buffers(L * M, params, state, points, ray_dirs, bounds)
+    check(_light_trace_begin_points(_c(starts), ptr(lights), M, L, ptr(params), ptr(state), ptr(points), ptr(ray_dirs), ptr(bounds),
+                                    stream_ptr()), "nsky_light_trace_begin_points")
+
+
+def sphere_trace_step_bounded(state, sdf, ray_dirs, bounds, params, iteration: int, steps: int, grace: int, points):
+    """one round of the march of rays that end at a light: state [6, T], sdf fp32 [T] at `points`, ray_dirs [T, 3], bounds [2, T] ->
+    state, points [T, 3]"""
+    T = points.shape[0]
+    _light_trace_buffers(T, params, state, points, ray_dirs, bounds)
+    assert sdf.dtype == torch.float32 and sdf.numel() == T and 0 <= iteration < steps
+    check(_sphere_trace_step_bounded(ptr(state), _c(sdf), ptr(ray_dirs), ptr(bounds), T, ptr(params), iteration, steps, grace, ptr(points),
+                                     stream_ptr()), "nsky_sphere_trace_step_bounded")
+
+
+def lights_composite(base, t, vis, acc, acc_threshold, lights, rgb, lin=None, light_lin=None, visibility=None):
+    """base: fp32 [R, 3] (one base under all Kb outputs) or [Kb, R, 3]; t [L, R, 3]; vis [L, R] or None; acc [R]; acc_threshold [1]
+    (device); lights [L, 16] -> rgb [Kb, R, 3] (sRGB, clamped) and, if given, lin [Kb, R, 3], light_lin [R, 3], visibility [L, R]"""
+    L, R, _ = t.shape
+    Kb = rgb.shape[0]
+    assert _lights_block(lights) == L and rgb.shape == (Kb, R, 3) and base.shape in ((R, 3), (Kb, R, 3))
+    assert acc.numel() == R and acc_threshold.numel() == 1 and (vis is None or vis.shape == (L, R)) and (lin is None or lin.shape == (Kb, R, 3))
+    assert (light_lin is None or light_lin.shape == (R, 3)) and (visibility is None or visibility.shape == (L, R))
+    assert all(x is None or x.dtype == torch.float32 for x in (base, t, vis, acc, acc_threshold, rgb, lin, light_lin, visibility))
+    stride = 0 if base.dim() == 2 else R * 3
+    check(_lights_composite(_c(base), stride, _c(t), _c(vis), _c(acc), _c(acc_threshold), ptr(lights), R, L, Kb, _c(rgb), _c(lin), _c(light_lin),
+                            _c(visibility), stream_ptr()), "nsky_lights_composite")
+
+
 # ---- a display transform: metered exposure, bloom, tone curve, sRGB, 8 bits (relight/display.py, csrc/display.hip)
 DISPLAY_BINS, DISPLAY_PARAMS, DISPLAY_MAX_RADIUS = 3072, 8, 96  # NSKY_DISPLAY_BINS / _PARAMS / _MAX_RADIUS
 DISPLAY_CURVES = {"clamp": 0, "reinhard": 1, "aces": 2, "hable": 3}  # NSKY_DISPLAY_CLAMP ..

@@ -19,11 +19,13 @@ from .. import hip, ops
 from ..cameras.rays import RayBundle
 from ..field_components.neusky_fieldheadnames import FieldHeadNames, NeuSkyFieldHeadNames
 from ..relight.lighting import FrameLighting, light_colours
+from ..relight.lights import lights_block, trace_light_shadows
 from ..relight.shadows import trace_params, trace_sun_shadows
 from ..relight.transfer import bake_rows
 
 SUN_KEYS = ("rgb", "lin", "shadow_map", "shadow_difference")
 SDF_SHADOW_KEYS = ("shadow_status",)  # joins them under sun_shadows="sdf"
+LIGHT_KEYS = ("light_lin", "light_visibility")  # of a frame with lights; `light_status` joins them under light_shadows
 
 
 # the static buffers of a frame, as FrameRenderer.static keeps them; a member that is none of the entry's own (`data`, `convention`, `scale`,
@@ -42,6 +44,9 @@ FrameDaylight = namedtuple("FrameDaylight", "lights turbidity exposure ground su
 # sun_shadows="sdf": the suns' shadows are marched through the SDF (relight/shadows.py).  params: the kernels' parameter block [6] (eps,
 # relax, min_step, tan_half, radius, bias); steps and grace are Python numbers, by-value arguments of the step kernel
 FrameTrace = namedtuple("FrameTrace", "params steps grace")
+# L relight.PointLight inside the scene: block [L, 16] (include/neusky_hip.h), the accumulation threshold [1] and the parameter block
+# [6] of their shadow march; steps and grace as FrameTrace's; shadows: whether the march runs at all (a Python bool)
+FrameLights = namedtuple("FrameLights", "block acc_threshold params steps grace shadows")
 
 
 @dataclass
@@ -49,8 +54,8 @@ class FrameLight:
     """the light of the active frame: directions [D, 3], the frame camera's colours at them [1, D, 3] and the upper-hemisphere subset, in
     static buffers; the camera and the (pinned) rotation of its latent; optionally an environment map, suns, a transfer-bake storage, a
     daylight sky (which takes the place of the latent's: `cols` is then not decoded and not read), a shadow march in place of the suns'
-    DDF queries; `linear`: a frame under the sky alone also keeps its linear image `lin` (a sun frame always does), for a display
-    transform"""
+    DDF queries, lamps inside the scene on top of whichever of these lights it; `linear`: a frame under the sky alone also keeps its
+    linear image `lin` (a sun frame and a frame with lamps always do), for a display transform"""
     dirs: torch.Tensor
     cols: torch.Tensor
     sel: torch.Tensor
@@ -63,6 +68,7 @@ class FrameLight:
     daylight: Optional[FrameDaylight] = None
     trace: Optional[FrameTrace] = None
     linear: bool = False
+    lights: Optional[FrameLights] = None
     key: tuple = field(init=False)
 
     def __post_init__(self, rotation_values):
@@ -70,7 +76,9 @@ class FrameLight:
         storage, shape and convention only, so a new rotation or exposure replays the chunk; a sun frame adds K and the sigmoid scale,
         so a new position, colour or threshold does; a daylight frame adds K once more and drops the camera, so a new turbidity,
         exposure, ground or camera does; a frame with marched shadows adds the march's length and leaving phase, so a new eps, bias or
-        angular diameter does; a sky frame that keeps its linear image says so (its chunk has one more output)."""
+        angular diameter does; a sky frame that keeps its linear image says so (its chunk has one more output); a frame with lamps adds
+        their number, whether their shadows are marched and that march's length and leaving phase, so a new position, intensity, cone,
+        radius, eps or bias replays the chunk."""
         env = self.envmap
         key = (self.cam, rotation_values) if env is None else ("envmap", env.data.data_ptr(), tuple(env.data.shape), env.convention)
         if self.daylight is not None:  # no latent is read: one chunk graph serves every camera
@@ -85,6 +93,8 @@ class FrameLight:
             key = (key, "sdf shadows", self.trace.steps, self.trace.grace)
         if self.linear and self.shading == "sky":
             key = (key, "linear")
+        if self.lights is not None:
+            key = (key, ("lights", self.lights.block.shape[0], self.lights.shadows, self.lights.steps, self.lights.grace))
         self.key = key
 
     @property
@@ -97,9 +107,12 @@ def shade(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -
     `shadow_difference` with suns, under the frame's sky or a daylight sky of each sun's own; the transfer keys and no `rgb` for a bake
     (no light enters).  A sky frame asked for its linear image adds `lin`: what the renderer's kernel computes beside `rgb` and drops."""
     if light.shading == "sky":
+        if light.lights is not None:  # (the lamps add to the linear image: the frame carries it)
+            return _add_lights(model, light.lights, so, ray_bundle, _sky_outputs(model, so), suns=False)
         return _sky_outputs(model, so) if light.linear else {"rgb": model.render_lambertian(so)}
     if light.shading in ("sun", "daylight"):
-        return _sun_outputs(model, light.sun, so, ray_bundle, light.daylight, light.trace)
+        out = _sun_outputs(model, light.sun, so, ray_bundle, light.daylight, light.trace)
+        return out if light.lights is None else _add_lights(model, light.lights, so, ray_bundle, out, suns=True)
     fo = so["field_outputs"]
     visibility = so["visibility_dict"]["visibility"] if model.config.use_visibility else None
     return bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], so["weights"][..., 0], so["illumination_directions"],
@@ -170,6 +183,36 @@ def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundl
     return out
 
 
+def _add_lights(model, lights: FrameLights, so: Dict[str, Any], ray_bundle: RayBundle, out: Dict[str, torch.Tensor],
+                suns: bool) -> Dict[str, torch.Tensor]:
+    """the frame's L lamps on top of a chunk lit by its sky (out: rgb, lin [R, 3]) or by sky and K suns (ray-major views of [K, R, 3]):
+    the lamps' transfer at the samples' positions, a march from each ray's rendered surface point to each lamp (or none), and the
+    composite, which adds the one lamp image to every base image (include/neusky_hip.h).  `rgb` and `lin` are replaced by the lit
+    ones; light_lin [R, 3], light_visibility [R, L] and, with shadows, light_status [R, L] (int8) join them."""
+    fo = so["field_outputs"]
+    a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
+    w = so["weights"][..., 0].contiguous()
+    x = so["ray_samples"].frustums.get_positions().to(torch.float32).contiguous()
+    R, L, dev = a.shape[0], lights.block.shape[0], a.device
+    t = torch.empty(L, R, 3, device=dev)
+    hip.light_transfer(x, a, n, w, lights.block, t)
+    vis = status = None
+    if lights.shadows:
+        march = trace_light_shadows(model.field, ray_bundle.origins, ray_bundle.directions, so["p2p_dist"], so["normal"], lights.block,
+                                    lights.params, lights.steps, lights.grace)
+        vis, status = march.visibility, march.status
+    base = out["lin"].permute(1, 0, 2).contiguous() if suns else out["lin"]  # [K, R, 3] (the storage _sun_outputs holds) or [R, 3]
+    Kb = base.shape[0] if suns else 1
+    rgb, lin = torch.empty(Kb, R, 3, device=dev), torch.empty(Kb, R, 3, device=dev)
+    light_lin, V = torch.empty(R, 3, device=dev), torch.empty(L, R, device=dev)
+    hip.lights_composite(base, t, vis, so["accumulation"].reshape(-1).contiguous(), lights.acc_threshold, lights.block, rgb, lin, light_lin, V)
+    out = {**out, "rgb": rgb.permute(1, 0, 2) if suns else rgb[0], "lin": lin.permute(1, 0, 2) if suns else lin[0], "light_lin": light_lin,
+           "light_visibility": V.t()}
+    if status is not None:
+        out["light_status"] = status.t()
+    return out
+
+
 class FrameRenderer:
     """one per model (`model.frames`); plain Python, nothing of it is in the model's state_dict"""
 
@@ -178,7 +221,8 @@ class FrameRenderer:
         self.active: Optional[FrameLight] = None
         # the static buffers, one named tuple per key, kept for the model's lifetime (a captured chunk holds their pointers): "sky" ->
         # FrameSky; ("envmap", device) -> FrameEnvmap; ("suns", K, device) -> FrameSuns; ("daylight", K, D, device) -> FrameDaylight;
-        # ("trace", device) -> FrameTrace.  Only "sky" is ever allocated again, on a new D or device, and takes the runners with it
+        # ("trace", device) -> FrameTrace; ("lights", L, device) -> FrameLights.  Only "sky" is ever allocated again, on a new D or device,
+        # and takes the runners with it
         self.static: Dict[Any, tuple] = {}
         # a chunk graph cached under a rotation's values reads the rotation through the pointer it was captured with: the first tensor
         # seen with these values is kept, and serves every later frame that asks for them (one entry per value ever seen)
@@ -217,7 +261,8 @@ class FrameRenderer:
             sky.cols.copy_(cols)
         suns = self._suns(lighting)
         self.active = FrameLight(sky.dirs, sky.cols, sky.sel, cam, rotation, values, self._envmap(envmap, rotation), suns, lighting.bake,
-                                 self._daylight(lighting.daylight, sky.dirs, suns), self._trace(lighting.shadow_trace), bool(linear))
+                                 self._daylight(lighting.daylight, sky.dirs, suns), self._trace(lighting.shadow_trace), bool(linear),
+                                 self._lights(lighting))
 
     def _envmap(self, envmap, rotation) -> Optional[FrameEnvmap]:
         if envmap is None:
@@ -275,6 +320,22 @@ class FrameRenderer:
         st.params.copy_(trace_params(shadow_trace))
         return st._replace(steps=shadow_trace["steps"], grace=shadow_trace["grace"])
 
+    def _lights(self, lighting: FrameLighting) -> Optional[FrameLights]:
+        lights = lighting.lights
+        if not lights:
+            return None
+        L, dev = len(lights), self.model.device
+        st = self._static(("lights", L, str(dev)), lambda: FrameLights(
+            torch.empty(L, hip.LIGHT_FLOATS, device=dev), torch.empty(1, device=dev), torch.empty(hip.TRACE_PARAMS, device=dev), None, None,
+            None))
+        st.block.copy_(lights_block(lights))
+        st.acc_threshold.copy_(torch.tensor([float(lighting.accumulation_mask_threshold)]))
+        trace = lighting.light_trace
+        if trace is None:
+            return st._replace(steps=0, grace=0, shadows=False)
+        st.params.copy_(trace_params(trace))
+        return st._replace(steps=trace["steps"], grace=trace["grace"], shadows=True)
+
     def end(self) -> None:
         self.active = None
 
@@ -326,8 +387,10 @@ class FrameRenderer:
         suns = lighting.suns
         sun_keys = list(SUN_KEYS + (SDF_SHADOW_KEYS if lighting.sun_shadows == "sdf" else ())) if suns is not None else []
         keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
-        if linear and suns is None:
+        if (linear or lighting.lights) and suns is None:
             keys.append("lin")
+        if lighting.lights:
+            keys += list(LIGHT_KEYS) + (["light_status"] if lighting.light_trace is not None else [])
         out = {k: [] for k in keys}
         early = to_cpu and antialias is None  # (the second pass resolves on the device: its frame goes to the host afterwards)
         try:

@@ -22,6 +22,9 @@ frame render with `daylight=` gives each of K suns its own sky from one field pa
 `trace_visibility` / `SphereTrace` (shadows.py, csrc/sphere_trace.hip): shadow rays sphere-traced through the SDF, with penumbrae; the
 frame render with `sun_shadows="sdf"` takes every sun's shadow from it instead of the DDF (`--sun-shadows sdf`).
 
+`PointLight` / `trace_visibility_to` (lights.py, csrc/lights.hip): point and spot lights inside the scene, with inverse-square falloff
+and shadow rays that end at the lamp; the frame render with `lights=` adds them to any sky and sun (`--light`, `--lights`).
+
 `DisplayTransform` (display.py, csrc/display.hip): from a linear image to a picture on the device: metered exposure, bloom, a tone curve,
 sRGB and 8 bits; the frame render and both transfers' `relight` take one as `display=` (`--tonemap`, `--auto-exposure`).
 
@@ -38,13 +41,16 @@ from .envmap import EnvironmentMap, envmap_labels, envmap_lookup, project_envmap
 from .envmap_sun import SunExtraction, extract_sun
 from .io import read_envmap, srgb_to_linear
 from .lighting import FrameLighting
+from .lights import (LIGHT_TRACE_DEFAULTS, MAX_LIGHTS, PointLight, as_lights, lights_block, load_lights, save_lights, trace_light_shadows,
+                     trace_visibility_to)
 from .shadows import ALIVE, ESCAPED, EXHAUSTED, HIT, SHADOW_DEFAULTS, TRACE_DEFAULTS, SphereTrace, trace_sun_shadows, trace_visibility
 from .sun import SunLight, sun_direction, sun_path, sun_solid_angle
 from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
 from .transfer_sh import SHRadianceTransfer, bake_transfer_sh, compress_transfer, light_basis, project_lights, sh_basis
 
-__all__ = ["ALIVE", "Antialias", "CameraPath", "DaylightSky", "DisplayTransform", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "FrameLighting", "HIT", "RadianceTransfer",
+__all__ = ["ALIVE", "Antialias", "CameraPath", "DaylightSky", "DisplayTransform", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "FrameLighting", "HIT", "LIGHT_TRACE_DEFAULTS", "MAX_LIGHTS", "PointLight", "RadianceTransfer",
            "SHADOW_DEFAULTS", "SHRadianceTransfer", "SphereTrace", "SunExtraction", "SunLight", "TRACE_DEFAULTS", "bake_transfer",
            "bake_transfer_sh", "bloom_weights", "camera_rays", "compress_transfer", "envmap_labels", "envmap_lookup", "extract_sun", "frame_display", "light_basis",
            "load_camera_path", "pack_fp16", "project_envmap", "project_lights", "r2_offsets", "read_envmap", "sh_basis", "srgb_to_linear", "sun_direction",
-           "subpixel_rays", "sun_path", "sun_solid_angle", "trace_sun_shadows", "trace_visibility", "unpack_fp16", "z_rotation"]
+           "subpixel_rays", "sun_path", "sun_solid_angle", "trace_sun_shadows", "trace_visibility", "unpack_fp16", "z_rotation", "as_lights", "lights_block", "load_lights", "save_lights",
+           "trace_light_shadows", "trace_visibility_to"]

@@ -120,8 +120,72 @@ def build_parser() -> argparse.ArgumentParser:
     aa.add_argument("--aa-accumulation", type=float, metavar="T", help="mark a difference of accumulation above T (default 0.1)")
     aa.add_argument("--aa-all", action="store_true", help="mark every pixel: plain supersampling")
     aa.add_argument("--aa-mask", action="store_true", help="also write the marked pixels of each frame as aa_CCCC_FFF.png (0 or 255)")
+    lamps = ap.add_argument_group("lights", "point and spot lights inside the scene (relight.PointLight), on top of the sky and any sun, with "
+                                  "shadow rays sphere-traced through the SDF to each lamp")
+    lamps.add_argument("--light", type=float, nargs=6, action="append", metavar=("X", "Y", "Z", "R", "G", "B"),
+                       help="an omnidirectional lamp at X Y Z (scene units) of intensity R G B (the colour of a sun that lights a facing "
+                            "surface as the lamp does from distance 1); repeatable")
+    lamps.add_argument("--light-radius", type=float, metavar="RHO", help="the radius of the lamps given by --light (default 0: hard shadows)")
+    lamps.add_argument("--lights", metavar="FILE.json", help="a list of lamps with every field of relight.PointLight; adds to --light")
+    lamps.add_argument("--no-light-shadows", action="store_true", help="the lamps cast no shadows: no march")
+    lamps.add_argument("--light-shadow-steps", type=int, metavar="N", help="rounds of the lamps' shadow march (default 96)")
+    lamps.add_argument("--light-shadow-bias", type=float, metavar="B", help="the lift of that march's start points off the surface (default 1e-2)")
+    lamps.add_argument("--light-map", action="store_true", help="also write the lamps' share of each frame as lights_CCCC_FFF.png")
+    lamps.add_argument("--light-path", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                       help="the first lamp moves along this segment: --light-steps frames per camera, from one set of chunk graphs")
+    lamps.add_argument("--light-steps", type=int, metavar="N", help="frames of --light-path")
     ap.add_argument("--device", default="cuda:0")
     return ap
+
+
+def parse_lights(ap: argparse.ArgumentParser, args):
+    """(lights, light_shadows, light_trace, path) of the frame render from the light flags: (None, True, None, None) with none of them;
+    path: the --light-steps positions of the first lamp along --light-path, or None"""
+    flags = (("--light-radius", args.light_radius), ("--no-light-shadows", args.no_light_shadows or None),
+             ("--light-shadow-steps", args.light_shadow_steps), ("--light-shadow-bias", args.light_shadow_bias),
+             ("--light-map", args.light_map or None), ("--light-path", args.light_path), ("--light-steps", args.light_steps))
+    if args.light is None and args.lights is None:
+        for flag, given in flags:
+            if given is not None:
+                ap.error(f"{flag} needs a light: --light or --lights")
+        return None, True, None, None
+    if args.transfer != "off":
+        ap.error("a baked transfer holds lights at infinity: --light and --lights exclude --transfer")
+    if args.light_radius is not None and args.light is None:
+        ap.error("--light-radius is the radius of the lamps given by --light")
+    from .lights import LIGHT_TRACE_DEFAULTS, PointLight, as_lights, load_lights
+    from .shadows import trace_settings
+    try:
+        lights = [PointLight(v[:3], v[3:], radius=args.light_radius or 0.0) for v in args.light or ()]
+        if args.lights is not None:
+            lights += list(load_lights(args.lights))
+        lights = as_lights(lights)
+    except (OSError, TypeError, ValueError) as e:
+        ap.error(str(e))
+    if not lights:
+        ap.error(f"{args.lights}: no lights")
+    trace = None
+    if args.no_light_shadows:
+        for flag, given in flags[2:4]:
+            if given is not None:
+                ap.error(f"{flag} shapes the lamps' shadow march: it excludes --no-light-shadows")
+    else:
+        trace = {k: LIGHT_TRACE_DEFAULTS[k] if v is None else v for k, v in (("steps", args.light_shadow_steps), ("bias", args.light_shadow_bias))}
+        try:
+            trace_settings(trace, LIGHT_TRACE_DEFAULTS)
+        except ValueError as e:
+            ap.error(str(e))
+    path = None
+    if (args.light_path is None) != (args.light_steps is None):
+        ap.error("--light-path and --light-steps go together")
+    if args.light_path is not None:
+        if args.light_steps < 1:
+            ap.error("--light-steps must be >= 1")
+        if args.turntable > 1 or (args.sun_steps or 1) > 1:
+            ap.error("--light-path moves a lamp from frame to frame: it excludes --turntable and --sun-steps above 1")
+        a, b, n = args.light_path[:3], args.light_path[3:], args.light_steps
+        path = [tuple(a[i] + (b[i] - a[i]) * (f / (n - 1) if n > 1 else 0.0) for i in range(3)) for f in range(n)]
+    return lights, not args.no_light_shadows, trace, path
 
 
 def parse_antialias(ap: argparse.ArgumentParser, args):
@@ -305,6 +369,7 @@ def main(argv=None) -> int:
     sun_shadows, shadow_trace = parse_shadows(ap, args)
     display = parse_display(ap, args)
     antialias = parse_antialias(ap, args)
+    lights, light_shadows, light_trace, light_path = parse_lights(ap, args)
 
     import numpy as np
     import torch
@@ -371,9 +436,12 @@ def main(argv=None) -> int:
     if extraction is not None:
         sun = extraction.sun(None)
     elif suns is not None:
-        sun = suns if args.sun_path is not None else suns[0]
+        # (a sun path of one step under a moving lamp is one sun: the lamp's frames are rendered one by one)
+        sun = suns if args.sun_path is not None and light_path is None else suns[0]
     marched = {} if sun is None else {"sun_shadows": sun_shadows, "shadow_trace": shadow_trace}  # (--extract-sun may have found none)
-    base = FrameLighting.of(None, envmap, sun, args.shadow_threshold, args.shadow_sigmoid_scale, daylight=daylight, **marched)
+    lamps = {} if lights is None else {"lights": lights, "light_shadows": light_shadows, "light_trace": light_trace}
+    light_rays = light_exhausted = 0  # of the lamps' shadow march
+    base = FrameLighting.of(None, envmap, sun, args.shadow_threshold, args.shadow_sigmoid_scale, daylight=daylight, **marched, **lamps)
     # with a display transform a frame's PNG comes from its 8-bit output (the bytes are what the host reads).  Under "sequence" the frames of
     # a camera share one exposure: frames that are not rendered together (a turntable) are metered into one histogram as they come and
     # wait, as linear images on the device, for the exposure of the whole camera
@@ -387,6 +455,19 @@ def main(argv=None) -> int:
         Image.fromarray(rgb8.cpu().numpy()).save(stem + ".png")
         if args.save_linear:
             np.save(stem + ".lin.npy", lin.cpu().numpy())
+
+    def write_lights(c, f, stem, light_lin, exposure=None):
+        """the lamps' share of a frame, through the frame's own path to a picture: the sRGB curve and 8 bits (the default display
+        transform is just that), or the frame's display transform at the frame's exposure"""
+        if args.light_map:
+            if display is None:
+                from .display import DisplayTransform
+                rgb8 = DisplayTransform().apply(light_lin.to(args.device))["rgb8"]
+            else:
+                rgb8 = display.apply(light_lin.to(args.device), exposure=exposure)["rgb8"]
+            Image.fromarray(rgb8.cpu().numpy()).save(os.path.join(args.output_dir, f"lights_{c:04d}_{f:03d}.png"))
+        if args.save_linear:
+            np.save(stem + ".lights.npy", light_lin.cpu().numpy())
 
     t1 = time.perf_counter()
     for c in range(len(cams)):
@@ -405,17 +486,24 @@ def main(argv=None) -> int:
                 baked = bake_transfer_sh(model, rb, order=args.sh_order, storage=args.transfer, chunk=args.chunk, camera_index=0)
             torch.cuda.synchronize()
             t_bake += time.perf_counter() - tb
-        sweep = args.sun_path is not None  # every frame of the sweep from one field pass per chunk: rendered at its first frame
-        for f in range(len(suns) if sweep else args.turntable):
+        sweep = args.sun_path is not None and light_path is None  # every frame of the sweep from one field pass per chunk: rendered at its first frame
+        for f in range(len(suns) if sweep else len(light_path) if light_path is not None else args.turntable):
             shadow = None
             if args.transfer == "off":
                 if f == 0 or not sweep:
-                    turned = {} if extraction is None else {"suns": (extraction.sun(rots[f]),)}
+                    rot = rots[0] if light_path is not None else rots[f]  # (a moving lamp: one rotation, every frame replays the chunks)
+                    turned = {} if extraction is None else {"suns": (extraction.sun(rot),)}
+                    if light_path is not None:
+                        turned["lights"] = (dataclasses.replace(lights[0], position=light_path[f]),) + tuple(lights[1:])
                     shown = {} if display is None else {"display": display}
                     if antialias is not None:
                         shown["antialias"] = antialias
-                    out = model.frames.render(rb, dataclasses.replace(base, rotation=rots[f], **turned), camera_index=0, chunk=args.chunk,
+                    out = model.frames.render(rb, dataclasses.replace(base, rotation=rot, **turned), camera_index=0, chunk=args.chunk,
                                               **shown)
+                    if light_trace is not None:
+                        from .shadows import EXHAUSTED
+                        light_rays += out["light_status"].numel()
+                        light_exhausted += int((out["light_status"] == EXHAUSTED).sum())
                     if display is not None and not together:
                         exposures.append(out["display_exposure"])
                     if antialias is not None:
@@ -452,9 +540,12 @@ def main(argv=None) -> int:
                 Image.fromarray(np.round(rgb * 255.0).astype(np.uint8)).save(stem + ".png")
             elif together:
                 hist = display.luminance_histogram(lin, mask, out=hist)  # (one image: the first call makes the [1, 3072] the rest add to)
-                pending.append((stem, lin))
+                pending.append((stem, lin, (c, f, out["light_lin"]) if lights is not None else None))
             else:
                 write_display(stem, rgb8, lin)
+            if lights is not None and not (display is not None and together):
+                E = None if display is None else out["display_exposure"].reshape(-1)[f:f + 1] if sweep else out["display_exposure"]
+                write_lights(c, f, stem, out["light_lin"], E)
             if args.save_hdr:
                 np.save(stem + ".npy", srgb_to_linear(rgb).astype(np.float32))
             if args.shadow_map and shadow is not None:  # (--extract-sun that found nothing has no shadow to write)
@@ -467,8 +558,10 @@ def main(argv=None) -> int:
         if pending:
             E = display.exposure_from_histogram(hist)
             exposures.append(E)
-            for stem, lin in pending:
+            for stem, lin, lit in pending:
                 write_display(stem, display.apply(lin, exposure=E)["rgb8"], lin)
+                if lit is not None:
+                    write_lights(lit[0], lit[1], stem, lit[2], E)
             pending, hist = [], None
     torch.cuda.synchronize()
     t_render = time.perf_counter() - t1
@@ -488,6 +581,12 @@ def main(argv=None) -> int:
     if sun_shadows == "sdf":
         print(f"sdf shadows: {exhausted} of {shadow_rays} shadow rays ({100.0 * exhausted / max(shadow_rays, 1):.3f}%) were still marching after "
               f"{shadow_trace['steps']} steps (raise --shadow-steps if that is too many)")
+    if lights is not None:
+        n = len(lights)
+        marched = "no shadows" if light_trace is None else (
+            f"{light_exhausted} of {light_rays} shadow rays ({100.0 * light_exhausted / max(light_rays, 1):.3f}%) were still marching after "
+            f"{light_trace['steps']} steps (raise --light-shadow-steps if that is too many)")
+        print(f"lights: {n} lamp{'s' if n > 1 else ''} | {marched}")
     return 0
 
 

@@ -4,8 +4,8 @@ Definitions: include/neusky_hip.h ("Adaptive antialiasing of a frame"); kernels:
 The frame render takes one ray through every pixel centre.  With `antialias=Antialias(S)` it then reads the frame's own G-buffer (depth,
 normal, accumulation) and its linear image, marks the pixels that differ from one of their 4 neighbours (`edge_mask`), traces S - 1 further
 rays through each marked pixel (`subpixel_rays`: made from the ray bundle itself, no camera is needed) and averages the S samples of
-`lin`, `albedo`, `accumulation` and `shadow_map` (`resolve`); `rgb` is the sRGB of the resolved `lin`.  `depth`, `p2p_dist`, `normal`,
-`shadow_difference` and `shadow_status` stay the centre ray's.  `aa_mask` (uint8 [H, W, 1]) and `aa_fraction` (the share of marked pixels,
+`lin`, `albedo`, `accumulation` and `shadow_map` (`resolve`; with lamps `light_lin` and `light_visibility` too); `rgb` is the sRGB of the
+resolved `lin`.  `depth`, `p2p_dist`, `normal`, `shadow_difference`, `shadow_status` and `light_status` stay the centre ray's.  `aa_mask` (uint8 [H, W, 1]) and `aa_fraction` (the share of marked pixels,
 a Python float) join the outputs.
 
 S = 4, the thresholds (colour 0.1, depth 0.02, normal 15 degrees, accumulation 0.1, covered 0.5) and the slices of 2^18 marked pixels are
@@ -24,7 +24,8 @@ from ..cameras.rays import RayBundle
 
 MAX_SAMPLES = 64
 R2_G = 1.32471795724474602596  # the plastic number: the real root of g^3 = g + 1
-RESOLVED_KEYS = ("lin", "albedo", "accumulation", "shadow_map")  # what the second pass's samples are averaged into (`rgb` follows `lin`)
+# what the second pass's samples are averaged into (`rgb` follows `lin`); the last two are a frame's with `lights`
+RESOLVED_KEYS = ("lin", "albedo", "accumulation", "shadow_map", "light_lin", "light_visibility")
 
 
 def r2_offsets(samples: int) -> torch.Tensor:

@@ -10,6 +10,7 @@ import torch
 
 from .. import hip
 from .envmap import project_envmap
+from .lights import LIGHT_TRACE_DEFAULTS, PointLight, as_lights
 from .shadows import SHADOW_DEFAULTS, trace_settings
 from .sun import SunLight, as_suns
 
@@ -60,12 +61,18 @@ class FrameLighting:
     min_step, grace, radius (default: the sphere collider's), angular_diameter_deg (0 gives a hard edge) and bias (the lift of the
     start point off the rendered surface along its normal, scene units); None under "ddf".  Only steps and grace are held by a
     captured chunk: the others replay it."""
+    # a frame with lamps is a LitFrameLighting, which adds these three as fields; a frame without them is this value, field for field
+    lights = None
+    light_shadows = True
+    light_trace = None
 
     @classmethod
     def of(cls, rotation: Optional[torch.Tensor] = None, envmap=None, sun=None, shadow_threshold: Optional[float] = None,
            shadow_sigmoid_scale: Optional[float] = None, accumulation_mask_threshold: float = 0.0, bake: Optional[str] = None,
-           daylight=None, sun_shadows: str = "ddf", shadow_trace: Optional[dict] = None) -> "FrameLighting":
-        """sun: one SunLight or a sequence of K; shadow_trace: any of SHADOW_DEFAULTS' keys, the rest take their defaults"""
+           daylight=None, sun_shadows: str = "ddf", shadow_trace: Optional[dict] = None, lights=None, light_shadows: bool = True,
+           light_trace: Optional[dict] = None) -> "FrameLighting":
+        """sun: one SunLight or a sequence of K; shadow_trace: any of SHADOW_DEFAULTS' keys, the rest take their defaults; lights: one
+        PointLight or a sequence of L (None or empty: none); light_trace: any of LIGHT_TRACE_DEFAULTS' keys"""
         if sun_shadows not in ("ddf", "sdf"):
             raise ValueError(f"sun_shadows: 'ddf' or 'sdf', got {sun_shadows!r}")
         if sun_shadows == "sdf":
@@ -83,8 +90,35 @@ class FrameLighting:
         suns, single = (None, True) if sun is None else as_suns(sun)
         if sun_shadows == "sdf":
             shadow_trace = trace_settings(shadow_trace, {**SHADOW_DEFAULTS, "radius": COLLIDER_RADIUS})
-        return cls(rotation, envmap, daylight, bake, None if suns is None else tuple(suns), single, shadow_threshold, shadow_sigmoid_scale,
-                   accumulation_mask_threshold, sun_shadows, shadow_trace)
+        lights = as_lights(lights) or None
+        if lights is None or not light_shadows:
+            if light_trace is not None:
+                raise ValueError("light_trace holds the parameters of the lamps' shadow march: it needs `lights` with light_shadows=True")
+        else:
+            light_trace = trace_settings(light_trace, {**LIGHT_TRACE_DEFAULTS, "radius": COLLIDER_RADIUS})
+        if lights is not None and bake is not None:
+            raise ValueError("a bake holds the transfer of lights at infinity: it excludes `lights`")
+        base = (rotation, envmap, daylight, bake, None if suns is None else tuple(suns), single, shadow_threshold, shadow_sigmoid_scale,
+                accumulation_mask_threshold, sun_shadows, shadow_trace)
+        return cls(*base) if lights is None else LitFrameLighting(*base, lights, bool(light_shadows), light_trace)
+
+
+@dataclass(frozen=True, eq=False)
+class LitFrameLighting(FrameLighting):
+    """what FrameLighting.of builds when lamps are given: a FrameLighting with their three fields"""
+    __hash__ = None
+
+    lights: Optional[Tuple[PointLight, ...]] = None
+    """L relight.PointLight inside the scene (include/neusky_hip.h: point and spot lights), added to the frame of any sky and of each of
+    K suns: `rgb` and `lin` are then lit by them too, and `light_lin` [*shape, 3] (their share of `lin`) and `light_visibility`
+    [*shape, L] join the outputs.  They go with the sky alone, `envmap`, `rotation`, suns, `daylight` and both `sun_shadows` modes, and
+    exclude `bake`.  None: the frame without the feature."""
+    light_shadows: bool = True
+    """the lamps' shadow rays are sphere-traced through the SDF field, each to its lamp (relight.lights); `light_status` [*shape, L]
+    (int8, the march's verdicts) then joins the outputs.  False: `light_visibility` is the accumulation mask alone."""
+    light_trace: Optional[dict] = None
+    """with lights and light_shadows, every parameter of that march (relight.lights.LIGHT_TRACE_DEFAULTS, checked by trace_settings):
+    steps, eps, relax, min_step, grace, radius and bias; None otherwise.  Only steps and grace are held by a captured chunk."""
 
 
 def light_colours(model, dirs: torch.Tensor, cam: int, rotation: Optional[torch.Tensor] = None, envmap=None) -> torch.Tensor:

@@ -44,14 +44,14 @@ def trace_settings(given, defaults) -> dict:
             raise ValueError(f"{k} must be finite, got {p[k]!r}")
     if not (p["eps"] > 0.0 and p["relax"] > 0.0 and p["min_step"] > 0.0 and p["radius"] > 0.0):
         raise ValueError("eps, relax, min_step and radius must be positive")
-    if not 0.0 <= p["angular_diameter_deg"] < 180.0:
+    if not 0.0 <= p.get("angular_diameter_deg", 0.0) < 180.0:  # (a march towards a lamp has none: relight.lights)
         raise ValueError(f"angular_diameter_deg must lie in [0, 180), got {p['angular_diameter_deg']!r}")
     return p
 
 
 def trace_params(p: dict) -> torch.Tensor:
     """the device parameter block of the kernels as a host tensor [6]: eps, relax, min_step, tan_half, radius, bias"""
-    tan_half = math.tan(math.radians(p["angular_diameter_deg"]) / 2.0)
+    tan_half = math.tan(math.radians(p.get("angular_diameter_deg", 0.0)) / 2.0)
     return torch.tensor([p["eps"], p["relax"], p["min_step"], tan_half, p["radius"], p.get("bias", 0.0)], dtype=torch.float64).to(torch.float32)
 
 
