@@ -473,21 +473,30 @@ __global__ void visibility_finish_fwd_kernel(const float* __restrict__ t_hat, co
   vis[(long)r * D + sel_index[j]] = 1.0f - sigmoidf_(u);
 }
 
+// The per-row term and the wave's share of the threshold's gradient are formed in double: scale (25) multiplies the float rounding
+// of surf_dist - t_hat - threshold into the sigmoid's argument, and where few rows are off saturation those roundings do not average
+// out of their sum.  One exp per row of a kernel that streams four floats per row.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
 __global__ void visibility_finish_bwd_kernel(const float* __restrict__ t_hat, const float* __restrict__ surf_dist,
                                              const float* __restrict__ threshold, float scale, const int* __restrict__ sel_index,
                                              int R, int Dv, int D, const float* __restrict__ d_vis, float* __restrict__ d_t_hat,
                                              float* __restrict__ d_threshold) {
   const long m = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  float gthr = 0.f;
+  double gthr = 0.0;
   if (m < (long)R * Dv) {
     const int r = (int)(m / Dv), j = (int)(m % Dv);
-    const float s = sigmoidf_(scale * (surf_dist[m] - t_hat[m] - threshold[0]));
-    const float g = d_vis[(long)r * D + sel_index[j]] * s * (1.0f - s) * scale;  // d vis / d t_hat = + s' * scale
-    d_t_hat[m] = g;
+    const double s = 1.0 / (1.0 + exp(-(double)scale * ((double)surf_dist[m] - (double)t_hat[m] - (double)threshold[0])));
+    const double g = (double)d_vis[(long)r * D + sel_index[j]] * s * (1.0 - s) * (double)scale;  // d vis / d t_hat = + s' * scale
+    d_t_hat[m] = (float)g;
     gthr = g;
   }
-  gthr = wave_sum(gthr);
-  if ((threadIdx.x & 63) == 0 && d_threshold && gthr != 0.0f) atomicAdd(d_threshold, gthr);
+  gthr = wave_sum_f64(gthr);
+  if ((threadIdx.x & 63) == 0 && d_threshold && gthr != 0.0) atomicAdd(d_threshold, (float)gthr);
 }
 
 

@@ -191,41 +191,55 @@ __global__ __launch_bounds__(256) void ddf_fit_rows_fwd_kernel(FitRowsArgs a) {
 }
 
 // gradient of the multi-view rows w.r.t. the fit rays' termination distance (the only differentiable input: the ground truth is
-// rendered from the SDF field and, with stop_sdf_gradients = False (neusky_config.py:45), trains it)
+// rendered from the SDF field and, with stop_sdf_gradients = False (neusky_config.py:45), trains it).  The arithmetic is double:
+// the sines' arguments 2 pi {1, 4} d_loc reach 60 and 1 / len reaches 10 / radius, so a float evaluation carries 5 .. 10 float
+// roundings of the result, and this is the one route by which the DDF-fit losses reach the SDF field.  N threads: the cost is nil.
+__device__ __forceinline__ void local_frame_f64(const double pos[3], double x[3], double y[3], double z[3]) {  // local_frame, in double
+  y[0] = -pos[0]; y[1] = -pos[1]; y[2] = -pos[2];
+  x[0] = -y[1]; x[1] = y[0]; x[2] = 0.0;
+  const double xn = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  if (xn > 0.0) { x[0] /= xn; x[1] /= xn; x[2] /= xn; }
+  else { x[0] = 1.0; x[1] = 0.0; x[2] = 0.0; }
+  z[0] = y[1] * x[2] - y[2] * x[1]; z[1] = y[2] * x[0] - y[0] * x[2]; z[2] = y[0] * x[1] - y[1] * x[0];
+  const double zn = sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);
+  z[0] /= zn; z[1] /= zn; z[2] /= zn;
+}
+
 __global__ __launch_bounds__(256) void ddf_fit_rows_bwd_kernel(const float* __restrict__ positions, const float* __restrict__ directions,
                                                                const float* __restrict__ term_dist, const float* __restrict__ mv_points,
                                                                const float* __restrict__ d_xrow, int ldx, int N,
                                                                float* __restrict__ d_term_dist) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= N) return;
-  const float pts[3] = {mv_points[j * 3], mv_points[j * 3 + 1], mv_points[j * 3 + 2]};
-  const float t = term_dist[j];
-  float dir[3], dv[3];
-  for (int c = 0; c < 3; ++c) { dir[c] = directions[j * 3 + c]; dv[c] = positions[j * 3 + c] + dir[c] * t - pts[c]; }
-  const float len = sqrtf(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
-  const float u[3] = {dv[0] / len, dv[1] / len, dv[2] / len};
-  float x[3], y[3], z[3];
-  local_frame(pts, x, y, z);
-  const float dl[3] = {x[0] * u[0] + x[1] * u[1] + x[2] * u[2], y[0] * u[0] + y[1] * u[1] + y[2] * u[2], z[0] * u[0] + z[1] * u[1] + z[2] * u[2]};
+  constexpr double PI2 = 6.283185307179586476925, HALF_PI = 1.5707963267948966192;
+  const double pts[3] = {mv_points[j * 3], mv_points[j * 3 + 1], mv_points[j * 3 + 2]};
+  const double t = term_dist[j];
+  double dir[3], dv[3];
+  for (int c = 0; c < 3; ++c) { dir[c] = directions[j * 3 + c]; dv[c] = (double)positions[j * 3 + c] + dir[c] * t - pts[c]; }
+  const double len = sqrt(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
+  const double u[3] = {dv[0] / len, dv[1] / len, dv[2] / len};
+  double x[3], y[3], z[3];
+  local_frame_f64(pts, x, y, z);
+  const double dl[3] = {x[0] * u[0] + x[1] * u[1] + x[2] * u[2], y[0] * u[0] + y[1] * u[1] + y[2] * u[2], z[0] * u[0] + z[1] * u[1] + z[2] * u[2]};
   const float* g = d_xrow + (long)j * ldx;
-  float gl[3];
+  double gl[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    float acc = g[i];
+    double acc = g[i];
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
-      const float w = TWO_PI * (f == 0 ? 1.0f : 4.0f);
-      const float arg = w * dl[i];
-      acc += w * (g[3 + i * 2 + f] * cosf(arg) + g[9 + i * 2 + f] * cosf(arg + 1.5707963267948966f));
+      const double w = PI2 * (f == 0 ? 1.0 : 4.0);
+      const double arg = w * dl[i];
+      acc += w * ((double)g[3 + i * 2 + f] * cos(arg) + (double)g[9 + i * 2 + f] * cos(arg + HALF_PI));
     }
     gl[i] = acc;
   }
-  float gu[3];
+  double gu[3];
   for (int c = 0; c < 3; ++c) gu[c] = x[c] * gl[0] + y[c] * gl[1] + z[c] * gl[2];
-  const float ug = u[0] * gu[0] + u[1] * gu[1] + u[2] * gu[2];
-  float gt = 0.0f;
+  const double ug = u[0] * gu[0] + u[1] * gu[1] + u[2] * gu[2];
+  double gt = 0.0;
   for (int c = 0; c < 3; ++c) gt += (gu[c] - u[c] * ug) / len * dir[c];
-  d_term_dist[j] = gt;
+  d_term_dist[j] = (float)gt;
 }
 
 // ---- RENI++ decoder inputs for every (latent set, direction) pair -------------------------------------------------------
