@@ -32,6 +32,9 @@ sRGB and 8 bits; the frame render and both transfers' `relight` take one as `dis
 image, `subpixel_rays` through the marked pixels, a resolve in linear light; the frame render takes one as `antialias=` (`--antialias`).
 
 `FrameLighting` (lighting.py): all of the above as the one value a frame's light is said in, with the rules between its options.
+
+sequence.py: the run of the command line: the plan of a camera's renders, the two sources of its frames, the writer of its files, the
+tally of its closing lines.
 """
 from .antialias import Antialias, r2_offsets, subpixel_rays
 from .cameras import CameraPath, camera_rays, load_camera_path

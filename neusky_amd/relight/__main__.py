@@ -6,7 +6,6 @@ the numbers of train / eval latent rows and the latent dimension from its latent
 from __future__ import annotations
 
 import argparse
-import dataclasses
 import math
 import os
 import sys
@@ -138,6 +137,13 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def refuse_given(ap: argparse.ArgumentParser, flags, message: str) -> None:
+    """ap.error for the first of `flags`, pairs (flag, value), whose value is not None: `message` with the flag in place of {}"""
+    for flag, given in flags:
+        if given is not None:
+            ap.error(message.format(flag))
+
+
 def parse_lights(ap: argparse.ArgumentParser, args):
     """(lights, light_shadows, light_trace, path) of the frame render from the light flags: (None, True, None, None) with none of them;
     path: the --light-steps positions of the first lamp along --light-path, or None"""
@@ -145,9 +151,7 @@ def parse_lights(ap: argparse.ArgumentParser, args):
              ("--light-shadow-steps", args.light_shadow_steps), ("--light-shadow-bias", args.light_shadow_bias),
              ("--light-map", args.light_map or None), ("--light-path", args.light_path), ("--light-steps", args.light_steps))
     if args.light is None and args.lights is None:
-        for flag, given in flags:
-            if given is not None:
-                ap.error(f"{flag} needs a light: --light or --lights")
+        refuse_given(ap, flags, "{} needs a light: --light or --lights")
         return None, True, None, None
     if args.transfer != "off":
         ap.error("a baked transfer holds lights at infinity: --light and --lights exclude --transfer")
@@ -166,9 +170,7 @@ def parse_lights(ap: argparse.ArgumentParser, args):
         ap.error(f"{args.lights}: no lights")
     trace = None
     if args.no_light_shadows:
-        for flag, given in flags[2:4]:
-            if given is not None:
-                ap.error(f"{flag} shapes the lamps' shadow march: it excludes --no-light-shadows")
+        refuse_given(ap, flags[2:4], "{} shapes the lamps' shadow march: it excludes --no-light-shadows")
     else:
         trace = {k: LIGHT_TRACE_DEFAULTS[k] if v is None else v for k, v in (("steps", args.light_shadow_steps), ("bias", args.light_shadow_bias))}
         try:
@@ -195,9 +197,7 @@ def parse_antialias(ap: argparse.ArgumentParser, args):
     given = {"colour": args.aa_colour, "depth": args.aa_depth, "normal_deg": args.aa_normal_deg, "accumulation": args.aa_accumulation}
     if args.antialias == 1:
         flags = [("--aa-" + k.replace("_", "-"), v) for k, v in given.items()] + [("--aa-all", args.aa_all or None), ("--aa-mask", args.aa_mask or None)]
-        for flag, value in flags:
-            if value is not None:
-                ap.error(f"{flag} needs --antialias S with S > 1")
+        refuse_given(ap, flags, "{} needs --antialias S with S > 1")
         return None
     if args.transfer != "off":
         ap.error(f"--antialias {args.antialias} traces further rays through the marked pixels: it goes with --transfer off, not --transfer {args.transfer}")
@@ -217,18 +217,14 @@ def parse_display(ap: argparse.ArgumentParser, args):
                  ("--meter-percentiles", args.meter_percentiles), ("--white-point", args.white_point), ("--bloom-sigma", args.bloom_sigma),
                  ("--bloom-threshold", args.bloom_threshold), ("--bloom-strength", args.bloom_strength))
     if args.tonemap is None:
-        for flag, given in dependent:
-            if given is not None:
-                ap.error(f"{flag} needs --tonemap")
+        refuse_given(ap, dependent, "{} needs --tonemap")
         return DisplayTransform() if args.save_linear else None
-    for flag, given in dependent[1:4]:
-        if given is not None and not metered:
-            ap.error(f"{flag} shapes the metered exposure: it needs --auto-exposure frame or --auto-exposure sequence")
+    if not metered:
+        refuse_given(ap, dependent[1:4], "{} shapes the metered exposure: it needs --auto-exposure frame or --auto-exposure sequence")
     if args.white_point is not None and args.tonemap != "reinhard":
         ap.error("--white-point is the white point of --tonemap reinhard")
-    for flag, given in dependent[6:]:
-        if given is not None and args.bloom_sigma is None:
-            ap.error(f"{flag} needs --bloom-sigma")
+    if args.bloom_sigma is None:
+        refuse_given(ap, dependent[6:], "{} needs --bloom-sigma")
     given = {"key": args.exposure_key, "ev": args.exposure_ev, "percentiles": args.meter_percentiles, "white": args.white_point,
              "bloom_sigma": args.bloom_sigma, "bloom_threshold": args.bloom_threshold, "bloom_strength": args.bloom_strength}
     try:
@@ -243,9 +239,7 @@ def parse_daylight(ap: argparse.ArgumentParser, args):
     from .daylight import DaylightSky
 
     if not args.daylight:
-        for flag, given in (("--turbidity", args.turbidity), ("--sky-exposure", args.sky_exposure), ("--ground", args.ground)):
-            if given is not None:
-                ap.error(f"{flag} needs --daylight")
+        refuse_given(ap, (("--turbidity", args.turbidity), ("--sky-exposure", args.sky_exposure), ("--ground", args.ground)), "{} needs --daylight")
         return None
     if args.extract_sun:
         ap.error("--extract-sun finds the sun in a map: it excludes --daylight")
@@ -274,31 +268,28 @@ def parse_suns(ap: argparse.ArgumentParser, args, daylight=None):
 
     fixed = args.sun_azimuth is not None or args.sun_elevation is not None
     any_sun = fixed or args.sun_path is not None
-    for flag, given in (("--sun-search-radius", args.sun_search_radius), ("--sun-min-peak-ratio", args.sun_min_peak_ratio)):
-        if given is not None and not args.extract_sun:
-            ap.error(f"{flag} needs --extract-sun")
+    if not args.extract_sun:
+        refuse_given(ap, (("--sun-search-radius", args.sun_search_radius), ("--sun-min-peak-ratio", args.sun_min_peak_ratio)),
+                     "{} needs --extract-sun")
     if args.extract_sun:
         if args.envmap is None:
             ap.error("--extract-sun finds the sun in a map: it needs --envmap")
         if args.transfer != "off":
             ap.error("a sun needs the per-sample normals the baked transfer does not keep: --extract-sun goes with --transfer off")
         diameter = None if args.sun_angular_diameter == SUN_ANGULAR_DIAMETER_DEG else args.sun_angular_diameter
-        for flag, given in (("--sun-azimuth", args.sun_azimuth), ("--sun-elevation", args.sun_elevation), ("--sun-path", args.sun_path),
-                            ("--sun-steps", args.sun_steps), ("--sun-colour", args.sun_colour), ("--sun-radiance", args.sun_radiance),
-                            ("--sun-angular-diameter", diameter)):
-            if given is not None:
-                ap.error(f"--extract-sun takes the sun's position and colour from the map: it excludes {flag}")
+        refuse_given(ap, (("--sun-azimuth", args.sun_azimuth), ("--sun-elevation", args.sun_elevation), ("--sun-path", args.sun_path),
+                          ("--sun-steps", args.sun_steps), ("--sun-colour", args.sun_colour), ("--sun-radiance", args.sun_radiance),
+                          ("--sun-angular-diameter", diameter)), "--extract-sun takes the sun's position and colour from the map: it excludes {}")
         if args.sun_search_radius is not None and not 0.0 < args.sun_search_radius < 45.0:
             ap.error("--sun-search-radius must lie in (0, 45) degrees")
         if args.sun_min_peak_ratio is not None and not args.sun_min_peak_ratio >= 0.0:
             ap.error("--sun-min-peak-ratio must be >= 0")
         return None
-    for flag, given in (("--sun-colour", args.sun_colour), ("--sun-radiance", args.sun_radiance), ("--sun-steps", args.sun_steps),
-                        ("--shadow-map", args.shadow_map or None), ("--shadow-threshold", args.shadow_threshold),
-                        ("--shadow-sigmoid-scale", args.shadow_sigmoid_scale)):
-        if given is not None and not any_sun:
-            ap.error(f"{flag} needs a sun: --sun-azimuth and --sun-elevation, --sun-path, or --extract-sun")
     if not any_sun:
+        refuse_given(ap, (("--sun-colour", args.sun_colour), ("--sun-radiance", args.sun_radiance), ("--sun-steps", args.sun_steps),
+                          ("--shadow-map", args.shadow_map or None), ("--shadow-threshold", args.shadow_threshold),
+                          ("--shadow-sigmoid-scale", args.shadow_sigmoid_scale)),
+                     "{} needs a sun: --sun-azimuth and --sun-elevation, --sun-path, or --extract-sun")
         return None
     if args.transfer != "off":
         ap.error("a sun needs the per-sample normals the baked transfer does not keep: sun flags go with --transfer off")
@@ -336,13 +327,10 @@ def parse_shadows(ap: argparse.ArgumentParser, args):
     marched = (("--shadow-steps", args.shadow_steps), ("--shadow-bias", args.shadow_bias),
                ("--shadow-angular-diameter", args.shadow_angular_diameter))
     if args.sun_shadows == "ddf":
-        for flag, given in marched:
-            if given is not None:
-                ap.error(f"{flag} needs --sun-shadows sdf")
+        refuse_given(ap, marched, "{} needs --sun-shadows sdf")
         return "ddf", None
-    for flag, given in (("--shadow-threshold", args.shadow_threshold), ("--shadow-sigmoid-scale", args.shadow_sigmoid_scale)):
-        if given is not None:
-            ap.error(f"{flag} shapes the DDF shadow: it excludes --sun-shadows sdf")
+    refuse_given(ap, (("--shadow-threshold", args.shadow_threshold), ("--shadow-sigmoid-scale", args.shadow_sigmoid_scale)),
+                 "{} shapes the DDF shadow: it excludes --sun-shadows sdf")
     if args.sun_azimuth is None and args.sun_path is None and not args.extract_sun:
         ap.error("--sun-shadows sdf needs a sun: --sun-azimuth and --sun-elevation, --sun-path, or --extract-sun")
     trace = {"steps": args.shadow_steps, "bias": args.shadow_bias, "angular_diameter_deg": args.shadow_angular_diameter}
@@ -354,32 +342,14 @@ def parse_shadows(ap: argparse.ArgumentParser, args):
     return "sdf", trace
 
 
-def main(argv=None) -> int:
-    ap = build_parser()
-    args = ap.parse_args(argv)
-    if args.turntable < 1:
-        ap.error("--turntable must be >= 1")
-    if args.sh_order is not None:
-        if args.transfer == "off":
-            ap.error("--sh-order keeps a baked transfer in spherical harmonics: it needs --transfer fp32 or --transfer fp16")
-        if not 0 <= args.sh_order <= 8:
-            ap.error("--sh-order must lie in 0..8")
-    daylight = parse_daylight(ap, args)
-    suns = parse_suns(ap, args, daylight)
-    sun_shadows, shadow_trace = parse_shadows(ap, args)
-    display = parse_display(ap, args)
-    antialias = parse_antialias(ap, args)
-    lights, light_shadows, light_trace, light_path = parse_lights(ap, args)
-
-    import numpy as np
+def load_scene(args, daylight, suns):
+    """(model, envmap, extraction): the checkpoint's model in eval mode and the run's light: --envmap's map (with --extract-sun the
+    SunExtraction found in it, and the map it left), else None; --latent-index is copied into eval row 0, which the frame render reads"""
     import torch
-    from PIL import Image
 
     from ..utils.checkpoints import load_reference_pipeline_state
-    from . import EnvironmentMap, FrameLighting, camera_rays, load_camera_path, srgb_to_linear, z_rotation
+    from . import EnvironmentMap
 
-    t0 = time.perf_counter()
-    cams = load_camera_path(args.camera_path)
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
     state = ckpt["pipeline"] if "pipeline" in ckpt else ckpt
     pipe = build_pipeline(state, args.device)
@@ -424,169 +394,63 @@ def main(argv=None) -> int:
             model.eval_scale[0].copy_(model.train_scale[args.latent_index])
             if args.exposure != 1.0:
                 model.eval_scale[0].mul_(args.exposure)
-    t_load = time.perf_counter() - t0
+    return model, envmap, extraction
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.turntable < 1:
+        ap.error("--turntable must be >= 1")
+    if args.sh_order is not None:
+        if args.transfer == "off":
+            ap.error("--sh-order keeps a baked transfer in spherical harmonics: it needs --transfer fp32 or --transfer fp16")
+        if not 0 <= args.sh_order <= 8:
+            ap.error("--sh-order must lie in 0..8")
+    daylight = parse_daylight(ap, args)
+    suns = parse_suns(ap, args, daylight)
+    sun_shadows, shadow_trace = parse_shadows(ap, args)
+    display = parse_display(ap, args)
+    antialias = parse_antialias(ap, args)
+    lights, light_shadows, light_trace, light_path = parse_lights(ap, args)
+
+    import torch
+
+    from . import FrameLighting, camera_rays, load_camera_path
+    from .sequence import BakedSource, FrameWriter, RenderSource, Tally, frame_plan
+
+    t0 = time.perf_counter()
+    cams = load_camera_path(args.camera_path)
+    model, envmap, extraction = load_scene(args, daylight, suns)
+    tally = Tally(t_load=time.perf_counter() - t0)
     os.makedirs(args.output_dir, exist_ok=True)
-    frames = 0
-    t_bake = t_relight = 0.0
-    shadow_rays = exhausted = 0  # of --sun-shadows sdf
-    sh_residual = None  # of --sh-order: the largest light_residual so far, a device tensor
-    # what every frame shares; a frame then differs by its rotation and, under an extracted sun, its sun: that sun turns with its sky, so
-    # the one given here only stands for "one sun" and every frame replaces it
+    shots = frame_plan(args.turntable, args.rotation_deg, suns, args.sun_path is not None, light_path, args.transfer)
+    # what every frame shares; a shot then differs by its rotation, its first lamp and, under an extracted sun, its sun: that sun turns
+    # with its sky, so the one given here only stands for "one sun" and every shot replaces it
     sun = None
     if extraction is not None:
         sun = extraction.sun(None)
     elif suns is not None:
-        # (a sun path of one step under a moving lamp is one sun: the lamp's frames are rendered one by one)
-        sun = suns if args.sun_path is not None and light_path is None else suns[0]
+        sun = suns if shots[0].sweep else suns[0]
     marched = {} if sun is None else {"sun_shadows": sun_shadows, "shadow_trace": shadow_trace}  # (--extract-sun may have found none)
     lamps = {} if lights is None else {"lights": lights, "light_shadows": light_shadows, "light_trace": light_trace}
-    light_rays = light_exhausted = 0  # of the lamps' shadow march
     base = FrameLighting.of(None, envmap, sun, args.shadow_threshold, args.shadow_sigmoid_scale, daylight=daylight, **marched, **lamps)
-    # with a display transform a frame's PNG comes from its 8-bit output (the bytes are what the host reads).  Under "sequence" the frames of
-    # a camera share one exposure: frames that are not rendered together (a turntable) are metered into one histogram as they come and
-    # wait, as linear images on the device, for the exposure of the whole camera
-    exposures = []  # device tensors: read once, at the end
-    together = display is not None and display.exposure == "sequence" and args.sun_path is None
-    pending, hist = [], None
-    floats = display is None or args.save_hdr  # whether the host reads a frame's float image at all
-    marked = []  # of --antialias: every frame's share of marked pixels
-
-    def write_display(stem, rgb8, lin):
-        Image.fromarray(rgb8.cpu().numpy()).save(stem + ".png")
-        if args.save_linear:
-            np.save(stem + ".lin.npy", lin.cpu().numpy())
-
-    def write_lights(c, f, stem, light_lin, exposure=None):
-        """the lamps' share of a frame, through the frame's own path to a picture: the sRGB curve and 8 bits (the default display
-        transform is just that), or the frame's display transform at the frame's exposure"""
-        if args.light_map:
-            if display is None:
-                from .display import DisplayTransform
-                rgb8 = DisplayTransform().apply(light_lin.to(args.device))["rgb8"]
-            else:
-                rgb8 = display.apply(light_lin.to(args.device), exposure=exposure)["rgb8"]
-            Image.fromarray(rgb8.cpu().numpy()).save(os.path.join(args.output_dir, f"lights_{c:04d}_{f:03d}.png"))
-        if args.save_linear:
-            np.save(stem + ".lights.npy", light_lin.cpu().numpy())
-
+    writer = FrameWriter(args, display, tally)
+    shared = {"chunk": args.chunk, "display": display, "floats": writer.floats, "deferred": writer.deferred}
+    if args.transfer == "off":
+        source = RenderSource(model, base, tally, antialias=antialias, extraction=extraction, **shared)
+    else:
+        source = BakedSource(model, envmap, tally, storage=args.transfer, sh_order=args.sh_order, **shared)
     t1 = time.perf_counter()
     for c in range(len(cams)):
-        rb = camera_rays(cams, c, args.device)
-        rots = []
-        for f in range(args.turntable):
-            angle = math.radians(args.rotation_deg) + 2.0 * math.pi * f / args.turntable
-            rots.append(None if angle == 0.0 else z_rotation(angle).to(args.device))
-        if args.transfer != "off":
-            from .transfer import LIGHTS_PER_PASS, bake_transfer
-            tb = time.perf_counter()
-            if args.sh_order is None:
-                baked = bake_transfer(model, rb, storage=args.transfer, chunk=args.chunk, camera_index=0)
-            else:
-                from .transfer_sh import bake_transfer_sh
-                baked = bake_transfer_sh(model, rb, order=args.sh_order, storage=args.transfer, chunk=args.chunk, camera_index=0)
-            torch.cuda.synchronize()
-            t_bake += time.perf_counter() - tb
-        sweep = args.sun_path is not None and light_path is None  # every frame of the sweep from one field pass per chunk: rendered at its first frame
-        for f in range(len(suns) if sweep else len(light_path) if light_path is not None else args.turntable):
-            shadow = None
-            if args.transfer == "off":
-                if f == 0 or not sweep:
-                    rot = rots[0] if light_path is not None else rots[f]  # (a moving lamp: one rotation, every frame replays the chunks)
-                    turned = {} if extraction is None else {"suns": (extraction.sun(rot),)}
-                    if light_path is not None:
-                        turned["lights"] = (dataclasses.replace(lights[0], position=light_path[f]),) + tuple(lights[1:])
-                    shown = {} if display is None else {"display": display}
-                    if antialias is not None:
-                        shown["antialias"] = antialias
-                    out = model.frames.render(rb, dataclasses.replace(base, rotation=rot, **turned), camera_index=0, chunk=args.chunk,
-                                              **shown)
-                    if light_trace is not None:
-                        from .shadows import EXHAUSTED
-                        light_rays += out["light_status"].numel()
-                        light_exhausted += int((out["light_status"] == EXHAUSTED).sum())
-                    if display is not None and not together:
-                        exposures.append(out["display_exposure"])
-                    if antialias is not None:
-                        marked.append(out["aa_fraction"])
-                if floats:
-                    rgb = (out["rgb"][f] if sweep else out["rgb"]).clamp(0.0, 1.0).cpu().numpy()
-                if display is not None:
-                    lin, rgb8, mask = (out[k][f] if sweep else out[k] for k in ("lin", "display_rgb8", "accumulation"))
-                if sun is not None:
-                    shadow = out["shadow_map"][f] if sweep else out["shadow_map"]
-            else:
-                if f % LIGHTS_PER_PASS == 0:  # one pass over the transfer lights the next 8 frames
-                    tr = time.perf_counter()
-                    shown = {} if display is None else {"display": display, "return_linear": True}
-                    relit = baked.relight(model, envmap=envmap, camera_index=0, rotations=rots[f:f + LIGHTS_PER_PASS], **shown)
-                    if display is not None and not together:
-                        exposures.append(relit["display_exposure"])
-                    if args.sh_order is not None:  # kept on the device: read once, at the end
-                        worst = relit["light_residual"].max()
-                        sh_residual = worst if sh_residual is None else torch.maximum(sh_residual, worst)
-                    if floats:
-                        batch = relit["rgb"].clamp(0.0, 1.0).cpu().numpy()
-                    t_relight += time.perf_counter() - tr
-                if floats:
-                    rgb = batch[f % LIGHTS_PER_PASS]
-                if display is not None:
-                    lin, rgb8, mask = relit["linear"][f % LIGHTS_PER_PASS], relit["display_rgb8"][f % LIGHTS_PER_PASS], baked.acc
-            if shadow is not None and sun_shadows == "sdf" and (not sweep or f == 0):  # (a sweep's status holds all its frames)
-                from .shadows import EXHAUSTED
-                shadow_rays += out["shadow_status"].numel()
-                exhausted += int((out["shadow_status"] == EXHAUSTED).sum())
-            stem = os.path.join(args.output_dir, f"frame_{c:04d}_{f:03d}")
-            if display is None:
-                Image.fromarray(np.round(rgb * 255.0).astype(np.uint8)).save(stem + ".png")
-            elif together:
-                hist = display.luminance_histogram(lin, mask, out=hist)  # (one image: the first call makes the [1, 3072] the rest add to)
-                pending.append((stem, lin, (c, f, out["light_lin"]) if lights is not None else None))
-            else:
-                write_display(stem, rgb8, lin)
-            if lights is not None and not (display is not None and together):
-                E = None if display is None else out["display_exposure"].reshape(-1)[f:f + 1] if sweep else out["display_exposure"]
-                write_lights(c, f, stem, out["light_lin"], E)
-            if args.save_hdr:
-                np.save(stem + ".npy", srgb_to_linear(rgb).astype(np.float32))
-            if args.shadow_map and shadow is not None:  # (--extract-sun that found nothing has no shadow to write)
-                grey = np.round(shadow[..., 0].clamp(0.0, 1.0).cpu().numpy() * 255.0).astype(np.uint8)
-                Image.fromarray(grey, mode="L").save(os.path.join(args.output_dir, f"shadow_{c:04d}_{f:03d}.png"))
-            if args.aa_mask:  # (a sun sweep's frames come from one render: they share its mask)
-                grey = out["aa_mask"][..., 0].cpu().numpy() * np.uint8(255)
-                Image.fromarray(grey, mode="L").save(os.path.join(args.output_dir, f"aa_{c:04d}_{f:03d}.png"))
-            frames += 1
-        if pending:
-            E = display.exposure_from_histogram(hist)
-            exposures.append(E)
-            for stem, lin, lit in pending:
-                write_display(stem, display.apply(lin, exposure=E)["rgb8"], lin)
-                if lit is not None:
-                    write_lights(lit[0], lit[1], stem, lit[2], E)
-            pending, hist = [], None
+        source.open(c, camera_rays(cams, c, args.device))
+        for shot in shots:
+            for frame in source.frames(shot):
+                writer.write(frame)
+        writer.end_camera()
     torch.cuda.synchronize()
-    t_render = time.perf_counter() - t1
-    transfer = "" if args.transfer == "off" else f" | transfer {args.transfer}: bake {t_bake:.3f}s relight {t_relight:.3f}s"
-    if args.sh_order is not None and sh_residual is not None:
-        transfer += (f" | sh order {args.sh_order} ({baked.C.shape[1]} coefficients, {baked.nbytes / 1e6:.1f} MB per camera): "
-                     f"largest light_residual {float(sh_residual):.3e}")
-    print(f"{args.output_dir}: {frames} frames {cams.width}x{cams.height} | load {t_load:.3f}s render {t_render:.3f}s "
-          f"({t_render / max(frames, 1):.3f}s/frame){transfer}")
-    if display is not None and exposures:
-        E = torch.cat([e.reshape(-1) for e in exposures])
-        how = "set" if not display.metered else "metered per frame" if display.exposure == "frame" else "metered per camera"
-        print(f"display: tonemap {display.curve} | exposure {how}: smallest {float(E.min()):.4g} largest {float(E.max()):.4g}")
-    if antialias is not None and marked:
-        how = "every pixel" if antialias.every_pixel else "the pixels its edge rule marks"
-        print(f"antialias: {antialias.samples} samples through {how} | share of marked pixels: smallest {min(marked):.4g} largest {max(marked):.4g}")
-    if sun_shadows == "sdf":
-        print(f"sdf shadows: {exhausted} of {shadow_rays} shadow rays ({100.0 * exhausted / max(shadow_rays, 1):.3f}%) were still marching after "
-              f"{shadow_trace['steps']} steps (raise --shadow-steps if that is too many)")
-    if lights is not None:
-        n = len(lights)
-        marched = "no shadows" if light_trace is None else (
-            f"{light_exhausted} of {light_rays} shadow rays ({100.0 * light_exhausted / max(light_rays, 1):.3f}%) were still marching after "
-            f"{light_trace['steps']} steps (raise --light-shadow-steps if that is too many)")
-        print(f"lights: {n} lamp{'s' if n > 1 else ''} | {marched}")
+    tally.t_render = time.perf_counter() - t1
+    tally.report(args, (cams.width, cams.height), display, antialias, shadow_trace, lights, light_trace)
     return 0
 
 
