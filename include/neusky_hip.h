@@ -299,6 +299,22 @@ int nsky_field_geo_bwd(const nsky_field_net* net, const void* stream_buf, const 
  * quad-native X: w(row) = g_sdf[row / 4] on value rows (the only ones that count for the bias), g_grad[row / 4][row % 4 - 1] on tangent rows. */
 int nsky_native_weighted_colsum(const float* X, int32_t nt, int32_t rows, const float* w4, int32_t n_out, const float* g_sdf,
                                 const float* g_grad, float* out, int32_t ldo, float* bias, nsky_stream_t stream);
+/* DIRECTIONAL mode of the geometry kernels: one forward-mode tangent per point, along a direction d (a pass whose only consumer of the
+ * sdf's gradient is its derivative along the ray).  A point is TWO row-sets {value, tangent along d}; PAIR-NATIVE matrices are tile-native
+ * [ceil32(2 N), width] whose row 2 n + j is row-set j of point n.  ET: the stacked encode matrix [2 N, ldE] = [E; Td] of
+ * nsky_encode_fwd_dir.  Outputs: sdf [N], cosv [N] (d sdf / dx . d), a0q / a1q / Eq pair-native; qmax as nsky_field_geo_fwd.  Same
+ * packed weight streams as the quad kernels. */
+int nsky_field_geo_fwd_dir(const nsky_field_net* net, const void* stream_buf, const float* scales, int32_t total_groups, const float* ET,
+                           int32_t ldE, int32_t N, float* a0q, float* a1q, float* Eq, float* sdf, float* cosv, float* qmax,
+                           nsky_stream_t stream);
+/* g_sdf [N], g_cos [N] (each optional) -> d1q / d0q (pair-native), dET [2 N, ldE] (stacked [dE; dTd], optional), gmax [2]. */
+int nsky_field_geo_bwd_dir(const nsky_field_net* net, const void* stream_buf, const float* scales, int32_t total_groups, int32_t N,
+                           const float* g_sdf, const float* g_cos, const float* a0q, const float* a1q, float* d1q, float* d0q, float* dET,
+                           int32_t ldE, float* gmax, nsky_stream_t stream);
+/* the pair form of nsky_native_weighted_colsum's quad weights over a pair-native X (one output): w(row) = g_sdf[row / 2] on even rows
+ * (the only ones that count for the bias), g_cos[row / 2] on odd rows. */
+int nsky_native_weighted_colsum_pair(const float* X, int32_t nt, int32_t rows, const float* g_sdf, const float* g_cos, float* out,
+                                     int32_t ldo, float* bias, nsky_stream_t stream);
 
 /* Per-ray reductions of the renderers, one pass each way: expected depth clipped to the global [min, max] of the sample mid
  * points and, if max_clamp > 0, to max_clamp (nerfstudio DepthRenderer('expected'); neusky_model.py:591, :1342-1353),
@@ -446,6 +462,15 @@ int64_t nsky_encode_bwd_workspace_bytes(const nsky_hashgrid_desc* g, int32_t P, 
 int nsky_encode_bwd(const nsky_hashgrid_desc* g, const float* x, int32_t P, int32_t mode, int32_t include_x,
                     int32_t pe_freqs, float pe_max_exp, const float* dY, int32_t lddy, const float* dT, float* dtable,
                     float* dx, void* workspace, nsky_stream_t stream);
+/* Directional mode: ONE tangent row-set along a per-ray direction, Td = sum_a d_a T_a [P, ldy] (stacked with Y: [Y; Td]), formed in
+ * registers from the three per-axis terms.  dirs [ceil(P / spr), 3]: point p takes direction p / spr (spr samples per ray; 1 = one
+ * direction per point).  The backward takes dTd [P, lddy] and adds to dtable what nsky_encode_bwd adds for dT_a = d_a dTd (workspace as
+ * for a tangent call of nsky_encode_bwd); positions get no gradient. */
+int nsky_encode_fwd_dir(const nsky_hashgrid_desc* g, const float* x, int32_t P, int32_t mode, int32_t include_x, int32_t pe_freqs,
+                        float pe_max_exp, const float* dirs, int32_t spr, float* Y, int32_t ldy, float* Td, nsky_stream_t stream);
+int nsky_encode_bwd_dir(const nsky_hashgrid_desc* g, const float* x, int32_t P, int32_t mode, int32_t include_x, int32_t pe_freqs,
+                        float pe_max_exp, const float* dirs, int32_t spr, const float* dY, int32_t lddy, const float* dTd,
+                        float* dtable, void* workspace, nsky_stream_t stream);
 
 /* corner rows (uint32 [P][L][8]) exactly as the encode kernels address the table - the integer
  * part of the hash encode, exposed for BIT-EXACT parity tests. */
@@ -487,6 +512,14 @@ int nsky_neus_weights_bwd(const float* sdf, const float* grad, const float* ray_
                           const float* ends, const float* variance, float cos_anneal, int32_t R, int32_t S,
                           const float* d_weights, const float* d_trans_bg, float* d_sdf, float* d_grad,
                           float* d_variance, nsky_stream_t stream);
+/* The same with the gradient as ONE precomputed column: cosv [R,S] = ray_dir . grad(sdf) (the directional field pass); the backward
+ * writes d_cos [R,S]. */
+int nsky_neus_weights_cos_fwd(const float* sdf, const float* cosv, const float* starts, const float* ends, const float* variance,
+                              float cos_anneal, int32_t R, int32_t S, float* alpha, float* weights, float* trans_bg,
+                              float* accumulation, float* depth, nsky_stream_t stream);
+int nsky_neus_weights_cos_bwd(const float* sdf, const float* cosv, const float* starts, const float* ends, const float* variance,
+                              float cos_anneal, int32_t R, int32_t S, const float* d_weights, const float* d_trans_bg, float* d_sdf,
+                              float* d_cos, float* d_variance, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * DDF sky-visibility ray set-up and sigmoid.  Replaces the geometry of NeuSkyFactoModel.compute_visibility,

@@ -22,6 +22,12 @@
 //                    quad-native (weight-gradient operands) and d(encode rows) in the stacked [E; T0; T1; T2] layout of the encode
 //                    backward.
 //
+// The two geometry kernels also come in a PAIR layout (template parameter RPP = 2 rows per point instead of 4), the DIRECTIONAL mode of
+// a pass whose only use of the gradient is its component along one direction d per point (the DDF-fit ground truth: NeuS needs
+// cos = d . grad sdf): the encode hands in [E; Td], Td = sum_a d_a T_a, a wave's 32 columns are 16 points x {value, tangent along d},
+// the saves are "pair-native" (row 2 n + j), the forward writes sdf [N] and cos [N], the backward takes g_sdf [N] and g_cos [N] and
+// writes dET stacked [dE; dTd].  The reverse above keeps its form with the sum over the ONE tangent lane.
+//
 // Workgroups are PERSISTENT (WAVES = 4 waves, two workgroups per CU with a 64 KB ring each): the grid is at most twice the CU count, a
 // workgroup walks the weight stream cyclically, round r gives wave w the row tile r * WAVES G + w * G + b (G workgroups, b =
 // blockIdx.x), so the tiles of the last, partial round are spread over the first waves of all workgroups and a wave without a tile
@@ -68,78 +74,105 @@ __global__ __launch_bounds__(256) void chain_pack_kernel(ChainLayers L, unsigned
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Cross-lane moves must execute with the whole quad enabled: never inside an arm of a `c ? a : b` whose condition differs between the
-// lanes of a quad (the arm runs under its own EXEC mask and the DPP move reads zeros from the disabled lanes): every quad move below
+// A point's row-sets sit in one GROUP of RPP adjacent lanes: RPP = 4, the quad {value, d/dx, d/dy, d/dz}; RPP = 2, the pair {value,
+// tangent along one direction} (two pairs per hardware quad).
+// Cross-lane moves must execute with the whole group enabled: never inside an arm of a `c ? a : b` whose condition differs between the
+// lanes of a group (the arm runs under its own EXEC mask and the DPP move reads zeros from the disabled lanes): every group move below
 // is a statement of its own, ahead of the selects that use it.
-template <int G>
-__device__ __forceinline__ float quad_bcast(float v) {  // the value of the quad's lane G in all four lanes
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), G * 0x55, 0xf, 0xf, true));
+template <int RPP, int G>
+__device__ __forceinline__ float grp_bcast(float v) {  // the value of the group's lane G in all its lanes
+  constexpr int ctrl = RPP == 4 ? G * 0x55 : (G == 0 ? 0xA0 : 0xF5);  // quad_perm [G,G,G,G] | [0,0,2,2] / [1,1,3,3]
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), ctrl, 0xf, 0xf, true));
 }
-__device__ __forceinline__ float quad_bcast0(float v) { return quad_bcast<0>(v); }
-__device__ __forceinline__ float quad_sum(float v) {  // sum over the quad, in all four lanes
+template <int RPP>
+__device__ __forceinline__ float grp_sum(float v) {  // sum over the group, in all its lanes
   v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true));  // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xf, 0xf, true));  // quad_perm [2,3,0,1]
+  if (RPP == 4) v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xf, 0xf, true));  // quad_perm [2,3,0,1]
   return v;
 }
-__device__ __forceinline__ float quad_max(float v) {
+template <int RPP>
+__device__ __forceinline__ float grp_max(float v) {
   v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xf, 0xf, true)));
+  if (RPP == 4) v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xf, 0xf, true)));
   return v;
 }
-// registers 4 j .. 4 j + 3 of the quad's lane 0 (the value lane) in lane j: the value row's sixteen features of a tile are worked on by
-// the four lanes of its quad, four each (the transcendental work of a softplus layer is needed for the value row only)
-__device__ __forceinline__ void quad_scatter_value(const float (&x)[16], int j, float (&mine)[4]) {
+// registers VPL j .. VPL j + VPL - 1 (VPL = 16 / RPP) of the group's lane 0 (the value lane) in lane j: the value row's sixteen
+// features of a tile are worked on by the lanes of its group, four (quad) or eight (pair) each (the transcendental work of a softplus
+// layer is needed for the value row only)
+template <int RPP>
+__device__ __forceinline__ void grp_scatter_value(const float (&x)[16], int j, float (&mine)[16 / RPP]) {
+  if constexpr (RPP == 4) {
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float b0 = quad_bcast0(x[q]), b1 = quad_bcast0(x[4 + q]), b2 = quad_bcast0(x[8 + q]), b3 = quad_bcast0(x[12 + q]);
-    mine[q] = j == 0 ? b0 : (j == 1 ? b1 : (j == 2 ? b2 : b3));
+    for (int q = 0; q < 4; ++q) {
+      const float b0 = grp_bcast<4, 0>(x[q]), b1 = grp_bcast<4, 0>(x[4 + q]), b2 = grp_bcast<4, 0>(x[8 + q]), b3 = grp_bcast<4, 0>(x[12 + q]);
+      mine[q] = j == 0 ? b0 : (j == 1 ? b1 : (j == 2 ? b2 : b3));
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const float b0 = grp_bcast<2, 0>(x[q]), b1 = grp_bcast<2, 0>(x[8 + q]);
+      mine[q] = j == 0 ? b0 : b1;
+    }
   }
 }
-// the reverse: element q of lane g -> register 4 g + q of every lane
-__device__ __forceinline__ void quad_gather_all(const float (&mine)[4], float (&all)[16]) {
+// the reverse: element q of lane g -> register VPL g + q of every lane
+template <int RPP>
+__device__ __forceinline__ void grp_gather_all(const float (&mine)[16 / RPP], float (&all)[16]) {
+  if constexpr (RPP == 4) {
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    all[q] = quad_bcast<0>(mine[q]); all[4 + q] = quad_bcast<1>(mine[q]); all[8 + q] = quad_bcast<2>(mine[q]); all[12 + q] = quad_bcast<3>(mine[q]);
+    for (int q = 0; q < 4; ++q) {
+      all[q] = grp_bcast<4, 0>(mine[q]); all[4 + q] = grp_bcast<4, 1>(mine[q]); all[8 + q] = grp_bcast<4, 2>(mine[q]); all[12 + q] = grp_bcast<4, 3>(mine[q]);
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { all[q] = grp_bcast<2, 0>(mine[q]); all[8 + q] = grp_bcast<2, 1>(mine[q]); }
   }
 }
 
 // =====================================================================================================================
-// geometry network forward, quad layout.  Stream: W0 (NT tiles, K = in_dim), W1 (NT tiles, K = H).
+// geometry network forward, quad (RPP = 4) or pair (RPP = 2) layout.  Stream: W0 (NT tiles, K = in_dim), W1 (NT tiles, K = H).
+// Pair layout: a wave's 32 columns are 16 points x {value, tangent along d}; the encode rows are stacked [E; Td], the saves are
+// "pair-native" (row 2 n + j), `grad` is the [N, 1] derivative of the sdf along d.
 struct GeoFwdArgs {
   nsky_field_net net;
   const unsigned char* stream; const float* scales; int total_groups;
-  const float* ET; int ldE;   // stacked encode rows [4 N, ldE]: row j N + n = row-set j of point n
-  int N, n_tiles;             // points; wave tiles of 8 points
-  float* a0q; float* a1q;     // quad-native [ceil32(4 N), H]
-  float* Eq;                  // quad-native [ceil32(4 N), 128] copy of the encode rows (optional)
+  const float* ET; int ldE;   // stacked encode rows [RPP N, ldE]: row j N + n = row-set j of point n
+  int N, n_tiles;             // points; wave tiles of 32 / RPP points
+  float* a0q; float* a1q;     // group-native [ceil32(RPP N), H]
+  float* Eq;                  // group-native [ceil32(RPP N), 128] copy of the encode rows (optional)
   float* a1max;               // [N] largest |a1| of the value row (optional)
-  float* sdf; float* grad;    // [N], [N, 3]
+  float* sdf; float* grad;    // [N], [N, RPP - 1]
   float* qmax;                // [2] (optional, caller zero-fills): max |Eq|, max |a0q| over value and tangent rows alike
 };
 
 // Epilogue of one 32-feature tile of a forward-mode softplus layer in the quad layout.  acc: this column's accumulator; inv: its
 // un-scale; bias_t / w_t: the layer's bias and (DOT) the sdf row, at the tile's first feature.  The value row's pre-activations are
-// spread over the quad (lane g: features 8 g + 4 h ..), softplus and sigmoid are evaluated there, the value row's outputs are stored
-// by the lanes that computed them, the sigmoids return to every lane for the tangent rows ta_k = tz_k sigmoid(beta z).
-// m: running row maximum of this lane's column; part_v / part_t: running dots with the sdf row (value row: quad partials).
-template <bool DOT>
+// spread over the group (quad: lane g takes features 8 g + 4 h ..; pair: lane g takes the pieces 2 g, 2 g + 1), softplus and sigmoid are
+// evaluated there, the value row's outputs are stored by the lanes that computed them, the sigmoids return to every lane for the
+// tangent rows ta_k = tz_k sigmoid(beta z).
+// m: running row maximum of this lane's column; part_v / part_t: running dots with the sdf row (value row: group partials).
+template <int RPP, bool DOT>
 __device__ __forceinline__ void geo_fwd_epilogue(const f32x16& acc, float inv, const float* bias_t, const float* w_t, float beta, float inv_beta, int lane,
                                                  float* blk_t, float& m, float& part_v, float& part_t) {
-  const int c = lane & 31, h = lane >> 5, j = c & 3;
-  float x[16], zv[4], sp[4], sg[4], S[16];
+  constexpr int VPL = 16 / RPP, PCS = VPL / 4;  // value-row features, and pieces of four, per lane of the group
+  const int c = lane & 31, h = lane >> 5, j = c & (RPP - 1);
+  float x[16], zv[VPL], sp[VPL], sg[VPL], S[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) x[r] = acc[r] * inv;
-  quad_scatter_value(x, j, zv);
-  const float4 b4 = *reinterpret_cast<const float4*>(bias_t + 8 * j + 4 * h);
-  const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
+  grp_scatter_value<RPP>(x, j, zv);
   float mv = 0.0f;
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    softplus_sig(zv[q] + bb[q], beta, inv_beta, sp[q], sg[q]);
-    mv = fmaxf(mv, sp[q]);
+  for (int u = 0; u < PCS; ++u) {
+    const float4 b4 = *reinterpret_cast<const float4*>(bias_t + 8 * (PCS * j + u) + 4 * h);
+    const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      softplus_sig(zv[4 * u + q] + bb[q], beta, inv_beta, sp[4 * u + q], sg[4 * u + q]);
+      mv = fmaxf(mv, sp[4 * u + q]);
+    }
   }
-  quad_gather_all(sg, S);
-  mv = quad_max(mv);
+  grp_gather_all<RPP>(sg, S);
+  mv = grp_max<RPP>(mv);
   float mt = 0.0f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -148,26 +181,31 @@ __device__ __forceinline__ void geo_fwd_epilogue(const f32x16& acc, float inv, c
   }
   m = fmaxf(m, j == 0 ? mv : mt);
   if (DOT) {
-    const float4 wv = *reinterpret_cast<const float4*>(w_t + 8 * j + 4 * h);
-    part_v = fmaf(sp[0], wv.x, fmaf(sp[1], wv.y, fmaf(sp[2], wv.z, fmaf(sp[3], wv.w, part_v))));
+#pragma unroll
+    for (int u = 0; u < PCS; ++u) {
+      const float4 wv = *reinterpret_cast<const float4*>(w_t + 8 * (PCS * j + u) + 4 * h);
+      part_v = fmaf(sp[4 * u], wv.x, fmaf(sp[4 * u + 1], wv.y, fmaf(sp[4 * u + 2], wv.z, fmaf(sp[4 * u + 3], wv.w, part_v))));
+    }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const float4 w4 = *reinterpret_cast<const float4*>(w_t + 8 * g + 4 * h);
       part_t = fmaf(x[4 * g], w4.x, fmaf(x[4 * g + 1], w4.y, fmaf(x[4 * g + 2], w4.z, fmaf(x[4 * g + 3], w4.w, part_t))));
     }
   }
-  // the value row's piece g (features 8 g + 4 h ..) from lane g of the quad; the tangent rows from their own lanes
-  stg4(blk_t + j * 256 + ((c & ~3) + 32 * h) * 4, make_float4(sp[0], sp[1], sp[2], sp[3]));
+  // the value row's piece g (features 8 g + 4 h ..) from the lane of the group that computed it; the tangent rows from their own lanes
+#pragma unroll
+  for (int u = 0; u < PCS; ++u)
+    stg4(blk_t + (PCS * j + u) * 256 + ((c & ~(RPP - 1)) + 32 * h) * 4, make_float4(sp[4 * u], sp[4 * u + 1], sp[4 * u + 2], sp[4 * u + 3]));
   if (j != 0) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) stg4(blk_t + g * 256 + lane * 4, make_float4(x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]));
   }
 }
 
-template <int KS0, bool ACTIVE>
+template <int RPP, int KS0, bool ACTIVE>
 __device__ __forceinline__ void geo_fwd_tile(const GeoFwdArgs& a, WStream& ws, const float* bl, const float* sl, long tile, int lane) {
-  const int c = lane & 31, h = lane >> 5, p = c >> 2, j = c & 3;
-  const long n = tile * 8 + p;
+  const int c = lane & 31, h = lane >> 5, p = c / RPP, j = c & (RPP - 1);
+  const long n = tile * (32 / RPP) + p;
   const bool live = ACTIVE && n < a.N;
   const long nc = n < a.N ? n : a.N - 1;
   const float beta = a.net.beta, inv_beta = 1.0f / beta;
@@ -217,7 +255,7 @@ __device__ __forceinline__ void geo_fwd_tile(const GeoFwdArgs& a, WStream& ws, c
   for (int t = 0; t < NT; ++t) {
     f32x16 acc;
     prod<KS0, PW, true, RG>(ws, ACTIVE, eh, el, acc);
-    if (ACTIVE) geo_fwd_epilogue<false>(acc, e_inv * sl[t], bl + 32 * t, nullptr, beta, inv_beta, lane, a0blk + t * 1024, m, part_v, part_t);
+    if (ACTIVE) geo_fwd_epilogue<RPP, false>(acc, e_inv * sl[t], bl + 32 * t, nullptr, beta, inv_beta, lane, a0blk + t * 1024, m, part_v, part_t);
   }
   f16x8 ah[KS], al[KS];
   float a_inv = 1.0f;
@@ -232,10 +270,10 @@ __device__ __forceinline__ void geo_fwd_tile(const GeoFwdArgs& a, WStream& ws, c
   for (int t = 0; t < NT; ++t) {
     f32x16 acc;
     prod<KS, PW, true, RG>(ws, ACTIVE, ah, al, acc);
-    if (ACTIVE) geo_fwd_epilogue<true>(acc, a_inv * sl[NT + t], bl + H + 32 * t, bl + 2 * H + 32 * t, beta, inv_beta, lane, a1blk + t * 1024, m, part_v, part_t);
+    if (ACTIVE) geo_fwd_epilogue<RPP, true>(acc, a_inv * sl[NT + t], bl + H + 32 * t, bl + 2 * H + 32 * t, beta, inv_beta, lane, a1blk + t * 1024, m, part_v, part_t);
   }
   if (ACTIVE) {
-    const float pq = quad_sum(part_v);  // the value row's dot: partials in the four lanes of the quad
+    const float pq = grp_sum<RPP>(part_v);  // the value row's dot: partials in the lanes of the group
     float part = j == 0 ? pq : part_t;
     part += __shfl_xor(part, 32, 64);  // the two lane halves hold different features of the same column
     m = fmaxf(m, __shfl_xor(m, 32, 64));
@@ -244,13 +282,13 @@ __device__ __forceinline__ void geo_fwd_tile(const GeoFwdArgs& a, WStream& ws, c
         a.sdf[n] = part + bl[3 * H];
         if (a.a1max) a.a1max[n] = m;
       } else {
-        a.grad[n * 3 + (j - 1)] = part;
+        a.grad[n * (RPP - 1) + (j - 1)] = part;
       }
     }
   }
 }
 
-template <int KS0>
+template <int KS0, int RPP = 4>
 __global__ __launch_bounds__(THREADS, 2) void field_geo_fwd_kernel(const GeoFwdArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[RING + (3 * H + 4 + 32) * 4];
   float* bl = reinterpret_cast<float*>(smem + RING);  // b0 | b1 | w_sdf | b_sdf
@@ -266,8 +304,8 @@ __global__ __launch_bounds__(THREADS, 2) void field_geo_fwd_kernel(const GeoFwdA
   const long G = gridDim.x;
   for (long base = 0; base < a.n_tiles; base += WAVES * G) {
     const long tile = base + wave * G + blockIdx.x;
-    if (tile < a.n_tiles) geo_fwd_tile<KS0, true>(a, ws, bl, sl, tile, lane);
-    else geo_fwd_tile<KS0, false>(a, ws, bl, sl, 0, lane);
+    if (tile < a.n_tiles) geo_fwd_tile<RPP, KS0, true>(a, ws, bl, sl, tile, lane);
+    else geo_fwd_tile<RPP, KS0, false>(a, ws, bl, sl, 0, lane);
   }
   ws_close();
 }
@@ -629,43 +667,47 @@ __global__ __launch_bounds__(THREADS, 2) void field_colour_bwd_kernel(const ColB
 }
 
 // =====================================================================================================================
-// geometry network backward, quad layout.  Stream: W1^T (NT tiles), W0^T (ceil(in_dim / 32) tiles); every K = H.
+// geometry network backward, quad (RPP = 4) or pair (RPP = 2) layout.  Stream: W1^T (NT tiles), W0^T (ceil(in_dim / 32) tiles); every
+// K = H.  Pair layout: g_grad is the [N, 1] gradient of the derivative along d, dET is stacked [dE; dTd].
 struct GeoBwdArgs {
   nsky_field_net net;
   const unsigned char* stream; const float* scales; int total_groups;
   int N, n_tiles;
   const float* g_sdf;          // [N] or null
-  const float* g_grad;         // [N, 3] or null
+  const float* g_grad;         // [N, RPP - 1] or null
   const float* da1v;           // native [ceil32(N), H] or null: gradient of the value rows of a1 from the colour path
   const float* dxpe;           // [N, 40] or null: added to the x / PE columns of the value rows of dET
   const float* a0q; const float* a1q;
-  float* d1q; float* d0q;      // quad-native [ceil32(4 N), H]
-  float* dET; int ldE;         // stacked [4 N, ldE]
+  float* d1q; float* d0q;      // group-native [ceil32(RPP N), H]
+  float* dET; int ldE;         // stacked [RPP N, ldE]
   float* gmax;                 // [2]: max |d1q|, |d0q| (caller zero-fills)
 };
 
 // reverse of one forward-mode softplus layer on a tile.  av: the saved layer outputs of this lane's column (value lane: a, tangent lanes:
 // ta_k); gin: the incoming gradient of those outputs -> dv: the pre-activation gradients (value lane: dz = da s + sum_k dta_k ta_k
 // beta (1 - s), tangent lanes: dtz_k = dta_k s), s = sigmoid(beta z) = 1 - exp(-beta a) recovered from the value row's saved output:
-// the exponentials are taken by the four lanes of the quad, four features each, and handed back to every lane.
+// the exponentials are taken by the lanes of the group, 16 / RPP features each, and handed back to every lane.  (Pair layout: the sum
+// over k has its one term.)
+template <int RPP>
 __device__ __forceinline__ void softplus_rev_tile(const float (&av)[16], const float (&gin)[16], float beta, int j, float (&dv)[16]) {
-  float a4[4], e4[4], E[16];
-  quad_scatter_value(av, j, a4);
+  constexpr int VPL = 16 / RPP;
+  float a4[VPL], e4[VPL], E[16];
+  grp_scatter_value<RPP>(av, j, a4);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) e4[q] = __expf(-beta * a4[q]);  // 1 - sigmoid(beta z)
-  quad_gather_all(e4, E);
+  for (int q = 0; q < VPL; ++q) e4[q] = __expf(-beta * a4[q]);  // 1 - sigmoid(beta z)
+  grp_gather_all<RPP>(e4, E);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const float cross = quad_sum(j == 0 ? 0.0f : gin[r] * av[r] * (beta * E[r]));
+    const float cross = grp_sum<RPP>(j == 0 ? 0.0f : gin[r] * av[r] * (beta * E[r]));
     const float s = 1.0f - E[r];
     dv[r] = j == 0 ? fmaf(gin[r], s, cross) : gin[r] * s;
   }
 }
 
-template <bool ACTIVE>
+template <int RPP, bool ACTIVE>
 __device__ __forceinline__ void geo_bwd_tile(const GeoBwdArgs& a, WStream& ws, const float* wl, const float* sl, long tile, int lane, int ct) {
-  const int c = lane & 31, h = lane >> 5, p = c >> 2, j = c & 3;
-  const long n = tile * 8 + p;
+  const int c = lane & 31, h = lane >> 5, p = c / RPP, j = c & (RPP - 1);
+  const long n = tile * (32 / RPP) + p;
   const bool live = ACTIVE && n < a.N;
   const long nc = n < a.N ? n : a.N - 1;
   const float beta = a.net.beta;
@@ -676,7 +718,7 @@ __device__ __forceinline__ void geo_bwd_tile(const GeoBwdArgs& a, WStream& ws, c
   if (ACTIVE) {
     // gradient of the sdf row's output: the value lane carries g_sdf, tangent lane k carries g_grad[k]
     float gq = 0.0f;
-    if (live) gq = j == 0 ? (a.g_sdf ? a.g_sdf[nc] : 0.0f) : (a.g_grad ? a.g_grad[nc * 3 + (j - 1)] : 0.0f);
+    if (live) gq = j == 0 ? (a.g_sdf ? a.g_sdf[nc] : 0.0f) : (a.g_grad ? a.g_grad[nc * (RPP - 1) + (j - 1)] : 0.0f);
     const float* dap = a.da1v ? a.da1v + ((nc >> 5) * NT) * 1024 + ((int)(nc & 31) + 32 * h) * 4 : nullptr;
     float avn[16];
     float4 ddn[4];
@@ -706,7 +748,7 @@ __device__ __forceinline__ void geo_bwd_tile(const GeoBwdArgs& a, WStream& ws, c
 #pragma unroll
         for (int q = 0; q < 4; ++q) gin[4 * g + q] = fmaf(gq, ww[q], dd[q]);
       }
-      softplus_rev_tile(av, gin, beta, j, dv);
+      softplus_rev_tile<RPP>(av, gin, beta, j, dv);
 #pragma unroll
       for (int r = 0; r < 16; ++r) m = fmaxf(m, fabsf(live ? dv[r] : 0.0f));
       store_tile(d1blk + t * 1024, lane, dv);
@@ -738,7 +780,7 @@ __device__ __forceinline__ void geo_bwd_tile(const GeoBwdArgs& a, WStream& ws, c
         av[r] = aq[r >> 2][r & 3];
         gin[r] = acc[r] * inv;
       }
-      softplus_rev_tile(av, gin, beta, j, dv);
+      softplus_rev_tile<RPP>(av, gin, beta, j, dv);
 #pragma unroll
       for (int r = 0; r < 16; ++r) m = fmaxf(m, fabsf(live ? dv[r] : 0.0f));
       store_tile(d0blk + u * 1024, lane, dv);
@@ -774,6 +816,7 @@ __device__ __forceinline__ void geo_bwd_tile(const GeoBwdArgs& a, WStream& ws, c
   }
 }
 
+template <int RPP = 4>
 __global__ __launch_bounds__(THREADS, 2) void field_geo_bwd_kernel(const GeoBwdArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[RING + (H + 32) * 4];
   float* wl = reinterpret_cast<float*>(smem + RING);  // w_sdf
@@ -789,8 +832,8 @@ __global__ __launch_bounds__(THREADS, 2) void field_geo_bwd_kernel(const GeoBwdA
   const long G = gridDim.x;
   for (long base = 0; base < a.n_tiles; base += WAVES * G) {
     const long tile = base + wave * G + blockIdx.x;
-    if (tile < a.n_tiles) geo_bwd_tile<true>(a, ws, wl, sl, tile, lane, ct);
-    else geo_bwd_tile<false>(a, ws, wl, sl, 0, lane, ct);
+    if (tile < a.n_tiles) geo_bwd_tile<RPP, true>(a, ws, wl, sl, tile, lane, ct);
+    else geo_bwd_tile<RPP, false>(a, ws, wl, sl, 0, lane, ct);
   }
   ws_close();
 }
@@ -798,12 +841,14 @@ __global__ __launch_bounds__(THREADS, 2) void field_geo_bwd_kernel(const GeoBwdA
 // =====================================================================================================================
 // out[o][f] += sum_rows w[row][o] X[row][f] over a tile-native X [rows, 32 nt] (o < n_out <= 4): the weight gradients of the
 // field's narrow output layers (the sdf row: 1 output over the quad-native a1; the albedo rows: 3 outputs over c1).
-// quad weights: w(row) = g_sdf[row >> 2] for row & 3 == 0, g_grad[row >> 2][(row & 3) - 1] otherwise (one output);
-// bias[o] += sum_rows w[row][o] (quad form: value rows only).
+// quad weights: w(row) = g_sdf[row >> 2] for row & 3 == 0, g_grad[row >> 2][(row & 3) - 1] otherwise (one output); pair weights (rpp = 2):
+// w(row) = g_sdf[row >> 1] for even rows, g_grad[row >> 1] for odd rows;
+// bias[o] += sum_rows w[row][o] (quad / pair form: value rows only).
 struct ColsumArgs {
   const float* X; int nt; int rows;
   const float* w4; int n_out;                  // [rows, 4] row-major, or null for the quad form
-  const float* g_sdf; const float* g_grad;     // quad form ([rows / 4], [rows / 4, 3]; either may be null)
+  const float* g_sdf; const float* g_grad;     // quad / pair form ([rows / rpp], [rows / rpp, rpp - 1]; either may be null)
+  int rpp;                                     // rows per point of that form: 4 or 2
   float* out; int ldo; float* bias;
   int blocks_per_wg;
 };
@@ -834,9 +879,9 @@ __global__ __launch_bounds__(512) void native_weighted_colsum_kernel(const Colsu
               const float4 q = ldg4(a.w4 + row * 4);
               w[u][0] = q.x; w[u][1] = q.y; w[u][2] = q.z; w[u][3] = q.w;
             } else {
-              const int j = (int)(row & 3);
-              const long n = row >> 2;
-              w[u][0] = j == 0 ? (a.g_sdf ? a.g_sdf[n] : 0.0f) : (a.g_grad ? a.g_grad[n * 3 + (j - 1)] : 0.0f);
+              const int j = (int)(row & (a.rpp - 1));
+              const long n = row >> (a.rpp == 4 ? 2 : 1);
+              w[u][0] = j == 0 ? (a.g_sdf ? a.g_sdf[n] : 0.0f) : (a.g_grad ? a.g_grad[n * (a.rpp - 1) + (j - 1)] : 0.0f);
               if (j == 0) bs[0] += w[u][0];
             }
           }
@@ -923,22 +968,36 @@ extern "C" int nsky_chain_pack(const nsky_chain_layer* layers, int32_t n_layers,
 
 #define NSKY_AL16(p) (((uintptr_t)(p) % 16) == 0)
 
+// rpp: rows per point, 4 (quad layout) or 2 (pair layout)
+static int field_geo_fwd_launch(int rpp, const char* who, const nsky_field_net* net, const void* stream_buf, const float* scales, int32_t total_groups,
+                                const float* ET, int32_t ldE, int32_t N, float* a0q, float* a1q, float* Eq, float* a1max, float* sdf, float* grad,
+                                float* qmax, nsky_stream_t stream) {
+  if (int rc = check_field_net(net, who)) return rc;
+  NSKY_CHECK_ARG(stream_buf && scales && ET && a0q && a1q && sdf && grad && N > 0 && net->b0 && net->b1 && net->w_sdf, "%s: null operand / empty batch", who);
+  NSKY_CHECK_ARG(ldE % 4 == 0 && ldE >= net->in_dim && NSKY_AL16(ET) && NSKY_AL16(a0q) && NSKY_AL16(a1q) && NSKY_AL16(stream_buf) && (!Eq || NSKY_AL16(Eq)),
+                 "%s: alignment / ldE", who);
+  NSKY_CHECK_ARG(ksteps_of(net->in_dim) == 5, "%s: encode rows of 68..80 columns expected, got %d", who, net->in_dim);
+  NSKY_CHECK_ARG(total_groups == NT * groups_of(net->in_dim) + NT * groups_of(H), "%s: stream of %d groups does not hold W0, W1", who, total_groups);
+  GeoFwdArgs a;
+  a.net = *net; a.stream = (const unsigned char*)stream_buf; a.scales = scales; a.total_groups = total_groups; a.ET = ET; a.ldE = ldE; a.N = N;
+  a.n_tiles = ceil_div(N, 32 / rpp); a.a0q = a0q; a.a1q = a1q; a.Eq = Eq; a.a1max = a1max; a.sdf = sdf; a.grad = grad; a.qmax = qmax;
+  const dim3 grid(persistent_grid(a.n_tiles));
+  if (rpp == 4) hipLaunchKernelGGL((field_geo_fwd_kernel<5, 4>), grid, dim3(THREADS), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((field_geo_fwd_kernel<5, 2>), grid, dim3(THREADS), 0, (hipStream_t)stream, a);
+  NSKY_CHECK_LAUNCH(who);
+  return NSKY_OK;
+}
+
 extern "C" int nsky_field_geo_fwd(const nsky_field_net* net, const void* stream_buf, const float* scales, int32_t total_groups, const float* ET,
                                   int32_t ldE, int32_t N, float* a0q, float* a1q, float* Eq, float* a1max, float* sdf, float* grad, float* qmax,
                                   nsky_stream_t stream) {
-  if (int rc = check_field_net(net, "nsky_field_geo_fwd")) return rc;
-  NSKY_CHECK_ARG(stream_buf && scales && ET && a0q && a1q && sdf && grad && N > 0 && net->b0 && net->b1 && net->w_sdf, "nsky_field_geo_fwd: null operand / empty batch");
-  NSKY_CHECK_ARG(ldE % 4 == 0 && ldE >= net->in_dim && NSKY_AL16(ET) && NSKY_AL16(a0q) && NSKY_AL16(a1q) && NSKY_AL16(stream_buf) && (!Eq || NSKY_AL16(Eq)),
-                 "nsky_field_geo_fwd: alignment / ldE");
-  NSKY_CHECK_ARG(ksteps_of(net->in_dim) == 5, "nsky_field_geo_fwd: encode rows of 68..80 columns expected, got %d", net->in_dim);
-  NSKY_CHECK_ARG(total_groups == NT * groups_of(net->in_dim) + NT * groups_of(H), "nsky_field_geo_fwd: stream of %d groups does not hold W0, W1", total_groups);
-  GeoFwdArgs a;
-  a.net = *net; a.stream = (const unsigned char*)stream_buf; a.scales = scales; a.total_groups = total_groups; a.ET = ET; a.ldE = ldE; a.N = N;
-  a.n_tiles = ceil_div(N, 8); a.a0q = a0q; a.a1q = a1q; a.Eq = Eq; a.a1max = a1max; a.sdf = sdf; a.grad = grad; a.qmax = qmax;
-  const dim3 grid(persistent_grid(a.n_tiles));
-  hipLaunchKernelGGL((field_geo_fwd_kernel<5>), grid, dim3(THREADS), 0, (hipStream_t)stream, a);
-  NSKY_CHECK_LAUNCH("nsky_field_geo_fwd");
-  return NSKY_OK;
+  return field_geo_fwd_launch(4, "nsky_field_geo_fwd", net, stream_buf, scales, total_groups, ET, ldE, N, a0q, a1q, Eq, a1max, sdf, grad, qmax, stream);
+}
+
+extern "C" int nsky_field_geo_fwd_dir(const nsky_field_net* net, const void* stream_buf, const float* scales, int32_t total_groups, const float* ET,
+                                      int32_t ldE, int32_t N, float* a0q, float* a1q, float* Eq, float* sdf, float* cosv, float* qmax,
+                                      nsky_stream_t stream) {
+  return field_geo_fwd_launch(2, "nsky_field_geo_fwd_dir", net, stream_buf, scales, total_groups, ET, ldE, N, a0q, a1q, Eq, nullptr, sdf, cosv, qmax, stream);
 }
 
 extern "C" int nsky_field_colour_fwd(const nsky_field_net* net, const void* stream_buf, const float* scales, int32_t total_groups, const float* ET,
@@ -975,33 +1034,59 @@ extern "C" int nsky_field_colour_bwd(const nsky_field_net* net, const void* stre
   return NSKY_OK;
 }
 
-extern "C" int nsky_field_geo_bwd(const nsky_field_net* net, const void* stream_buf, const float* scales, int32_t total_groups, int32_t N,
-                                  const float* g_sdf, const float* g_grad, const float* da1v, const float* dxpe, const float* a0q, const float* a1q,
-                                  float* d1q, float* d0q, float* dET, int32_t ldE, float* gmax, nsky_stream_t stream) {
-  if (int rc = check_field_net(net, "nsky_field_geo_bwd")) return rc;
-  NSKY_CHECK_ARG(stream_buf && scales && a0q && a1q && d1q && d0q && gmax && N > 0 && net->w_sdf, "nsky_field_geo_bwd: null operand / empty batch");
+static int field_geo_bwd_launch(int rpp, const char* who, const nsky_field_net* net, const void* stream_buf, const float* scales, int32_t total_groups,
+                                int32_t N, const float* g_sdf, const float* g_grad, const float* da1v, const float* dxpe, const float* a0q,
+                                const float* a1q, float* d1q, float* d0q, float* dET, int32_t ldE, float* gmax, nsky_stream_t stream) {
+  if (int rc = check_field_net(net, who)) return rc;
+  NSKY_CHECK_ARG(stream_buf && scales && a0q && a1q && d1q && d0q && gmax && N > 0 && net->w_sdf, "%s: null operand / empty batch", who);
   NSKY_CHECK_ARG(NSKY_AL16(a0q) && NSKY_AL16(a1q) && NSKY_AL16(d1q) && NSKY_AL16(d0q) && (!da1v || NSKY_AL16(da1v)) && (!dxpe || NSKY_AL16(dxpe)) &&
-                     (!dET || (NSKY_AL16(dET) && ldE % 4 == 0 && ldE >= net->in_dim)), "nsky_field_geo_bwd: alignment / ldE");
+                     (!dET || (NSKY_AL16(dET) && ldE % 4 == 0 && ldE >= net->in_dim)), "%s: alignment / ldE", who);
   const int ct = (net->in_dim + 31) / 32;
-  NSKY_CHECK_ARG(total_groups == (NT + ct) * groups_of(H), "nsky_field_geo_bwd: stream of %d groups does not hold W1^T, W0^T", total_groups);
+  NSKY_CHECK_ARG(total_groups == (NT + ct) * groups_of(H), "%s: stream of %d groups does not hold W1^T, W0^T", who, total_groups);
   GeoBwdArgs a;
-  a.net = *net; a.stream = (const unsigned char*)stream_buf; a.scales = scales; a.total_groups = total_groups; a.N = N; a.n_tiles = ceil_div(N, 8);
+  a.net = *net; a.stream = (const unsigned char*)stream_buf; a.scales = scales; a.total_groups = total_groups; a.N = N; a.n_tiles = ceil_div(N, 32 / rpp);
   a.g_sdf = g_sdf; a.g_grad = g_grad; a.da1v = da1v; a.dxpe = dxpe; a.a0q = a0q; a.a1q = a1q; a.d1q = d1q; a.d0q = d0q; a.dET = dET; a.ldE = ldE; a.gmax = gmax;
-  hipLaunchKernelGGL(field_geo_bwd_kernel, dim3(persistent_grid(a.n_tiles)), dim3(THREADS), 0, (hipStream_t)stream, a);
-  NSKY_CHECK_LAUNCH("nsky_field_geo_bwd");
+  const dim3 grid(persistent_grid(a.n_tiles));
+  if (rpp == 4) hipLaunchKernelGGL(field_geo_bwd_kernel<4>, grid, dim3(THREADS), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(field_geo_bwd_kernel<2>, grid, dim3(THREADS), 0, (hipStream_t)stream, a);
+  NSKY_CHECK_LAUNCH(who);
   return NSKY_OK;
 }
 
-extern "C" int nsky_native_weighted_colsum(const float* X, int32_t nt, int32_t rows, const float* w4, int32_t n_out, const float* g_sdf,
-                                           const float* g_grad, float* out, int32_t ldo, float* bias, nsky_stream_t stream) {
+extern "C" int nsky_field_geo_bwd(const nsky_field_net* net, const void* stream_buf, const float* scales, int32_t total_groups, int32_t N,
+                                  const float* g_sdf, const float* g_grad, const float* da1v, const float* dxpe, const float* a0q, const float* a1q,
+                                  float* d1q, float* d0q, float* dET, int32_t ldE, float* gmax, nsky_stream_t stream) {
+  return field_geo_bwd_launch(4, "nsky_field_geo_bwd", net, stream_buf, scales, total_groups, N, g_sdf, g_grad, da1v, dxpe, a0q, a1q, d1q, d0q, dET, ldE,
+                              gmax, stream);
+}
+
+extern "C" int nsky_field_geo_bwd_dir(const nsky_field_net* net, const void* stream_buf, const float* scales, int32_t total_groups, int32_t N,
+                                      const float* g_sdf, const float* g_cos, const float* a0q, const float* a1q, float* d1q, float* d0q, float* dET,
+                                      int32_t ldE, float* gmax, nsky_stream_t stream) {
+  return field_geo_bwd_launch(2, "nsky_field_geo_bwd_dir", net, stream_buf, scales, total_groups, N, g_sdf, g_cos, nullptr, nullptr, a0q, a1q, d1q, d0q,
+                              dET, ldE, gmax, stream);
+}
+
+static int weighted_colsum_launch(int rpp, const float* X, int32_t nt, int32_t rows, const float* w4, int32_t n_out, const float* g_sdf,
+                                  const float* g_grad, float* out, int32_t ldo, float* bias, nsky_stream_t stream) {
   NSKY_CHECK_ARG(X && out && nt >= 1 && rows >= 0 && NSKY_AL16(X) && ldo >= 32 * nt, "nsky_native_weighted_colsum: bad argument");
-  NSKY_CHECK_ARG(w4 ? (n_out >= 1 && n_out <= 4 && NSKY_AL16(w4)) : (n_out == 1 && rows % 4 == 0), "nsky_native_weighted_colsum: weights (n_out %d)", n_out);
+  NSKY_CHECK_ARG(w4 ? (n_out >= 1 && n_out <= 4 && NSKY_AL16(w4)) : (n_out == 1 && rows % rpp == 0), "nsky_native_weighted_colsum: weights (n_out %d)", n_out);
   if (rows == 0) return NSKY_OK;
   ColsumArgs a;
-  a.X = X; a.nt = nt; a.rows = rows; a.w4 = w4; a.n_out = n_out; a.g_sdf = g_sdf; a.g_grad = g_grad; a.out = out; a.ldo = ldo; a.bias = bias;
+  a.X = X; a.nt = nt; a.rows = rows; a.w4 = w4; a.n_out = n_out; a.g_sdf = g_sdf; a.g_grad = g_grad; a.rpp = rpp; a.out = out; a.ldo = ldo; a.bias = bias;
   const int row_blocks = ceil_div(rows, 32);
   a.blocks_per_wg = ceil_div(row_blocks, 256);  // one workgroup per CU: every one ends with 512 n_out atomics onto the same 256 n_out addresses
   hipLaunchKernelGGL(native_weighted_colsum_kernel, dim3(ceil_div(row_blocks, a.blocks_per_wg)), dim3(512), 0, (hipStream_t)stream, a);
   NSKY_CHECK_LAUNCH("nsky_native_weighted_colsum");
   return NSKY_OK;
+}
+
+extern "C" int nsky_native_weighted_colsum(const float* X, int32_t nt, int32_t rows, const float* w4, int32_t n_out, const float* g_sdf,
+                                           const float* g_grad, float* out, int32_t ldo, float* bias, nsky_stream_t stream) {
+  return weighted_colsum_launch(4, X, nt, rows, w4, n_out, g_sdf, g_grad, out, ldo, bias, stream);
+}
+
+extern "C" int nsky_native_weighted_colsum_pair(const float* X, int32_t nt, int32_t rows, const float* g_sdf, const float* g_cos, float* out,
+                                                int32_t ldo, float* bias, nsky_stream_t stream) {
+  return weighted_colsum_launch(2, X, nt, rows, nullptr, 1, g_sdf, g_cos, out, ldo, bias, stream);
 }

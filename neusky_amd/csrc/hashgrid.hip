@@ -1,6 +1,7 @@
 // Multiresolution hash-grid encode (tiny-cuda-nn HashGrid semantics, fp32 table) fused with the rest
 // of the MLP input row (raw position, NeRF positional encoding) and, optionally, the forward-mode
-// input Jacobian (three tangent rows per point).
+// input Jacobian (three tangent rows per point; or, directional mode, ONE: its contraction with a
+// per-ray direction).
 //
 // Work decomposition: a workgroup = 4 waves owns 64 consecutive points; lane = point, wave w walks
 // levels w, w+4, w+8, w+12 so that a wave-instruction's 64 gathers all hit ONE level's slab of the
@@ -130,10 +131,13 @@ __host__ __device__ __forceinline__ int row_width(int include_x, int pe_freqs, i
   return (include_x ? 3 : 0) + 6 * pe_freqs + 2 * n_levels;
 }
 
-template <bool TANGENTS>
+// DIR (with TANGENTS): ONE tangent row per point, Td = sum_a d_a T_a along the direction d = dirs[p / spr] (rays of spr samples), formed
+// from the three per-axis terms while they are in registers; T is then [P, ldy].
+template <bool TANGENTS, bool DIR = false>
 __global__ __launch_bounds__(256) void encode_fwd_kernel(Grid g, const float* __restrict__ x, int P, int mode, int include_x,
-                                                         int pe_freqs, float pe_max_exp, float* __restrict__ Y, int ldy, float* __restrict__ T) {
-  constexpr int NT = TANGENTS ? 4 : 1;
+                                                         int pe_freqs, float pe_max_exp, float* __restrict__ Y, int ldy, float* __restrict__ T,
+                                                         const float* __restrict__ dirs = nullptr, int spr = 1) {
+  constexpr int NT = TANGENTS ? (DIR ? 2 : 4) : 1;
   __shared__ float S[NT][PB][LDS_LD];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int p = blockIdx.x * PB + lane;
@@ -145,6 +149,11 @@ __global__ __launch_bounds__(256) void encode_fwd_kernel(Grid g, const float* __
   if (valid) { xv[0] = x[(long)p * 3]; xv[1] = x[(long)p * 3 + 1]; xv[2] = x[(long)p * 3 + 2]; }
   float pos[3], J[3][3];
   grid_position(xv, mode, pos, J);
+  float dv[3] = {0.f, 0.f, 0.f};
+  if (DIR && valid) {
+    const long r = p / spr;
+    dv[0] = dirs[r * 3]; dv[1] = dirs[r * 3 + 1]; dv[2] = dirs[r * 3 + 2];
+  }
 
   // zero the pad columns and (wave 0) fill x / PE
   for (int c = width + wave; c < ldy && c < MAXW; c += 4)
@@ -154,7 +163,8 @@ __global__ __launch_bounds__(256) void encode_fwd_kernel(Grid g, const float* __
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       S[0][lane][a] = xv[a];
-      if (TANGENTS)
+      if (TANGENTS && DIR) S[1][lane][a] = dv[a];
+      if (TANGENTS && !DIR)
 #pragma unroll
         for (int k = 0; k < 3; ++k) S[1 + k][lane][a] = (a == k) ? 1.0f : 0.0f;
     }
@@ -172,10 +182,15 @@ __global__ __launch_bounds__(256) void encode_fwd_kernel(Grid g, const float* __
       S[0][lane][pe0 + npe + c] = sinf(arg2);
       if (TANGENTS) {
         const float d1 = cosf(arg) * TWO_PI * freq, d2 = cosf(arg2) * TWO_PI * freq;
+        if (DIR) {
+          S[1][lane][pe0 + c] = dv[i] * d1;
+          S[1][lane][pe0 + npe + c] = dv[i] * d2;
+        } else {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          S[1 + k][lane][pe0 + c] = (i == k) ? d1 : 0.0f;
-          S[1 + k][lane][pe0 + npe + c] = (i == k) ? d2 : 0.0f;
+          for (int k = 0; k < 3; ++k) {
+            S[1 + k][lane][pe0 + c] = (i == k) ? d1 : 0.0f;
+            S[1 + k][lane][pe0 + npe + c] = (i == k) ? d2 : 0.0f;
+          }
         }
       }
     }
@@ -223,10 +238,21 @@ __global__ __launch_bounds__(256) void encode_fwd_kernel(Grid g, const float* __
     S[0][lane][feat0 + 2 * level] = f0;
     S[0][lane][feat0 + 2 * level + 1] = f1;
     if (TANGENTS) {
+      float t0[3], t1[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        S[1 + k][lane][feat0 + 2 * level] = d0[0] * J[0][k] + d0[1] * J[1][k] + d0[2] * J[2][k];
-        S[1 + k][lane][feat0 + 2 * level + 1] = d1[0] * J[0][k] + d1[1] * J[1][k] + d1[2] * J[2][k];
+        t0[k] = d0[0] * J[0][k] + d0[1] * J[1][k] + d0[2] * J[2][k];
+        t1[k] = d1[0] * J[0][k] + d1[1] * J[1][k] + d1[2] * J[2][k];
+      }
+      if (DIR) {
+        S[1][lane][feat0 + 2 * level] = dv[0] * t0[0] + dv[1] * t0[1] + dv[2] * t0[2];
+        S[1][lane][feat0 + 2 * level + 1] = dv[0] * t1[0] + dv[1] * t1[1] + dv[2] * t1[2];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          S[1 + k][lane][feat0 + 2 * level] = t0[k];
+          S[1 + k][lane][feat0 + 2 * level + 1] = t1[k];
+        }
       }
     }
   }
@@ -237,7 +263,8 @@ __global__ __launch_bounds__(256) void encode_fwd_kernel(Grid g, const float* __
   for (int idx = threadIdx.x; idx < nrows * wcols; idx += 256) {
     const int r = idx / wcols, c = idx % wcols;
     Y[(long)(p0 + r) * ldy + c] = S[0][r][c];
-    if (TANGENTS)
+    if (TANGENTS && DIR) T[(long)(p0 + r) * ldy + c] = S[1][r][c];
+    if (TANGENTS && !DIR)
 #pragma unroll
       for (int k = 0; k < 3; ++k) T[((long)k * P + p0 + r) * ldy + c] = S[1 + k][r][c];
   }
@@ -355,7 +382,7 @@ struct CornerTerm {
 template <bool TANGENTS>
 __device__ __forceinline__ CornerTerm corner_term(const Grid& g, int level, int k, int f, const float pos[3], const float J[3][3],
                                                   const float* __restrict__ dY, const float* __restrict__ dT, int P, int p,
-                                                  int lddy, int feat0) {
+                                                  int lddy, int feat0, const float* __restrict__ dirs = nullptr, int spr = 1) {
   const float scale = g.scale[level];
   const uint32_t res = (uint32_t)g.resolution[level];
   const uint32_t size = g.offset[level + 1] - g.offset[level];
@@ -381,7 +408,8 @@ __device__ __forceinline__ CornerTerm corner_term(const Grid& g, int level, int 
     const float cz = ((k & 4) ? dw[2] : -dw[2]) * wx * wy;
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
-      const float gt = dT[((long)t * P + p) * lddy + col];
+      // directional call (dirs): dT is the ONE row-set dTd [P, lddy] and dT_t = d_t dTd
+      const float gt = dirs ? dirs[(long)(p / spr) * 3 + t] * dT[(long)p * lddy + col] : dT[((long)t * P + p) * lddy + col];
       a = fmaf(gt, cx * J[0][t] + cy * J[1][t] + cz * J[2][t], a);
     }
   }
@@ -394,7 +422,7 @@ template <bool TANGENTS>
 __global__ __launch_bounds__(256) void encode_bwd_scatter_kernel(Grid g, const float* __restrict__ x, int P, int mode, int feat0,
                                                                  const float* __restrict__ dY, int lddy,
                                                                  const float* __restrict__ dT, float* __restrict__ dtable,
-                                                                 int level0) {
+                                                                 int level0, const float* __restrict__ dirs, int spr) {
   const int p = blockIdx.x * 16 + (threadIdx.x >> 4);
   if (p >= P) return;
   const int k = (threadIdx.x >> 1) & 7, f = threadIdx.x & 1;
@@ -402,7 +430,7 @@ __global__ __launch_bounds__(256) void encode_bwd_scatter_kernel(Grid g, const f
   const float xv[3] = {x[(long)p * 3], x[(long)p * 3 + 1], x[(long)p * 3 + 2]};
   float pos[3], J[3][3];
   grid_position(xv, mode, pos, J);
-  const CornerTerm ct = corner_term<TANGENTS>(g, level, k, f, pos, J, dY, dT, P, p, lddy, feat0);
+  const CornerTerm ct = corner_term<TANGENTS>(g, level, k, f, pos, J, dY, dT, P, p, lddy, feat0, dirs, spr);
   atomicAdd(dtable + 2l * ct.idx + f, ct.a);
 }
 
@@ -411,7 +439,7 @@ template <bool TANGENTS>
 __global__ __launch_bounds__(256) void encode_bwd_coarse_kernel(Grid g, const float* __restrict__ x, int P, int mode, int feat0,
                                                                 const float* __restrict__ dY, int lddy,
                                                                 const float* __restrict__ dT, float* __restrict__ dtable,
-                                                                int n_coarse, int points_per_block) {
+                                                                int n_coarse, int points_per_block, const float* __restrict__ dirs, int spr) {
   extern __shared__ float acc[];  // 2 * offset[n_coarse] floats
   const int nflt = 2 * (int)g.offset[n_coarse];
   for (int i = threadIdx.x; i < nflt; i += 256) acc[i] = 0.0f;
@@ -424,7 +452,7 @@ __global__ __launch_bounds__(256) void encode_bwd_coarse_kernel(Grid g, const fl
     float pos[3], J[3][3];
     grid_position(xv, mode, pos, J);
     for (int level = 0; level < n_coarse; ++level) {
-      const CornerTerm ct = corner_term<TANGENTS>(g, level, k, f, pos, J, dY, dT, P, p, lddy, feat0);
+      const CornerTerm ct = corner_term<TANGENTS>(g, level, k, f, pos, J, dY, dT, P, p, lddy, feat0, dirs, spr);
       atomicAdd(acc + 2 * ct.idx + f, ct.a);  // ds_add_f32
     }
   }
@@ -484,8 +512,9 @@ constexpr uint32_t HASH_P1 = 2654435761u, HASH_P2 = 805459861u;
 // Tangent calls: an owner needs dY and the three dT column pairs of its level for 1 point in 8 -- four 8-byte pieces from four rows
 // 288 bytes apart and a batch apart (measured: 2.2 GB of HBM / Infinity-Cache fetches per 98 304-point call, the kernel's bound).  One
 // pass packs them level-major, 32 bytes per (level, point), so that an entry is one aligned 32-byte read.
+// Directional calls (dirs): dT is the one row-set dTd [P, lddy]; the same record is written with dT_a = d_a dTd, so the owners run unchanged.
 __global__ __launch_bounds__(256) void owner_pack_kernel(const float* __restrict__ dY, const float* __restrict__ dT, int P, int lddy, int feat0,
-                                                         int n_levels, float* __restrict__ packed) {
+                                                         int n_levels, float* __restrict__ packed, const float* __restrict__ dirs, int spr) {
   // a wave: 4 points x 16 levels (lanes = (point, level): the 16 level pairs of a row are 128 contiguous bytes)
   const int lane = threadIdx.x & 63;
   const long p = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
@@ -493,9 +522,15 @@ __global__ __launch_bounds__(256) void owner_pack_kernel(const float* __restrict
   if (p >= P || l >= n_levels) return;
   const long o = p * lddy + feat0 + 2 * l;
   const float2 gy = load2(dY + o);
-  const float2 g0 = load2(dT + o);
-  const float2 g1 = load2(dT + (long)P * lddy + o);
-  const float2 g2 = load2(dT + 2l * P * lddy + o);
+  float2 g0 = load2(dT + o), g1, g2;
+  if (dirs) {
+    const float* d = dirs + (p / spr) * 3;
+    const float2 gd = g0;
+    g0 = make_float2(d[0] * gd.x, d[0] * gd.y); g1 = make_float2(d[1] * gd.x, d[1] * gd.y); g2 = make_float2(d[2] * gd.x, d[2] * gd.y);
+  } else {
+    g1 = load2(dT + (long)P * lddy + o);
+    g2 = load2(dT + 2l * P * lddy + o);
+  }
   float4* dst = reinterpret_cast<float4*>(packed + ((long)l * P + p) * 8);
   dst[0] = make_float4(gy.x, gy.y, g0.x, g0.y);
   dst[1] = make_float4(g1.x, g1.y, g2.x, g2.y);
@@ -812,22 +847,38 @@ int make_grid(const nsky_hashgrid_desc* d, Grid& g, const char* who) {
 
 }  // namespace
 
-extern "C" int nsky_encode_fwd(const nsky_hashgrid_desc* d, const float* x, int32_t P, int32_t mode, int32_t include_x,
-                               int32_t pe_freqs, float pe_max_exp, float* Y, int32_t ldy, float* T, nsky_stream_t stream) {
+// dirs: null, or the directional mode's [ceil(P / spr), 3] directions (T is then the one row-set Td [P, ldy])
+static int encode_fwd_launch(const nsky_hashgrid_desc* d, const float* x, int32_t P, int32_t mode, int32_t include_x, int32_t pe_freqs,
+                             float pe_max_exp, float* Y, int32_t ldy, float* T, const float* dirs, int32_t spr, nsky_stream_t stream) {
   Grid g;
   if (int rc = make_grid(d, g, "nsky_encode_fwd")) return rc;
   if (P == 0) return NSKY_OK;
   NSKY_CHECK_ARG(x && Y && P > 0, "nsky_encode_fwd: null x/Y or negative P");
+  NSKY_CHECK_ARG(!dirs || (T && spr >= 1), "nsky_encode_fwd_dir: directions without a tangent row-set, or spr %d < 1", spr);
   NSKY_CHECK_ARG(mode >= 0 && mode <= 2 && pe_freqs >= 0 && pe_freqs <= 6, "nsky_encode_fwd: bad mode/pe_freqs");
   const int width = row_width(include_x, pe_freqs, g.n_levels);
   NSKY_CHECK_ARG(width <= MAXW && ldy >= width && ldy <= MAXW, "nsky_encode_fwd: row width %d / ldy %d unsupported (max %d)", width, ldy, MAXW);
   dim3 grid(ceil_div(P, PB));
-  if (T)
+  if (dirs)
+    hipLaunchKernelGGL((encode_fwd_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, g, x, P, mode, include_x, pe_freqs, pe_max_exp, Y, ldy, T,
+                       dirs, spr);
+  else if (T)
     hipLaunchKernelGGL(encode_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g, x, P, mode, include_x, pe_freqs, pe_max_exp, Y, ldy, T);
   else
     hipLaunchKernelGGL(encode_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, g, x, P, mode, include_x, pe_freqs, pe_max_exp, Y, ldy, T);
   NSKY_CHECK_LAUNCH("nsky_encode_fwd");
   return NSKY_OK;
+}
+
+extern "C" int nsky_encode_fwd(const nsky_hashgrid_desc* d, const float* x, int32_t P, int32_t mode, int32_t include_x,
+                               int32_t pe_freqs, float pe_max_exp, float* Y, int32_t ldy, float* T, nsky_stream_t stream) {
+  return encode_fwd_launch(d, x, P, mode, include_x, pe_freqs, pe_max_exp, Y, ldy, T, nullptr, 1, stream);
+}
+
+extern "C" int nsky_encode_fwd_dir(const nsky_hashgrid_desc* d, const float* x, int32_t P, int32_t mode, int32_t include_x, int32_t pe_freqs,
+                                   float pe_max_exp, const float* dirs, int32_t spr, float* Y, int32_t ldy, float* Td, nsky_stream_t stream) {
+  NSKY_CHECK_ARG(dirs && Td, "nsky_encode_fwd_dir: null directions / Td");
+  return encode_fwd_launch(d, x, P, mode, include_x, pe_freqs, pe_max_exp, Y, ldy, Td, dirs, spr, stream);
 }
 
 static bool owner_geometry_ok(const Grid& g) {  // every level: at most 32 chunks; hashed slabs of 2^T entries (tcnn's geometry)
@@ -850,9 +901,10 @@ extern "C" int64_t nsky_encode_bwd_workspace_bytes(const nsky_hashgrid_desc* d, 
   return owner_bitmap_bytes(g, P) + (tangents ? (int64_t)g.n_levels * P * 8 * (int64_t)sizeof(float) : 0);  // bitmaps | packed gradients
 }
 
-extern "C" int nsky_encode_bwd(const nsky_hashgrid_desc* d, const float* x, int32_t P, int32_t mode, int32_t include_x,
-                               int32_t pe_freqs, float pe_max_exp, const float* dY, int32_t lddy, const float* dT, float* dtable,
-                               float* dx, void* workspace, nsky_stream_t stream) {
+// dirs: null, or the directional mode's [ceil(P / spr), 3] directions (dT is then the one row-set dTd [P, lddy]; no dx)
+static int encode_bwd_launch(const nsky_hashgrid_desc* d, const float* x, int32_t P, int32_t mode, int32_t include_x, int32_t pe_freqs,
+                             float pe_max_exp, const float* dY, int32_t lddy, const float* dT, float* dtable, float* dx, void* workspace,
+                             const float* dirs, int32_t spr, nsky_stream_t stream) {
   Grid g;
   if (int rc = make_grid(d, g, "nsky_encode_bwd")) return rc;
   if (P == 0) return NSKY_OK;
@@ -870,7 +922,7 @@ extern "C" int nsky_encode_bwd(const nsky_hashgrid_desc* d, const float* x, int3
     oa.packed = nullptr;
     if (dT) {
       float* packed = reinterpret_cast<float*>(static_cast<char*>(workspace) + owner_bitmap_bytes(g, P));
-      hipLaunchKernelGGL(owner_pack_kernel, dim3(ceil_div(P, 16)), dim3(256), 0, s, dY, dT, P, lddy, feat0, g.n_levels, packed);
+      hipLaunchKernelGGL(owner_pack_kernel, dim3(ceil_div(P, 16)), dim3(256), 0, s, dY, dT, P, lddy, feat0, g.n_levels, packed, dirs, spr);
       oa.packed = packed;
     }
     oa.words = ceil_div(P, BM_POINTS) * (BM_POINTS / 32);
@@ -930,18 +982,18 @@ extern "C" int nsky_encode_bwd(const nsky_hashgrid_desc* d, const float* x, int3
       }();
       (void)attr_set;
       if (dT) {
-        hipLaunchKernelGGL(encode_bwd_coarse_kernel<true>, grid, dim3(256), smem, s, g, x, P, mode, feat0, dY, lddy, dT, dtable, n_coarse, ppb);
+        hipLaunchKernelGGL(encode_bwd_coarse_kernel<true>, grid, dim3(256), smem, s, g, x, P, mode, feat0, dY, lddy, dT, dtable, n_coarse, ppb, dirs, spr);
       } else {
-        hipLaunchKernelGGL(encode_bwd_coarse_kernel<false>, grid, dim3(256), smem, s, g, x, P, mode, feat0, dY, lddy, dT, dtable, n_coarse, ppb);
+        hipLaunchKernelGGL(encode_bwd_coarse_kernel<false>, grid, dim3(256), smem, s, g, x, P, mode, feat0, dY, lddy, dT, dtable, n_coarse, ppb, dirs, spr);
       }
       NSKY_CHECK_LAUNCH("nsky_encode_bwd(coarse)");
     }
     if (n_coarse < g.n_levels) {
       dim3 grid(ceil_div(P, 16), g.n_levels - n_coarse);
       if (dT)
-        hipLaunchKernelGGL(encode_bwd_scatter_kernel<true>, grid, dim3(256), 0, s, g, x, P, mode, feat0, dY, lddy, dT, dtable, n_coarse);
+        hipLaunchKernelGGL(encode_bwd_scatter_kernel<true>, grid, dim3(256), 0, s, g, x, P, mode, feat0, dY, lddy, dT, dtable, n_coarse, dirs, spr);
       else
-        hipLaunchKernelGGL(encode_bwd_scatter_kernel<false>, grid, dim3(256), 0, s, g, x, P, mode, feat0, dY, lddy, dT, dtable, n_coarse);
+        hipLaunchKernelGGL(encode_bwd_scatter_kernel<false>, grid, dim3(256), 0, s, g, x, P, mode, feat0, dY, lddy, dT, dtable, n_coarse, dirs, spr);
       NSKY_CHECK_LAUNCH("nsky_encode_bwd(scatter)");
     }
   }
@@ -952,6 +1004,19 @@ extern "C" int nsky_encode_bwd(const nsky_hashgrid_desc* d, const float* x, int3
     NSKY_CHECK_LAUNCH("nsky_encode_bwd(dx)");
   }
   return NSKY_OK;
+}
+
+extern "C" int nsky_encode_bwd(const nsky_hashgrid_desc* d, const float* x, int32_t P, int32_t mode, int32_t include_x,
+                               int32_t pe_freqs, float pe_max_exp, const float* dY, int32_t lddy, const float* dT, float* dtable,
+                               float* dx, void* workspace, nsky_stream_t stream) {
+  return encode_bwd_launch(d, x, P, mode, include_x, pe_freqs, pe_max_exp, dY, lddy, dT, dtable, dx, workspace, nullptr, 1, stream);
+}
+
+extern "C" int nsky_encode_bwd_dir(const nsky_hashgrid_desc* d, const float* x, int32_t P, int32_t mode, int32_t include_x, int32_t pe_freqs,
+                                   float pe_max_exp, const float* dirs, int32_t spr, const float* dY, int32_t lddy, const float* dTd,
+                                   float* dtable, void* workspace, nsky_stream_t stream) {
+  NSKY_CHECK_ARG(dirs && dTd && dtable && spr >= 1, "nsky_encode_bwd_dir: null directions / dTd / dtable, or spr %d < 1", spr);
+  return encode_bwd_launch(d, x, P, mode, include_x, pe_freqs, pe_max_exp, dY, lddy, dTd, dtable, nullptr, workspace, dirs, spr, stream);
 }
 
 extern "C" int nsky_hash_indices(const nsky_hashgrid_desc* d, const float* x, int32_t P, int32_t mode, uint32_t* idx,

@@ -193,11 +193,11 @@ struct AlphaTerms {
   bool clip_pass;
 };
 
-__device__ __forceinline__ AlphaTerms neus_alpha_terms(float sdf, const float g[3], const float d[3], float delta, float inv_s,
-                                                      float anneal) {
+// cosv = d . grad(sdf), formed by the caller (neus_alpha_terms) or handed in as one precomputed column (the directional field pass)
+__device__ __forceinline__ AlphaTerms neus_alpha_terms_cos(float sdf, float cosv, float delta, float inv_s, float anneal) {
   AlphaTerms t;
   t.inv_s = inv_s;
-  t.cosv = d[0] * g[0] + d[1] * g[1] + d[2] * g[2];
+  t.cosv = cosv;
   t.ic = -(fmaxf(-t.cosv * 0.5f + 0.5f, 0.0f) * (1.0f - anneal) + fmaxf(-t.cosv, 0.0f) * anneal);
   const float nxt = sdf + t.ic * delta * 0.5f, prv = sdf - t.ic * delta * 0.5f;
   t.prev_cdf = sigmoidf_(prv * inv_s);
@@ -208,18 +208,25 @@ __device__ __forceinline__ AlphaTerms neus_alpha_terms(float sdf, const float g[
   return t;
 }
 
+__device__ __forceinline__ AlphaTerms neus_alpha_terms(float sdf, const float g[3], const float d[3], float delta, float inv_s,
+                                                      float anneal) {
+  return neus_alpha_terms_cos(sdf, d[0] * g[0] + d[1] * g[1] + d[2] * g[2], delta, inv_s, anneal);
+}
+
 __global__ __launch_bounds__(256) void neus_weights_fwd_kernel(const float* __restrict__ sdf, const float* __restrict__ grad,
                                                                const float* __restrict__ ray_dirs, const float* __restrict__ starts,
                                                                const float* __restrict__ ends, const float* __restrict__ variance,
                                                                float anneal, int R, int S, float* __restrict__ alpha_out,
                                                                float* __restrict__ weights, float* __restrict__ trans_bg,
-                                                               float* __restrict__ acc_out, float* __restrict__ depth_out) {
+                                                               float* __restrict__ acc_out, float* __restrict__ depth_out, int gcols) {
+  // gcols = 3: grad [R S, 3], cos = ray_dirs . grad; gcols = 1: grad [R S] is that cosine already (ray_dirs unused, may be null)
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
   const int CH = (S + 63) / 64;
   const float inv_s = fminf(fmaxf(expf(variance[0] * 10.0f), 1e-6f), 1e6f);
-  const float d[3] = {ray_dirs[(long)r * 3], ray_dirs[(long)r * 3 + 1], ray_dirs[(long)r * 3 + 2]};
+  float d[3] = {0.f, 0.f, 0.f};
+  if (gcols == 3) { d[0] = ray_dirs[(long)r * 3]; d[1] = ray_dirs[(long)r * 3 + 1]; d[2] = ray_dirs[(long)r * 3 + 2]; }
   float al[MAXCH], mid[MAXCH];
   float prod = 1.0f;
 #pragma unroll
@@ -228,9 +235,14 @@ __global__ __launch_bounds__(256) void neus_weights_fwd_kernel(const float* __re
     al[q] = 0.0f; mid[q] = 0.0f;
     if (q < CH && s < S) {
       const long o = (long)r * S + s;
-      const float g[3] = {grad[o * 3], grad[o * 3 + 1], grad[o * 3 + 2]};
       const float st = starts[o], en = ends[o];
-      AlphaTerms t = neus_alpha_terms(sdf[o], g, d, en - st, inv_s, anneal);
+      AlphaTerms t;
+      if (gcols == 3) {
+        const float g[3] = {grad[o * 3], grad[o * 3 + 1], grad[o * 3 + 2]};
+        t = neus_alpha_terms(sdf[o], g, d, en - st, inv_s, anneal);
+      } else {
+        t = neus_alpha_terms_cos(sdf[o], grad[o], en - st, inv_s, anneal);
+      }
       al[q] = t.alpha; mid[q] = 0.5f * (st + en);
       if (alpha_out) alpha_out[o] = t.alpha;
       prod *= (1.0f - t.alpha + 1e-7f);
@@ -264,7 +276,8 @@ __global__ __launch_bounds__(256) void neus_weights_bwd_kernel(const float* __re
                                                                const float* __restrict__ ends, const float* __restrict__ variance,
                                                                float anneal, int R, int S, const float* __restrict__ d_weights,
                                                                const float* __restrict__ d_trans_bg, float* __restrict__ d_sdf,
-                                                               float* __restrict__ d_grad, float* __restrict__ d_variance) {
+                                                               float* __restrict__ d_grad, float* __restrict__ d_variance, int gcols) {
+  // gcols as in the forward; gcols = 1: d_grad [R S] is the gradient of the cosine column
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -272,7 +285,8 @@ __global__ __launch_bounds__(256) void neus_weights_bwd_kernel(const float* __re
   const float e10 = expf(variance[0] * 10.0f);
   const float inv_s = fminf(fmaxf(e10, 1e-6f), 1e6f);
   const bool invs_pass = (e10 >= 1e-6f && e10 <= 1e6f);
-  const float d[3] = {ray_dirs[(long)r * 3], ray_dirs[(long)r * 3 + 1], ray_dirs[(long)r * 3 + 2]};
+  float d[3] = {0.f, 0.f, 0.f};
+  if (gcols == 3) { d[0] = ray_dirs[(long)r * 3]; d[1] = ray_dirs[(long)r * 3 + 1]; d[2] = ray_dirs[(long)r * 3 + 2]; }
   AlphaTerms tt[MAXCH];
   float sd[MAXCH], dl[MAXCH];
   float prod = 1.0f;
@@ -282,9 +296,13 @@ __global__ __launch_bounds__(256) void neus_weights_bwd_kernel(const float* __re
     tt[q].alpha = 0.f;
     if (q < CH && s < S) {
       const long o = (long)r * S + s;
-      const float g[3] = {grad[o * 3], grad[o * 3 + 1], grad[o * 3 + 2]};
       sd[q] = sdf[o]; dl[q] = ends[o] - starts[o];
-      tt[q] = neus_alpha_terms(sd[q], g, d, dl[q], inv_s, anneal);
+      if (gcols == 3) {
+        const float g[3] = {grad[o * 3], grad[o * 3 + 1], grad[o * 3 + 2]};
+        tt[q] = neus_alpha_terms(sd[q], g, d, dl[q], inv_s, anneal);
+      } else {
+        tt[q] = neus_alpha_terms_cos(sd[q], grad[o], dl[q], inv_s, anneal);
+      }
       prod *= (1.0f - tt[q].alpha + 1e-7f);
     }
   }
@@ -315,7 +333,7 @@ __global__ __launch_bounds__(256) void neus_weights_bwd_kernel(const float* __re
       const AlphaTerms& t = tt[q];
       float galpha = gw[q] * Tq[q] - suffix / (1.0f - t.alpha + 1e-7f);
       suffix = fmaf(gw[q], w[q], suffix);
-      float gs = 0.f, gg[3] = {0.f, 0.f, 0.f};
+      float gs = 0.f, gg[3] = {0.f, 0.f, 0.f}, gcos = 0.f;
       if (t.clip_pass) {
         // a = (p + e)/(c + e), p = c - n, c = prev_cdf, n = next_cdf
         const float den = t.prev_cdf + 1e-5f;
@@ -331,12 +349,13 @@ __global__ __launch_bounds__(256) void neus_weights_bwd_kernel(const float* __re
         float dic = 0.f;
         if (-t.cosv * 0.5f + 0.5f > 0.0f) dic += 0.5f * (1.0f - anneal);
         if (-t.cosv > 0.0f) dic += anneal;
-        const float gcos = gic * dic;
+        gcos = gic * dic;
         gg[0] = gcos * d[0]; gg[1] = gcos * d[1]; gg[2] = gcos * d[2];
       }
       const long o = (long)r * S + s;
       d_sdf[o] = gs;
-      d_grad[o * 3] = gg[0]; d_grad[o * 3 + 1] = gg[1]; d_grad[o * 3 + 2] = gg[2];
+      if (gcols == 3) { d_grad[o * 3] = gg[0]; d_grad[o * 3 + 1] = gg[1]; d_grad[o * 3 + 2] = gg[2]; }
+      else d_grad[o] = gcos;
     }
   }
   gvar = wave_sum(gvar);
@@ -904,8 +923,20 @@ extern "C" int nsky_neus_weights_fwd(const float* sdf, const float* grad, const 
   NSKY_CHECK_ARG(sdf && grad && ray_dirs && starts && ends && variance && weights, "nsky_neus_weights_fwd: null argument");
   NSKY_CHECK_ARG(R > 0 && S > 0 && S <= 64 * MAXCH, "nsky_neus_weights_fwd: S=%d out of range (<= %d)", S, 64 * MAXCH);
   hipLaunchKernelGGL(neus_weights_fwd_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, (hipStream_t)stream, sdf, grad, ray_dirs, starts,
-                     ends, variance, cos_anneal, R, S, alpha, weights, trans_bg, accumulation, depth);
+                     ends, variance, cos_anneal, R, S, alpha, weights, trans_bg, accumulation, depth, 3);
   NSKY_CHECK_LAUNCH("nsky_neus_weights_fwd");
+  return NSKY_OK;
+}
+
+extern "C" int nsky_neus_weights_cos_fwd(const float* sdf, const float* cosv, const float* starts, const float* ends, const float* variance,
+                                         float cos_anneal, int32_t R, int32_t S, float* alpha, float* weights, float* trans_bg,
+                                         float* accumulation, float* depth, nsky_stream_t stream) {
+  if (R == 0) return NSKY_OK;
+  NSKY_CHECK_ARG(sdf && cosv && starts && ends && variance && weights, "nsky_neus_weights_cos_fwd: null argument");
+  NSKY_CHECK_ARG(R > 0 && S > 0 && S <= 64 * MAXCH, "nsky_neus_weights_cos_fwd: S=%d out of range (<= %d)", S, 64 * MAXCH);
+  hipLaunchKernelGGL(neus_weights_fwd_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, (hipStream_t)stream, sdf, cosv, (const float*)nullptr, starts,
+                     ends, variance, cos_anneal, R, S, alpha, weights, trans_bg, accumulation, depth, 1);
+  NSKY_CHECK_LAUNCH("nsky_neus_weights_cos_fwd");
   return NSKY_OK;
 }
 
@@ -917,8 +948,20 @@ extern "C" int nsky_neus_weights_bwd(const float* sdf, const float* grad, const 
   NSKY_CHECK_ARG(sdf && grad && ray_dirs && starts && ends && variance && d_weights && d_sdf && d_grad, "nsky_neus_weights_bwd: null argument");
   NSKY_CHECK_ARG(R > 0 && S > 0 && S <= 64 * MAXCH, "nsky_neus_weights_bwd: S=%d out of range (<= %d)", S, 64 * MAXCH);
   hipLaunchKernelGGL(neus_weights_bwd_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, (hipStream_t)stream, sdf, grad, ray_dirs, starts,
-                     ends, variance, cos_anneal, R, S, d_weights, d_trans_bg, d_sdf, d_grad, d_variance);
+                     ends, variance, cos_anneal, R, S, d_weights, d_trans_bg, d_sdf, d_grad, d_variance, 3);
   NSKY_CHECK_LAUNCH("nsky_neus_weights_bwd");
+  return NSKY_OK;
+}
+
+extern "C" int nsky_neus_weights_cos_bwd(const float* sdf, const float* cosv, const float* starts, const float* ends, const float* variance,
+                                         float cos_anneal, int32_t R, int32_t S, const float* d_weights, const float* d_trans_bg, float* d_sdf,
+                                         float* d_cos, float* d_variance, nsky_stream_t stream) {
+  if (R == 0) return NSKY_OK;
+  NSKY_CHECK_ARG(sdf && cosv && starts && ends && variance && d_weights && d_sdf && d_cos, "nsky_neus_weights_cos_bwd: null argument");
+  NSKY_CHECK_ARG(R > 0 && S > 0 && S <= 64 * MAXCH, "nsky_neus_weights_cos_bwd: S=%d out of range (<= %d)", S, 64 * MAXCH);
+  hipLaunchKernelGGL(neus_weights_bwd_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, (hipStream_t)stream, sdf, cosv, (const float*)nullptr, starts,
+                     ends, variance, cos_anneal, R, S, d_weights, d_trans_bg, d_sdf, d_cos, d_variance, 1);
+  NSKY_CHECK_LAUNCH("nsky_neus_weights_cos_bwd");
   return NSKY_OK;
 }
 

@@ -218,7 +218,10 @@ class SDFAlbedoField(FieldBase):
         Wc2p = self._wn(self.clin2, "c2", lambda o, i: list(range(o)) + [-1] * (pad4(o) - o), lambda o, i: list(range(i)))
         return (Wc0p, self.clin0.bias.contiguous(), Wc1, self.clin1.bias.contiguous(), Wc2p, ops.pad_bias(self.clin2.bias))
 
-    def _encode(self, positions_flat: torch.Tensor, tangents: bool, need_dx: bool) -> torch.Tensor:
+    def _encode(self, positions_flat: torch.Tensor, tangents: bool, need_dx: bool, tangent_dirs: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if tangent_dirs is not None:
+            return ops.HashEncodeFn.apply(positions_flat, self.encoding.table, self.geom, self.grid_mode, True, 6, 5.0,
+                                          tangents, need_dx, tangent_dirs)
         return ops.HashEncodeFn.apply(positions_flat, self.encoding.table, self.geom, self.grid_mode, True, 6, 5.0,
                                       tangents, need_dx)
 
@@ -233,11 +236,26 @@ class SDFAlbedoField(FieldBase):
         sdf = ops.sdf_value_apply(E, *self._geo_weights(), self.softplus_beta, True)
         return sdf[:, None]
 
-    def field_values(self, positions_flat: torch.Tensor, want_albedo: bool = True):
+    def field_values(self, positions_flat: torch.Tensor, want_albedo: bool = True, tangent_dirs: Optional[torch.Tensor] = None):
         """sdf [N], gradients [N,3], albedo [N,3] at flat positions (sdf_albedo_field.py:225-246).  want_albedo=False: the
-        colour net is skipped each way and albedo comes back as zeros (geometry-only passes: DDF-fit ground truth, grid probe)."""
-        ET = self._encode(positions_flat.detach(), True, False)
-        return ops.field_apply(ET, *self._geo_weights(), *self._colour_weights(), self.softplus_beta, want_albedo)
+        colour net is skipped each way and albedo comes back as zeros (geometry-only passes: DDF-fit ground truth, grid probe).
+        tangent_dirs [R,3] (N = R * S, point n on ray n // S; geometry only): the gradient comes back as ONE column [N,1], the sdf's
+        derivative along the ray -- on the fused kernels as one forward-mode tangent per point (two row-sets instead of four each
+        way); on the per-layer path (exact-fp32 policy, unsupported shapes) as the contraction of the full gradient: same interface,
+        same result, no saving."""
+        if tangent_dirs is None:
+            ET = self._encode(positions_flat.detach(), True, False)
+            return ops.field_apply(ET, *self._geo_weights(), *self._colour_weights(), self.softplus_beta, want_albedo)
+        assert not want_albedo, "the directional mode is geometry only"
+        gw, cw = self._geo_weights(), self._colour_weights()
+        dirs = tangent_dirs.detach().reshape(-1, 3).contiguous()
+        N = positions_flat.shape[0]
+        if ops.field_directional_ok(ops.pad4(3 + 36 + 2 * self.geom.n_levels), gw[0], gw[2], gw[4], cw[0], cw[2]):  # (the encode rows' ld)
+            ET = self._encode(positions_flat.detach(), True, False, dirs)
+            return ops.field_apply(ET, *gw, *cw, self.softplus_beta, False, directional=True)
+        sdf, grad, albedo = self.field_values(positions_flat, False)
+        d = dirs.repeat_interleave(N // dirs.shape[0], 0)
+        return sdf, (grad * d).sum(-1, keepdim=True), albedo
 
     def get_colors(self, points: torch.Tensor, geo_features: torch.Tensor) -> torch.Tensor:
         """sdf_albedo_field.py:185-209: albedo of the colour network at `points` given their geometric features:
@@ -272,16 +290,26 @@ class SDFAlbedoField(FieldBase):
         return w  # with a single sample, weight == alpha
 
     def get_outputs(self, ray_samples: RaySamples, density_embedding=None, return_alphas: bool = False,
-                    want_albedo: bool = True, extra_points: Optional[torch.Tensor] = None) -> Dict:
+                    want_albedo: bool = True, extra_points: Optional[torch.Tensor] = None, want_normals: bool = True) -> Dict:
         """sdf_albedo_field.py:211-269.  Besides the reference keys, `weights` [R,S,1], `bg_transmittance` [R,1],
         `accumulation` [R,1] and `p2p_dist` [R,1] come out of the same fused NeuS kernel when return_alphas.
         extra_points [P,3]: isolated points evaluated in the same pass; their sdf / gradients come back as `extra_sdf` [P] and
-        `extra_gradients` [P,3]."""
+        `extra_gradients` [P,3].
+        want_normals=False (geometry only, with return_alphas): the pass whose only use of the gradient is its cosine with the ray
+        (NeuS alphas): NORMALS and GRADIENT are left out, the directional field mode computes that cosine alone."""
         if ray_samples.camera_indices is None:
             raise AttributeError("Camera indices are not provided.")
         fr = ray_samples.frustums
         R, S = fr.origins.shape[:2]
         x = fr.get_start_positions().reshape(-1, 3)
+        if not want_normals:
+            assert return_alphas and not want_albedo and extra_points is None, "want_normals=False: a geometry-only alpha pass"
+            sdf, cosv, albedo = self.field_values(x, False, tangent_dirs=fr.directions[:, 0])
+            w, tbg, acc, dep = ops.NeusWeightsFn.apply(sdf.view(R, S), cosv.view(R, S, 1), fr.directions[:, 0].contiguous(),
+                                                       fr.starts.reshape(R, S), fr.ends.reshape(R, S),
+                                                       self.deviation_network.variance, self._cos_anneal_ratio)
+            return {NeuSkyFieldHeadNames.ALBEDO: albedo.view(R, S, 3), FieldHeadNames.SDF: sdf.view(R, S, 1), "weights": w[..., None],
+                    "bg_transmittance": tbg[:, None], "accumulation": acc[:, None], "p2p_dist_unclipped": dep[:, None]}
         n_main = x.shape[0]
         if extra_points is not None:  # isolated points evaluated in the same pass (tail rows): the model's hash-grid density probe
             x = torch.cat([x, extra_points.reshape(-1, 3)], 0)
@@ -316,5 +344,6 @@ class SDFAlbedoField(FieldBase):
         return outputs
 
     def forward(self, ray_samples: RaySamples, compute_normals: bool = False, return_alphas: bool = False,
-                want_albedo: bool = True, extra_points: Optional[torch.Tensor] = None) -> Dict:
-        return self.get_outputs(ray_samples, return_alphas=return_alphas, want_albedo=want_albedo, extra_points=extra_points)
+                want_albedo: bool = True, extra_points: Optional[torch.Tensor] = None, want_normals: bool = True) -> Dict:
+        return self.get_outputs(ray_samples, return_alphas=return_alphas, want_albedo=want_albedo, extra_points=extra_points,
+                                want_normals=want_normals)

@@ -173,6 +173,10 @@ _encode_fwd = _sig("nsky_encode_fwd", C.POINTER(HashGridDesc), C.c_void_p, C.c_i
                    C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
 _encode_bwd = _sig("nsky_encode_bwd", C.POINTER(HashGridDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                    C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_encode_fwd_dir = _sig("nsky_encode_fwd_dir", C.POINTER(HashGridDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                       C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
+_encode_bwd_dir = _sig("nsky_encode_bwd_dir", C.POINTER(HashGridDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                       C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _encode_bwd_ws = _lib.nsky_encode_bwd_workspace_bytes
 _encode_bwd_ws.restype = C.c_int64
 _encode_bwd_ws.argtypes = [C.POINTER(HashGridDesc), C.c_int32, C.c_int32]
@@ -214,6 +218,37 @@ def encode_bwd(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, dY, dT, dt
         workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device) if nbytes > 0 else None
     check(_encode_bwd(C.byref(desc), ptr(x), P, mode, int(include_x), pe_freqs, pe_max_exp, ptr(dY), ld(dY),
                       ptr(dT), ptr(dtable), ptr(dx), ptr(workspace), stream_ptr()), "nsky_encode_bwd")
+
+
+def _check_dirs(dirs, P):
+    """directions of the directional encode: [R, 3] with P = R * spr (point p takes direction p // spr) -> spr"""
+    R = dirs.shape[0]
+    assert dirs.shape == (R, 3) and dirs.is_contiguous() and dirs.dtype == torch.float32 and R >= 1 and P % R == 0, (dirs.shape, P)
+    return P // R
+
+
+def encode_fwd_dir(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, dirs, Y, Td):
+    """Y [P, ld] and ONE tangent row-set Td [P, ld] = sum_a d_a T_a; dirs [R, 3], P = R * spr"""
+    P = x.shape[0]
+    assert x.shape == (P, 3) and x.is_contiguous() and Y.shape[0] == P and Td.shape == Y.shape and Y.is_contiguous() and Td.is_contiguous()
+    spr = _check_dirs(dirs, P)
+    check(_encode_fwd_dir(C.byref(grid_desc(geom, table)), ptr(x), P, mode, int(include_x), pe_freqs, pe_max_exp, ptr(dirs), spr, ptr(Y), ld(Y),
+                          ptr(Td), stream_ptr()), "nsky_encode_fwd_dir")
+    return Y
+
+
+def encode_bwd_dir(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, dirs, dY, dTd, dtable, workspace="auto"):
+    """the table gradient of encode_fwd_dir: what encode_bwd adds for dT_a = d_a dTd"""
+    P = x.shape[0]
+    assert dTd.shape == dY.shape and dY.shape[0] == P and dTd.is_contiguous() and dY.is_contiguous() and ld(dTd) == ld(dY)
+    assert dtable.shape == table.shape and dtable.is_contiguous()
+    spr = _check_dirs(dirs, P)
+    desc = grid_desc(geom, table)
+    if isinstance(workspace, str):
+        nbytes = _encode_bwd_ws(C.byref(desc), P, 1)
+        workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device) if nbytes > 0 else None
+    check(_encode_bwd_dir(C.byref(desc), ptr(x), P, mode, int(include_x), pe_freqs, pe_max_exp, ptr(dirs), spr, ptr(dY), ld(dY), ptr(dTd),
+                          ptr(dtable), ptr(workspace), stream_ptr()), "nsky_encode_bwd_dir")
 
 
 def hash_indices(geom, table, x, mode):
@@ -345,6 +380,8 @@ _hemi_fwd = _sig("nsky_hemi_composite_fwd", _P, _P, _P, _P, _P, _P, _P, _P, _I, 
 _hemi_bwd = _sig("nsky_hemi_composite_bwd", _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P)
 _neus_fwd = _sig("nsky_neus_weights_fwd", _P, _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P)
 _neus_bwd = _sig("nsky_neus_weights_bwd", _P, _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P)
+_neus_cos_fwd = _sig("nsky_neus_weights_cos_fwd", _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P)
+_neus_cos_bwd = _sig("nsky_neus_weights_cos_bwd", _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P)
 _vis_rays = _sig("nsky_visibility_rays", _P, _P, _P, _P, _I, _I, _F, _P, _P, _I, _P, _P, _P)
 _vis_fin_fwd = _sig("nsky_visibility_finish_fwd", _P, _P, _P, _F, _P, _I, _I, _I, _P, _P)
 _vis_fin_bwd = _sig("nsky_visibility_finish_bwd", _P, _P, _P, _F, _P, _I, _I, _I, _P, _P, _P, _P)
@@ -382,6 +419,21 @@ def neus_weights_bwd(sdf, grad, ray_dirs, starts, ends, variance, anneal, d_weig
     R, S = sdf.shape
     check(_neus_bwd(_c(sdf), _c(grad), _c(ray_dirs), _c(starts), _c(ends), _c(variance), anneal, R, S, _c(d_weights),
                     _c(d_trans_bg), _c(d_sdf), _c(d_grad), _c(d_variance), stream_ptr()), "nsky_neus_weights_bwd")
+
+
+def neus_weights_cos_fwd(sdf, cosv, starts, ends, variance, anneal, alpha, weights, trans_bg, acc, depth):
+    """neus_weights_fwd with the gradient as one precomputed column cosv [R, S] = ray_dir . grad(sdf)"""
+    R, S = sdf.shape
+    assert cosv.numel() == R * S
+    check(_neus_cos_fwd(_c(sdf), _c(cosv), _c(starts), _c(ends), _c(variance), anneal, R, S, _c(alpha), _c(weights), _c(trans_bg), _c(acc),
+                        _c(depth), stream_ptr()), "nsky_neus_weights_cos_fwd")
+
+
+def neus_weights_cos_bwd(sdf, cosv, starts, ends, variance, anneal, d_weights, d_trans_bg, d_sdf, d_cos, d_variance):
+    R, S = sdf.shape
+    assert cosv.numel() == R * S and d_cos.numel() == R * S
+    check(_neus_cos_bwd(_c(sdf), _c(cosv), _c(starts), _c(ends), _c(variance), anneal, R, S, _c(d_weights), _c(d_trans_bg), _c(d_sdf),
+                        _c(d_cos), _c(d_variance), stream_ptr()), "nsky_neus_weights_cos_bwd")
 
 
 _ray_reduce_fwd = _sig("nsky_ray_reduce_fwd", _P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P)
@@ -978,6 +1030,12 @@ _field_geo_bwd = _sig("nsky_field_geo_bwd", C.POINTER(FieldNet), C.c_void_p, C.c
                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
 _native_wcolsum = _sig("nsky_native_weighted_colsum", C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                        C.c_int32, C.c_void_p, C.c_void_p)
+_field_geo_fwd_dir = _sig("nsky_field_geo_fwd_dir", C.POINTER(FieldNet), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_field_geo_bwd_dir = _sig("nsky_field_geo_bwd_dir", C.POINTER(FieldNet), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
+_native_wcolsum_pair = _sig("nsky_native_weighted_colsum_pair", C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                            C.c_void_p, C.c_void_p)
 
 
 def chain_layer(W, rows, K, transposed=False) -> ChainLayer:
@@ -1040,6 +1098,34 @@ def native_weighted_colsum(X, nt, rows, out, bias=None, w4=None, n_out=1, g_sdf=
     """out[o] += sum_rows w[row][o] X[row] over a tile-native X [rows, 32 nt]; w4 [rows, 4], or the quad form (g_sdf / g_grad)"""
     check(_native_wcolsum(ptr(X), nt, rows, ptr(w4), n_out, ptr(g_sdf), ptr(g_grad), ptr(out), ld(out) if out.dim() == 2 else out.shape[0],
                           ptr(bias), stream_ptr()), "nsky_native_weighted_colsum")
+
+
+def field_geo_fwd_dir(net: FieldNet, pack, ET, N, a0q, a1q, Eq, sdf, cosv, qmax=None):
+    """the directional (pair-layout) geometry forward: ET stacked [E; Td] [2 N, ld]; sdf [N], cosv [N]; a0q / a1q / Eq pair-native"""
+    stream, scales, groups = pack
+    assert ET.shape[0] == 2 * N and sdf.numel() == N and cosv.numel() == N and a0q.shape[0] >= film_rows(2 * N) and a1q.shape[0] >= film_rows(2 * N)
+    assert Eq is None or Eq.shape[0] >= film_rows(2 * N)
+    check(_field_geo_fwd_dir(C.byref(net), ptr(stream), ptr(scales), groups, ptr(ET), ld(ET), N, ptr(a0q), ptr(a1q), ptr(Eq), ptr(sdf), ptr(cosv),
+                             ptr(qmax), stream_ptr()), "nsky_field_geo_fwd_dir")
+
+
+def field_geo_bwd_dir(net: FieldNet, pack, N, g_sdf, g_cos, a0q, a1q, d1q, d0q, dET, gmax):
+    stream, scales, groups = pack
+    assert (g_sdf is None or g_sdf.numel() == N) and (g_cos is None or g_cos.numel() == N) and (dET is None or dET.shape[0] == 2 * N)
+    assert min(a0q.shape[0], a1q.shape[0], d1q.shape[0], d0q.shape[0]) >= film_rows(2 * N)
+    check(_field_geo_bwd_dir(C.byref(net), ptr(stream), ptr(scales), groups, N, ptr(g_sdf), ptr(g_cos), ptr(a0q), ptr(a1q), ptr(d1q), ptr(d0q),
+                             ptr(dET), 0 if dET is None else ld(dET), ptr(gmax), stream_ptr()), "nsky_field_geo_bwd_dir")
+
+
+def native_weighted_colsum_pair(X, nt, rows, out, bias=None, g_sdf=None, g_cos=None):
+    """the pair form over a pair-native X: w(row) = g_sdf[row // 2] on even rows (bias: those only), g_cos[row // 2] on odd rows"""
+    check(_native_wcolsum_pair(ptr(X), nt, rows, ptr(g_sdf), ptr(g_cos), ptr(out), ld(out) if out.dim() == 2 else out.shape[0], ptr(bias),
+                               stream_ptr()), "nsky_native_weighted_colsum_pair")
+
+
+def pair_native_to_rows(buf, N: int, width: int):
+    """pair-native [ceil32(2 N), width] -> [2, N, width] (row-set major; tests)"""
+    return film_native_to_rows(buf, 2 * N, width).reshape(N, 2, width).permute(1, 0, 2)
 
 
 def quad_native_to_rows(buf, N: int, width: int):

@@ -95,6 +95,9 @@ class NeuSkyFactoModelConfig(ConfigBase):
     near_plane: float = 0.05
     visibility_threshold: Union[str, float] = "learnable"
     render_ambient_light: bool = False
+    # the DDF-fit ground-truth pass of the train step carries ONE forward-mode tangent per point, along the ray (its only consumer of
+    # the sdf's gradient is the NeuS cosine), instead of the full input Jacobian; False: the full (quad) form, for comparison
+    ddf_fit_directional: bool = True
     # eval-latent fitting (neusky_model.py:151-168, values of neusky_config.py:142-149)
     eval_latent_optimise_method: str = "per_image"      # per_image | nerf_osr_holdout | nerf_osr_envmap
     eval_latent_sample_region: str = "full_image"       # left_image_half | right_image_half | full_image
@@ -718,20 +721,26 @@ class NeuSkyFactoModel(ModelBase):
         return metrics_dict, images_dict
 
     def generate_ddf_ground_truth(self, ray_bundle: RayBundle, mask_threshold: float = 0.5, log_depth: bool = False,
-                                  randoms=None) -> Dict[str, Any]:
-        """neusky_model.py:1337-1367: second sampler + field pass on the DDF-fit rays"""
+                                  randoms=None, want_normals: bool = True) -> Dict[str, Any]:
+        """neusky_model.py:1337-1367: second sampler + field pass on the DDF-fit rays.
+        want_normals=False (the train step, whose DDF losses read no normals): no "normals" key, and with config.ddf_fit_directional
+        the field pass runs in its directional mode"""
         ray_bundle = self.collider(ray_bundle)
         sub = None if randoms is None or "ddf_jitters" not in randoms else {"jitters": randoms["ddf_jitters"]}
         ray_samples, _, _, _, _ = self._sample(ray_bundle, sub)
-        fo = self.field(ray_samples, return_alphas=True, want_albedo=False)  # depth / mask / normals only (:1337-1367)
-        weights = fo["weights"]
+        # (switch off: the full form exactly as before, normals formed and reduced whether or not they are handed on)
+        directional = not want_normals and self.config.ddf_fit_directional
+        fo = self.field(ray_samples, return_alphas=True, want_albedo=False, want_normals=not directional)  # depth / mask / normals only (:1337-1367)
         p2p, accumulations, normals, _ = self.ray_reductions(
-            weights, ray_samples, fo[FieldHeadNames.NORMALS], None,
+            fo["weights"], ray_samples, None if directional else fo[FieldHeadNames.NORMALS], None,
             max_clamp=2 * self.visibility_field.ddf_radius if self.visibility_field is not None else 0.0)
         mask = (accumulations > mask_threshold).float()
         if log_depth:  # :1354-1355
             p2p = torch.log(p2p + 1e-6)
-        return {"ray_bundle": ray_bundle, "accumulations": accumulations, "mask": mask, "termination_dist": p2p, "normals": normals}
+        out = {"ray_bundle": ray_bundle, "accumulations": accumulations, "mask": mask, "termination_dist": p2p}
+        if want_normals:
+            out["normals"] = normals
+        return out
 
     def _eval_fit_bundle(self, datamanager):
         """:1544-1575: the rays of one fitting step and, for nerf_osr_envmap, the per-session z-rotations"""

@@ -666,17 +666,26 @@ def weight_norm_maps(out_features: int, in_features: int, rows, cols, device):
 # hash-grid encode
 # =============================================================================================
 class HashEncodeFn(torch.autograd.Function):
-    """rows = [x | PE(x) | hash(x)] (+ three tangent row blocks).  Output [P, ld] or stacked [4P, ld]."""
+    """rows = [x | PE(x) | hash(x)] (+ three tangent row blocks).  Output [P, ld] or stacked [4P, ld].
+    tangent_dirs [R, 3] (P = R * spr; point p takes direction p // spr; with tangents): the directional mode, ONE tangent row block
+    Td = sum_a d_a T_a, output stacked [2P, ld] = [E; Td]; positions then get no gradient."""
 
     @staticmethod
-    def forward(ctx, x, table, geom, mode, include_x, pe_freqs, pe_max_exp, tangents, need_dx):
+    def forward(ctx, x, table, geom, mode, include_x, pe_freqs, pe_max_exp, tangents, need_dx, tangent_dirs=None):
         P = x.shape[0]
         width = (3 if include_x else 0) + 6 * pe_freqs + 2 * geom.n_levels
         ldy = pad4(width)
         x = x.contiguous()
-        out = torch.empty((4 * P if tangents else P), ldy, device=x.device)
-        T = out[P:].view(3, P, ldy) if tangents else None
-        hip.encode_fwd(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, out[:P], T)
+        ctx.dirs = None
+        if tangent_dirs is not None:
+            assert tangents and not need_dx, "directional encode: tangents without an input gradient"
+            ctx.dirs = tangent_dirs.detach().contiguous()
+            out = torch.empty(2 * P, ldy, device=x.device)
+            hip.encode_fwd_dir(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, ctx.dirs, out[:P], out[P:])
+        else:
+            out = torch.empty((4 * P if tangents else P), ldy, device=x.device)
+            T = out[P:].view(3, P, ldy) if tangents else None
+            hip.encode_fwd(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, out[:P], T)
         ctx.save_for_backward(x, table)
         ctx.cfg = (geom, mode, include_x, pe_freqs, pe_max_exp, tangents, need_dx, P, ldy)
         # Parameters re-homed into an optimizer slab (engine._Group) own a pre-zeroed gradient view: the backward scatters
@@ -690,20 +699,23 @@ class HashEncodeFn(torch.autograd.Function):
         geom, mode, include_x, pe_freqs, pe_max_exp, tangents, need_dx, P, ldy = ctx.cfg
         if not ctx.needs_input_grad[1]:  # a frozen table (the eval-latent fit): only the input gradient, no scatter
             if not need_dx:
-                return None, None, None, None, None, None, None, None, None
+                return None, None, None, None, None, None, None, None, None, None
             dx = torch.empty(P, 3, device=x.device)
             hip.encode_bwd(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, d_out.contiguous()[:P], None, None, dx)
-            return dx, None, None, None, None, None, None, None, None
+            return dx, None, None, None, None, None, None, None, None, None
         d_out = d_out.contiguous()
         # engine.Optimizers.zero_grad_all: a sunk parameter's .grad stays its slab view.  (A parameter first used after step 0 -- a
         # loss enabled later -- arrives here with .grad dropped: it takes the slow path once and sinks from the next step on.)
         view = _sink_grad(ctx.sink, from_first_pass=True)
         accumulate = view is not None
         dtable = view.view_as(table) if accumulate else zeros_like(table)
+        if ctx.dirs is not None:
+            hip.encode_bwd_dir(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, ctx.dirs, d_out[:P], d_out[P:], dtable)
+            return None, (None if accumulate else dtable), None, None, None, None, None, None, None, None
         dx = torch.empty(P, 3, device=x.device) if need_dx else None
         dT = d_out[P:].view(3, P, ldy) if tangents else None
         hip.encode_bwd(geom, table, x, mode, include_x, pe_freqs, pe_max_exp, d_out[:P], dT, dtable, dx)
-        return dx, (None if accumulate else dtable), None, None, None, None, None, None, None
+        return dx, (None if accumulate else dtable), None, None, None, None, None, None, None, None
 
 
 # =============================================================================================
@@ -758,7 +770,13 @@ def _film_fused_ok(x, cond, n_map, n_film, wb) -> bool:
 
 
 def field_fused_ok(ET, W0, W1, W2, Wc0, Wc1) -> bool:
-    return (FWD_PRECISION == hip.PREC_F16X2 and ET.shape[0] >= 4 and ld(ET) == W0.shape[1]
+    return ET.shape[0] >= 4 and field_directional_ok(ld(ET), W0, W1, W2, Wc0, Wc1)
+
+
+def field_directional_ok(ldE, W0, W1, W2, Wc0, Wc1) -> bool:
+    """the fused field kernels take encode rows of leading dimension ldE (any batch): the condition of their directional mode, which
+    the per-layer path does not have (fields.SDFAlbedoField.field_values decides on it BEFORE it encodes)"""
+    return (FWD_PRECISION == hip.PREC_F16X2 and ldE == W0.shape[1]
             and hip.field_supported(W0.shape[1], W0.shape[0], W2.shape[0] - 4, Wc1.shape[0], Wc0.shape[1]))
 
 
@@ -773,9 +791,16 @@ def film_apply(x, cond, n_map, n_film, train_weights, need_dcond, *wb):
     return node.apply(x, cond, n_map, n_film, train_weights, need_dcond, *wb)
 
 
-def field_apply(ET, *args):
-    """the field on stacked encode rows: the fused chain kernels where they apply, otherwise the per-layer path"""
+def field_apply(ET, *args, directional=False):
+    """the field on stacked encode rows: the fused chain kernels where they apply, otherwise the per-layer path.
+    directional: ET is [E; Td] of the directional encode and the second output is [N, 1], the sdf's derivative along d (geometry only;
+    fused kernels only: a missing kernel is an error, not a fall-back)"""
     W0, _, W1, _, W2, _, Wc0, _, Wc1 = args[:9]
+    if directional:
+        if not field_directional_ok(ld(ET), W0, W1, W2, Wc0, Wc1):
+            raise RuntimeError("field_apply: the directional mode exists on the fused field kernels only (see field_directional_ok)")
+        beta = args[12]
+        return FieldChainFn.apply(ET, *args[:12], beta, False, True)
     return (FieldChainFn if field_fused_ok(ET, W0, W1, W2, Wc0, Wc1) else SDFAlbedoFn).apply(ET, *args)
 
 
@@ -1227,7 +1252,10 @@ def _field_pack(kind, weights, layers_fn):
 class FieldChainFn(torch.autograd.Function):
     """SDFAlbedoFn's contract (same arguments, same outputs) on the fused field kernels: geometry network with forward-mode tangents
     in the quad layout, colour path, and the hand-derived reverse of both; every product fp32-grade (fp16 hi + residual planes on
-    power-of-two pre-scaled operands), weight gradients by the streaming tile-native kernel."""
+    power-of-two pre-scaled operands), weight gradients by the streaming tile-native kernel.
+
+    directional: the pair layout -- ET is [E; Td] [2N, ld] (HashEncodeFn with tangent_dirs), a point is two row-sets {value, tangent
+    along d}, the second output is [N, 1] = d sdf / dx . d; geometry only (want_albedo False).  Same packed weight streams."""
 
     NPE = 39  # x (3) + PE6 (36): the leading columns of an encode row that also feed the colour net
 
@@ -1237,23 +1265,29 @@ class FieldChainFn(torch.autograd.Function):
         return hip.field_net(Kin, FieldChainFn.NPE, beta, b0, b1, W2[GF], b2[GF:GF + 1], b2[:GF], bc0, bc1, Wc2, bc2)
 
     @staticmethod
-    def forward(ctx, ET, W0, b0, W1, b1, W2, b2, Wc0, bc0, Wc1, bc1, Wc2, bc2, beta, want_albedo=True):
-        N = ET.shape[0] // 4
+    def forward(ctx, ET, W0, b0, W1, b1, W2, b2, Wc0, bc0, Wc1, bc1, Wc2, bc2, beta, want_albedo=True, directional=False):
+        rpp = 2 if directional else 4  # row-sets per point
+        assert not (directional and want_albedo), "the directional mode is geometry only"
+        N = ET.shape[0] // rpp
         dev = ET.device
         GF = W2.shape[0] - 4
         Kin = W0.shape[1]
         save = any(ctx.needs_input_grad)
         net = FieldChainFn._net(Kin, beta, b0, b1, W2, b2, bc0, bc1, Wc2, bc2)
-        Mq, Mp = hip.film_rows(4 * N), hip.film_rows(N)
+        Mq, Mp = hip.film_rows(rpp * N), hip.film_rows(N)
         a0q, a1q = torch.empty(Mq, 256, device=dev), torch.empty(Mq, 256, device=dev)
         Eq = torch.empty(Mq, 128, device=dev) if save else None
-        a1max = torch.empty(N, device=dev)
-        sdf, grad = torch.empty(N, device=dev), torch.empty(N, 3, device=dev)
+        sdf, grad = torch.empty(N, device=dev), torch.empty(N, rpp - 1, device=dev)
         pk = _field_pack("geo_fwd", (W0, W1), lambda: [hip.chain_layer(W0, 256, Kin), hip.chain_layer(W1, 256, 256)])
         # largest |Eq|, |a0q| (tangent rows included): the operand scales of the first two layers' weight gradients
         qmax = zeros(2, device=dev) if save else None
-        hip.field_geo_fwd(net, pk, ET, N, a0q, a1q, Eq, a1max, sdf, grad, qmax)
+        if directional:
+            hip.field_geo_fwd_dir(net, pk, ET, N, a0q, a1q, Eq, sdf, grad, qmax)
+        else:
+            a1max = torch.empty(N, device=dev)
+            hip.field_geo_fwd(net, pk, ET, N, a0q, a1q, Eq, a1max, sdf, grad, qmax)
         ctx.qmax = qmax
+        ctx.rpp = rpp
         if want_albedo:
             a1v = torch.empty(Mp, 256, device=dev) if save else None
             feat, c0, c1 = torch.empty(Mp, 256, device=dev), torch.empty(Mp, 256, device=dev), torch.empty(Mp, 256, device=dev)
@@ -1281,10 +1315,11 @@ class FieldChainFn(torch.autograd.Function):
     def backward(ctx, g_sdf, g_grad, g_alb):
         ET, a0q, a1q, Eq, a1v, feat, xpe, c0, c1, alb, W0, b0, W1, b1, W2, b2, Wc0, bc0, Wc1, bc1, Wc2, bc2 = ctx.saved_tensors
         N, GF, Kin, beta = ctx.cfg
+        rpp = ctx.rpp
         dev = ET.device
         colour = ctx.want_albedo and g_alb is not None
         net = FieldChainFn._net(Kin, beta, b0, b1, W2, b2, bc0, bc1, Wc2, bc2)
-        Mq, Mp = hip.film_rows(4 * N), hip.film_rows(N)
+        Mq, Mp = hip.film_rows(rpp * N), hip.film_rows(N)
         gmax = zeros(8, device=dev)
         g_sdf = None if g_sdf is None else g_sdf.contiguous()
         g_grad = None if g_grad is None else g_grad.contiguous()
@@ -1297,31 +1332,37 @@ class FieldChainFn(torch.autograd.Function):
                                                                   hip.chain_layer(W2, 256, 256, True)])
             hip.field_colour_bwd(net, pk, N, g_alb.contiguous(), alb, c0, c1, dpc2, dpc1, dpc0, dfeat, dxpe, da1v, gmax[:3])
         d1q, d0q = torch.empty(Mq, 256, device=dev), torch.empty(Mq, 256, device=dev)
-        dET = torch.empty(4 * N, ld(ET), device=dev) if ctx.needs_input_grad[0] else None
+        dET = torch.empty(rpp * N, ld(ET), device=dev) if ctx.needs_input_grad[0] else None
         pk = _field_pack("geo_bwd", (W1, W0), lambda: [hip.chain_layer(W1, 256, 256, True), hip.chain_layer(W0, Kin, 256, True)])
-        hip.field_geo_bwd(net, pk, N, g_sdf, g_grad, da1v, dxpe, a0q, a1q, d1q, d0q, dET, gmax[4:6])
+        if rpp == 2:
+            hip.field_geo_bwd_dir(net, pk, N, g_sdf, g_grad, a0q, a1q, d1q, d0q, dET, gmax[4:6])
+        else:
+            hip.field_geo_bwd(net, pk, N, g_sdf, g_grad, da1v, dxpe, a0q, a1q, d1q, d0q, dET, gmax[4:6])
         none6 = (None,) * 6
         if not any(ctx.needs_input_grad[1:13]):  # frozen field (the eval-latent fit): only the encode rows' gradient
-            return (dET, *none6, *none6, None, None)
+            return (dET, *none6, *none6, None, None, None)
         # ---- parameter gradients: every dense layer's by the streaming tile-native kernel (value rows only for the biases of the
         # quad-native gradients), the two narrow output layers' by weighted column sums
         dW2, db2, f_2 = shared_grad(W2, b2)
         dW1, db1, f_1 = shared_grad(W1, b1)
         dW0, db0, f_0 = shared_grad(W0, b0)
-        R4 = 4 * N
+        R4 = rpp * N  # rows of the quad- / pair-native operands
         qmax = ctx.qmax
         # (the accumulators are read by the weight-norm nodes at the end of the pass, which join the side stream: async_weight_gradients)
 
         def launch_geo():
-            hip.wgrad_native_batch([hip.wgrad_problem(d1q, 8, a0q, 8, R4, dW1, db1, gmax[4:5], 8.0, bias_row_mod=4, b_scale_max=qmax[1:2])], R4)
-            hip.wgrad_native_batch([hip.wgrad_problem(d0q, 8, Eq, 4, R4, dW0, db0, gmax[5:6], 64.0, width_b=Kin, bias_row_mod=4, b_scale_max=qmax[0:1])], R4)
-            hip.native_weighted_colsum(a1q, 8, R4, dW2[GF], db2[GF:GF + 1], g_sdf=g_sdf, g_grad=g_grad)
+            hip.wgrad_native_batch([hip.wgrad_problem(d1q, 8, a0q, 8, R4, dW1, db1, gmax[4:5], 8.0, bias_row_mod=rpp, b_scale_max=qmax[1:2])], R4)
+            hip.wgrad_native_batch([hip.wgrad_problem(d0q, 8, Eq, 4, R4, dW0, db0, gmax[5:6], 64.0, width_b=Kin, bias_row_mod=rpp, b_scale_max=qmax[0:1])], R4)
+            if rpp == 2:
+                hip.native_weighted_colsum_pair(a1q, 8, R4, dW2[GF], db2[GF:GF + 1], g_sdf=g_sdf, g_cos=g_grad)
+            else:
+                hip.native_weighted_colsum(a1q, 8, R4, dW2[GF], db2[GF:GF + 1], g_sdf=g_sdf, g_grad=g_grad)
 
         k = first_only  # later nodes of the pass added in place; slab-resident biases return nothing
         if not colour:
             async_weight_gradients(launch_geo, [d1q, a0q, d0q, Eq, a1q, g_sdf, g_grad, gmax, qmax])
             join_unless_sunk(db0, db1, db2)
-            return (dET, k(f_0, dW0), k(f_0, db0), k(f_1, dW1), k(f_1, db1), k(f_2, dW2), k(f_2, db2), *none6, None, None)
+            return (dET, k(f_0, dW0), k(f_0, db0), k(f_1, dW1), k(f_1, db1), k(f_2, dW2), k(f_2, db2), *none6, None, None, None)
         dWc2, dbc2, f_c2 = shared_grad(Wc2, bc2)
         dWc1, dbc1, f_c1 = shared_grad(Wc1, bc1)
         dWc0, dbc0, f_c0 = shared_grad(Wc0, bc0)
@@ -1337,7 +1378,7 @@ class FieldChainFn(torch.autograd.Function):
         async_weight_gradients(launch_all, [d1q, a0q, d0q, Eq, a1q, g_sdf, g_grad, gmax, qmax, dfeat, a1v, dpc1, c0, dpc0, feat, xpe, c1, dpc2])
         join_unless_sunk(db0, db1, db2, dbc0, dbc1, dbc2)
         return (dET, k(f_0, dW0), k(f_0, db0), k(f_1, dW1), k(f_1, db1), k(f_2, dW2), k(f_2, db2), k(f_c0, dWc0), k(f_c0, dbc0),
-                k(f_c1, dWc1), k(f_c1, dbc1), k(f_c2, dWc2), k(f_c2, dbc2), None, None)
+                k(f_c1, dWc1), k(f_c1, dbc1), k(f_c2, dWc2), k(f_c2, dbc2), None, None, None)
 
 
 _SDF_STREAMS: dict = {}
@@ -1523,7 +1564,8 @@ class SplitRowsFn(torch.autograd.Function):
 
 
 class NeusWeightsFn(torch.autograd.Function):
-    """NeuS alpha + transmittance + weights; returns weights [R,S], T_bg [R], accumulation [R], depth [R] (unclipped)."""
+    """NeuS alpha + transmittance + weights; returns weights [R,S], T_bg [R], accumulation [R], depth [R] (unclipped).
+    grad [R,S,3], or ONE precomputed column [R,S,1] = ray_dir . grad(sdf) (the directional field pass; ray_dirs is then not read)."""
 
     @staticmethod
     def forward(ctx, sdf, grad, ray_dirs, starts, ends, variance, anneal):
@@ -1533,7 +1575,10 @@ class NeusWeightsFn(torch.autograd.Function):
         starts, ends = starts.contiguous(), ends.contiguous()
         w = torch.empty(R, S, device=dev)
         tb, acc, dep = torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
-        hip.neus_weights_fwd(sdf, grad, ray_dirs, starts, ends, variance, anneal, None, w, tb, acc, dep)
+        if grad.shape[-1] == 1:
+            hip.neus_weights_cos_fwd(sdf, grad, starts, ends, variance, anneal, None, w, tb, acc, dep)
+        else:
+            hip.neus_weights_fwd(sdf, grad, ray_dirs, starts, ends, variance, anneal, None, w, tb, acc, dep)
         ctx.save_for_backward(sdf, grad, ray_dirs, starts, ends, variance, w)
         ctx.anneal = anneal
         ctx.set_materialize_grads(False)  # absent output gradients arrive as None, not as zero-filled tensors
@@ -1546,8 +1591,11 @@ class NeusWeightsFn(torch.autograd.Function):
         dsdf, dgrad = torch.empty_like(sdf), torch.empty_like(grad)
         dvar = zeros_like(variance)
         dw = zeros_like(w) if dw is None else dw.contiguous()
-        hip.neus_weights_bwd(sdf, grad, ray_dirs, starts, ends, variance, ctx.anneal, dw,
-                             None if dtb is None else dtb.contiguous(), dsdf, dgrad, dvar)
+        dtb = None if dtb is None else dtb.contiguous()
+        if grad.shape[-1] == 1:
+            hip.neus_weights_cos_bwd(sdf, grad, starts, ends, variance, ctx.anneal, dw, dtb, dsdf, dgrad, dvar)
+        else:
+            hip.neus_weights_bwd(sdf, grad, ray_dirs, starts, ends, variance, ctx.anneal, dw, dtb, dsdf, dgrad, dvar)
         return dsdf, dgrad, None, None, None, dvar, None
 
 

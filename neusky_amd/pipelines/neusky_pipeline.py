@@ -152,12 +152,15 @@ class NeuSkyPipeline(PipelineBase):
                            metadata={"directions_norm": torch.ones(o.shape[0], 1, device=dev)})
         else:
             rb = self.visibility_train_sampler()
-        data = self.model.generate_ddf_ground_truth(rb, self.config.visibility_accumulation_mask_threshold, randoms=randoms)
+        # (the DDF losses read termination_dist / mask / accumulations only: no normals, which lets the field pass run directionally)
+        data = self.model.generate_ddf_ground_truth(rb, self.config.visibility_accumulation_mask_threshold, randoms=randoms,
+                                                    want_normals=False)
         data["sky_ray_bundle"] = randoms["sky_ray_bundle"] if randoms is not None and "sky_ray_bundle" in randoms else \
             self.datamanager.get_sky_ray_bundle(self.config.num_sky_rays)
         if self.config.stop_sdf_gradients:
             for k in ["accumulations", "mask", "termination_dist", "normals"]:
-                data[k] = data[k].detach()
+                if k in data:
+                    data[k] = data[k].detach()
         return data
 
     # ------------------------------------------------------------------ gradients (the DDP wrapper's job, :198-199)
