@@ -62,26 +62,35 @@ __global__ __launch_bounds__(256) void main_losses_fwd_kernel(nsky_main_losses_d
   const long n_grid = 3l * d.P;
   const long total = d.R + (d.eik ? N : 0) + (d.grid ? n_grid : 0) + (d.sdf_term ? d.M : 0);
   const float invR = 1.0f / d.R;
+  if (d.weights) {  // :963-967; sixteen lanes share a ray's S weights (whole lines per group), then four exchanges
+    const int sub = threadIdx.x & 15;
+    const long groups = (long)gridDim.x * blockDim.x / 16;
+    for (long r = ((long)blockIdx.x * blockDim.x + threadIdx.x) / 16; r < d.R; r += groups) {
+      float s = 0.f;
+      for (int k = sub; k < d.S; k += 16) s += d.weights[r * d.S + k];
+#pragma unroll
+      for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      if (sub == 0) {
+        const float fg = d.mask[4 * r + 1];
+        wsum[r] = s;
+        float ws = fminf(fmaxf(s, 1e-3f), 1.0f - 1e-3f);
+        if (s != s) ws = 0.5f;
+        const float l = -(fg * fmaxf(logf(ws), -100.0f) + (1.0f - fg) * fmaxf(logf(1.0f - ws), -100.0f));
+        loc[2] += l * invR;
+      }
+    }
+  }
   for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += (long)gridDim.x * blockDim.x) {
     long i = w;
     if (i < d.R) {
       const int r = (int)i;
-      const float fg = d.mask[4 * r + 1], gm = d.mask[4 * r + 2], sky = d.mask[4 * r + 3];
+      const float gm = d.mask[4 * r + 2], sky = d.mask[4 * r + 3];
       if (d.rgb) {  // :947-950
         const float keep = 1.0f - sky;
         float s = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) s += fabsf(d.image[3 * r + c] * keep - d.rgb[3 * r + c] * keep);
         loc[0] += s * (invR / 3.0f);
-      }
-      if (d.weights) {  // :963-967
-        float s = 0.f;
-        for (int k = 0; k < d.S; ++k) s += d.weights[(long)r * d.S + k];
-        wsum[r] = s;
-        float ws = fminf(fmaxf(s, 1e-3f), 1.0f - 1e-3f);
-        if (s != s) ws = 0.5f;
-        const float l = -(fg * fmaxf(logf(ws), -100.0f) + (1.0f - fg) * fmaxf(logf(1.0f - ws), -100.0f));
-        loc[2] += l * invR;
       }
       if (d.normal) {  // :995-1000 + monosdf_normal_loss
         const float p[3] = {d.normal[3 * r] * gm, d.normal[3 * r + 1] * gm, d.normal[3 * r + 2] * gm};
@@ -225,7 +234,21 @@ __device__ __forceinline__ void depth_pair(const nsky_ddf_losses_desc& d, int i,
 
 __global__ __launch_bounds__(256) void ddf_losses_fwd_kernel(nsky_ddf_losses_desc d, float* __restrict__ terms) {
   float loc[NT_DDF] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  const long total = (long)d.Mr + d.Mm + d.Ms;
+  {  // :475-483, the [M] - [M,1] broadcast: mean over i, j of relu(a_j - b_i)^2; a wave per row, lanes stride the other index
+    const int lane = threadIdx.x & 63;
+    const long waves = (long)gridDim.x * blockDim.x / 64;
+    const float scale = 1.0f / ((float)d.Mm * (float)d.Mm);
+    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) / 64; i < d.Mm; i += waves) {
+      const float a = d.mv_expected[i];
+      float s = 0.f;
+      for (int k = lane; k < d.Mm; k += 64) {
+        const float h = fmaxf(a - d.mv_term[k], 0.0f);
+        s = fmaf(h, h, s);
+      }
+      loc[3] += s * scale;  // block_accumulate() sums the lanes
+    }
+  }
+  const long total = (long)d.Mr + d.Ms;
   for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += (long)gridDim.x * blockDim.x) {
     long i = w;
     if (i < d.Mr) {
@@ -245,17 +268,6 @@ __global__ __launch_bounds__(256) void ddf_losses_fwd_kernel(nsky_ddf_losses_des
       continue;
     }
     i -= d.Mr;
-    if (i < d.Mm) {  // :475-483, the [M] - [M,1] broadcast: mean over i, j of relu(a_j - b_i)^2
-      const float a = d.mv_expected[i];
-      float s = 0.f;
-      for (int k = 0; k < d.Mm; ++k) {
-        const float h = fmaxf(a - d.mv_term[k], 0.0f);
-        s = fmaf(h, h, s);
-      }
-      loc[3] += s * (1.0f / ((float)d.Mm * (float)d.Mm));
-      continue;
-    }
-    i -= d.Mm;
     loc[4] += fabsf(d.sky_expected[i] - d.sky_term[i]) * (1.0f / d.Ms);  // :485-490
   }
   block_accumulate<NT_DDF>(loc, terms);
@@ -265,7 +277,25 @@ __global__ __launch_bounds__(256) void ddf_losses_bwd_kernel(nsky_ddf_losses_des
                                                              float* __restrict__ d_expected, float* __restrict__ d_sdf,
                                                              float* __restrict__ d_mv, float* __restrict__ d_sky,
                                                              float* __restrict__ d_term, float* __restrict__ d_mv_term) {
-  const long total = (long)d.Mr + d.Mm + d.Ms;
+  if (d_mv || d_mv_term) {  // a wave per row i of the [M, M] broadcast; both sums run over the other index in one pass
+    const int lane = threadIdx.x & 63;
+    const long waves = (long)gridDim.x * blockDim.x / 64;
+    const float c = g[3] * 2.0f * (1.0f / ((float)d.Mm * (float)d.Mm));
+    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) / 64; i < d.Mm; i += waves) {
+      const float a = d.mv_expected[i], b = d.mv_term[i];
+      float sa = 0.f, sb = 0.f;
+      for (int k = lane; k < d.Mm; k += 64) {
+        sa += fmaxf(a - d.mv_term[k], 0.0f);
+        sb += fmaxf(d.mv_expected[k] - b, 0.0f);  // row i of the transposed broadcast: -sum_j relu(a_j - b_i)
+      }
+      sa = wave_sum(sa); sb = wave_sum(sb);
+      if (lane == 0) {
+        if (d_mv) d_mv[i] = c * sa;
+        if (d_mv_term) d_mv_term[i] = -c * sb;
+      }
+    }
+  }
+  const long total = (long)d.Mr + d.Ms;
   for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += (long)gridDim.x * blockDim.x) {
     long i = w;
     if (i < d.Mr) {
@@ -297,23 +327,6 @@ __global__ __launch_bounds__(256) void ddf_losses_bwd_kernel(nsky_ddf_losses_des
       continue;
     }
     i -= d.Mr;
-    if (i < d.Mm) {
-      const float c = g[3] * 2.0f * (1.0f / ((float)d.Mm * (float)d.Mm));
-      if (d_mv) {
-        const float a = d.mv_expected[i];
-        float s = 0.f;
-        for (int k = 0; k < d.Mm; ++k) s += fmaxf(a - d.mv_term[k], 0.0f);
-        d_mv[i] = c * s;
-      }
-      if (d_mv_term) {  // row i of the [M,M] broadcast: -sum_j relu(a_j - b_i)
-        const float b = d.mv_term[i];
-        float s = 0.f;
-        for (int k = 0; k < d.Mm; ++k) s += fmaxf(d.mv_expected[k] - b, 0.0f);
-        d_mv_term[i] = -c * s;
-      }
-      continue;
-    }
-    i -= d.Mm;
     if (d_sky) d_sky[i] = g[4] * sgnf(d.sky_expected[i] - d.sky_term[i]) * (1.0f / d.Ms);
   }
 }
@@ -321,6 +334,13 @@ __global__ __launch_bounds__(256) void ddf_losses_bwd_kernel(nsky_ddf_losses_des
 int grid_for(long total) {
   long b = (total + 255) / 256;
   return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+}
+
+// the kernels that end in atomics on a handful of words: `threads` is the most one of their loops can use; at most 256 workgroups, so a
+// word receives at most 256 atomics (they serialise at the memory side) and a thread makes a few grid-stride passes
+int reduce_grid_for(long threads) {
+  long b = (threads + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > 256 ? 256 : b));
 }
 
 // The scalar training metrics of one model in ONE launch (one workgroup): PSNR = 10 log10(peak^2 / mean(((pred - gt) mask)^2))
@@ -414,7 +434,8 @@ extern "C" int nsky_main_losses_fwd(const nsky_main_losses_desc* d, float* terms
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(terms, 0, NT_MAIN * sizeof(float), s) != hipSuccess) { nsky_set_error("nsky_main_losses_fwd: memset failed"); return NSKY_ERR_LAUNCH; }
   const long total = d->R + (d->eik ? (long)d->R * d->S : 0) + (d->grid ? 3l * d->P : 0) + (d->sdf_term ? d->M : 0);
-  hipLaunchKernelGGL(main_losses_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, *d, terms, wsum);
+  const long ray_threads = d->weights ? 16l * d->R : 0;  // sixteen lanes per ray for the weight sums
+  hipLaunchKernelGGL(main_losses_fwd_kernel, dim3(reduce_grid_for(total > ray_threads ? total : ray_threads)), dim3(256), 0, s, *d, terms, wsum);
   NSKY_CHECK_LAUNCH("nsky_main_losses_fwd");
   return NSKY_OK;
 }
@@ -443,7 +464,8 @@ extern "C" int nsky_ddf_losses_fwd(const nsky_ddf_losses_desc* d, float* terms, 
   if (hipMemsetAsync(terms, 0, NT_DDF * sizeof(float), s) != hipSuccess) { nsky_set_error("nsky_ddf_losses_fwd: memset failed"); return NSKY_ERR_LAUNCH; }
   const long total = (long)d->Mr + d->Mm + d->Ms;
   if (total == 0) return NSKY_OK;
-  hipLaunchKernelGGL(ddf_losses_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, *d, terms);
+  const long stream_threads = (long)d->Mr + d->Ms, pair_threads = 64l * d->Mm;  // a wave per multi-view row
+  hipLaunchKernelGGL(ddf_losses_fwd_kernel, dim3(reduce_grid_for(stream_threads > pair_threads ? stream_threads : pair_threads)), dim3(256), 0, s, *d, terms);
   NSKY_CHECK_LAUNCH("nsky_ddf_losses_fwd");
   return NSKY_OK;
 }
@@ -454,7 +476,8 @@ extern "C" int nsky_ddf_losses_bwd(const nsky_ddf_losses_desc* d, const float* d
   NSKY_CHECK_ARG((!d_sdf || d->sdf) && (!d_expected || d->expected), "nsky_ddf_losses_bwd: a gradient was requested for an absent input");
   const long total = (long)d->Mr + d->Mm + d->Ms;
   if (total == 0) return NSKY_OK;
-  hipLaunchKernelGGL(ddf_losses_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, *d, d_terms, d_expected, d_sdf,
+  const long stream_threads = (long)d->Mr + d->Ms, pair_threads = 64l * d->Mm;  // a wave per multi-view row
+  hipLaunchKernelGGL(ddf_losses_bwd_kernel, dim3(grid_for(stream_threads > pair_threads ? stream_threads : pair_threads)), dim3(256), 0, (hipStream_t)stream, *d, d_terms, d_expected, d_sdf,
                      d_mv_expected, d_sky_expected, d_term, d_mv_term);
   NSKY_CHECK_LAUNCH("nsky_ddf_losses_bwd");
   return NSKY_OK;

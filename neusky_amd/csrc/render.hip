@@ -12,19 +12,58 @@
 namespace {
 
 constexpr int MAXD = 1024;  // max illumination directions
-constexpr int JPL = MAXD / 64;
 
-// one workgroup (4 waves) per ray; wave w takes samples w, w+4, ...; lanes stride the D directions
+// The three-term products of these kernels, in the one form their results have always had: (x0 y0 + rn(x1 y1)) + rn(x2 y2), the first
+// product fused, the other two rounded on their own.  Written out with contraction off so that no rearrangement of the loops around
+// them changes which products the compiler fuses: the rendered colours and their gradients stay bit for bit what they were.
+__device__ __forceinline__ float dot3(float x0, float y0, float x1, float y1, float x2, float y2) {
+#pragma clang fp contract(off)
+  const float p1 = x1 * y1, p2 = x2 * y2;
+  return fmaf(x0, y0, p1) + p2;
+}
+
+// sum_c gcomp_c (albedo_c I_c - bg_c) with the roundings it has always had: channels 0 and 1 round their product before the background
+// is taken off, channel 2 fuses it; the sum starts from channel 1's term
+__device__ __forceinline__ float weight_gradient(const float (&gcomp)[3], const float (&bgc)[3], float al0, float I0, float al1, float I1, float al2,
+                                                 float I2) {
+#pragma clang fp contract(off)
+  const float r0 = al0 * I0, r1 = al1 * I1;
+  const float t0 = r0 - bgc[0], t1 = r1 - bgc[1], t2 = fmaf(I2, al2, -bgc[2]);
+  const float g1 = gcomp[1] * t1;
+  return fmaf(gcomp[2], t2, fmaf(gcomp[0], t0, g1));
+}
+
+// Four wave sums for the price of seven exchanges instead of twenty-four: at the xor-32 level a lane keeps one value of a pair and hands
+// the other to its partner, at the xor-16 level likewise for the two pairs, and the last four levels carry one value per 16-lane group.
+// Every value is added in exactly the tree wave_sum() uses ((l, l^32), then ^16, ^8, ...; float addition commutes), so the totals are
+// bit-equal to four wave_sum() calls.  They come back to all lanes through SGPRs.
+__device__ __forceinline__ float lane_value(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+__device__ __forceinline__ void wave_sum4(float& v0, float& v1, float& v2, float& v3, int lane) {
+  const bool h32 = (lane & 32) != 0, h16 = (lane & 16) != 0;
+  const float a = (h32 ? v1 : v0) + __shfl_xor(h32 ? v0 : v1, 32, 64);
+  const float b = (h32 ? v3 : v2) + __shfl_xor(h32 ? v2 : v3, 32, 64);
+  float x = (h16 ? b : a) + __shfl_xor(h16 ? a : b, 16, 64);
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+  v0 = lane_value(x, 0); v2 = lane_value(x, 16); v1 = lane_value(x, 32); v3 = lane_value(x, 48);
+}
+
+// One workgroup (4 waves) per ray; wave w takes samples w, w+4, ...; lanes stride the D directions.  A lane's directions j = lane + 64 q
+// never change, so their (direction, visibility x colour) rows are read into registers once (NQ = ceil(D / 64) rounded up to 4, 8 or 16;
+// rows past D are zero and add nothing), and a wave reads the normals / albedo / weights of up to 64 of its samples with one load per
+// lane and hands them round by readlane: the sample loop touches no memory.
+template <int NQ>
 __global__ __launch_bounds__(256) void hemi_fwd_kernel(const float* __restrict__ albedo, const float* __restrict__ normals,
                                                        const float* __restrict__ weights, const float* __restrict__ dirs,
                                                        const float* __restrict__ cam_colours, const int* __restrict__ cam_of_ray,
                                                        const float* __restrict__ vis, const float* __restrict__ bg, int R, int S,
                                                        int D, float* __restrict__ rgb, float* __restrict__ lin) {
-  __shared__ float sdir[MAXD * 3];
-  __shared__ float svl[MAXD * 3];
+  __shared__ float sdir[NQ * 64 * 3];
+  __shared__ float svl[NQ * 64 * 3];
   __shared__ float red[4][4];
   const int r = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const float* col = cam_colours + (long)cam_of_ray[r] * D * 3;
   for (int i = threadIdx.x; i < D * 3; i += 256) {
     sdir[i] = dirs[i];
@@ -32,24 +71,43 @@ __global__ __launch_bounds__(256) void hemi_fwd_kernel(const float* __restrict__
     svl[i] = v * col[i];
   }
   __syncthreads();
+  float lx[NQ], ly[NQ], lz[NQ], v0[NQ], v1[NQ], v2[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int j = lane + 64 * q;
+    const bool in = j < D;
+    lx[q] = in ? sdir[3 * j] : 0.0f; ly[q] = in ? sdir[3 * j + 1] : 0.0f; lz[q] = in ? sdir[3 * j + 2] : 0.0f;
+    v0[q] = in ? svl[3 * j] : 0.0f; v1[q] = in ? svl[3 * j + 1] : 0.0f; v2[q] = in ? svl[3 * j + 2] : 0.0f;
+  }
   float c0 = 0.f, c1 = 0.f, c2 = 0.f, wsum = 0.f;
-  for (int s = wave; s < S; s += 4) {
-    const long o = ((long)r * S + s) * 3;
-    const float nx = normals[o], ny = normals[o + 1], nz = normals[o + 2];
-    float cnt = 0.f, a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    for (int j = lane; j < D; j += 64) {
-      float d = nx * sdir[3 * j] + ny * sdir[3 * j + 1] + nz * sdir[3 * j + 2];
-      d = fminf(fmaxf(d, 0.0f), 1.0f);
-      cnt += d > 0.0f ? 1.0f : 0.0f;
-      a0 = fmaf(d, svl[3 * j], a0); a1 = fmaf(d, svl[3 * j + 1], a1); a2 = fmaf(d, svl[3 * j + 2], a2);
+  const int mine = S > wave ? (S - wave + 3) / 4 : 0;  // samples of this wave
+  for (int base = 0; base < mine; base += 64) {
+    const int sl = wave + 4 * (base + lane);  // lane l holds the inputs of the wave's sample base + l
+    float pn0 = 0.f, pn1 = 0.f, pn2 = 0.f, pa0 = 0.f, pa1 = 0.f, pa2 = 0.f, pw = 0.f;
+    if (sl < S) {
+      const long o = ((long)r * S + sl) * 3;
+      pn0 = normals[o]; pn1 = normals[o + 1]; pn2 = normals[o + 2];
+      pa0 = albedo[o]; pa1 = albedo[o + 1]; pa2 = albedo[o + 2];
+      pw = weights[(long)r * S + sl];
     }
-    cnt = wave_sum(cnt); a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
-    const float inv = 1.0f / (cnt > 0.0f ? cnt : 1.0f);
-    const float w = weights[(long)r * S + s];
-    c0 = fmaf(w, albedo[o] * a0 * inv, c0);
-    c1 = fmaf(w, albedo[o + 1] * a1 * inv, c1);
-    c2 = fmaf(w, albedo[o + 2] * a2 * inv, c2);
-    wsum += w;
+    const int here = min(64, mine - base);
+    for (int k = 0; k < here; ++k) {
+      const float nx = lane_value(pn0, k), ny = lane_value(pn1, k), nz = lane_value(pn2, k);
+      float cnt = 0.f, a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const float d = fminf(fmaxf(dot3(nx, lx[q], ny, ly[q], nz, lz[q]), 0.0f), 1.0f);
+        cnt += d > 0.0f ? 1.0f : 0.0f;
+        a0 = fmaf(d, v0[q], a0); a1 = fmaf(d, v1[q], a1); a2 = fmaf(d, v2[q], a2);
+      }
+      wave_sum4(cnt, a0, a1, a2, lane);
+      const float inv = 1.0f / (cnt > 0.0f ? cnt : 1.0f);
+      const float w = lane_value(pw, k);
+      c0 = fmaf(w, lane_value(pa0, k) * a0 * inv, c0);
+      c1 = fmaf(w, lane_value(pa1, k) * a1 * inv, c1);
+      c2 = fmaf(w, lane_value(pa2, k) * a2 * inv, c2);
+      wsum += w;
+    }
   }
   if (lane == 0) { red[wave][0] = c0; red[wave][1] = c1; red[wave][2] = c2; red[wave][3] = wsum; }
   __syncthreads();
@@ -62,7 +120,9 @@ __global__ __launch_bounds__(256) void hemi_fwd_kernel(const float* __restrict__
   }
 }
 
-__global__ __launch_bounds__(256) void hemi_bwd_kernel(const float* __restrict__ albedo, const float* __restrict__ normals,
+// the backward recomputes the forward's sums with the same registers and keeps A[q][c] = sum_s gI_c clamp(n.l_j) beside them
+template <int NQ>
+__global__ __launch_bounds__(256, NQ <= 8 ? 4 : 1) void hemi_bwd_kernel(const float* __restrict__ albedo, const float* __restrict__ normals,
                                                        const float* __restrict__ weights, const float* __restrict__ dirs,
                                                        const float* __restrict__ cam_colours, const int* __restrict__ cam_of_ray,
                                                        const float* __restrict__ vis, const float* __restrict__ bg,
@@ -70,12 +130,12 @@ __global__ __launch_bounds__(256) void hemi_bwd_kernel(const float* __restrict__
                                                        int S, int D, float* __restrict__ d_albedo, float* __restrict__ d_normals,
                                                        float* __restrict__ d_weights, float* __restrict__ d_cam_colours,
                                                        float* __restrict__ d_vis, float* __restrict__ d_bg) {
-  __shared__ float sdir[MAXD * 3];
-  __shared__ float svl[MAXD * 3];
-  __shared__ float sA[4][MAXD * 3];  // per-wave sum_s gI_c * clamp(n.l_j)
+  __shared__ float sdir[NQ * 64 * 3];
+  __shared__ float svl[NQ * 64 * 3];
+  __shared__ float sA[4][NQ * 64 * 3];  // per-wave sum_s gI_c * clamp(n.l_j)
   __shared__ float red[4];
   const int r = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int cam = cam_of_ray[r];
   const float* col = cam_colours + (long)cam * D * 3;
   for (int i = threadIdx.x; i < D * 3; i += 256) {
@@ -90,69 +150,91 @@ __global__ __launch_bounds__(256) void hemi_bwd_kernel(const float* __restrict__
     gcomp[c] = d_rgb[(long)r * 3 + c] * srgb_bwd(lin[(long)r * 3 + c]);
     bgc[c] = bg[(long)r * 3 + c];
   }
-  float A[JPL][3];
+  float lx[NQ], ly[NQ], lz[NQ], v0[NQ], v1[NQ], v2[NQ];
+  float A[NQ][3];
 #pragma unroll
-  for (int q = 0; q < JPL; ++q) A[q][0] = A[q][1] = A[q][2] = 0.0f;
+  for (int q = 0; q < NQ; ++q) {
+    const int j = lane + 64 * q;
+    const bool in = j < D;
+    lx[q] = in ? sdir[3 * j] : 0.0f; ly[q] = in ? sdir[3 * j + 1] : 0.0f; lz[q] = in ? sdir[3 * j + 2] : 0.0f;
+    v0[q] = in ? svl[3 * j] : 0.0f; v1[q] = in ? svl[3 * j + 1] : 0.0f; v2[q] = in ? svl[3 * j + 2] : 0.0f;
+    A[q][0] = A[q][1] = A[q][2] = 0.0f;
+  }
   float wsum = 0.f;
-  for (int s = wave; s < S; s += 4) {
-    const long o = ((long)r * S + s) * 3;
-    const float nx = normals[o], ny = normals[o + 1], nz = normals[o + 2];
-    float cnt = 0.f, a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    for (int j = lane; j < D; j += 64) {
-      float d = nx * sdir[3 * j] + ny * sdir[3 * j + 1] + nz * sdir[3 * j + 2];
-      d = fminf(fmaxf(d, 0.0f), 1.0f);
-      cnt += d > 0.0f ? 1.0f : 0.0f;
-      a0 = fmaf(d, svl[3 * j], a0); a1 = fmaf(d, svl[3 * j + 1], a1); a2 = fmaf(d, svl[3 * j + 2], a2);
+  const int mine = S > wave ? (S - wave + 3) / 4 : 0;  // samples of this wave
+  for (int base = 0; base < mine; base += 64) {
+    const int sl = wave + 4 * (base + lane);  // lane l holds the inputs of the wave's sample base + l
+    float pn0 = 0.f, pn1 = 0.f, pn2 = 0.f, pa0 = 0.f, pa1 = 0.f, pa2 = 0.f, pw = 0.f;
+    if (sl < S) {
+      const long o = ((long)r * S + sl) * 3;
+      pn0 = normals[o]; pn1 = normals[o + 1]; pn2 = normals[o + 2];
+      pa0 = albedo[o]; pa1 = albedo[o + 1]; pa2 = albedo[o + 2];
+      pw = weights[(long)r * S + sl];
     }
-    cnt = wave_sum(cnt); a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
-    const float inv = 1.0f / (cnt > 0.0f ? cnt : 1.0f);
-    const float w = weights[(long)r * S + s];
-    const float al0 = albedo[o], al1 = albedo[o + 1], al2 = albedo[o + 2];
-    const float I0 = a0 * inv, I1 = a1 * inv, I2 = a2 * inv;
-    // d comp / d w_s = rad_c - bg_c ; d comp / d albedo = w I ; d comp / d I = w albedo
-    const float gw = gcomp[0] * (al0 * I0 - bgc[0]) + gcomp[1] * (al1 * I1 - bgc[1]) + gcomp[2] * (al2 * I2 - bgc[2]);
-    const float gI0 = gcomp[0] * w * al0 * inv, gI1 = gcomp[1] * w * al1 * inv, gI2 = gcomp[2] * w * al2 * inv;
-    float gn0 = 0.f, gn1 = 0.f, gn2 = 0.f;
+    const int here = min(64, mine - base);
+    for (int k = 0; k < here; ++k) {
+      const float nx = lane_value(pn0, k), ny = lane_value(pn1, k), nz = lane_value(pn2, k);
+      float cnt = 0.f, a0 = 0.f, a1 = 0.f, a2 = 0.f;
 #pragma unroll
-    for (int q = 0; q < JPL; ++q) {
-      const int j = lane + 64 * q;
-      if (j < D) {
-        const float lx = sdir[3 * j], ly = sdir[3 * j + 1], lz = sdir[3 * j + 2];
-        const float draw = nx * lx + ny * ly + nz * lz;
+      for (int q = 0; q < NQ; ++q) {
+        const float d = fminf(fmaxf(dot3(nx, lx[q], ny, ly[q], nz, lz[q]), 0.0f), 1.0f);
+        cnt += d > 0.0f ? 1.0f : 0.0f;
+        a0 = fmaf(d, v0[q], a0); a1 = fmaf(d, v1[q], a1); a2 = fmaf(d, v2[q], a2);
+      }
+      wave_sum4(cnt, a0, a1, a2, lane);
+      const float inv = 1.0f / (cnt > 0.0f ? cnt : 1.0f);
+      const float w = lane_value(pw, k);
+      const float al0 = lane_value(pa0, k), al1 = lane_value(pa1, k), al2 = lane_value(pa2, k);
+      const float I0 = a0 * inv, I1 = a1 * inv, I2 = a2 * inv;
+      // d comp / d w_s = rad_c - bg_c ; d comp / d albedo = w I ; d comp / d I = w albedo
+      const float gw = weight_gradient(gcomp, bgc, al0, I0, al1, I1, al2, I2);
+      const float gI0 = gcomp[0] * w * al0 * inv, gI1 = gcomp[1] * w * al1 * inv, gI2 = gcomp[2] * w * al2 * inv;
+      float gn0 = 0.f, gn1 = 0.f, gn2 = 0.f, unused = 0.f;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const float draw = dot3(nx, lx[q], ny, ly[q], nz, lz[q]);
         const float dc = fminf(fmaxf(draw, 0.0f), 1.0f);
         // torch.clamp_ passes gradient on the closed interval [0, 1]
         if (draw >= 0.0f && draw <= 1.0f) {
-          const float qj = gI0 * svl[3 * j] + gI1 * svl[3 * j + 1] + gI2 * svl[3 * j + 2];
-          gn0 = fmaf(qj, lx, gn0); gn1 = fmaf(qj, ly, gn1); gn2 = fmaf(qj, lz, gn2);
+          const float qj = dot3(gI0, v0[q], gI1, v1[q], gI2, v2[q]);
+          gn0 = fmaf(qj, lx[q], gn0); gn1 = fmaf(qj, ly[q], gn1); gn2 = fmaf(qj, lz[q], gn2);
         }
         A[q][0] = fmaf(gI0, dc, A[q][0]); A[q][1] = fmaf(gI1, dc, A[q][1]); A[q][2] = fmaf(gI2, dc, A[q][2]);
       }
+      wave_sum4(gn0, gn1, gn2, unused, lane);
+      if (lane == 0) {
+        const long o = ((long)r * S + wave + 4 * (base + k)) * 3;
+        d_albedo[o] = gcomp[0] * w * I0; d_albedo[o + 1] = gcomp[1] * w * I1; d_albedo[o + 2] = gcomp[2] * w * I2;
+        d_normals[o] = gn0; d_normals[o + 1] = gn1; d_normals[o + 2] = gn2;
+        d_weights[(long)r * S + wave + 4 * (base + k)] = gw;
+      }
+      wsum += w;
     }
-    gn0 = wave_sum(gn0); gn1 = wave_sum(gn1); gn2 = wave_sum(gn2);
-    if (lane == 0) {
-      d_albedo[o] = gcomp[0] * w * I0; d_albedo[o + 1] = gcomp[1] * w * I1; d_albedo[o + 2] = gcomp[2] * w * I2;
-      d_normals[o] = gn0; d_normals[o + 1] = gn1; d_normals[o + 2] = gn2;
-      d_weights[(long)r * S + s] = gw;
-    }
-    wsum += w;
   }
 #pragma unroll
-  for (int q = 0; q < JPL; ++q) {
+  for (int q = 0; q < NQ; ++q) {
     const int j = lane + 64 * q;
     if (j < D) { sA[wave][3 * j] = A[q][0]; sA[wave][3 * j + 1] = A[q][1]; sA[wave][3 * j + 2] = A[q][2]; }
   }
   if (lane == 0) red[wave] = wsum;
   __syncthreads();
-  for (int j = threadIdx.x; j < D; j += 256) {
-    float gv = 0.f;
-    const float v = vis ? vis[(long)r * D + j] : 1.0f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float a = sA[0][3 * j + c] + sA[1][3 * j + c] + sA[2][3 * j + c] + sA[3][3 * j + c];
-      gv = fmaf(a, col[3 * j + c], gv);
-      if (d_cam_colours) atomicAdd(d_cam_colours + ((long)cam * D + j) * 3 + c, a * v);
+  // the waves' sums meet in sA[0]; a thread walks the camera's row of [D, 3] linearly, so a wave's atomics are 256 contiguous bytes
+  for (int i = threadIdx.x; i < D * 3; i += 256) {
+    const float a = sA[0][i] + sA[1][i] + sA[2][i] + sA[3][i];
+    sA[0][i] = a;
+    if (d_cam_colours) {
+      const float v = vis ? vis[(long)r * D + i / 3] : 1.0f;
+      atomicAdd(d_cam_colours + (long)cam * D * 3 + i, a * v);
     }
-    if (d_vis) d_vis[(long)r * D + j] = gv;
+  }
+  if (d_vis) {
+    __syncthreads();
+    for (int j = threadIdx.x; j < D; j += 256) {
+      float gv = 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) gv = fmaf(sA[0][3 * j + c], col[3 * j + c], gv);
+      d_vis[(long)r * D + j] = gv;
+    }
   }
   if (threadIdx.x < 3) {
     const float acc = red[0] + red[1] + red[2] + red[3];
@@ -505,17 +587,27 @@ __global__ void visibility_finish_bwd_kernel(const float* __restrict__ t_hat, co
                                              const float* __restrict__ threshold, float scale, const int* __restrict__ sel_index,
                                              int R, int Dv, int D, const float* __restrict__ d_vis, float* __restrict__ d_t_hat,
                                              float* __restrict__ d_threshold) {
-  const long m = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  // grid-stride over the rows; the workgroup's share of the threshold's gradient leaves as ONE atomic (the word is a single address:
+  // its atomics serialise at the memory side, so their count, not the rows' bytes, used to set this kernel's time)
+  __shared__ double red[4];
+  const long n = (long)R * Dv;
+  const double thr = (double)threshold[0];
   double gthr = 0.0;
-  if (m < (long)R * Dv) {
+  for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < n; m += (long)gridDim.x * blockDim.x) {
     const int r = (int)(m / Dv), j = (int)(m % Dv);
-    const double s = 1.0 / (1.0 + exp(-(double)scale * ((double)surf_dist[m] - (double)t_hat[m] - (double)threshold[0])));
+    const double s = 1.0 / (1.0 + exp(-(double)scale * ((double)surf_dist[m] - (double)t_hat[m] - thr)));
     const double g = (double)d_vis[(long)r * D + sel_index[j]] * s * (1.0 - s) * (double)scale;  // d vis / d t_hat = + s' * scale
     d_t_hat[m] = (float)g;
-    gthr = g;
+    gthr += g;
   }
+  if (!d_threshold) return;
   gthr = wave_sum_f64(gthr);
-  if ((threadIdx.x & 63) == 0 && d_threshold && gthr != 0.0) atomicAdd(d_threshold, (float)gthr);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = gthr;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double t = (red[0] + red[1]) + (red[2] + red[3]);
+    if (t != 0.0) atomicAdd(d_threshold, (float)t);
+  }
 }
 
 
@@ -658,14 +750,17 @@ __global__ __launch_bounds__(256) void interlevel_kernel(const float* __restrict
   int* cover = reinterpret_cast<int*>(diff + (n + 1));
   for (int i = lane; i <= n; i += 64) {
     bins[i] = sb[(long)r * (n + 1) + i];
+    cy[i] = i == 0 ? 0.0f : wp[(long)r * n + i - 1];  // the whole wave brings wp in; lane 0 then sums it in place
     if (BWD) { diff[i] = 0.0f; cover[i] = 0; }
   }
+  __builtin_amdgcn_wave_barrier();
+  __threadfence_block();
   if (lane == 0) {  // sequential prefix sums (n <= 1023, the host's LDS limit), the order torch.cumsum uses on one row
     float acc = 0.0f;
-    cy[0] = 0.0f;
-    for (int i = 0; i < n; ++i) {
-      acc += wp[(long)r * n + i];
-      cy[i + 1] = acc;
+#pragma unroll 8
+    for (int i = 1; i <= n; ++i) {
+      acc += cy[i];
+      cy[i] = acc;
     }
   }
   __builtin_amdgcn_wave_barrier();
@@ -696,15 +791,19 @@ __global__ __launch_bounds__(256) void interlevel_kernel(const float* __restrict
   }
   __builtin_amdgcn_wave_barrier();
   __threadfence_block();
-  if (lane == 0) {
+  if (lane == 0) {  // the same sequential order as before, in place; the row then leaves with all lanes
     float acc = 0.0f;
     int cnt = 0;
+#pragma unroll 8
     for (int i = 0; i < n; ++i) {
       acc += diff[i];
       cnt += cover[i];
-      d_wp[(long)r * n + i] = cnt > 0 ? acc : 0.0f;
+      diff[i] = cnt > 0 ? acc : 0.0f;
     }
   }
+  __builtin_amdgcn_wave_barrier();
+  __threadfence_block();
+  for (int i = lane; i < n; i += 64) d_wp[(long)r * n + i] = diff[i];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -732,35 +831,46 @@ __device__ __forceinline__ void atomic_max_float(float* addr, float v) {
   }
 }
 
-__global__ __launch_bounds__(256) void ray_reduce_fwd_kernel(const float* __restrict__ w, const float* __restrict__ starts,
-                                                             const float* __restrict__ ends, const float* __restrict__ normals,
-                                                             const float* __restrict__ albedo, int R, int S, float* __restrict__ sums,
-                                                             float* __restrict__ bounds) {
-  const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= R) return;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+constexpr int RR_WAVES = 16, RR_MAX_BLOCKS = 32;
+
+__global__ __launch_bounds__(RR_WAVES * 64) void ray_reduce_fwd_kernel(const float* __restrict__ w, const float* __restrict__ starts,
+                                                                       const float* __restrict__ ends, const float* __restrict__ normals,
+                                                                       const float* __restrict__ albedo, int R, int S,
+                                                                       float* __restrict__ sums, float* __restrict__ bounds) {
+  // RR_WAVES waves per workgroup, a wave per ray, grid-stride over the rays; the clip bounds of all the workgroup's rays meet in LDS
+  // and leave as one CAS loop each (the two words are single addresses: every update of them serialises)
+  __shared__ float smn[RR_WAVES], smx[RR_WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float mn = 3.0e38f, mx = -3.0e38f;
-  for (int k = lane; k < S; k += 64) {
-    const long i = (long)r * S + k;
-    const float wk = w[i], mid = (starts[i] + ends[i]) * 0.5f;
-    mn = fminf(mn, mid); mx = fmaxf(mx, mid);
-    acc[0] = fmaf(wk, mid, acc[0]);
-    acc[1] += wk;
-    if (normals)
+  for (int r = blockIdx.x * RR_WAVES + wave; r < R; r += gridDim.x * RR_WAVES) {
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int k = lane; k < S; k += 64) {
+      const long i = (long)r * S + k;
+      const float wk = w[i], mid = (starts[i] + ends[i]) * 0.5f;
+      mn = fminf(mn, mid); mx = fmaxf(mx, mid);
+      acc[0] = fmaf(wk, mid, acc[0]);
+      acc[1] += wk;
+      if (normals)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) acc[2 + c] = fmaf(wk, normals[i * 3 + c], acc[2 + c]);
-    if (albedo)
+        for (int c = 0; c < 3; ++c) acc[2 + c] = fmaf(wk, normals[i * 3 + c], acc[2 + c]);
+      if (albedo)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) acc[5 + c] = fmaf(wk, albedo[i * 3 + c], acc[5 + c]);
+        for (int c = 0; c < 3; ++c) acc[5 + c] = fmaf(wk, albedo[i * 3 + c], acc[5 + c]);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+    if (lane == 0) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sums[(long)r * 8 + j] = acc[j];
+    }
   }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
-#pragma unroll
   for (int off = 32; off > 0; off >>= 1) { mn = fminf(mn, __shfl_xor(mn, off, 64)); mx = fmaxf(mx, __shfl_xor(mx, off, 64)); }
-  if (lane == 0) {
+  if (lane == 0) { smn[wave] = mn; smx[wave] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) sums[(long)r * 8 + j] = acc[j];
+    for (int v = 1; v < RR_WAVES; ++v) { mn = fminf(mn, smn[v]); mx = fmaxf(mx, smx[v]); }
     atomic_min_float(bounds, mn);
     atomic_max_float(bounds + 1, mx);
   }
@@ -894,8 +1004,9 @@ extern "C" int nsky_hemi_composite_fwd(const float* albedo, const float* normals
   if (R == 0) return NSKY_OK;
   NSKY_CHECK_ARG(albedo && normals && weights && dirs && cam_colours && cam_of_ray && bg && rgb, "nsky_hemi_composite_fwd: null argument");
   NSKY_CHECK_ARG(R > 0 && S > 0 && D > 0 && D <= MAXD, "nsky_hemi_composite_fwd: bad sizes R=%d S=%d D=%d (D <= %d)", R, S, D, MAXD);
-  hipLaunchKernelGGL(hemi_fwd_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, albedo, normals, weights, dirs, cam_colours,
-                     cam_of_ray, vis, bg, R, S, D, rgb, lin);
+  auto kernel = D <= 256 ? hemi_fwd_kernel<4> : D <= 512 ? hemi_fwd_kernel<8> : hemi_fwd_kernel<MAXD / 64>;
+  hipLaunchKernelGGL(kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, albedo, normals, weights, dirs, cam_colours, cam_of_ray, vis, bg,
+                     R, S, D, rgb, lin);
   NSKY_CHECK_LAUNCH("nsky_hemi_composite_fwd");
   return NSKY_OK;
 }
@@ -909,8 +1020,9 @@ extern "C" int nsky_hemi_composite_bwd(const float* albedo, const float* normals
   NSKY_CHECK_ARG(albedo && normals && weights && dirs && cam_colours && cam_of_ray && bg && lin && d_rgb && d_albedo && d_normals &&
                      d_weights && d_bg, "nsky_hemi_composite_bwd: null argument");
   NSKY_CHECK_ARG(R > 0 && S > 0 && D > 0 && D <= MAXD, "nsky_hemi_composite_bwd: bad sizes R=%d S=%d D=%d (D <= %d)", R, S, D, MAXD);
-  hipLaunchKernelGGL(hemi_bwd_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, albedo, normals, weights, dirs, cam_colours,
-                     cam_of_ray, vis, bg, lin, d_rgb, R, S, D, d_albedo, d_normals, d_weights, d_cam_colours, d_vis, d_bg);
+  auto kernel = D <= 256 ? hemi_bwd_kernel<4> : D <= 512 ? hemi_bwd_kernel<8> : hemi_bwd_kernel<MAXD / 64>;
+  hipLaunchKernelGGL(kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, albedo, normals, weights, dirs, cam_colours, cam_of_ray, vis, bg,
+                     lin, d_rgb, R, S, D, d_albedo, d_normals, d_weights, d_cam_colours, d_vis, d_bg);
   NSKY_CHECK_LAUNCH("nsky_hemi_composite_bwd");
   return NSKY_OK;
 }
@@ -997,7 +1109,8 @@ extern "C" int nsky_visibility_finish_bwd(const float* t_hat, const float* surf_
   NSKY_CHECK_ARG(t_hat && surf_dist && threshold && sel_index && d_vis && d_t_hat && R > 0 && Dv > 0 && D >= Dv,
                  "nsky_visibility_finish_bwd: bad argument");
   const long n = (long)R * Dv;
-  hipLaunchKernelGGL(visibility_finish_bwd_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, t_hat, surf_dist,
+  const long blocks = ceil_div(n, 256);  // at most 256 workgroups: one atomic each into d_threshold
+  hipLaunchKernelGGL(visibility_finish_bwd_kernel, dim3(blocks < 256 ? blocks : 256), dim3(256), 0, (hipStream_t)stream, t_hat, surf_dist,
                      threshold, scale, sel_index, R, Dv, D, d_vis, d_t_hat, d_threshold);
   NSKY_CHECK_LAUNCH("nsky_visibility_finish_bwd");
   return NSKY_OK;
@@ -1056,8 +1169,11 @@ extern "C" int nsky_ray_reduce_fwd(const float* weights, const float* starts, co
   NSKY_CHECK_ARG(weights && starts && ends && sums && bounds && p2p && accumulation && R > 0 && S > 0, "nsky_ray_reduce_fwd: bad argument");
   NSKY_CHECK_ARG((normals != nullptr) == (normal != nullptr) && (albedo != nullptr) == (albedo_acc != nullptr),
                  "nsky_ray_reduce_fwd: normals / albedo inputs and outputs go together");
-  hipLaunchKernelGGL(ray_reduce_fwd_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, (hipStream_t)stream, weights, starts, ends, normals, albedo,
-                     R, S, sums, bounds);
+  // every workgroup has a ray; RR_MAX_BLOCKS updates reach each clip bound at the train step's ray counts, and a frame chunk's larger
+  // ray sets keep at most eight rays per wave
+  const int blocks = ceil_div(R, RR_WAVES), cap = ceil_div(R, RR_WAVES * 8) > RR_MAX_BLOCKS ? ceil_div(R, RR_WAVES * 8) : RR_MAX_BLOCKS;
+  hipLaunchKernelGGL(ray_reduce_fwd_kernel, dim3(blocks < cap ? blocks : cap), dim3(RR_WAVES * 64), 0, (hipStream_t)stream, weights, starts,
+                     ends, normals, albedo, R, S, sums, bounds);
   hipLaunchKernelGGL(ray_reduce_finish_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, (hipStream_t)stream, sums, bounds, R, max_clamp, p2p,
                      accumulation, normal, albedo_acc);
   NSKY_CHECK_LAUNCH("nsky_ray_reduce_fwd");
