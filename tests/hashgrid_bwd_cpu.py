@@ -20,17 +20,18 @@ C_LATTICE = 1.6e-6
 
 
 # ---- the gradient ---------------------------------------------------------------------------------------------------------------
-def grid_position(x, mode):
-    """x [P,3] -> pos [P,3] fed to the grid and J [P,3,3], J[p,a,k] = d pos_a / d x_k, in float64.
+def grid_position(x, mode, dtype=torch.float64):
+    """x [P,3] -> pos [P,3] fed to the grid and J [P,3,3], J[p,a,k] = d pos_a / d x_k, in float64 (or in `dtype`:
+    float32 gives what plain float32 arithmetic makes of the same formulas).
     mode 0: pos = x.  mode 1 / 2: the L-infinity / L2 scene contraction c(x), then pos = (c + 2) / 4."""
-    x = x.detach().to(torch.float64)
+    x = x.detach().to(dtype)
     P = x.shape[0]
-    eye = torch.eye(3, dtype=torch.float64).expand(P, 3, 3)
+    eye = torch.eye(3, dtype=dtype).expand(P, 3, 3)
     if mode == 0:
         return x.clone(), eye.clone()
     if mode == 1:
         m, im = x.abs().max(-1)
-        dm = torch.zeros(P, 3, dtype=torch.float64)  # d m / d x_k
+        dm = torch.zeros(P, 3, dtype=dtype)  # d m / d x_k
         dm[torch.arange(P), im] = torch.sign(x[torch.arange(P), im])
     else:
         m = (x * x).sum(-1).sqrt()
