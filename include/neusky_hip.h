@@ -160,7 +160,8 @@ int nsky_film_chain_fwd(const nsky_film_net* net, const void* stream_buf, const 
  *        dL/dF_i in columns i hidden.. and dL/dphase_i in columns (n_film + i) hidden..; dfp_rowmax [ceil32(M)] = max |dfp| of each
  *        batch row.  F and phase are re-formed from h_last (the last mapping activation), z_save[i] is read back.
  *   nsky_film_chain_bwd_map (direction 2): dfp, dfp_rowmax, h_save[l] -> dpre_save[l] = dL/d(pre-activation of mapping layer l)
- *        (tile-native) and d_cond [M, ldcond] (row-major, pad columns zeroed; optional).
+ *        (tile-native) and d_cond [M, ldcond] (row-major, optional): the first pad4(cond_dim) columns of a row are written, the pad
+ *        columns among them with zero; columns beyond them (ldcond may be wider) are left as they are.
  * gmax (caller zero-fills): largest magnitude of each gradient matrix, for nsky_gemm_f32's a_scale_max -- bwd_film writes
  *        [i] = max |dz_save[i]| (i < n_film) and [n_film] = max |dfp|; bwd_map writes [l] = max |dpre_save[l]| (l < n_map).
  * Frozen weights (only the weight gradients read dz_save / dpre_save; d_x, dfp, dfp_rowmax, gmax[n_film] and d_cond are the same
@@ -171,8 +172,9 @@ int nsky_film_chain_fwd(const nsky_film_net* net, const void* stream_buf, const 
  *        it stored, and has layer l in registers before it stores the first tile of layer l - 1).  Also accepted at hidden 128.
  *        In both forms bwd_map leaves gmax[l] as passed.  A mix of NULL and non-NULL entries, or of shared and distinct ones, is
  *        an error, and so is a NULL dpre_save at hidden 256.
- * hidden must be a multiple of 128 for the backward streams.  d_x (optional, [M, ldx], ldx <= 16): gradient w.r.t. the FiLM input
- * rows (the DDF's multi-view rays differentiate through their direction rows, neusky/models/ddf_model.py:297-322). */
+ * hidden must be a multiple of 128 for the backward streams.  d_x (optional, [M, ldx], ldx <= 16; the first pad4(x_dim) columns of a row
+ * are written, as for d_cond): gradient w.r.t. the FiLM input rows (the DDF's multi-view rays differentiate through their direction
+ * rows, neusky/models/ddf_model.py:297-322). */
 int nsky_film_chain_bwd_film(const nsky_film_net* net, const void* stream_buf, const float* table, int32_t M, const float* d_res,
                              int32_t ldres, const float* h_last, const float* const* z_save, float* const* dz_save, float* dfp,
                              float* dfp_rowmax, float* gmax, float* d_x, int32_t ldx, nsky_stream_t stream);

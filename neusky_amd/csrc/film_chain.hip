@@ -443,7 +443,7 @@ struct BwdFilmArgs {
   float* dfp;                      // native [ceil32(M), 2 n_film H]: dF of layer i in columns i H .., dphase in (n_film + i) H ..
   float* dfp_rowmax;               // [ceil32(M)] max |dfp| per batch row
   float* gmax;                     // zero-initialised by the caller: [i] = max |dz_save[i]| (KEEP only), [n_film] = max |dfp|
-  float* d_x; int ldx;             // optional [M, ldx]: gradient w.r.t. the FiLM input rows (pad columns zeroed)
+  float* d_x; int ldx;             // optional [M, ldx]: gradient w.r.t. the FiLM input rows (columns < pad4(x_dim) written, pads zero)
   int full_wgs, tail_wgs, tail_k;  // (unused by the four-wave kernel)
 };
 
@@ -631,7 +631,7 @@ __device__ __forceinline__ void film_bwd4_tile(const BwdFilmArgs& a, WStream& ws
           const float inv = dz_inv * sl[tile];
 #pragma unroll
           for (int g = 0; g < 2; ++g)
-            if (8 * g + 4 * h < a.ldx)
+            if (8 * g + 4 * h < ((net.x_dim + 3) & ~3))  // the row's pad4(x_dim) columns (pads zero: zero weight rows); ldx may be wider
               stg4(a.d_x + row * a.ldx + 8 * g + 4 * h, make_float4(acc[4 * g] * inv, acc[4 * g + 1] * inv, acc[4 * g + 2] * inv, acc[4 * g + 3] * inv));
         }
         ++tile;
@@ -855,7 +855,7 @@ __device__ __forceinline__ void film_bwd_map_tile(const BwdMapArgs& a, WStream& 
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             const int fo = 32 * u + 8 * g + 4 * h;
-            if (fo < a.ldcond)
+            if (fo < ((net.cond_dim + 3) & ~3))  // the row's pad4(cond_dim) columns (pads zero: zero weight rows); ldcond may be wider
               stg4(a.d_cond + row * a.ldcond + fo, make_float4(acc[4 * g] * inv, acc[4 * g + 1] * inv, acc[4 * g + 2] * inv, acc[4 * g + 3] * inv));
           }
         }

@@ -915,9 +915,11 @@ class FilmChainFn(torch.autograd.Function):
         dfp = torch.empty(Mp, 2 * n_film * H, device=dev)
         rowmax = torch.empty(Mp, device=dev)
         gmax = zeros(n_film + 1 + n_map, device=dev)
-        d_x = torch.empty(M, ld(x), device=dev) if need_dx else None  # the DDF's multi-view rays (ddf_model.py:297-322)
+        # (the kernels write a row's pad4(dim) columns: the columns of a wider input row take no part and get a zero gradient)
+        alloc = lambda t, w: (torch.empty if ld(t) == w else zeros)(M, ld(t), device=dev)  # noqa: E731
+        d_x = alloc(x, fw[0].shape[1]) if need_dx else None  # the DDF's multi-view rays (ddf_model.py:297-322)
         hip.film_chain_bwd_film(net1, s1, t1, M, d_res, hs[-1], zs, dzs, dfp, rowmax, gmax[:n_film + 1], d_x)
-        d_cond = torch.empty(M, ld(cond), device=dev) if need_dcond else None
+        d_cond = alloc(cond, mw[0].shape[1]) if need_dcond else None
         want_map = need_dcond or train_w
         if train_w:
             dpres = [torch.empty(Mp, Hm, device=dev) for _ in range(n_map)]
