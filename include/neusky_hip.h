@@ -831,6 +831,56 @@ int nsky_mesh_compact_faces(const int32_t* corner_cells, int64_t F, const int32_
                             int32_t* faces_out, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Connected components of a mesh, and the removal of the small ones ("floaters").  No counterpart in the reference;
+ * neusky_amd/exporter/components.py drives these kernels (csrc/components.hip), before simplification.
+ *   inputs:   faces [F][3] int32 over V vertices (V, F fit int32); for the compaction also vertices [V][3] fp32 and the optional normals
+ *             [V][3] fp32 and colours [V][3] uint8.  Only integers are compared and only bits are copied: no tolerance anywhere.
+ *   1 connect: two faces are connected when they share a vertex INDEX (not a position: marching cubes emits one vertex per crossing
+ *             grid edge, so its faces share indices).  A component is a class of the transitive closure.  This is vertex
+ *             connectivity; libraries that split by edge adjacency differ from it only where two bodies touch in one vertex.
+ *   2 root:   the root of a component is its smallest vertex index: a property of the mesh alone, so nothing below depends on the
+ *             order of the faces or on scheduling.
+ *   3 size:   the size of a component is its face count (on a marching-cubes mesh triangles are near-uniform, so this is area up to a
+ *             factor; an area criterion would need ordered fp64 sums to be repeatable and is not offered).
+ *   4 rank:   components sorted by size descending, ties by root ascending; rank 0 is the largest.  The sort key is the int64
+ *             (F - size) * 2^31 + root.  C = the number of components (<= F).
+ *   5 loose:  a vertex that no face references belongs to no component: label -1.  It is dropped by the compaction.
+ *   6 filter: a face stays when keep_component[rank of its component] != 0; a vertex stays when a staying face references it.  Both
+ *             keep their input order; a staying face keeps its orientation, its corners re-indexed; attributes are copied bit for bit.
+ *   7 union-find (link): parent[V] is the identity on entry.  link(x, y): walk x and y to root candidates; while they differ, with hi the
+ *             larger and lo the smaller, old = CAS(&parent[hi], hi, lo): old == hi ends it, else the walk goes on from old (the value
+ *             the compare-and-swap returned; nothing is re-read) and lo.  Invariant: parent[x] <= x.  Every access to parent in the
+ *             link kernel is an agent-scope relaxed atomic (the per-XCD L2s are not coherent for plain accesses).  Finds halve
+ *             paths (parent[x] <- parent[parent[x]], a relaxed atomic store): that only moves a non-root's pointer to an ancestor.
+ *   8 ends:   termination does not depend on a load being fresh.  A stale parent value is an ancestor in an older forest: same
+ *             component, an index no smaller than the current one.  A failed compare-and-swap returns the memory-side value, strictly
+ *             smaller than the node it was tried on.  So every step of every loop descends, a find takes fewer than V steps and a hook
+ *             fewer than 2 V rounds; no thread waits for another (no lock, no flag, nothing wave64 divergence could deadlock).  Those
+ *             bounds are the loops' caps: a thread that reaches one, or meets parent[x] outside [0, x], ORs a bit into *status and
+ *             leaves; the caller reads *status with its other counters and treats non-zero as an error.  One launch each: there is no
+ *             "repeat until nothing changes" on the host.
+ * nsky_cc_link:    faces, parent[V] (the identity on entry)  ->  parent, a forest whose trees are the components, each rooted at its
+ *                  smallest index.  *status |= NSKY_CC_STATUS_INDEX for a face index outside [0, V) (the face is skipped),
+ *                  NSKY_CC_STATUS_LINK at a cap.  The caller zeroes *status (int32, device memory).
+ * nsky_cc_flatten: a launch of its own, so the link pass is complete and visible  ->  vertex_root[V] (a loose vertex is its own root)
+ *                  and face_root[F] = the root of each face's first corner.  Read-only finds.  NSKY_CC_STATUS_FLATTEN at a cap.
+ * nsky_cc_select:  face_labels[F] = the rank of each face's component, keep_component[C] uint8  ->  keep[F] uint8 (0 / 1) and
+ *                  vertex_used[V] uint8, zeroed by the caller, set to 1 for the corners of kept faces (plain stores of one value).
+ * nsky_cc_compact: face_ends[F] / vertex_ends[V] = inclusive scans (int64) of keep / vertex_used, F_out / V_out their last entries  ->
+ *                  vertices_out[V_out][3], normals_out / colours_out where normals / colours are not NULL, faces_out[F_out][3]. */
+#define NSKY_CC_STATUS_INDEX 1
+#define NSKY_CC_STATUS_LINK 2
+#define NSKY_CC_STATUS_FLATTEN 4
+int nsky_cc_link(const int32_t* faces, int64_t F, int64_t V, int32_t* parent, int32_t* status, nsky_stream_t stream);
+int nsky_cc_flatten(const int32_t* parent, int64_t V, const int32_t* faces, int64_t F, int32_t* vertex_root, int32_t* face_root,
+                    int32_t* status, nsky_stream_t stream);
+int nsky_cc_select(const int32_t* faces, int64_t F, int64_t V, const int32_t* face_labels, const uint8_t* keep_component, int64_t C,
+                   uint8_t* keep, uint8_t* vertex_used, nsky_stream_t stream);
+int nsky_cc_compact(const float* vertices, const float* normals, const uint8_t* colours, int64_t V, const int32_t* faces, int64_t F,
+                    const uint8_t* keep, const int64_t* face_ends, const uint8_t* vertex_used, const int64_t* vertex_ends, int64_t V_out,
+                    int64_t F_out, float* vertices_out, float* normals_out, uint8_t* colours_out, int32_t* faces_out, nsky_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Texture baking on a per-triangle-pair atlas (the layout of nerfstudio's textured-mesh export, with a gutter).  No counterpart in
  * the reference; neusky_amd/exporter/texture.py drives these two kernels (csrc/texture.hip) around the field's fused value chain.
  *   layout:   P = px_per_uv_triangle >= 1; a square has Q = P + 3 texels per side; faces 2 s (lower) and 2 s + 1 (upper) share square s;

@@ -2,7 +2,8 @@
 
 An --output ending in .obj writes a textured Wavefront OBJ instead (mesh.obj, mesh.mtl, mesh.png): the albedo baked into a
 per-triangle-pair atlas on the mesh that is written, that is after --target-num-faces / --simplify-cell-size.
-The flags carry the names of nerfstudio's `ns-export marching-cubes`.  The field is built from the `neusky` method's config; no
+--keep-largest-components K / --min-component-faces N drop floaters (small connected components) from the marching-cubes mesh, before
+any simplification.  The other flags carry the names of nerfstudio's `ns-export marching-cubes`.  The field is built from the `neusky` method's config; no
 dataset is needed (the scene box and the number of training images come from the checkpoint)."""
 from __future__ import annotations
 
@@ -35,6 +36,10 @@ def build_parser() -> argparse.ArgumentParser:
                           help="simplify the mesh by vertex clustering to at most N faces (nerfstudio's --target-num-faces; off by default)")
     simplify.add_argument("--simplify-cell-size", type=float, default=None, metavar="H",
                           help="simplify the mesh by vertex clustering on cubic cells of edge H (scene units; off by default)")
+    ap.add_argument("--keep-largest-components", type=int, default=None, metavar="K",
+                    help="drop floaters: keep the K connected components with the most faces (before simplification; off by default)")
+    ap.add_argument("--min-component-faces", type=int, default=None, metavar="N",
+                    help="drop floaters: keep the connected components with at least N faces (with --keep-largest-components: both hold)")
     ap.add_argument("--px-per-uv-triangle", type=int, default=None, metavar="P",
                     help=".obj output: texels along a leg of each face's texture triangle (nerfstudio's --px-per-uv-triangle; default 4)")
     ap.add_argument("--texture-normal-map", action="store_true",
@@ -50,9 +55,13 @@ def main(argv=None) -> int:
         ap.error("--px-per-uv-triangle and --texture-normal-map need an --output ending in .obj")
     if args.px_per_uv_triangle is not None and args.px_per_uv_triangle < 1:
         ap.error("--px-per-uv-triangle must be >= 1")
+    if args.keep_largest_components is not None and args.keep_largest_components < 1:
+        ap.error("--keep-largest-components must be >= 1")
+    if args.min_component_faces is not None and args.min_component_faces < 1:
+        ap.error("--min-component-faces must be >= 1")
 
     import torch
-    from . import bake_texture, extract_mesh, load_field_state, simplify_mesh, write_obj, write_ply
+    from . import bake_texture, extract_mesh, load_field_state, remove_floaters, simplify_mesh, write_obj, write_ply
 
     t0 = time.perf_counter()
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
@@ -66,16 +75,27 @@ def main(argv=None) -> int:
     t_load = time.perf_counter() - t0
     timings = {}
     simplifying = args.target_num_faces is not None or args.simplify_cell_size is not None
-    # with simplification the attributes are evaluated once, on the vertices that are written
+    filtering = args.keep_largest_components is not None or args.min_component_faces is not None
+    # with floater removal or simplification the attributes are evaluated once, on the vertices that are written
     mesh = extract_mesh(field, args.resolution, args.bounding_box_min, args.bounding_box_max, args.isosurface_threshold,
-                        attributes=not args.no_attributes and not simplifying, timings=timings)
+                        attributes=not args.no_attributes and not simplifying and not filtering, timings=timings)
     before = ""
+    if filtering or simplifying:
+        before = f"V {mesh.vertices.shape[0]} F {mesh.faces.shape[0]}"
+    if filtering:
+        t1 = time.perf_counter()
+        found = {}
+        mesh = remove_floaters(mesh, keep_largest=args.keep_largest_components, min_faces=args.min_component_faces, info=found)
+        torch.cuda.synchronize()
+        timings["components"] = time.perf_counter() - t1
+        before += f", components {found['components']} -> {found['kept_components']}"
     if simplifying:
-        before = f"V {mesh.vertices.shape[0]} F {mesh.faces.shape[0]} -> "
         t1 = time.perf_counter()
         mesh = simplify_mesh(mesh, cell_size=args.simplify_cell_size, target_num_faces=args.target_num_faces)
         torch.cuda.synchronize()
         timings["simplify"] = time.perf_counter() - t1
+    if filtering or simplifying:
+        before += " -> "
         if not args.no_attributes:
             from .mesh import vertex_attributes
             t1 = time.perf_counter()

@@ -1312,6 +1312,48 @@ def mesh_compact_faces(corner_cells, keep, ends, faces_out):
                               Fo, ptr(_typed(faces_out, torch.int32, Fo, 3)), stream_ptr()), "nsky_mesh_compact_faces")
 
 
+# ---- connected components of a mesh (exporter/components.py drives link -> flatten -> rank (torch) -> select -> scan (torch) -> compact)
+CC_STATUS_INDEX, CC_STATUS_LINK, CC_STATUS_FLATTEN = 1, 2, 4  # NSKY_CC_STATUS_*
+_cc_link = _sig("nsky_cc_link", C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_cc_flatten = _sig("nsky_cc_flatten", C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_cc_select = _sig("nsky_cc_select", C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_cc_compact = _sig("nsky_cc_compact", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                   C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def cc_link(faces, parent, status):
+    """faces: int32 [F, 3]; parent: int32 [V], the identity on entry, a forest on return; status: int32 [1], zeroed by the caller"""
+    F, V = faces.shape[0], parent.shape[0]
+    check(_cc_link(ptr(_typed(faces, torch.int32, F, 3)), F, V, ptr(_typed(parent, torch.int32, V)), ptr(_typed(status, torch.int32, 1)),
+                   stream_ptr()), "nsky_cc_link")
+
+
+def cc_flatten(parent, faces, vertex_root, face_root, status):
+    """parent: int32 [V] after cc_link -> vertex_root: int32 [V], face_root: int32 [F] (the root of the first corner)"""
+    F, V = faces.shape[0], parent.shape[0]
+    check(_cc_flatten(ptr(_typed(parent, torch.int32, V)), V, ptr(_typed(faces, torch.int32, F, 3)), F, ptr(_typed(vertex_root, torch.int32, V)),
+                      ptr(_typed(face_root, torch.int32, F)), ptr(_typed(status, torch.int32, 1)), stream_ptr()), "nsky_cc_flatten")
+
+
+def cc_select(faces, face_labels, keep_component, keep, vertex_used):
+    """face_labels: int32 [F]; keep_component: uint8 [C] -> keep: uint8 [F]; vertex_used: uint8 [V], zeroed by the caller"""
+    F, V, Cn = faces.shape[0], vertex_used.shape[0], keep_component.shape[0]
+    check(_cc_select(ptr(_typed(faces, torch.int32, F, 3)), F, V, ptr(_typed(face_labels, torch.int32, F)),
+                     ptr(_typed(keep_component, torch.uint8, Cn)), Cn, ptr(_typed(keep, torch.uint8, F)),
+                     ptr(_typed(vertex_used, torch.uint8, V)), stream_ptr()), "nsky_cc_select")
+
+
+def cc_compact(vertices, normals, colours, faces, keep, face_ends, vertex_used, vertex_ends, vertices_out, normals_out, colours_out, faces_out):
+    """face_ends: int64 [F] / vertex_ends: int64 [V], the inclusive scans of keep / vertex_used; the outputs are sized by their last
+    entries; normals fp32 [V, 3] / colours uint8 [V, 3] or None, each with its output"""
+    V, F, Vo, Fo = vertices.shape[0], faces.shape[0], vertices_out.shape[0], faces_out.shape[0]
+    check(_cc_compact(ptr(_typed(vertices, torch.float32, V, 3)), ptr(_typed(normals, torch.float32, V, 3)), ptr(_typed(colours, torch.uint8, V, 3)),
+                      V, ptr(_typed(faces, torch.int32, F, 3)), F, ptr(_typed(keep, torch.uint8, F)), ptr(_typed(face_ends, torch.int64, F)),
+                      ptr(_typed(vertex_used, torch.uint8, V)), ptr(_typed(vertex_ends, torch.int64, V)), Vo, Fo,
+                      ptr(_typed(vertices_out, torch.float32, Vo, 3)), ptr(_typed(normals_out, torch.float32, Vo, 3)),
+                      ptr(_typed(colours_out, torch.uint8, Vo, 3)), ptr(_typed(faces_out, torch.int32, Fo, 3)), stream_ptr()), "nsky_cc_compact")
+
+
 # ---- texture baking on a per-triangle-pair atlas (exporter/texture.py drives texel points -> the field's value chain -> texel store)
 TEXTURE_MAX_SIZE = 16384  # NSKY_TEXTURE_MAX_SIZE
 _texture_texel_points = _sig("nsky_texture_texel_points", C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
