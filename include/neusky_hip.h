@@ -122,7 +122,7 @@ int nsky_weighted_colsum_f32(const float* X, int32_t M, int32_t N, int32_t ldx, 
  *        x_dim <= 16, out_dim <= 4, at most NSKY_FILM_MAX_LAYERS layers each.
  *   nsky_film_stream_layout: bytes of the packed weight stream and number of 32-feature weight tiles.
  *   nsky_film_pack: once per optimisation step: every weight tile -> power-of-two scaled fp16 hi + fp16 residual planes in
- *        MFMA-fragment order (direction 0 = forward stream, 1 = backward stream), plus `table` (NSKY_FILM_TABLE_FLOATS
+ *        MFMA-fragment order (direction 0 = forward stream, 1 = FiLM backward, 2 = mapping backward, 3 = FiLM backward on saved operands), plus `table` (NSKY_FILM_TABLE_FLOATS
  *        floats, 16-byte aligned): every bias of the network followed by one reciprocal scale per tile.
  *   nsky_film_chain_fwd: cond [M, ldcond] (first cond_dim columns), x [M, ldx] -> res [M, ldres] (first out_dim columns,
  *        raw head output; columns out_dim..3 are written too).  Side outputs, each a TILE-NATIVE [ceil32(M), hidden] matrix
@@ -181,6 +181,23 @@ int nsky_film_chain_bwd_film(const nsky_film_net* net, const void* stream_buf, c
 int nsky_film_chain_bwd_map(const nsky_film_net* net, const void* stream_buf, const float* table, int32_t M, const float* dfp,
                             const float* dfp_rowmax, const float* const* h_save, float* const* dpre_save, float* d_cond,
                             int32_t ldcond, float* gmax, nsky_stream_t stream);
+/* The chain on SAVED FiLM operands: instead of re-forming F and phase from h_last in the backward (two hidden x hidden products per
+ * FiLM layer), the forward keeps what its epilogue forms from them and the backward reads it back.
+ *   nsky_film_chain_fwd_saved: nsky_film_chain_fwd plus f_save[i] = 15 F_i + 30 and arg_save[i] = f_i z_i + phase_i (the sine's argument),
+ *        each a tile-native [ceil32(M), hidden] matrix like z_save[i]; every entry of both lists is required.  res and the other side
+ *        outputs are the bits nsky_film_chain_fwd writes.
+ *   nsky_film_chain_bwd_film_saved: nsky_film_chain_bwd_film with z_save[i], f_save[i], arg_save[i] in place of h_last; stream / table
+ *        packed with direction 3 (direction 1 without the F and phase tiles: the transposed FiLM tiles of layers n_film-1 .. 1, then
+ *        the layer-0 input tile).  dz_save, dfp, dfp_rowmax, gmax and d_x as in nsky_film_chain_bwd_film, frozen form included, and
+ *        the same bits: g = dY cos(arg), dz = g f, dF = 15 g z, dphase = g on the values the re-form would rebuild. */
+int nsky_film_chain_fwd_saved(const nsky_film_net* net, const void* stream_buf, const float* table, const float* cond,
+                              int32_t ldcond, const float* x, int32_t ldx, int32_t M, float* const* h_save, float* const* z_save,
+                              float* const* y_save, float* const* f_save, float* const* arg_save, float* res, int32_t ldres,
+                              nsky_stream_t stream);
+int nsky_film_chain_bwd_film_saved(const nsky_film_net* net, const void* stream_buf, const float* table, int32_t M, const float* d_res,
+                                   int32_t ldres, const float* const* z_save, const float* const* f_save, const float* const* arg_save,
+                                   float* const* dz_save, float* dfp, float* dfp_rowmax, float* gmax, float* d_x, int32_t ldx,
+                                   nsky_stream_t stream);
 /* SDF value chain: SDFAlbedoField.get_sdf_at_pos (neusky/fields/sdf_albedo_field.py:169-174; nerfstudio SDFField geometry network:
  * Linear + Softplus(beta) twice, then the sdf row of the last Linear) for M encode rows, forward and backward as one kernel each
  * (csrc/sdf_chain.hip; the weight-stream machinery of the FiLM-SIREN chain, csrc/chain.h: nsky_sdf_stream_layout / nsky_sdf_pack once per optimizer step and

@@ -41,6 +41,8 @@ constexpr int FWD_FRAG_BUFFERS = 3;
 //   (skipped for i = 0); then the mapping head transposed, k-group outer: for kg (128 of the 2 n_film H head rows): for u:
 //   tile (rows = hidden features 32 u.., k = head rows 128 kg ..); then mapping layers n_map-1 .. 1 transposed (for u: tile,
 //   K = H); then mapping layer 0 transposed: tiles over ceil(cond_dim / 32) input-feature tiles, K = H.
+// Direction 3 (FiLM backward on the saved f and sine argument, film_bwd4s_kernel): direction 1 without the F and phase tiles: for FiLM
+//   layer i = n_film-1 .. 1: for u: transposed FiLM weight tile; then the layer-0 input tile (rows = x features).
 // Every tile occupies a whole number of groups.
 struct Layout {
   int NT, Gc, Gx, Gh;
@@ -105,6 +107,11 @@ __host__ __device__ inline void bwd_film_layout(const nsky_film_net& n, long& to
   n_tiles = n.n_film * NT * 2 + (n.n_film - 1) * NT + 1;  // last: first FiLM layer transposed (rows = x features) -> d_x
   total_groups = (long)n_tiles * Gh;
 }
+__host__ __device__ inline void bwd_film_saved_layout(const nsky_film_net& n, long& total_groups, int& n_tiles) {
+  const int NT = n.hidden / 32, Gh = groups_of(n.hidden);
+  n_tiles = (n.n_film - 1) * NT + 1;  // last: first FiLM layer transposed (rows = x features) -> d_x
+  total_groups = (long)n_tiles * Gh;
+}
 __host__ __device__ inline void bwd_map_layout(const nsky_film_net& n, long& total_groups, int& n_tiles) {
   const int NT = n.hidden / 32, Gh = groups_of(n.hidden);
   const int nkb = 2 * n.n_film * n.hidden / 64, ct = (n.cond_dim + 31) / 32;
@@ -134,6 +141,21 @@ __device__ inline TileDesc bwd_film_tile(const nsky_film_net& n, int idx) {
   return d;
 }
 
+// direction 3: the transposed tiles of direction 1, in its order, and nothing else
+__device__ inline TileDesc bwd_film_saved_tile(const nsky_film_net& n, int idx) {
+  TileDesc d;
+  const int NT = n.hidden / 32, H = n.hidden, Gh = groups_of(H);
+  d.group = (long)idx * Gh;
+  d.nrows = 32; d.K = H; d.k0 = 0; d.transposed = 1;
+  if (idx == (n.n_film - 1) * NT) {
+    d.W = n.film_w[0]; d.ld = n.film_ld[0]; d.row0 = 0; d.nrows = n.x_dim;
+    return d;
+  }
+  const int i = n.n_film - 1 - idx / NT, u = idx % NT;
+  d.W = n.film_w[i]; d.ld = n.film_ld[i]; d.row0 = 32 * u;
+  return d;
+}
+
 __device__ inline TileDesc bwd_map_tile(const nsky_film_net& n, int idx) {
   TileDesc d;
   const int NT = n.hidden / 32, H = n.hidden, Gh = groups_of(H);
@@ -160,7 +182,8 @@ __device__ inline TileDesc bwd_map_tile(const nsky_film_net& n, int idx) {
 __host__ __device__ inline void dir_layout(const nsky_film_net& n, int direction, long& total_groups, int& n_tiles) {
   if (direction == 0) { const Layout L = fwd_layout(n); total_groups = L.total_groups; n_tiles = L.n_tiles; }
   else if (direction == 1) bwd_film_layout(n, total_groups, n_tiles);
-  else bwd_map_layout(n, total_groups, n_tiles);
+  else if (direction == 2) bwd_map_layout(n, total_groups, n_tiles);
+  else bwd_film_saved_layout(n, total_groups, n_tiles);
 }
 
 // bias table: [mapping layer l: H][mapping head: 2 n_film H][FiLM layer i: H][head: 32]
@@ -190,7 +213,8 @@ __global__ __launch_bounds__(256) void film_pack_kernel(nsky_film_net net, int d
     return;
   }
   const TileDesc d = direction == 0 ? fwd_tile(net, fwd_layout(net), blockIdx.x)
-                                    : (direction == 1 ? bwd_film_tile(net, blockIdx.x) : bwd_map_tile(net, blockIdx.x));
+                                    : (direction == 1 ? bwd_film_tile(net, blockIdx.x)
+                                                      : (direction == 2 ? bwd_map_tile(net, blockIdx.x) : bwd_film_saved_tile(net, blockIdx.x)));
   pack_tile(d, stream, table + BIAS_FLOATS, w, red);
 }
 
@@ -207,13 +231,17 @@ struct FwdArgs {
   float* z_save[MAXL];  // FiLM pre-activations W y + b, native [ceil32(M), H]; NULL = not kept
   float* y_save[MAXL];  // FiLM outputs, native [ceil32(M), H]: also the hand-off to the next layer (entries may alias two ping-pong
                         // buffers when nothing is kept); all NULL = film_fwd_kernel<.., KEEP_Y = false>, the hand-off stays in registers
+  float* f_save[MAXL];    // film_fwd_kernel<.., SAVE_FA = true>: f = 15 F + 30 and the sine argument f z + phase of every FiLM layer, native
+  float* arg_save[MAXL];  // [ceil32(M), H], as the epilogue forms them (the operands of film_bwd4s_kernel); all NULL = not kept
   float* res; int ldres;
 };
 
 
 // KEEP_Y = false (frozen weights: only the weight gradients read the kept FiLM outputs; H = 128, where the registers are there): a
 // layer's output is scaled and split into the next layer's operand planes tile by tile as it is formed and never goes to memory
-template <int H, int KSC, bool KEEP_Y = true>
+// SAVE_FA: the epilogue's f and sine argument go out beside z (the backward then reads them back instead of re-forming F and phase
+// from the last mapping activation); nothing else in the kernel's arithmetic changes
+template <int H, int KSC, bool KEEP_Y = true, bool SAVE_FA = false>
 __global__ __launch_bounds__(256, 1) void film_fwd_kernel(const FwdArgs a) {
   constexpr int NT = H / 32, KS = H / 16;
   __shared__ __attribute__((aligned(16))) unsigned char smem[RING_BYTES + (BIAS_FLOATS + SCALE_FLOATS) * 4];
@@ -331,6 +359,8 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(const FwdArgs a) {
     // a wave whose tile lies wholly beyond M stores nothing and reads tile 0 back (in bounds; its results are never stored)
     float* zblk = a.z_save[i] ? a.z_save[i] + (wave_live ? rt : 0) * NT * 1024 : nullptr;
     float* yblk = KEEP_Y ? a.y_save[i] + (wave_live ? rt : 0) * NT * 1024 : nullptr;
+    float* fblk = SAVE_FA ? a.f_save[i] + (wave_live ? rt : 0) * NT * 1024 : nullptr;
+    float* ablk = SAVE_FA ? a.arg_save[i] + (wave_live ? rt : 0) * NT * 1024 : nullptr;
     f16x8 nh[KEEP_Y ? 1 : KS], nl[KEEP_Y ? 1 : KS];  // (KEEP_Y = false) the planes of this layer's output
     for (int t = 0; t < NT; ++t) {
       f32x16 aF, aP, aZ;
@@ -348,7 +378,7 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(const FwdArgs a) {
       }
       const float iF = h_inv * sl[tile], iP = h_inv * sl[tile + 1], iZ = z_unscale * sl[tile + 2];
       tile += 3;
-      float zz[16], yy[16];
+      float zz[16], yy[16], ff[SAVE_FA ? 16 : 1], aa[SAVE_FA ? 16 : 1];
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int fo = 32 * t + 8 * g + 4 * h;
@@ -361,11 +391,17 @@ __global__ __launch_bounds__(256, 1) void film_fwd_kernel(const FwdArgs a) {
           const int r = 4 * g + q;
           const float F = fmaf(aF[r], iF, bf[q]), P = fmaf(aP[r], iP, bp[q]), z = fmaf(aZ[r], iZ, bz[q]);
           zz[r] = z;
-          yy[r] = sin_cw(fmaf(fmaf(15.0f, F, 30.0f), z, P));
+          const float f = fmaf(15.0f, F, 30.0f), arg = fmaf(f, z, P);
+          yy[r] = sin_cw(arg);
+          if constexpr (SAVE_FA) { ff[r] = f; aa[r] = arg; }
         }
       }
       if (wave_live) {
         if (zblk) store_tile_nt(zblk + t * 1024, lane, zz);
+        if constexpr (SAVE_FA) {
+          store_tile_nt(fblk + t * 1024, lane, ff);
+          store_tile_nt(ablk + t * 1024, lane, aa);
+        }
         if constexpr (KEEP_Y) store_tile(yblk + t * 1024, lane, yy);
       }
       if constexpr (!KEEP_Y) {
@@ -439,7 +475,9 @@ struct BwdFilmArgs {
   const float* d_res; int ldres;   // [M, ldres] gradient of the raw head output (first out_dim columns)
   const float* h_last;             // native [ceil32(M), H]
   const float* z_save[MAXL];       // native
-  float* dz_save[MAXL];            // native [ceil32(M), H]; all NULL = film_bwd4_kernel<H, KEEP = false>
+  const float* f_save[MAXL];       // (film_bwd4s_kernel: the forward's saved f = 15 F + 30 and sine argument, native; h_last is not read)
+  const float* arg_save[MAXL];
+  float* dz_save[MAXL];          // native [ceil32(M), H]; all NULL = film_bwd4_kernel<H, KEEP = false>
   float* dfp;                      // native [ceil32(M), 2 n_film H]: dF of layer i in columns i H .., dphase in (n_film + i) H ..
   float* dfp_rowmax;               // [ceil32(M)] max |dfp| per batch row
   float* gmax;                     // zero-initialised by the caller: [i] = max |dz_save[i]| (KEEP only), [n_film] = max |dfp|
@@ -666,8 +704,226 @@ __global__ __launch_bounds__(256, 1) void film_bwd4_kernel(const BwdFilmArgs a) 
   ws_close();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same backward on SAVED operands: the forward (film_fwd_kernel<.., SAVE_FA>) kept f = 15 F + 30 and the sine argument of every
+// FiLM tile, so pass 1 is no product at all -- z, f and arg of a tile come in, dz, dF and dphase go out, 6 KB per row and layer -- and
+// the weight stream (direction 3) carries the transposed FiLM tiles of pass 2 alone.  The h planes, the F / phase accumulators and the
+// bias table are gone with the re-form: 10 of the 14 H x H products per row at the DDF's depth.
+// Order of a wave's work: pass 1 of the last layer; then per layer i = n_film-1 .. 1 pass 2 of layer i followed by pass 1 of layer
+// i - 1 (ONE loop body, so that tile 0 of layer i - 1, requested in front of the last product of pass 2, is consumed in straight-line
+// code: no load in flight crosses a back-edge or a join); then layer 0's input tile.
+// The tile operands are hidden loads in two buffers, one tile ahead.  Counted waits (one in-order vector-memory counter; a store counts
+// like a load): younger than the loads of tile t are the stores of tile t - 1 (at least NST instructions: each 16-byte store is one or
+// more) and the 12 loads of tile t + 1; younger than a layer's tile 0 the DMA pieces of one product and the loads of tile 1.
+template <int N>
+__device__ __forceinline__ void hidden_wait12(f32x4 (&q)[12]) {
+  asm volatile("s_waitcnt vmcnt(%12)"
+               : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]), "+v"(q[4]), "+v"(q[5]), "+v"(q[6]), "+v"(q[7]), "+v"(q[8]), "+v"(q[9]),
+                 "+v"(q[10]), "+v"(q[11])
+               : "n"(N) : "memory");
+}
+
+// z | f | arg of tile t of layer i -> q[0..3] | q[4..7] | q[8..11]
+template <int H>
+__device__ __forceinline__ void film_bwd4s_request(const BwdFilmArgs& a, f32x4 (&q)[12], int i, int t, long rt, int lane) {
+  constexpr int NT = H / 32;
+  int toff = t * 1024;
+  asm volatile("" : "+s"(toff));  // (an opaque offset: film_bwd4_tile)
+  const float* zp = a.z_save[i] + rt * NT * 1024 + toff;
+  const float* fp = a.f_save[i] + rt * NT * 1024 + toff;
+  const float* ap = a.arg_save[i] + rt * NT * 1024 + toff;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) q[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+  hidden_load4_s<0>(q[0], zp, lane * 16);
+  hidden_load4_s<1024>(q[1], zp, lane * 16);
+  hidden_load4_s<2048>(q[2], zp, lane * 16);
+  hidden_load4_s<3072>(q[3], zp, lane * 16);
+  hidden_load4_s<0>(q[4], fp, lane * 16);
+  hidden_load4_s<1024>(q[5], fp, lane * 16);
+  hidden_load4_s<2048>(q[6], fp, lane * 16);
+  hidden_load4_s<3072>(q[7], fp, lane * 16);
+  hidden_load4_s<0>(q[8], ap, lane * 16);
+  hidden_load4_s<1024>(q[9], ap, lane * 16);
+  hidden_load4_s<2048>(q[10], ap, lane * 16);
+  hidden_load4_s<3072>(q[11], ap, lane * 16);
+}
+
+// pass 1 of layer i: dY -> dz in place, dF, dphase.  On entry the loads of tile 0 are in flight in q[0] with N0 younger operations
+// behind them by the time tile 1 has been requested.
+template <int H, bool KEEP, int N0>
+__device__ __forceinline__ void film_bwd4s_pass1(const BwdFilmArgs& a, f32x4 (&q)[2][12], f32x16 (&dY)[H / 32], int i, long rt, int lane,
+                                                 float& dz_max, float& fp_max) {
+  constexpr int NT = H / 32, NST = KEEP ? 12 : 8;
+  const int n_film = a.net.n_film;
+  float* dzp = KEEP ? a.dz_save[i] + rt * NT * 1024 : nullptr;
+  float* dFp = a.dfp + (rt * (2 * n_film * NT) + (long)i * NT) * 1024;
+  float* dPp = a.dfp + (rt * (2 * n_film * NT) + (long)(n_film + i) * NT) * 1024;
+  dz_max = 0.0f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    int toff = t * 1024;
+    asm volatile("" : "+s"(toff));
+    float *dzt = dzp + toff, *dFt = dFp + toff, *dPt = dPp + toff;
+    f32x4(&c)[12] = q[t & 1];
+    if (t + 1 < NT) film_bwd4s_request<H>(a, q[(t + 1) & 1], i, t + 1, rt, lane);
+    if (t == 0) hidden_wait12<N0>(c);
+    else if (t + 1 < NT) hidden_wait12<NST + 12>(c);
+    else hidden_wait12<NST>(c);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      float dzv[4], dFv[4], dPv[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int r = 4 * g + k;
+        const float z = c[g][k], f = c[4 + g][k];
+        const float gc = dY[t][r] * cos_cw(c[8 + g][k]);
+        dzv[k] = gc * f;
+        dFv[k] = 15.0f * gc * z;
+        dPv[k] = gc;
+        dY[t][r] = dzv[k];
+        dz_max = fmaxf(dz_max, fabsf(dzv[k]));
+        fp_max = fmaxf(fp_max, fmaxf(fabsf(dFv[k]), fabsf(gc)));
+      }
+      if constexpr (KEEP) {
+        stg4(dzt + (g * 256 + lane * 4), make_float4(dzv[0], dzv[1], dzv[2], dzv[3]));
+        stg4(dFt + (g * 256 + lane * 4), make_float4(dFv[0], dFv[1], dFv[2], dFv[3]));
+        stg4(dPt + (g * 256 + lane * 4), make_float4(dPv[0], dPv[1], dPv[2], dPv[3]));
+      } else {  // (as vectors: film_bwd4_tile)
+        *reinterpret_cast<f32x4*>(dFt + (g * 256 + lane * 4)) = f32x4{dFv[0], dFv[1], dFv[2], dFv[3]};
+        *reinterpret_cast<f32x4*>(dPt + (g * 256 + lane * 4)) = f32x4{dPv[0], dPv[1], dPv[2], dPv[3]};
+      }
+      asm volatile("" : "+v"(dz_max), "+v"(fp_max));
+    }
+  }
+}
+
+// The head gradient of one feature with its form stated: film_bwd4_tile leaves the four-term sum to the compiler, which fuses it
+// differently from element to element and from instantiation to instantiation (most as the chain below, some as three plain additions).
+// Here every instantiation computes the same bits; with out_dim = 1 (three terms exactly zero) they are film_bwd4_tile's too.
+__device__ __forceinline__ float head_grad(const float4& dr, float w0, float w1, float w2, float w3) {
+  return fmaf(dr.w, w3, fmaf(dr.z, w2, fmaf(dr.x, w0, dr.y * w1)));
+}
+
+template <int H, bool ACTIVE, bool KEEP>
+__device__ __forceinline__ void film_bwd4s_tile(const BwdFilmArgs& a, WStream& ws, const float* sl, const float* wo, long rt, int lane) {
+  constexpr int NT = H / 32, KS = H / 16, GH = (KS + GSLABS - 1) / GSLABS, PW = 4;
+  static_assert(NT % 2 == 0, "tile 0 of every layer lands in buffer 0");
+  const nsky_film_net& net = a.net;
+  const int c = lane & 31, h = lane >> 5;
+  const long row = rt * 32 + c;
+  const bool live = ACTIVE && row < a.M;
+  const long rowc = row < a.M ? row : a.M - 1;
+  const int n_film = net.n_film;
+  f32x16 dY[NT];  // gradient w.r.t. the layer's sine outputs on entry to a layer, its dz after pass 1
+  f32x4 q[2][12];
+  if (ACTIVE) {
+    // head gradient -> dY of the last FiLM layer (register 4 g + k of tile t = feature 32 t + 8 g + 4 h + k)
+    const float4 dr = ldg4(a.d_res + rowc * a.ldres);
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int fo = 32 * t + 8 * g + 4 * h;
+        const float4 w0 = *reinterpret_cast<const float4*>(wo + fo), w1 = *reinterpret_cast<const float4*>(wo + H + fo);
+        const float4 w2 = *reinterpret_cast<const float4*>(wo + 2 * H + fo), w3 = *reinterpret_cast<const float4*>(wo + 3 * H + fo);
+        dY[t][4 * g] = head_grad(dr, w0.x, w1.x, w2.x, w3.x);
+        dY[t][4 * g + 1] = head_grad(dr, w0.y, w1.y, w2.y, w3.y);
+        dY[t][4 * g + 2] = head_grad(dr, w0.z, w1.z, w2.z, w3.z);
+        dY[t][4 * g + 3] = head_grad(dr, w0.w, w1.w, w2.w, w3.w);
+      }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // compiler-visible loads: none pending when the hidden loads are counted
+  } else {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dY[t][r] = 0.0f;
+  }
+  float fp_max = 0.0f, dz_max = 0.0f;
+  int tile = 0;
+  // the planes of W_i^T dz: dz from the registers, pre-scaled by the row's maximum
+  auto split_dz = [&](int i, f16x8(&dh_)[KS], f16x8(&dl_)[KS]) __attribute__((always_inline)) {
+    float dz_inv = 1.0f;
+    if (ACTIVE) {
+      if constexpr (KEEP) publish_max(a.gmax + i, dz_max, live, true, lane);
+      const float s = row_scale(dz_max, dz_inv);
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        float x8[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x8[j] = dY[ks >> 1][8 * (ks & 1) + j] * s;
+        split8(x8, dh_[ks], dl_[ks]);
+      }
+    }
+    return dz_inv;
+  };
+  if (ACTIVE) {
+    film_bwd4s_request<H>(a, q[0], n_film - 1, 0, rt, lane);
+    film_bwd4s_pass1<H, KEEP, 12>(a, q, dY, n_film - 1, rt, lane, dz_max, fp_max);
+  }
+  for (int i = n_film - 1; i > 0; --i) {
+    // ---- pass 2 of layer i: dY of the layer below = W_i^T dz
+    {
+      f16x8 dh_[KS], dl_[KS];
+      const float dz_inv = split_dz(i, dh_, dl_);
+#pragma unroll
+      for (int u = 0; u < NT; ++u) {
+        if (ACTIVE && u == NT - 1) film_bwd4s_request<H>(a, q[0], i - 1, 0, rt, lane);
+        f32x16 acc;
+        prod<KS, PW>(ws, ACTIVE, dh_, dl_, acc);
+        if (ACTIVE) {
+          const float inv = dz_inv * sl[tile];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dY[u][r] = acc[r] * inv;
+        }
+        ++tile;
+      }
+    }
+    // ---- pass 1 of layer i - 1 (tile 0 requested above: the GH transitions x PW pieces of one product and tile 1 are younger)
+    if (ACTIVE) film_bwd4s_pass1<H, KEEP, GH * PW + 12>(a, q, dY, i - 1, rt, lane, dz_max, fp_max);
+  }
+  // ---- the gradient w.r.t. the input rows, one tile
+  {
+    f16x8 dh_[KS], dl_[KS];
+    const float dz_inv = split_dz(0, dh_, dl_);
+    f32x16 acc;
+    prod<KS, PW>(ws, ACTIVE, dh_, dl_, acc);
+    if (ACTIVE && a.d_x && live) {
+      const float inv = dz_inv * sl[tile];
+#pragma unroll
+      for (int g = 0; g < 2; ++g)
+        if (8 * g + 4 * h < ((net.x_dim + 3) & ~3))  // the row's pad4(x_dim) columns (pads zero: zero weight rows); ldx may be wider
+          stg4(a.d_x + row * a.ldx + 8 * g + 4 * h, make_float4(acc[4 * g] * inv, acc[4 * g + 1] * inv, acc[4 * g + 2] * inv, acc[4 * g + 3] * inv));
+    }
+  }
+  if (ACTIVE) {
+    fp_max = fmaxf(fp_max, __shfl_xor(fp_max, 32, 64));
+    if (h == 0) a.dfp_rowmax[row] = fp_max;
+    publish_max(a.gmax + n_film, fp_max, live, true, lane);
+  }
+}
+
+template <int H, bool KEEP = true>
+__global__ __launch_bounds__(256, 1) void film_bwd4s_kernel(const BwdFilmArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[RING_BYTES + SCALE_FLOATS * 4 + 4 * H * 4];
+  float* sl = reinterpret_cast<float*>(smem + RING_BYTES);
+  float* wo = sl + SCALE_FLOATS;  // head weights [4][H] (rows >= out_dim zero)
+  const nsky_film_net& net = a.net;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  for (int i = tid; i < SCALE_FLOATS; i += 256) sl[i] = a.table[BIAS_FLOATS + i];
+  for (int i = tid; i < 4 * H; i += 256) wo[i] = (i / H) < net.out_dim ? net.out_w[(long)(i / H) * net.out_ld + (i % H)] : 0.0f;
+  __syncthreads();
+  WStream ws;
+  ws_open(ws, a.stream, smem, wave, lane);
+  const long n_tiles = (a.M + 31) / 32;
+  const long rt = (long)blockIdx.x * 4 + wave;
+  if (rt < n_tiles) film_bwd4s_tile<H, true, KEEP>(a, ws, sl, wo, rt, lane);
+  else film_bwd4s_tile<H, false, KEEP>(a, ws, sl, wo, 0, lane);
+  ws_close();
+}
+
 // =====================================================================================================================
-// Backward, mapping network.  dh = sum over the 2 n_film H head rows of Wmo^T dfp (k-block outer: 64 head rows of dfp are
+// Backward, mapping network. dh = sum over the 2 n_film H head rows of Wmo^T dfp (k-block outer: 64 head rows of dfp are
 // fetched tile-native one block ahead with hidden loads, pre-scaled by the row's maximum over ALL of dfp and split; dfp is read
 // ONCE), then the
 // mapping layers backwards, hidden state in registers as in the forward: dpre = dh * leaky'(h) is stored tile-native (weight
@@ -907,7 +1163,7 @@ int check_net(const nsky_film_net* n, const char* who) {
 
 extern "C" int nsky_film_stream_layout(const nsky_film_net* net, int32_t direction, int64_t* stream_bytes, int32_t* n_tiles) {
   if (int rc = check_net(net, "nsky_film_stream_layout")) return rc;
-  NSKY_CHECK_ARG(direction >= 0 && direction <= 2, "nsky_film_stream_layout: direction %d", direction);
+  NSKY_CHECK_ARG(direction >= 0 && direction <= 3, "nsky_film_stream_layout: direction %d", direction);
   long groups;
   int tiles;
   dir_layout(*net, direction, groups, tiles);
@@ -919,7 +1175,7 @@ extern "C" int nsky_film_stream_layout(const nsky_film_net* net, int32_t directi
 
 extern "C" int nsky_film_pack(const nsky_film_net* net, int32_t direction, void* stream_buf, float* table, nsky_stream_t stream) {
   if (int rc = check_net(net, "nsky_film_pack")) return rc;
-  NSKY_CHECK_ARG(direction >= 0 && direction <= 2 && stream_buf && table && ((uintptr_t)stream_buf % 16) == 0 && ((uintptr_t)table % 16) == 0, "nsky_film_pack: bad arguments");
+  NSKY_CHECK_ARG(direction >= 0 && direction <= 3 && stream_buf && table && ((uintptr_t)stream_buf % 16) == 0 && ((uintptr_t)table % 16) == 0, "nsky_film_pack: bad arguments");
   long groups;
   int tiles;
   dir_layout(*net, direction, groups, tiles);
@@ -930,9 +1186,11 @@ extern "C" int nsky_film_pack(const nsky_film_net* net, int32_t direction, void*
   return NSKY_OK;
 }
 
-extern "C" int nsky_film_chain_fwd(const nsky_film_net* net, const void* stream_buf, const float* table, const float* cond,
-                                   int32_t ldcond, const float* x, int32_t ldx, int32_t M, float* const* h_save, float* const* z_save,
-                                   float* const* y_save, float* res, int32_t ldres, nsky_stream_t stream) {
+namespace {
+// nsky_film_chain_fwd, and with f_save / arg_save its saved-operand form
+int film_chain_fwd(const nsky_film_net* net, const void* stream_buf, const float* table, const float* cond, int32_t ldcond, const float* x,
+                   int32_t ldx, int32_t M, float* const* h_save, float* const* z_save, float* const* y_save, float* const* f_save,
+                   float* const* arg_save, float* res, int32_t ldres, nsky_stream_t stream) {
   if (int rc = check_net(net, "nsky_film_chain_fwd")) return rc;
   NSKY_CHECK_ARG(stream_buf && table && cond && x && res && M > 0, "nsky_film_chain_fwd: null operand / empty batch");
   NSKY_CHECK_ARG(ldcond % 4 == 0 && ldcond >= ((net->cond_dim + 3) & ~3) && ldx % 4 == 0 && ldx >= ((net->x_dim + 3) & ~3) && ldres >= 4 && ldres % 4 == 0,
@@ -947,29 +1205,58 @@ extern "C" int nsky_film_chain_fwd(const nsky_film_net* net, const void* stream_
     a.h_save[l] = (h_save && l < net->n_map) ? h_save[l] : nullptr;
     a.z_save[l] = (z_save && l < net->n_film) ? z_save[l] : nullptr;
     a.y_save[l] = (y_save && l < net->n_film) ? y_save[l] : nullptr;
+    a.f_save[l] = (f_save && l < net->n_film) ? f_save[l] : nullptr;
+    a.arg_save[l] = (arg_save && l < net->n_film) ? arg_save[l] : nullptr;
   }
   // FiLM outputs not kept: all of y_save NULL, the hand-off in registers (hidden 128 only; at 256 the caller passes ping-pong buffers)
   const bool keep_y = a.y_save[0] != nullptr;
   NSKY_CHECK_ARG(keep_y || net->hidden == 128, "nsky_film_chain_fwd: NULL y_save needs hidden 128 (hidden %d: pass two ping-pong buffers)", net->hidden);
   for (int l = 0; l < net->n_film; ++l)
     NSKY_CHECK_ARG((a.y_save[l] != nullptr) == keep_y && ((uintptr_t)a.y_save[l] % 16) == 0, "nsky_film_chain_fwd: y_save[%d] missing / unaligned", l);
+  // f and the sine argument kept for film_bwd4s_kernel: every entry of both, or none
+  const bool save_fa = a.f_save[0] != nullptr;
+  for (int l = 0; l < net->n_film; ++l)
+    NSKY_CHECK_ARG((a.f_save[l] != nullptr) == save_fa && (a.arg_save[l] != nullptr) == save_fa && ((uintptr_t)a.f_save[l] % 16) == 0 &&
+                       ((uintptr_t)a.arg_save[l] % 16) == 0, "nsky_film_chain_fwd_saved: f_save / arg_save[%d] missing / unaligned", l);
   const dim3 grid(ceil_div(M, 128));
   const int ksc = ksteps_of(net->cond_dim);
-#define NSKY_FILM_FWD(HH, KK, KEEP) hipLaunchKernelGGL((film_fwd_kernel<HH, KK, KEEP>), grid, dim3(256), 0, (hipStream_t)stream, a)
-  if (net->hidden == 256) { if (ksc <= 4) NSKY_FILM_FWD(256, 4, true); else NSKY_FILM_FWD(256, 20, true); }
-  else if (keep_y) { if (ksc <= 4) NSKY_FILM_FWD(128, 4, true); else NSKY_FILM_FWD(128, 20, true); }
-  else { if (ksc <= 4) NSKY_FILM_FWD(128, 4, false); else NSKY_FILM_FWD(128, 20, false); }
+#define NSKY_FILM_FWD(HH, KK, KEEP)                                                                                              \
+  {                                                                                                                              \
+    if (save_fa) hipLaunchKernelGGL((film_fwd_kernel<HH, KK, KEEP, true>), grid, dim3(256), 0, (hipStream_t)stream, a);          \
+    else hipLaunchKernelGGL((film_fwd_kernel<HH, KK, KEEP, false>), grid, dim3(256), 0, (hipStream_t)stream, a);                 \
+  }
+  if (net->hidden == 256) { if (ksc <= 4) NSKY_FILM_FWD(256, 4, true) else NSKY_FILM_FWD(256, 20, true) }
+  else if (keep_y) { if (ksc <= 4) NSKY_FILM_FWD(128, 4, true) else NSKY_FILM_FWD(128, 20, true) }
+  else { if (ksc <= 4) NSKY_FILM_FWD(128, 4, false) else NSKY_FILM_FWD(128, 20, false) }
 #undef NSKY_FILM_FWD
   NSKY_CHECK_LAUNCH("nsky_film_chain_fwd");
   return NSKY_OK;
 }
+}  // namespace
+
+extern "C" int nsky_film_chain_fwd(const nsky_film_net* net, const void* stream_buf, const float* table, const float* cond,
+                                   int32_t ldcond, const float* x, int32_t ldx, int32_t M, float* const* h_save, float* const* z_save,
+                                   float* const* y_save, float* res, int32_t ldres, nsky_stream_t stream) {
+  return film_chain_fwd(net, stream_buf, table, cond, ldcond, x, ldx, M, h_save, z_save, y_save, nullptr, nullptr, res, ldres, stream);
+}
+
+extern "C" int nsky_film_chain_fwd_saved(const nsky_film_net* net, const void* stream_buf, const float* table, const float* cond,
+                                         int32_t ldcond, const float* x, int32_t ldx, int32_t M, float* const* h_save, float* const* z_save,
+                                         float* const* y_save, float* const* f_save, float* const* arg_save, float* res, int32_t ldres,
+                                         nsky_stream_t stream) {
+  NSKY_CHECK_ARG(f_save && arg_save, "nsky_film_chain_fwd_saved: null f_save / arg_save");
+  return film_chain_fwd(net, stream_buf, table, cond, ldcond, x, ldx, M, h_save, z_save, y_save, f_save, arg_save, res, ldres, stream);
+}
 
 
-extern "C" int nsky_film_chain_bwd_film(const nsky_film_net* net, const void* stream_buf, const float* table, int32_t M, const float* d_res,
-                                        int32_t ldres, const float* h_last, const float* const* z_save, float* const* dz_save, float* dfp,
-                                        float* dfp_rowmax, float* gmax, float* d_x, int32_t ldx, nsky_stream_t stream) {
+namespace {
+// nsky_film_chain_bwd_film (h_last; f_save and arg_save NULL), and its saved-operand form (h_last NULL; stream of direction 3)
+int film_chain_bwd_film(const nsky_film_net* net, const void* stream_buf, const float* table, int32_t M, const float* d_res, int32_t ldres,
+                        const float* h_last, const float* const* z_save, const float* const* f_save, const float* const* arg_save,
+                        float* const* dz_save, float* dfp, float* dfp_rowmax, float* gmax, float* d_x, int32_t ldx, nsky_stream_t stream) {
   if (int rc = check_net(net, "nsky_film_chain_bwd_film")) return rc;
-  NSKY_CHECK_ARG(stream_buf && table && d_res && h_last && z_save && dfp && dfp_rowmax && gmax && M > 0, "nsky_film_chain_bwd_film: null operand / empty batch");
+  const bool saved = f_save != nullptr;
+  NSKY_CHECK_ARG(stream_buf && table && d_res && (h_last || saved) && z_save && dfp && dfp_rowmax && gmax && M > 0, "nsky_film_chain_bwd_film: null operand / empty batch");
   NSKY_CHECK_ARG(ldres >= 4 && ldres % 4 == 0 && ((uintptr_t)d_res % 16) == 0 && ((uintptr_t)h_last % 16) == 0 && ((uintptr_t)dfp % 16) == 0 &&
                      ((uintptr_t)stream_buf % 16) == 0 && ((uintptr_t)table % 16) == 0, "nsky_film_chain_bwd_film: alignment / ldres");
   NSKY_CHECK_ARG(net->hidden % 128 == 0, "nsky_film_chain_bwd_film: hidden %% 128");
@@ -979,19 +1266,44 @@ extern "C" int nsky_film_chain_bwd_film(const nsky_film_net* net, const void* st
   if (d_x) NSKY_CHECK_ARG(ldx % 4 == 0 && ldx >= ((net->x_dim + 3) & ~3) && ldx <= 16 && ((uintptr_t)d_x % 16) == 0, "nsky_film_chain_bwd_film: d_x layout (ldx %d)", ldx);
   for (int l = 0; l < MAXL; ++l) {
     a.z_save[l] = l < net->n_film ? z_save[l] : nullptr;
+    a.f_save[l] = (saved && l < net->n_film) ? f_save[l] : nullptr;
+    a.arg_save[l] = (saved && l < net->n_film) ? arg_save[l] : nullptr;
     a.dz_save[l] = (dz_save && l < net->n_film) ? dz_save[l] : nullptr;
   }
+  for (int l = 0; saved && l < net->n_film; ++l)
+    NSKY_CHECK_ARG(a.f_save[l] && a.arg_save[l] && ((uintptr_t)a.f_save[l] % 16) == 0 && ((uintptr_t)a.arg_save[l] % 16) == 0,
+                   "nsky_film_chain_bwd_film_saved: f_save / arg_save[%d]", l);
   const bool keep = a.dz_save[0] != nullptr;  // dz not kept (frozen weights): all of dz_save NULL
   for (int l = 0; l < net->n_film; ++l)
     NSKY_CHECK_ARG(a.z_save[l] && (a.dz_save[l] != nullptr) == keep && ((uintptr_t)a.z_save[l] % 16) == 0 && ((uintptr_t)a.dz_save[l] % 16) == 0, "nsky_film_chain_bwd_film: z_save / dz_save[%d]", l);
   a.full_wgs = a.tail_wgs = a.tail_k = 0;  // (four row tiles per workgroup, one per wave: no tail plan)
   const dim3 grid(ceil_div(ceil_div(M, 32), 4));
-#define NSKY_FILM_BWD4(HH, KEEP) hipLaunchKernelGGL((film_bwd4_kernel<HH, KEEP>), grid, dim3(256), 0, (hipStream_t)stream, a)
-  if (net->hidden == 256) { if (keep) NSKY_FILM_BWD4(256, true); else NSKY_FILM_BWD4(256, false); }
-  else { if (keep) NSKY_FILM_BWD4(128, true); else NSKY_FILM_BWD4(128, false); }
+#define NSKY_FILM_BWD4(HH, KEEP)                                                                                       \
+  {                                                                                                                    \
+    if (saved) hipLaunchKernelGGL((film_bwd4s_kernel<HH, KEEP>), grid, dim3(256), 0, (hipStream_t)stream, a);          \
+    else hipLaunchKernelGGL((film_bwd4_kernel<HH, KEEP>), grid, dim3(256), 0, (hipStream_t)stream, a);                 \
+  }
+  if (net->hidden == 256) { if (keep) NSKY_FILM_BWD4(256, true) else NSKY_FILM_BWD4(256, false) }
+  else { if (keep) NSKY_FILM_BWD4(128, true) else NSKY_FILM_BWD4(128, false) }
 #undef NSKY_FILM_BWD4
   NSKY_CHECK_LAUNCH("nsky_film_chain_bwd_film");
   return NSKY_OK;
+}
+}  // namespace
+
+extern "C" int nsky_film_chain_bwd_film(const nsky_film_net* net, const void* stream_buf, const float* table, int32_t M, const float* d_res,
+                                        int32_t ldres, const float* h_last, const float* const* z_save, float* const* dz_save, float* dfp,
+                                        float* dfp_rowmax, float* gmax, float* d_x, int32_t ldx, nsky_stream_t stream) {
+  NSKY_CHECK_ARG(h_last, "nsky_film_chain_bwd_film: null h_last");
+  return film_chain_bwd_film(net, stream_buf, table, M, d_res, ldres, h_last, z_save, nullptr, nullptr, dz_save, dfp, dfp_rowmax, gmax, d_x, ldx, stream);
+}
+
+extern "C" int nsky_film_chain_bwd_film_saved(const nsky_film_net* net, const void* stream_buf, const float* table, int32_t M, const float* d_res,
+                                              int32_t ldres, const float* const* z_save, const float* const* f_save,
+                                              const float* const* arg_save, float* const* dz_save, float* dfp, float* dfp_rowmax, float* gmax,
+                                              float* d_x, int32_t ldx, nsky_stream_t stream) {
+  NSKY_CHECK_ARG(f_save && arg_save, "nsky_film_chain_bwd_film_saved: null f_save / arg_save");
+  return film_chain_bwd_film(net, stream_buf, table, M, d_res, ldres, nullptr, z_save, f_save, arg_save, dz_save, dfp, dfp_rowmax, gmax, d_x, ldx, stream);
 }
 
 extern "C" int nsky_film_chain_bwd_map(const nsky_film_net* net, const void* stream_buf, const float* table, int32_t M, const float* dfp,

@@ -727,6 +727,7 @@ def ddf_losses_bwd(desc: DDFLossesDesc, d_terms, d_expected, d_sdf, d_mv_expecte
 # ------------------------------------------------------------------------------------------ fused FiLM-SIREN chain
 FILM_MAX_LAYERS = 12
 FILM_TABLE_FLOATS = 6656  # biases + reciprocal tile scales written by nsky_film_pack
+FILM_SAVED_WIDTHS = (256,)  # hidden widths whose chain runs on saved FiLM operands by default (film_saved_operands)
 
 
 class FilmNet(C.Structure):
@@ -746,6 +747,11 @@ _film_fwd = _sig("nsky_film_chain_fwd", C.POINTER(FilmNet), C.c_void_p, C.c_void
 
 _film_bwd_film = _sig("nsky_film_chain_bwd_film", C.POINTER(FilmNet), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)
+_film_fwd_saved = _sig("nsky_film_chain_fwd_saved", C.POINTER(FilmNet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                       C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)
+_film_bwd_film_saved = _sig("nsky_film_chain_bwd_film_saved", C.POINTER(FilmNet), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                            C.c_void_p)
 _film_bwd_map = _sig("nsky_film_chain_bwd_map", C.POINTER(FilmNet), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
 
@@ -1147,9 +1153,30 @@ def film_keepless(hidden: int) -> str:
     return "registers" if hidden == 128 else "buffers"
 
 
-def film_chain_fwd(net: FilmNet, stream_buf, scales, cond, x, M, h_save, z_save, y_save, res):
+def film_saved_operands(hidden: int) -> bool:
+    """whether the chain of this width keeps f = 15 F + 30 and the sine argument of every FiLM layer in the forward (film_chain_fwd, f_save / arg_save)
+    and reads them back in the backward (film_chain_bwd_film, the same lists) instead of re-forming F and phase from the last mapping activation:
+    two hidden x hidden products per layer less, 2 x 4 bytes per row and feature more written and read.  The default per width follows
+    the same-box step measurement (profiles/film_saved_operands_ab.txt); NSKY_FILM_SAVED=0|1 overrides it for
+    both widths, NSKY_FILM_SAVED=128 or 256 (comma-separated) names the widths that save"""
+    env = os.environ.get("NSKY_FILM_SAVED", "")
+    if env in ("0", "1"):
+        return env == "1"
+    if env:
+        return str(hidden) in env.split(",")
+    return hidden in FILM_SAVED_WIDTHS
+
+
+def film_chain_fwd(net: FilmNet, stream_buf, scales, cond, x, M, h_save, z_save, y_save, res, f_save=None, arg_save=None):
     """see include/neusky_hip.h; h_save / z_save: lists (entries may be None) or None; y_save: list of [M, hidden] tensors, or None
-    (film_keepless(hidden) == "registers")"""
+    (film_keepless(hidden) == "registers"); f_save / arg_save: both None, or lists of tile-native [ceil32(M), hidden] tensors that take
+    f = 15 F + 30 and the sine argument of every FiLM layer (nsky_film_chain_fwd_saved: the operands of film_chain_bwd_film's saved form)"""
+    if f_save is not None or arg_save is not None:
+        check(_film_fwd_saved(C.byref(net), ptr(stream_buf), ptr(scales), ptr(cond), ld(cond), ptr(x), ld(x), M,
+                              _ptr_array(h_save, net.n_map), _ptr_array(z_save, net.n_film), _ptr_array(y_save, net.n_film),
+                              _ptr_array(f_save, net.n_film), _ptr_array(arg_save, net.n_film), ptr(res), ld(res), stream_ptr()),
+              "nsky_film_chain_fwd_saved")
+        return res
     check(_film_fwd(C.byref(net), ptr(stream_buf), ptr(scales), ptr(cond), ld(cond), ptr(x), ld(x), M,
                     _ptr_array(h_save, net.n_map), _ptr_array(z_save, net.n_film), _ptr_array(y_save, net.n_film), ptr(res), ld(res),
                     stream_ptr()), "nsky_film_chain_fwd")
@@ -1176,9 +1203,17 @@ def film_rows_to_native(x, width: int):
     return full.reshape(R, 32, width // 32, 4, 2, 4).permute(0, 2, 3, 4, 1, 5).contiguous().reshape(R * 32, width)
 
 
-def film_chain_bwd_film(net: FilmNet, stream_buf, table, M, d_res, h_last, z_save, dz_save, dfp, dfp_rowmax, gmax, d_x=None):
+def film_chain_bwd_film(net: FilmNet, stream_buf, table, M, d_res, h_last, z_save, dz_save, dfp, dfp_rowmax, gmax, d_x=None, f_save=None,
+                        arg_save=None):
     """gmax: zero-filled float tensor [n_film + 1]; d_x: optional [M, ldx] output; dz_save: None = not kept (frozen weights; only
-    gmax[n_film] is written); see include/neusky_hip.h"""
+    gmax[n_film] is written); see include/neusky_hip.h.  f_save / arg_save (both, from film_chain_fwd): the saved-operand form
+    (nsky_film_chain_bwd_film_saved) -- stream_buf / table packed with direction 3, h_last is not read and may be None"""
+    if f_save is not None or arg_save is not None:
+        check(_film_bwd_film_saved(C.byref(net), ptr(stream_buf), ptr(table), M, ptr(d_res), ld(d_res), _ptr_array(z_save, net.n_film),
+                                   _ptr_array(f_save, net.n_film), _ptr_array(arg_save, net.n_film), _ptr_array(dz_save, net.n_film),
+                                   ptr(dfp), ptr(dfp_rowmax), ptr(gmax), ptr(d_x), ld(d_x) if d_x is not None else 0, stream_ptr()),
+              "nsky_film_chain_bwd_film_saved")
+        return
     check(_film_bwd_film(C.byref(net), ptr(stream_buf), ptr(table), M, ptr(d_res), ld(d_res), ptr(h_last), _ptr_array(z_save, net.n_film),
                          _ptr_array(dz_save, net.n_film), ptr(dfp), ptr(dfp_rowmax), ptr(gmax), ptr(d_x), ld(d_x) if d_x is not None else 0,
                          stream_ptr()), "nsky_film_chain_bwd_film")

@@ -832,7 +832,8 @@ def _film_unpack(wb, n_map, n_film):
 
 
 def _film_stream(wb, n_map, n_film, direction=0):
-    """per-step cache of one packed weight stream of a network (direction 0 forward, 1 FiLM backward, 2 mapping backward;
+    """per-step cache of one packed weight stream of a network (direction 0 forward, 1 FiLM backward, 2 mapping backward, 3 FiLM
+    backward on saved operands;
     dropped by begin_step when any of its weights is trainable: the optimiser changed them) -> (descriptor, stream bytes, bias / scale table)"""
     key = (wb[0].data_ptr(), wb[0]._version, wb[-2].data_ptr(), n_map, n_film, direction)
 
@@ -882,10 +883,16 @@ class FilmChainFn(torch.autograd.Function):
         hs = [torch.empty(Mp, Hm, device=dev) for _ in range(n_map)] if save else None
         zs = [torch.empty(Mp, H, device=dev) for _ in range(n_film)] if save else None
         res = torch.empty(M, n_out_p, device=dev)
-        hip.film_chain_fwd(net, stream, scales, cond, x, M, hs, zs, ys, res)
+        # saved operands (hip.film_saved_operands): f and the sine argument of every FiLM layer go out beside z, and the backward
+        # reads them back instead of re-forming F and phase from the last mapping activation
+        saved = save and hip.film_saved_operands(H)
+        fs = [torch.empty(Mp, H, device=dev) for _ in range(n_film)] if saved else None
+        ags = [torch.empty(Mp, H, device=dev) for _ in range(n_film)] if saved else None
+        hip.film_chain_fwd(net, stream, scales, cond, x, M, hs, zs, ys, res, fs, ags)
         if not save:
             return res
         ctx.save_for_backward(x, cond, *hs, *(ys if keep_y else []), *zs, *wb)
+        ctx.film_fa = (fs, ags)  # (buffers of this node alone, neither inputs nor outputs: kept on the context, freed with it)
         ctx.cfg = (n_map, n_film, train_w, need_dcond, M, H, Hm, x.requires_grad)
         # weights that ARE optimizer-slab parameters (no padding copy in between) take their gradient in place
         ctx.sinks = [_sink_param(w) for w in wb]
@@ -895,9 +902,11 @@ class FilmChainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_res):
         """two chain kernels (csrc/film_chain.hip) produce every pre-activation gradient as a tile-native matrix (F / phase are
-        re-formed in registers: no [M, 2 n_film H] matrix is read or recomputed through HBM) and d_cond; the parameter gradients
-        are weight-gradient GEMMs straight over those matrices."""
+        re-formed in registers: no [M, 2 n_film H] matrix is read or recomputed through HBM -- or, hip.film_saved_operands, f and
+        the sine argument the forward kept are read back in their place) and d_cond; the parameter gradients are weight-gradient
+        GEMMs straight over those matrices."""
         n_map, n_film, train_w, need_dcond, M, H, Hm, need_dx = ctx.cfg  # (train_w: the weights take gradients, see forward)
+        fs, ags = ctx.film_fa  # (saved operands, or None: see forward)
         sv = ctx.saved_tensors
         x, cond = sv[0], sv[1]
         hs = list(sv[2:2 + n_map])
@@ -909,7 +918,7 @@ class FilmChainFn(torch.autograd.Function):
         dev = x.device
         Mp = hip.film_rows(M)
         d_res = d_res.contiguous()
-        net1, s1, t1 = _film_stream(wb, n_map, n_film, 1)
+        net1, s1, t1 = _film_stream(wb, n_map, n_film, 1 if fs is None else 3)
         net2, s2, t2 = _film_stream(wb, n_map, n_film, 2)
         dzs = [torch.empty(Mp, H, device=dev) for _ in range(n_film)] if train_w else None  # (the weight gradients' operand alone)
         dfp = torch.empty(Mp, 2 * n_film * H, device=dev)
@@ -918,7 +927,7 @@ class FilmChainFn(torch.autograd.Function):
         # (the kernels write a row's pad4(dim) columns: the columns of a wider input row take no part and get a zero gradient)
         alloc = lambda t, w: (torch.empty if ld(t) == w else zeros)(M, ld(t), device=dev)  # noqa: E731
         d_x = alloc(x, fw[0].shape[1]) if need_dx else None  # the DDF's multi-view rays (ddf_model.py:297-322)
-        hip.film_chain_bwd_film(net1, s1, t1, M, d_res, hs[-1], zs, dzs, dfp, rowmax, gmax[:n_film + 1], d_x)
+        hip.film_chain_bwd_film(net1, s1, t1, M, d_res, hs[-1], zs, dzs, dfp, rowmax, gmax[:n_film + 1], d_x, fs, ags)
         d_cond = alloc(cond, mw[0].shape[1]) if need_dcond else None
         want_map = need_dcond or train_w
         if train_w:
