@@ -204,7 +204,12 @@ int nsky_film_chain_bwd_film_saved(const nsky_film_net* net, const void* stream_
  * direction, 0 = forward, 1 = backward).  a0_save / a1_save: the two softplus outputs, tile-native [ceil32(M), hidden] (scratch in
  * inference).  _bwd: g_sdf [M] -> dz1 / dz0 (tile-native pre-activation gradients: the operands of the weight gradients,
  * nsky_wgrad_native), dE [M, ldE] (optional), dw2 [hidden] += sum_rows g a1 and db2 [1] += sum_rows g (optional), gmax [2] = max |dz1|, max |dz0| (caller
- * zero-fills).  hidden = 256, in_dim <= 80 (multiple of 4). */
+ * zero-fills).  hidden = 256, in_dim 4..80 (multiple of 4).
+ * What is read and written: _fwd reads columns [0, in_dim) of rows [0, M) of E (ldE >= in_dim, ldE % 4 == 0: the columns behind them and
+ * the rows behind M are never read) and writes sdf[0 .. M).  _bwd writes columns [0, in_dim) of rows [0, M) of dE and nothing else:
+ * whatever a wider ldE leaves behind them, and every row from M on, is left as it is.  The tile-native matrices are written for the
+ * rows < M (the rows of the last wave tile behind M: unspecified).  E, dE and the tile-native matrices are 16-byte aligned.  Anything
+ * else (M <= 0 included) is refused with an error return and nothing is launched. */
 typedef struct {
   int32_t in_dim, hidden;
   const float* w0; int32_t ld0; const float* b0;   /* [hidden, in_dim] */

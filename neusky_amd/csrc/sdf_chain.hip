@@ -285,7 +285,7 @@ __global__ __launch_bounds__(512, 2) void sdf_bwd_kernel(const SdfBwdArgs a) {
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
           const int fo = 32 * u + 8 * gq + 4 * h;
-          if (fo < a.ldE)
+          if (fo < a.net.in_dim)  // columns [0, in_dim) and nothing else: whatever the leading dimension leaves behind them is the caller's
             stg4(a.dE + row * a.ldE + fo, make_float4(acc[4 * gq] * inv, acc[4 * gq + 1] * inv, acc[4 * gq + 2] * inv, acc[4 * gq + 3] * inv));
         }
       }
@@ -361,6 +361,9 @@ extern "C" int nsky_sdf_chain_bwd(const nsky_sdf_net* net, const void* stream_bu
                                   float* db2, float* gmax, nsky_stream_t stream) {
   if (int rc = check_sdf_net(net, "nsky_sdf_chain_bwd")) return rc;
   NSKY_CHECK_ARG(stream_buf && table && g_sdf && a0_save && a1_save && dz1 && dz0 && gmax && M > 0, "nsky_sdf_chain_bwd: bad argument");
+  NSKY_CHECK_ARG(((uintptr_t)a0_save % 16) == 0 && ((uintptr_t)a1_save % 16) == 0 && ((uintptr_t)dz1 % 16) == 0 && ((uintptr_t)dz0 % 16) == 0 &&
+                     ((uintptr_t)stream_buf % 16) == 0,
+                 "nsky_sdf_chain_bwd: alignment");
   if (dE) NSKY_CHECK_ARG(ldE % 4 == 0 && ldE >= net->in_dim && ((uintptr_t)dE % 16) == 0, "nsky_sdf_chain_bwd: dE layout");
   SdfBwdArgs a;
   a.net = *net; a.stream = (const unsigned char*)stream_buf; a.table = table; a.M = M; a.g = g_sdf; a.a0 = a0_save; a.a1 = a1_save;

@@ -1442,7 +1442,13 @@ class SdfChainFn(torch.autograd.Function):
         net, stream, table = _sdf_stream(W0, b0, W1, b1, W2, b2, GF, beta, 1)
         Mp = hip.film_rows(M)
         dZ1 = torch.empty(Mp, Hd, device=dev); dZ0 = torch.empty(Mp, Hd, device=dev)
+        # the kernel writes columns [0, Kin) of a [M, ld(E)] buffer; autograd takes E's own shape: a view when E is one of a wider buffer
         dE = torch.empty(M, ld(E), device=dev) if ctx.needs_input_grad[0] else None
+        dE_out = dE
+        if dE is not None and E.shape[1] > Kin:
+            dE[:, Kin:E.shape[1]].zero_()  # (columns of E the weights do not read)
+        if dE is not None and E.shape[1] != ld(E):
+            dE_out = dE[:, :E.shape[1]]
         gmax = zeros(4, device=dev)
         dW0 = db0 = dW1 = db1 = dW2 = db2 = None
         f0 = f1 = f2 = False
@@ -1463,7 +1469,7 @@ class SdfChainFn(torch.autograd.Function):
             async_weight_gradients(launch, [dZ1, A0, dZ0, E, gmax])
             join_unless_sunk(db0, db1)  # (db2's share came from the chain kernel above, on this stream)
         k = first_only  # later nodes of the pass added in place; slab-resident biases return nothing
-        return dE, k(f0, dW0), k(f0, db0), k(f1, dW1), k(f1, db1), k(f2, dW2), k(f2, db2), None, None
+        return dE_out, k(f0, dW0), k(f0, db0), k(f1, dW1), k(f1, db1), k(f2, dW2), k(f2, db2), None, None
 
 
 class SdfLayersFn(torch.autograd.Function):
