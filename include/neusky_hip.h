@@ -1242,6 +1242,63 @@ int nsky_lights_composite(const float* base, int64_t base_stride, const float* t
                           float* light_lin, float* visibility, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Height fog and haze with shadowed sun shafts (neusky_amd/relight/atmosphere.py, csrc/atmosphere.hip): a participating medium between
+ * the camera and what a frame shows, applied to a chunk's linear image after its suns and lamps.
+ * The medium:
+ *   density [3] >= 0   the extinction coefficient per scene unit at height base_height, per channel
+ *   H                  the scale height: sigma_c(z) = density_c exp(-(z - base_height) / H), z up; H = 0 in the block stands for a
+ *                      homogeneous medium (sigma_c = density_c everywhere)
+ *   albedo [3]         the single-scattering albedo, in [0, 1]
+ *   g                  the Henyey-Greenstein parameter, |g| <= 0.99
+ *   far > 0            the path length, from the ray origin, given to what lies behind the scene: the background, and the see-through
+ *                      share of a ray.  far / H <= 60, so that no exponential overflows
+ *   background         whether the sky behind the scene is fogged too
+ *   params:  fp32 [12] in device memory = density (0..2), albedo (3..5), H, base_height, g, far, background (1 or 0), pad.  Only M and
+ *            Kb are by value: a captured graph replays under a new density, height, albedo, anisotropy, far or background flag.
+ * Per ray and per base image b (one per sun of a sun or daylight frame, one for a sky frame), channel c implied:
+ *   inputs:  origin o, unit direction d, t_s = clamp(depth, 0, far) (the ray's rendered depth along it), A = clamp(accumulation, 0, 1),
+ *            the linear image lin_b after suns and lamps, the background colour B_b behind the ray.
+ *   optical depth:  tau(t) = density E t phi(d_z t / H),  E = exp(clamp(-(o_z - base_height) / H, -80, 80)),
+ *            phi(u) = (1 - exp(-u)) / u, evaluated as -expm1(-u) / u, and as 1 - u / 2 + u u / 6 for |u| < 1e-4; a homogeneous medium
+ *            has E = 1 and phi = 1.  This is the integral of sigma along the ray from 0 to t.  T(t) = exp(-tau(t)).
+ *   source:  J_b(m) = albedo (Abar_b + 2 pi p_g(<d, s_k>) C_k V_k(m) up_k)
+ *            Abar_b    the mean of the frame's light colours over all D light directions of base b: an equal-area lattice, so this is
+ *                      (1 / 4 pi) times the integral of the sky's radiance.  Sky in-scatter is NOT shadowed: an approximation.
+ *            s_k, C_k  the sun's direction and colour; C = L Omega / (2 pi), so 2 pi C is the sun's L Omega
+ *            p_g(mu) = (1 / 4 pi) (1 - g^2) / (1 + g^2 - 2 g mu)^1.5
+ *            up_k = 1 when s_k,z > 0, else 0: a set sun adds nothing.  A sky frame has no sun term.
+ *            V_k(m)    the sun's visibility from the midpoint o + (m + 0.5) (far / M) d of segment m; 1 when M = 0 or vis is NULL.
+ *   in-scatter to t_e:  with t_m = m far / Mseg for m = 0..Mseg, Mseg = max(M, 1):
+ *            S_b(t_e) = sum_m J_b(m) (T(min(t_m, t_e)) - T(min(t_{m+1}, t_e))), m ascending:
+ *            exact for a source that is piecewise constant along the ray, for any density profile; with M = 0 it is J (1 - T(t_e)).
+ *   pixel:   out_b = T(t_s) (lin_b - (1 - A) B_b) + A S_b(t_s) + (1 - A) X_b,  X_b = T(far) B_b + S_b(far) with `background`, else B_b
+ *            rgb = clamp(linear_to_sRGB(out), 0, 1);  transmittance = T(t_s);
+ *            inscatter_b = A S_b(t_s) + (1 - A) S_b(far) with `background`, else A S_b(t_s);
+ *            light_lin <- light_lin T(t_s), so that it stays the lamps' share of lin.
+ * The rule uses the ray's rendered depth, as the suns' and the lamps' shadows do, not a per-sample transmittance inside the alpha
+ * composite, and adds no glow around lamps.  Every default of relight.Atmosphere is a design choice, not a measurement.
+ * nsky_atmosphere_rows:   origins, directions [R,3]; params; M  ->  row_origins, row_directions [M R,3], row_depth [M R]: row i = m R + r
+ *                         holds ray r and the depth (m + 0.5) (far / M), formed in fp64 and rounded once: what nsky_ddf_query_rows and
+ *                         nsky_sphere_trace_begin take to put a shadow query at the midpoint of segment m.
+ * nsky_atmosphere_apply:  origins, directions [R,3]; depth, accumulation [R]; lin_in [Kb,R,3] through its strides (k, r), in floats, the
+ *                         channels contiguous (a frame of K suns is ray-major in memory); background [Kb,R,3] with background_stride =
+ *                         3 R, or [R,3] with 0; abar [Kb,3]; sun_dirs, sun_colours [Kb,3] or both NULL; vis [M,Kb,R] through its strides
+ *                         (m, k, r) or NULL; params  ->  lin, rgb, inscatter [Kb,R,3] through the strides (k, r) they share;
+ *                         transmittance [R,3]; light_lin [R,3] in place, or NULL.  One thread per ray; everything in fp64 from the fp32
+ *                         inputs, every output rounded once.
+ * Flat indices are int64.  No atomics and a fixed summation order: every output is bitwise repeatable.  Nothing is read on the host. */
+#define NSKY_ATMOSPHERE_FLOATS 12
+#define NSKY_ATMOSPHERE_MAX_SHAFTS 64
+int nsky_atmosphere_rows(const float* origins, const float* directions, const float* params, int64_t R, int32_t M, float* row_origins,
+                         float* row_directions, float* row_depth, nsky_stream_t stream);
+int nsky_atmosphere_apply(const float* origins, const float* directions, const float* depth, const float* accumulation, const float* lin_in,
+                          int64_t lin_stride_k, int64_t lin_stride_r, const float* background, int64_t background_stride, const float* abar,
+                          const float* sun_dirs, const float* sun_colours, const float* vis, int64_t vis_stride_m, int64_t vis_stride_k,
+                          int64_t vis_stride_r, const float* params, int64_t R, int32_t M, int32_t Kb, float* lin, float* rgb,
+                          float* inscatter, int64_t out_stride_k, int64_t out_stride_r, float* transmittance, float* light_lin,
+                          nsky_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * A display transform: from a linear, high-dynamic-range image to a picture (neusky_amd/relight/display.py, csrc/display.hip):
  * metered exposure, an optional bloom, a tone curve, the sRGB transfer function and the rounding to 8 bits, all on the device.
  * Input: lin [K,H,W,3] fp32 (P = H W pixels per image), and optionally mask [K,H,W] fp32 (a frame's accumulation).

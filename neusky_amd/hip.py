@@ -1774,6 +1774,61 @@ def lights_composite(base, t, vis, acc, acc_threshold, lights, rgb, lin=None, li
                             _c(visibility), stream_ptr()), "nsky_lights_composite")
 
 
+# ---- height fog and haze with shadowed sun shafts (relight/atmosphere.py, csrc/atmosphere.hip)
+ATMOSPHERE_FLOATS = 12  # NSKY_ATMOSPHERE_FLOATS: density (0..2), albedo (3..5), H (0: homogeneous), base_height, g, far, background, -
+ATMOSPHERE_MAX_SHAFTS = 64
+_atmosphere_rows = _sig("nsky_atmosphere_rows", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                        C.c_void_p)
+_atmosphere_apply = _sig("nsky_atmosphere_apply", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def _atmosphere_block(params):
+    assert params.shape == (ATMOSPHERE_FLOATS,) and params.dtype == torch.float32 and params.is_contiguous()
+
+
+def atmosphere_rows(origins, directions, params, M: int, row_origins, row_directions, row_depth):
+    """origins, directions: fp32 [R, 3]; params [12] (device) -> row_origins, row_directions [M R, 3], row_depth [M R]: row m R + r is ray r
+    with the depth of the midpoint of segment m"""
+    R = origins.shape[0]
+    _atmosphere_block(params)
+    assert 1 <= M <= ATMOSPHERE_MAX_SHAFTS and origins.shape == (R, 3) and directions.shape == (R, 3)
+    assert row_origins.shape == (M * R, 3) and row_directions.shape == (M * R, 3) and row_depth.shape == (M * R,)
+    assert all(x.dtype == torch.float32 for x in (origins, directions, row_origins, row_directions, row_depth))
+    assert all(x.is_contiguous() for x in (row_origins, row_directions, row_depth))
+    check(_atmosphere_rows(_c(origins), _c(directions), ptr(params), R, M, ptr(row_origins), ptr(row_directions), ptr(row_depth), stream_ptr()),
+          "nsky_atmosphere_rows")
+
+
+def atmosphere_apply(origins, directions, depth, accumulation, lin_in, background, abar, sun_dirs, sun_colours, vis, params, M: int, lin, rgb,
+                     inscatter, transmittance, light_lin=None):
+    """origins, directions: fp32 [R, 3]; depth, accumulation [R]; lin_in [Kb, R, 3] through its strides (the last one 1: a frame of K suns
+    is ray-major in memory); background [R, 3] (one under all Kb) or [Kb, R, 3]; abar [Kb, 3]; sun_dirs, sun_colours [Kb, 3] or both None;
+    vis [M, Kb, R] through its strides, or None; params [12] (device) -> lin, rgb, inscatter [Kb, R, 3] through the strides they share,
+    transmittance [R, 3], and light_lin [R, 3] scaled in place, if given"""
+    Kb, R, _ = lin_in.shape
+    _atmosphere_block(params)
+    assert 0 <= M <= ATMOSPHERE_MAX_SHAFTS and origins.shape == (R, 3) and directions.shape == (R, 3) and depth.numel() == R
+    assert accumulation.numel() == R and background.shape in ((R, 3), (Kb, R, 3)) and abar.shape == (Kb, 3) and transmittance.shape == (R, 3)
+    assert (sun_dirs is None) == (sun_colours is None) and (sun_dirs is None or (sun_dirs.shape == (Kb, 3) and sun_colours.shape == (Kb, 3)))
+    assert vis is None or (sun_dirs is not None and M >= 1 and vis.shape == (M, Kb, R))
+    assert light_lin is None or (light_lin.shape == (R, 3) and light_lin.is_contiguous())
+    assert all(x is None or x.dtype == torch.float32 for x in (origins, directions, depth, accumulation, lin_in, background, abar, sun_dirs,
+                                                                sun_colours, vis, lin, rgb, inscatter, transmittance, light_lin))
+    ls_k, ls_r = _aa_strided(lin_in, Kb, R, 3, "the linear images")
+    os_k, os_r = _aa_strided(lin, Kb, R, 3, "the fogged images")
+    for x in (rgb, inscatter):
+        if _aa_strided(x, Kb, R, 3, "the fogged images") != (os_k, os_r):
+            raise ValueError(f"lin, rgb and inscatter share their strides, got {lin.stride()}, {rgb.stride()}, {inscatter.stride()}")
+    vs = (0, 0, 0) if vis is None else vis.stride()
+    assert transmittance.is_contiguous() and all(s >= 0 for s in vs)
+    stride = 0 if background.dim() == 2 else R * 3
+    check(_atmosphere_apply(_c(origins), _c(directions), _c(depth), _c(accumulation), ptr(lin_in), ls_k, ls_r, _c(background), stride, _c(abar),
+                            _c(sun_dirs), _c(sun_colours), ptr(vis), vs[0], vs[1], vs[2], ptr(params), R, M, Kb, ptr(lin), ptr(rgb),
+                            ptr(inscatter), os_k, os_r, ptr(transmittance), ptr(light_lin), stream_ptr()), "nsky_atmosphere_apply")
+
+
 # ---- a display transform: metered exposure, bloom, tone curve, sRGB, 8 bits (relight/display.py, csrc/display.hip)
 DISPLAY_BINS, DISPLAY_PARAMS, DISPLAY_MAX_RADIUS = 3072, 8, 96  # NSKY_DISPLAY_BINS / _PARAMS / _MAX_RADIUS
 DISPLAY_CURVES = {"clamp": 0, "reinhard": 1, "aces": 2, "hable": 3}  # NSKY_DISPLAY_CLAMP ..

@@ -47,6 +47,9 @@ FrameTrace = namedtuple("FrameTrace", "params steps grace")
 # L relight.PointLight inside the scene: block [L, 16] (include/neusky_hip.h), the accumulation threshold [1] and the parameter block
 # [6] of their shadow march; steps and grace as FrameTrace's; shadows: whether the march runs at all (a Python bool)
 FrameLights = namedtuple("FrameLights", "block acc_threshold params steps grace shadows")
+# a relight.Atmosphere: params: the kernels' parameter block [12] (include/neusky_hip.h: every number of the medium); abar [Kb, 3]: the
+# mean light colour of each base image's sky; samples: shaft_samples M, a Python number, a by-value argument of both kernels
+FrameAtmosphere = namedtuple("FrameAtmosphere", "params abar samples")
 
 
 @dataclass
@@ -55,7 +58,8 @@ class FrameLight:
     static buffers; the camera and the (pinned) rotation of its latent; optionally an environment map, suns, a transfer-bake storage, a
     daylight sky (which takes the place of the latent's: `cols` is then not decoded and not read), a shadow march in place of the suns'
     DDF queries, lamps inside the scene on top of whichever of these lights it; `linear`: a frame under the sky alone also keeps its
-    linear image `lin` (a sun frame and a frame with lamps always do), for a display transform"""
+    linear image `lin` (a sun frame and a frame with lamps or an atmosphere always do), for a display transform; a medium the frame is
+    seen through, applied last"""
     dirs: torch.Tensor
     cols: torch.Tensor
     sel: torch.Tensor
@@ -69,6 +73,7 @@ class FrameLight:
     trace: Optional[FrameTrace] = None
     linear: bool = False
     lights: Optional[FrameLights] = None
+    atmosphere: Optional[FrameAtmosphere] = None
     key: tuple = field(init=False)
 
     def __post_init__(self, rotation_values):
@@ -78,7 +83,8 @@ class FrameLight:
         exposure, ground or camera does; a frame with marched shadows adds the march's length and leaving phase, so a new eps, bias or
         angular diameter does; a sky frame that keeps its linear image says so (its chunk has one more output); a frame with lamps adds
         their number, whether their shadows are marched and that march's length and leaving phase, so a new position, intensity, cone,
-        radius, eps or bias replays the chunk."""
+        radius, eps or bias replays the chunk; a frame seen through an atmosphere adds its shaft samples and nothing else, so a new
+        density, height, albedo, anisotropy, far or background flag replays the chunk."""
         env = self.envmap
         key = (self.cam, rotation_values) if env is None else ("envmap", env.data.data_ptr(), tuple(env.data.shape), env.convention)
         if self.daylight is not None:  # no latent is read: one chunk graph serves every camera
@@ -95,6 +101,8 @@ class FrameLight:
             key = (key, "linear")
         if self.lights is not None:
             key = (key, ("lights", self.lights.block.shape[0], self.lights.shadows, self.lights.steps, self.lights.grace))
+        if self.atmosphere is not None:
+            key = (key, ("atmosphere", self.atmosphere.samples))
         self.key = key
 
     @property
@@ -105,11 +113,19 @@ class FrameLight:
 def shade(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -> Dict[str, torch.Tensor]:
     """what the active frame's shading mode adds to a chunk's outputs: `rgb` under the sky alone; `rgb`, `lin`, `shadow_map` and
     `shadow_difference` with suns, under the frame's sky or a daylight sky of each sun's own; the transfer keys and no `rgb` for a bake
-    (no light enters).  A sky frame asked for its linear image adds `lin`: what the renderer's kernel computes beside `rgb` and drops."""
+    (no light enters).  A sky frame asked for its linear image adds `lin`: what the renderer's kernel computes beside `rgb` and drops.
+    An atmosphere is applied last, to whatever lit the chunk, and never to a bake."""
+    out = _lit_outputs(model, light, so, ray_bundle)
+    if light.atmosphere is None or light.shading == "bake":
+        return out
+    return _apply_atmosphere(model, light, so, ray_bundle, out)
+
+
+def _lit_outputs(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -> Dict[str, torch.Tensor]:
     if light.shading == "sky":
         if light.lights is not None:  # (the lamps add to the linear image: the frame carries it)
             return _add_lights(model, light.lights, so, ray_bundle, _sky_outputs(model, so), suns=False)
-        return _sky_outputs(model, so) if light.linear else {"rgb": model.render_lambertian(so)}
+        return _sky_outputs(model, so) if light.linear or light.atmosphere is not None else {"rgb": model.render_lambertian(so)}
     if light.shading in ("sun", "daylight"):
         out = _sun_outputs(model, light.sun, so, ray_bundle, light.daylight, light.trace)
         return out if light.lights is None else _add_lights(model, light.lights, so, ray_bundle, out, suns=True)
@@ -213,6 +229,39 @@ def _add_lights(model, lights: FrameLights, so: Dict[str, Any], ray_bundle: RayB
     return out
 
 
+def _apply_atmosphere(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """the frame's medium in front of a lit chunk (include/neusky_hip.h: height fog): out holds rgb, lin [R, 3] or, under K suns, the
+    ray-major views of [K, R, 3], which the kernel reads through their strides.  With shaft samples M the K suns are queried once more
+    at M points along every ray, by the frame's own shadow mode: M R rows through the DDF (with no visibility network: no shadow, as
+    for the surface) or through the march, which lifts a start point with no normal along the sun's direction.  `rgb` and `lin` are
+    replaced by the fogged ones, `light_lin` is scaled in place; atmosphere_transmittance [R, 3] and atmosphere_inscatter (shaped as
+    lin) join them."""
+    atm, sun = light.atmosphere, light.sun
+    suns = sun is not None
+    lin_in = out["lin"].permute(1, 0, 2) if suns else out["lin"][None]  # [Kb, R, 3]: under suns the storage _sun_outputs holds
+    Kb, R, dev = lin_in.shape[0], lin_in.shape[1], lin_in.device
+    o, d = ray_bundle.origins.detach().contiguous(), ray_bundle.directions.detach().contiguous()
+    M, vis = atm.samples, None
+    if M > 0 and (light.trace is not None or model.config.use_visibility):
+        rows_o, rows_d, rows_t = torch.empty(M * R, 3, device=dev), torch.empty(M * R, 3, device=dev), torch.empty(M * R, device=dev)
+        hip.atmosphere_rows(o, d, atm.params, M, rows_o, rows_d, rows_t)
+        if light.trace is not None:
+            march = trace_sun_shadows(model.field, rows_o, rows_d, rows_t, torch.zeros(M * R, 3, device=dev), sun.dirs, light.trace.params,
+                                      light.trace.steps, light.trace.grace)
+            vis = march.visibility.view(Kb, M, R).permute(1, 0, 2)
+        else:
+            vd = model.compute_visibility_compact(rows_o, rows_d, rows_t[:, None], sun.dirs, sun.threshold, sun.scale, sel=sun.sel)
+            vis = vd["visibility"].view(M, R, Kb).permute(0, 2, 1)
+    rgb, lin, inscatter = torch.empty(Kb, R, 3, device=dev), torch.empty(Kb, R, 3, device=dev), torch.empty(Kb, R, 3, device=dev)
+    transmittance = torch.empty(R, 3, device=dev)
+    hip.atmosphere_apply(o, d, so["p2p_dist"].detach().reshape(-1).contiguous(), so["accumulation"].reshape(-1).contiguous(), lin_in,
+                         so["hdr_background_colours"].contiguous(), atm.abar, sun.dirs if suns else None, sun.colours if suns else None, vis,
+                         atm.params, M, lin, rgb, inscatter, transmittance, out.get("light_lin"))
+    ray_major = (lambda t: t.permute(1, 0, 2)) if suns else (lambda t: t[0])
+    return {**out, "rgb": ray_major(rgb), "lin": ray_major(lin), "atmosphere_transmittance": transmittance,
+            "atmosphere_inscatter": ray_major(inscatter)}
+
+
 class FrameRenderer:
     """one per model (`model.frames`); plain Python, nothing of it is in the model's state_dict"""
 
@@ -221,8 +270,8 @@ class FrameRenderer:
         self.active: Optional[FrameLight] = None
         # the static buffers, one named tuple per key, kept for the model's lifetime (a captured chunk holds their pointers): "sky" ->
         # FrameSky; ("envmap", device) -> FrameEnvmap; ("suns", K, device) -> FrameSuns; ("daylight", K, D, device) -> FrameDaylight;
-        # ("trace", device) -> FrameTrace; ("lights", L, device) -> FrameLights.  Only "sky" is ever allocated again, on a new D or device,
-        # and takes the runners with it
+        # ("trace", device) -> FrameTrace; ("lights", L, device) -> FrameLights; ("atmosphere", Kb, device) -> FrameAtmosphere.  Only "sky"
+        # is ever allocated again, on a new D or device, and takes the runners with it
         self.static: Dict[Any, tuple] = {}
         # a chunk graph cached under a rotation's values reads the rotation through the pointer it was captured with: the first tensor
         # seen with these values is kept, and serves every later frame that asks for them (one entry per value ever seen)
@@ -260,9 +309,10 @@ class FrameRenderer:
         if cols is not None:
             sky.cols.copy_(cols)
         suns = self._suns(lighting)
+        daylight = self._daylight(lighting.daylight, sky.dirs, suns)
         self.active = FrameLight(sky.dirs, sky.cols, sky.sel, cam, rotation, values, self._envmap(envmap, rotation), suns, lighting.bake,
-                                 self._daylight(lighting.daylight, sky.dirs, suns), self._trace(lighting.shadow_trace), bool(linear),
-                                 self._lights(lighting))
+                                 daylight, self._trace(lighting.shadow_trace), bool(linear), self._lights(lighting),
+                                 self._atmosphere(lighting.atmosphere, sky, suns, daylight))
 
     def _envmap(self, envmap, rotation) -> Optional[FrameEnvmap]:
         if envmap is None:
@@ -336,6 +386,18 @@ class FrameRenderer:
         st.params.copy_(trace_params(trace))
         return st._replace(steps=trace["steps"], grace=trace["grace"], shadows=True)
 
+    def _atmosphere(self, atmosphere, sky: FrameSky, suns: Optional[FrameSuns], daylight: Optional[FrameDaylight]) -> Optional[FrameAtmosphere]:
+        """the medium's parameter block, and the mean light colour of each base image's sky: of the frame's one sky under every sun, or
+        of each sun's own daylight sky"""
+        if atmosphere is None:
+            return None
+        Kb, dev = 1 if suns is None else suns.dirs.shape[0], sky.dirs.device
+        st = self._static(("atmosphere", Kb, str(dev)), lambda: FrameAtmosphere(
+            torch.empty(hip.ATMOSPHERE_FLOATS, device=dev), torch.empty(Kb, 3, device=dev), None))
+        st.params.copy_(atmosphere.block())
+        st.abar.copy_(sky.cols[0].mean(0, keepdim=True).expand(Kb, 3) if daylight is None else daylight.lights.mean(1))
+        return st._replace(samples=atmosphere.shaft_samples)
+
     def end(self) -> None:
         self.active = None
 
@@ -363,7 +425,9 @@ class FrameRenderer:
         display_exposure (and, to a frame under the sky alone, its `lin`); it runs on the assembled frame, after the chunks, so its
         parameters touch no chunk graph.  antialias: a relight.Antialias: a second pass of sub-pixel rays through the pixels its edge rule
         marks, through the same runner and inside the same begin / end, resolved into `lin` (and `rgb` from it), `albedo`, `accumulation`
-        and `shadow_map`; adds aa_mask and aa_fraction (and `lin` as `display` does); `display` then sees the resolved frame."""
+        and `shadow_map`; adds aa_mask and aa_fraction (and `lin` as `display` does); `display` then sees the resolved frame.  Under an
+        atmosphere both see the fogged frame: every sub-pixel sample is fogged at its own depth; atmosphere_transmittance and
+        atmosphere_inscatter stay the centre ray's, as `depth` does."""
         model = self.model
         assert not model.training, "call model.eval() first"
         chunk = chunk or max(model.config.eval_num_rays_per_chunk, 4096)
@@ -386,9 +450,14 @@ class FrameRenderer:
         self.begin(camera_index, lighting, linear=linear)
         suns = lighting.suns
         sun_keys = list(SUN_KEYS + (SDF_SHADOW_KEYS if lighting.sun_shadows == "sdf" else ())) if suns is not None else []
+        fogged = lighting.atmosphere is not None and lighting.bake is None
+        if fogged and suns is not None:  # (shaped as `lin`: K leads)
+            sun_keys.append("atmosphere_inscatter")
         keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
-        if (linear or lighting.lights) and suns is None:
+        if (linear or lighting.lights or fogged) and suns is None:
             keys.append("lin")
+        if fogged:
+            keys += ["atmosphere_transmittance"] + (["atmosphere_inscatter"] if suns is None else [])
         if lighting.lights:
             keys += list(LIGHT_KEYS) + (["light_status"] if lighting.light_trace is not None else [])
         out = {k: [] for k in keys}

@@ -882,13 +882,13 @@ class NeuSkyFactoModel(ModelBase):
                     shadow_threshold: Optional[float] = None, shadow_sigmoid_scale: Optional[float] = None,
                     accumulation_mask_threshold: float = 0.0, daylight=None, sun_shadows: str = "ddf",
                     shadow_trace: Optional[dict] = None, lights=None, light_shadows: bool = True,
-                    light_trace: Optional[dict] = None) -> None:
+                    light_trace: Optional[dict] = None, atmosphere=None) -> None:
         """decode the illumination of ONE camera for a whole frame (the reference re-decodes it in each of the
         8100 chunks of a 1080p frame, neusky_model.py:1413-1432; the result is the same).  The frame stays active until end_frame.
         The lighting keywords: relight.FrameLighting, which documents and checks them."""
         self.frames.begin(camera_index, FrameLighting.of(rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold,
                                                          daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace, lights=lights,
-                                                         light_shadows=light_shadows, light_trace=light_trace))
+                                                         light_shadows=light_shadows, light_trace=light_trace, atmosphere=atmosphere))
 
     def end_frame(self) -> None:
         self.frames.end()
@@ -900,17 +900,18 @@ class NeuSkyFactoModel(ModelBase):
                                           shadow_sigmoid_scale: Optional[float] = None,
                                           accumulation_mask_threshold: float = 0.0, daylight=None, sun_shadows: str = "ddf",
                                           shadow_trace: Optional[dict] = None, display=None, antialias=None, lights=None,
-                                          light_shadows: bool = True, light_trace: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+                                          light_shadows: bool = True, light_trace: Optional[dict] = None,
+                                          atmosphere=None) -> Dict[str, torch.Tensor]:
         """neusky_model.py:1369-1501: chunked full-frame render.  The reference chunks at eval_num_rays_per_chunk = 256
         (8100 python iterations per 1080p frame); any chunk size gives the same image, so a larger static chunk is used
         and its forward is captured once in a HIP graph and replayed per chunk (BASELINE config 5).
         Outputs [*shape, C]: rgb, albedo, accumulation, depth, p2p_dist, normal, and what the lighting adds.  The lighting keywords
-        (rotation, envmap, sun, the thresholds, daylight, sun_shadows, shadow_trace, lights, light_shadows, light_trace):
+        (rotation, envmap, sun, the thresholds, daylight, sun_shadows, shadow_trace, lights, light_shadows, light_trace, atmosphere):
         relight.FrameLighting, which documents and checks them.
         display: a relight.DisplayTransform of the frame's linear image (FrameRenderer.render): display_rgb8, display_rgb, display_exposure.
         antialias: a relight.Antialias: sub-pixel rays through the pixels its edge rule marks, resolved in linear light: aa_mask, aa_fraction."""
         lighting = FrameLighting.of(rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold,
                                     daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace, lights=lights,
-                                    light_shadows=light_shadows, light_trace=light_trace)
+                                    light_shadows=light_shadows, light_trace=light_trace, atmosphere=atmosphere)
         return self.frames.render(camera_ray_bundle, lighting, to_cpu=to_cpu, camera_index=camera_index, chunk=chunk, use_graph=use_graph,
                                   display=display, antialias=antialias)

@@ -31,12 +31,16 @@ sRGB and 8 bits; the frame render and both transfers' `relight` take one as `dis
 `Antialias` (antialias.py, csrc/antialias.hip): adaptive supersampling of a frame: an edge mask from the frame's own G-buffer and linear
 image, `subpixel_rays` through the marked pixels, a resolve in linear light; the frame render takes one as `antialias=` (`--antialias`).
 
+`Atmosphere` (atmosphere.py, csrc/atmosphere.hip): height fog and haze between the camera and the frame, with the suns' in-scatter
+shadowed along the ray by the frame's own shadow mode; the frame render takes one as `atmosphere=` (`--fog-density`, `--fog-shafts`).
+
 `FrameLighting` (lighting.py): all of the above as the one value a frame's light is said in, with the rules between its options.
 
 sequence.py: the run of the command line: the plan of a camera's renders, the two sources of its frames, the writer of its files, the
 tally of its closing lines.
 """
 from .antialias import Antialias, r2_offsets, subpixel_rays
+from .atmosphere import Atmosphere
 from .cameras import CameraPath, camera_rays, load_camera_path
 from .daylight import DaylightSky
 from .display import DisplayTransform, bloom_weights, frame_display
@@ -51,7 +55,7 @@ from .sun import SunLight, sun_direction, sun_path, sun_solid_angle
 from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
 from .transfer_sh import SHRadianceTransfer, bake_transfer_sh, compress_transfer, light_basis, project_lights, sh_basis
 
-__all__ = ["ALIVE", "Antialias", "CameraPath", "DaylightSky", "DisplayTransform", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "FrameLighting", "HIT", "LIGHT_TRACE_DEFAULTS", "MAX_LIGHTS", "PointLight", "RadianceTransfer",
+__all__ = ["ALIVE", "Antialias", "Atmosphere", "CameraPath", "DaylightSky", "DisplayTransform", "ESCAPED", "EXHAUSTED", "EnvironmentMap", "FrameLighting", "HIT", "LIGHT_TRACE_DEFAULTS", "MAX_LIGHTS", "PointLight", "RadianceTransfer",
            "SHADOW_DEFAULTS", "SHRadianceTransfer", "SphereTrace", "SunExtraction", "SunLight", "TRACE_DEFAULTS", "bake_transfer",
            "bake_transfer_sh", "bloom_weights", "camera_rays", "compress_transfer", "envmap_labels", "envmap_lookup", "extract_sun", "frame_display", "light_basis",
            "load_camera_path", "pack_fp16", "project_envmap", "project_lights", "r2_offsets", "read_envmap", "sh_basis", "srgb_to_linear", "sun_direction",

@@ -6,6 +6,7 @@ the numbers of train / eval latent rows and the latent dimension from its latent
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import math
 import os
 import sys
@@ -133,6 +134,21 @@ def build_parser() -> argparse.ArgumentParser:
     lamps.add_argument("--light-path", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                        help="the first lamp moves along this segment: --light-steps frames per camera, from one set of chunk graphs")
     lamps.add_argument("--light-steps", type=int, metavar="N", help="frames of --light-path")
+    fog = ap.add_argument_group("atmosphere", "height fog or haze between the camera and the frame (relight.Atmosphere): the frame is "
+                                "attenuated to each ray's depth and gains the sky's and the suns' light scattered into the ray")
+    fog.add_argument("--fog-density", type=float, nargs="+", metavar="D",
+                     help="the extinction coefficient per scene unit at --fog-base-height, one number or R G B; turns the feature on, "
+                          "the flags below need it")
+    fog.add_argument("--fog-scale-height", type=float, metavar="H", help="the density falls off as exp(-(z - base) / H) (default: homogeneous)")
+    fog.add_argument("--fog-base-height", type=float, metavar="Z", help="the height --fog-density holds at (default 0)")
+    fog.add_argument("--fog-albedo", type=float, nargs="+", metavar="A", help="the single-scattering albedo, one number or R G B (default 1)")
+    fog.add_argument("--fog-anisotropy", type=float, metavar="G", help="the Henyey-Greenstein parameter, |G| <= 0.99 (default 0: isotropic)")
+    fog.add_argument("--fog-far", type=float, metavar="T", help="the path length given to what lies behind the scene (default 2)")
+    fog.add_argument("--fog-shafts", type=int, metavar="M",
+                     help="shadow the suns' in-scatter at M points along every ray (0..64, default 0), by --sun-shadows' mode: M further "
+                          "shadow queries per ray and sun")
+    fog.add_argument("--fog-clear-background", action="store_true", help="leave the sky behind the scene as it is (a daylight sky has its own atmosphere)")
+    fog.add_argument("--fog-map", action="store_true", help="also write the transmittance of each frame as fog_CCCC_FFF.png")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -188,6 +204,32 @@ def parse_lights(ap: argparse.ArgumentParser, args):
         a, b, n = args.light_path[:3], args.light_path[3:], args.light_steps
         path = [tuple(a[i] + (b[i] - a[i]) * (f / (n - 1) if n > 1 else 0.0) for i in range(3)) for f in range(n)]
     return lights, not args.no_light_shadows, trace, path
+
+
+def parse_atmosphere(ap: argparse.ArgumentParser, args):
+    """the relight.Atmosphere of --fog-density and its flags; None without it"""
+    flags = (("--fog-density", args.fog_density), ("--fog-scale-height", args.fog_scale_height), ("--fog-base-height", args.fog_base_height),
+             ("--fog-albedo", args.fog_albedo), ("--fog-anisotropy", args.fog_anisotropy), ("--fog-far", args.fog_far),
+             ("--fog-shafts", args.fog_shafts), ("--fog-clear-background", args.fog_clear_background or None), ("--fog-map", args.fog_map or None))
+    if args.transfer != "off":
+        refuse_given(ap, flags, "a baked transfer has no depth to fog: {} goes with --transfer off, not --transfer " + args.transfer)
+    if args.fog_density is None:
+        refuse_given(ap, flags[1:], "{} needs --fog-density")
+        return None
+    from .atmosphere import Atmosphere
+
+    for flag, v in (("--fog-density", args.fog_density), ("--fog-albedo", args.fog_albedo)):
+        if v is not None and len(v) not in (1, 3):
+            ap.error(f"{flag} takes one number or R G B")
+    if args.fog_shafts and args.sun_azimuth is None and args.sun_path is None and not args.extract_sun:
+        ap.error("--fog-shafts shadows the suns' in-scatter: it needs a sun: --sun-azimuth and --sun-elevation, --sun-path, or --extract-sun")
+    one = lambda v: v[0] if len(v) == 1 else tuple(v)  # noqa: E731
+    given = {"scale_height": args.fog_scale_height, "base_height": args.fog_base_height, "anisotropy": args.fog_anisotropy, "far": args.fog_far,
+             "albedo": None if args.fog_albedo is None else one(args.fog_albedo), "shaft_samples": args.fog_shafts}
+    try:
+        return Atmosphere(one(args.fog_density), background=not args.fog_clear_background, **{k: v for k, v in given.items() if v is not None})
+    except ValueError as e:
+        ap.error(str(e))
 
 
 def parse_antialias(ap: argparse.ArgumentParser, args):
@@ -413,6 +455,7 @@ def main(argv=None) -> int:
     display = parse_display(ap, args)
     antialias = parse_antialias(ap, args)
     lights, light_shadows, light_trace, light_path = parse_lights(ap, args)
+    atmosphere = parse_atmosphere(ap, args)
 
     import torch
 
@@ -434,7 +477,10 @@ def main(argv=None) -> int:
         sun = suns if shots[0].sweep else suns[0]
     marched = {} if sun is None else {"sun_shadows": sun_shadows, "shadow_trace": shadow_trace}  # (--extract-sun may have found none)
     lamps = {} if lights is None else {"lights": lights, "light_shadows": light_shadows, "light_trace": light_trace}
-    base = FrameLighting.of(None, envmap, sun, args.shadow_threshold, args.shadow_sigmoid_scale, daylight=daylight, **marched, **lamps)
+    if atmosphere is not None and sun is None and atmosphere.shaft_samples > 0:  # (--extract-sun found none: nothing to shadow)
+        atmosphere = dataclasses.replace(atmosphere, shaft_samples=0)
+    fog = {} if atmosphere is None else {"atmosphere": atmosphere}
+    base = FrameLighting.of(None, envmap, sun, args.shadow_threshold, args.shadow_sigmoid_scale, daylight=daylight, **marched, **lamps, **fog)
     writer = FrameWriter(args, display, tally)
     shared = {"chunk": args.chunk, "display": display, "floats": writer.floats, "deferred": writer.deferred}
     if args.transfer == "off":
@@ -450,7 +496,9 @@ def main(argv=None) -> int:
         writer.end_camera()
     torch.cuda.synchronize()
     tally.t_render = time.perf_counter() - t1
-    tally.report(args, (cams.width, cams.height), display, antialias, shadow_trace, lights, light_trace)
+    suns_per_render = 0 if sun is None else len(suns) if shots[0].sweep else 1
+    tally.report(args, (cams.width, cams.height), display, antialias, shadow_trace, lights, light_trace, atmosphere, suns_per_render,
+                 bool(model.config.use_visibility))
     return 0
 
 

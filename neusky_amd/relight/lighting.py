@@ -9,6 +9,7 @@ from typing import Any, Optional, Tuple
 import torch
 
 from .. import hip
+from .atmosphere import Atmosphere
 from .envmap import project_envmap
 from .lights import LIGHT_TRACE_DEFAULTS, PointLight, as_lights
 from .shadows import SHADOW_DEFAULTS, trace_settings
@@ -65,14 +66,17 @@ class FrameLighting:
     lights = None
     light_shadows = True
     light_trace = None
+    # a frame seen through a medium is a FoggedFrameLighting (or a FoggedLitFrameLighting), which adds this one as a field
+    atmosphere = None
 
     @classmethod
     def of(cls, rotation: Optional[torch.Tensor] = None, envmap=None, sun=None, shadow_threshold: Optional[float] = None,
            shadow_sigmoid_scale: Optional[float] = None, accumulation_mask_threshold: float = 0.0, bake: Optional[str] = None,
            daylight=None, sun_shadows: str = "ddf", shadow_trace: Optional[dict] = None, lights=None, light_shadows: bool = True,
-           light_trace: Optional[dict] = None) -> "FrameLighting":
+           light_trace: Optional[dict] = None, atmosphere: Optional[Atmosphere] = None) -> "FrameLighting":
         """sun: one SunLight or a sequence of K; shadow_trace: any of SHADOW_DEFAULTS' keys, the rest take their defaults; lights: one
-        PointLight or a sequence of L (None or empty: none); light_trace: any of LIGHT_TRACE_DEFAULTS' keys"""
+        PointLight or a sequence of L (None or empty: none); light_trace: any of LIGHT_TRACE_DEFAULTS' keys; atmosphere: a
+        relight.Atmosphere or None"""
         if sun_shadows not in ("ddf", "sdf"):
             raise ValueError(f"sun_shadows: 'ddf' or 'sdf', got {sun_shadows!r}")
         if sun_shadows == "sdf":
@@ -98,9 +102,19 @@ class FrameLighting:
             light_trace = trace_settings(light_trace, {**LIGHT_TRACE_DEFAULTS, "radius": COLLIDER_RADIUS})
         if lights is not None and bake is not None:
             raise ValueError("a bake holds the transfer of lights at infinity: it excludes `lights`")
+        if atmosphere is not None:
+            if not isinstance(atmosphere, Atmosphere):
+                raise ValueError(f"atmosphere: a relight.Atmosphere, got {atmosphere!r}")
+            if bake is not None:
+                raise ValueError("a bake takes the place of the shading: it has no image for an atmosphere to fog")
+            if atmosphere.shaft_samples > 0 and suns is None:
+                raise ValueError("shaft_samples shadows the suns' in-scatter: it needs `sun`")
         base = (rotation, envmap, daylight, bake, None if suns is None else tuple(suns), single, shadow_threshold, shadow_sigmoid_scale,
                 accumulation_mask_threshold, sun_shadows, shadow_trace)
-        return cls(*base) if lights is None else LitFrameLighting(*base, lights, bool(light_shadows), light_trace)
+        if lights is None:
+            return cls(*base) if atmosphere is None else FoggedFrameLighting(*base, atmosphere)
+        lit = (*base, lights, bool(light_shadows), light_trace)
+        return LitFrameLighting(*lit) if atmosphere is None else FoggedLitFrameLighting(*lit, atmosphere)
 
 
 @dataclass(frozen=True, eq=False)
@@ -119,6 +133,26 @@ class LitFrameLighting(FrameLighting):
     light_trace: Optional[dict] = None
     """with lights and light_shadows, every parameter of that march (relight.lights.LIGHT_TRACE_DEFAULTS, checked by trace_settings):
     steps, eps, relax, min_step, grace, radius and bias; None otherwise.  Only steps and grace are held by a captured chunk."""
+
+
+@dataclass(frozen=True, eq=False)
+class FoggedFrameLighting(FrameLighting):
+    """what FrameLighting.of builds when an atmosphere is given and no lamps: a FrameLighting with its field"""
+    __hash__ = None
+
+    atmosphere: Optional[Atmosphere] = None
+    """a relight.Atmosphere (include/neusky_hip.h: height fog): fog or haze between the camera and the frame, applied last, to the image
+    of any sky, of each of K suns and of the lamps: `rgb` and `lin` are then seen through it, and `atmosphere_transmittance`
+    [*shape, 3] and `atmosphere_inscatter` (shaped as `lin`) join the outputs.  It goes with everything but `bake`; shaft_samples > 0
+    needs `suns`, whose shadow mode then shadows their in-scatter too.  None: the frame without the feature."""
+
+
+@dataclass(frozen=True, eq=False)
+class FoggedLitFrameLighting(LitFrameLighting):
+    """what FrameLighting.of builds when lamps and an atmosphere are given: a LitFrameLighting with FoggedFrameLighting's field"""
+    __hash__ = None
+
+    atmosphere: Optional[Atmosphere] = None
 
 
 def light_colours(model, dirs: torch.Tensor, cam: int, rotation: Optional[torch.Tensor] = None, envmap=None) -> torch.Tensor:

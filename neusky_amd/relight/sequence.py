@@ -66,6 +66,8 @@ class Frame:
     light_lin: Optional[torch.Tensor] = None  # the lamps' share of `lin`
     aa_mask: Optional[torch.Tensor] = None  # (a sweep's frames come from one render: they share its mask)
     exposure: Optional[torch.Tensor] = None  # with a display transform and lamps: what the render showed the frame at, for the lamps' picture
+    transmittance: Optional[torch.Tensor] = None  # under an atmosphere: T to each ray's depth (a sweep's frames share it)
+    inscatter: Optional[torch.Tensor] = None  # under an atmosphere: what the medium added to the frame's `lin`
 
 
 class Tally:
@@ -78,9 +80,12 @@ class Tally:
         self.shadow_rays = self.exhausted = 0  # of --sun-shadows sdf
         self.light_rays = self.light_exhausted = 0  # of the lamps' shadow march
         self.sh_residual = self.sh_store = None  # of --sh-order: the largest light_residual so far, and a camera's (coefficients, bytes)
+        self.transmittances = []  # of --fog-density: every render's mean transmittance, device tensors
 
-    def report(self, args, size, display, antialias, shadow_trace, lights, light_trace) -> None:
-        """size: the frames' (width, height); shadow_trace: of --sun-shadows sdf, else None; the rest as the parse_* functions return them"""
+    def report(self, args, size, display, antialias, shadow_trace, lights, light_trace, atmosphere=None, suns: int = 0,
+               ddf_shadows: bool = True) -> None:
+        """size: the frames' (width, height); shadow_trace: of --sun-shadows sdf, else None; suns: per render; ddf_shadows: whether the
+        model has a visibility network (without one the DDF mode shadows nothing); the rest as the parse_* functions return them"""
         transfer = "" if args.transfer == "off" else f" | transfer {args.transfer}: bake {self.t_bake:.3f}s relight {self.t_relight:.3f}s"
         if self.sh_residual is not None:
             transfer += (f" | sh order {args.sh_order} ({self.sh_store[0]} coefficients, {self.sh_store[1] / 1e6:.1f} MB per camera): "
@@ -104,6 +109,17 @@ class Tally:
             marched = "no shadows" if light_trace is None else still.format(self.light_exhausted, self.light_rays, share, light_trace["steps"],
                                                                             "--light-shadow-steps")
             print(f"lights: {len(lights)} lamp{'s' if len(lights) > 1 else ''} | {marched}")
+        if atmosphere is not None and self.transmittances:
+            T = torch.stack(self.transmittances)
+            rows = atmosphere.extra_shadow_rows(suns)
+            if rows == 0:
+                what = "no shafts"
+            elif shadow_trace is None and not ddf_shadows:
+                what = f"{atmosphere.shaft_samples} shaft samples, unshadowed (the model has no visibility network): no extra rows"
+            else:
+                what = (f"{atmosphere.shaft_samples} shaft samples x {suns} sun{'s' if suns > 1 else ''}: {rows} extra "
+                        f"{'DDF rows' if shadow_trace is None else 'marched shadow rays'} per ray")
+            print(f"fog: mean transmittance smallest {float(T.min()):.4g} largest {float(T.max()):.4g} | {what}")
 
 
 class RenderSource:
@@ -137,10 +153,15 @@ class RenderSource:
             tally.exposures.append(out["display_exposure"])
         if "antialias" in self.shown:
             tally.marked.append(out["aa_fraction"])
+        fogged = base.atmosphere is not None
+        if fogged:
+            tally.transmittances.append(out["atmosphere_transmittance"].mean())
         for i, f in enumerate(shot.frames):
             own = (lambda k: out[k][i]) if shot.sweep else out.__getitem__  # (a sweep's images lead with its frames)
             frame = Frame(self.camera, f, shadow=own("shadow_map") if base.suns is not None else None,
-                          light_lin=out["light_lin"] if base.lights else None, aa_mask=out["aa_mask"] if "antialias" in self.shown else None)
+                          light_lin=out["light_lin"] if base.lights else None, aa_mask=out["aa_mask"] if "antialias" in self.shown else None,
+                          transmittance=out["atmosphere_transmittance"] if fogged else None,
+                          inscatter=own("atmosphere_inscatter") if fogged else None)
             if self.floats:
                 frame.rgb = own("rgb").clamp(0.0, 1.0).cpu().numpy()
             if display is not None:
@@ -196,7 +217,7 @@ class FrameWriter:
     The lamps' share of a frame goes through the frame's own path to a picture."""
 
     def __init__(self, args, display, tally: Tally):
-        """args: output_dir, sun_path and the flags save_hdr, save_linear, shadow_map, aa_mask, light_map.  What the sources ask the
+        """args: output_dir, sun_path and the flags save_hdr, save_linear, shadow_map, aa_mask, light_map, fog_map.  What the sources ask the
         writer: floats, whether anything reads a frame's float image on the host, and deferred: under "sequence" the frames of a sun
         path are metered by the one render that yields them; any others are not rendered together, and wait"""
         self.args, self.display, self.tally = args, display, tally
@@ -225,6 +246,12 @@ class FrameWriter:
             Image.fromarray(grey, mode="L").save(self._path("shadow", frame, ".png"))
         if args.aa_mask and frame.aa_mask is not None:
             Image.fromarray(frame.aa_mask[..., 0].cpu().numpy() * np.uint8(255), mode="L").save(self._path("aa", frame, ".png"))
+        if frame.transmittance is not None:
+            if args.fog_map:
+                T8 = np.round(frame.transmittance.clamp(0.0, 1.0).cpu().numpy() * 255.0).astype(np.uint8)
+                Image.fromarray(T8).save(self._path("fog", frame, ".png"))
+            if args.save_linear:
+                np.save(self._path("frame", frame, ".inscatter.npy"), frame.inscatter.cpu().numpy())
         self.tally.frames += 1
 
     def _shown(self, frame: Frame, rgb8: torch.Tensor, exposure: Optional[torch.Tensor]) -> None:
