@@ -27,7 +27,7 @@ extern "C" {
 typedef void* nsky_stream_t; /* hipStream_t */
 
 const char* nsky_last_error(void);
-int nsky_abi_version(void); /* 16 (bumped when a struct layout or an entry point's signature changes) */
+int nsky_abi_version(void); /* 17 (bumped when a struct layout or an entry point's signature changes) */
 
 /* ------------------------------------------------------------------------------------------
  * Dense layer on the matrix cores: C[M,N] = epilogue( sum_k A(m,k) * B(n,k) + bias[n] )
@@ -1162,8 +1162,11 @@ int nsky_sun_composite_skies(const float* lin_skies, const float* t, const float
  * nsky_sphere_trace_begin_points: starts [M,3]; directions [T / dir_div, 3]  ->  the same from explicit start points (T a multiple of M).
  * nsky_sphere_trace_step:         state, sdf [T] at `points`, directions, params, iteration  ->  state, points [T,3].  Rule steps 3-6 of
  *                                 this iteration, then p = fma(t, s, x) and rule step 1 of the next (none after iteration steps - 1).
- *                                 Dead rays keep their point to the bit (their t no longer moves).  16-byte accesses when T % 4 == 0
- *                                 and state, sdf and points are 16-byte aligned, else 4-byte ones; the results are the same.
+ *                                 Dead rays keep their point to the bit (their t no longer moves).  bounds NULL: the rule as above.
+ *                                 bounds [2][T] = t_end, tan_half of each ray's own (nsky_light_trace_begin): the march towards a
+ *                                 light below; it needs dir_div == 1, directions [T,3].  16-byte accesses when T % 4 == 0 and state,
+ *                                 sdf and points (with bounds: directions and bounds too) are 16-byte aligned, else 4-byte ones; the
+ *                                 results are the same.
  * nsky_sphere_trace_finish:       state  ->  vis [T] (= m), status [T] (int8, ALIVE reported as EXHAUSTED), t [T].
  * Flat indices are int64.  No atomics: every output is bitwise repeatable.  Nothing is read on the host. */
 #define NSKY_TRACE_ALIVE 0
@@ -1175,13 +1178,13 @@ int nsky_sphere_trace_begin(const float* origins, const float* directions, const
                             int64_t R, int32_t K, const float* params, float* state, float* points, nsky_stream_t stream);
 int nsky_sphere_trace_begin_points(const float* starts, const float* directions, int64_t M, int64_t T, int64_t dir_div, const float* params,
                                    float* state, float* points, nsky_stream_t stream);
-int nsky_sphere_trace_step(float* state, const float* sdf, const float* directions, int64_t T, int64_t dir_div, const float* params,
-                           int32_t iteration, int32_t steps, int32_t grace, float* points, nsky_stream_t stream);
+int nsky_sphere_trace_step(float* state, const float* sdf, const float* directions, const float* bounds, int64_t T, int64_t dir_div,
+                           const float* params, int32_t iteration, int32_t steps, int32_t grace, float* points, nsky_stream_t stream);
 int nsky_sphere_trace_finish(const float* state, int64_t T, float* vis, int8_t* status, float* t, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Point and spot lights inside the scene, with sphere-traced shadows (neusky_amd/relight/lights.py, csrc/lights.hip, and the bounded
- * step in csrc/sphere_trace.hip).  Every light above is at infinity; a lamp has a direction and a distance of its own at every sample,
+ * Point and spot lights inside the scene, with sphere-traced shadows (neusky_amd/relight/lights.py, csrc/lights.hip, and the step of
+ * csrc/sphere_trace.hip with bounds).  Every light above is at infinity; a lamp has a direction and a distance of its own at every sample,
  * and its shadow ray ends at the lamp: geometry behind the lamp does not shadow it.
  * A light:
  *   p [3]          position, scene units
@@ -1220,9 +1223,8 @@ int nsky_sphere_trace_finish(const float* state, int64_t T, float* vis, int8_t* 
  *                       [6][T], points [T,3], ray_dirs [T,3], bounds [2][T] (t_end, tan_half), T = L R.  Rule step 1 of iteration 0
  *                       is applied here.
  * nsky_light_trace_begin_points:  starts [M,3]  ->  the same from explicit start points (T = L M).
- * nsky_sphere_trace_step_bounded:  nsky_sphere_trace_step with a direction row of each ray's own (ray_dirs) and bounds.  16-byte
- *                       accesses when T % 4 == 0 and state, sdf, ray_dirs, bounds and points are 16-byte aligned, else 4-byte ones;
- *                       the results are the same.  nsky_sphere_trace_finish ends the march.
+ *                       The march is nsky_sphere_trace_step with ray_dirs as its directions, dir_div = 1 and these bounds;
+ *                       nsky_sphere_trace_finish ends it.
  * nsky_lights_composite:  base [Kb,R,3] with base_stride = 3 R, or [R,3] with base_stride = 0; t [L,R,3]; vis [L,R] or NULL; acc [R];
  *                       acc_threshold [1] (device memory); lights  ->  rgb, lin [Kb,R,3] (lin may be NULL) and, unless NULL, light_lin
  *                       [R,3] and visibility [L,R] (= V).
@@ -1235,8 +1237,6 @@ int nsky_light_trace_begin(const float* origins, const float* directions, const 
                            nsky_stream_t stream);
 int nsky_light_trace_begin_points(const float* starts, const float* lights, int64_t M, int32_t L, const float* params, float* state,
                                   float* points, float* ray_dirs, float* bounds, nsky_stream_t stream);
-int nsky_sphere_trace_step_bounded(float* state, const float* sdf, const float* ray_dirs, const float* bounds, int64_t T, const float* params,
-                                   int32_t iteration, int32_t steps, int32_t grace, float* points, nsky_stream_t stream);
 int nsky_lights_composite(const float* base, int64_t base_stride, const float* t, const float* vis, const float* acc,
                           const float* acc_threshold, const float* lights, int64_t R, int32_t L, int32_t Kb, float* rgb, float* lin,
                           float* light_lin, float* visibility, nsky_stream_t stream);

@@ -8,20 +8,20 @@
 //              up to 8 lights; the factor cosine spot / max(q, min_distance^2) is formed in fp64 (a square root and two divisions per
 //              sample and light) and rounded once; a lane keeps 24 fp32 sums, finished with wave_sum.
 //   begin      one thread per shadow ray i = l R + r: the start point as nsky_sphere_trace_begin forms it, then the ray's own direction,
-//              end and penumbra width in fp64, rounded once.  The march itself is nsky_sphere_trace_step_bounded (csrc/sphere_trace.hip).
+//              end and penumbra width in fp64, rounded once (the start point and the store of the begun ray: csrc/trace.h).  The march
+//              itself is nsky_sphere_trace_step with these bounds (csrc/sphere_trace.hip).
 //   composite  one thread per (ray, channel): the L terms in fp64, l ascending, added to each of the Kb base images with one rounding.
 // No atomics, a fixed reduction order: two runs agree bit for bit.  Flat indices are 64-bit.  Nothing here synchronises with the host.
 #include <algorithm>
 
 #include "numerics.h"
-#include "../../include/neusky_hip.h"
+#include "trace.h"
 
 namespace {
 
 constexpr int kMaxLightsPerPass = 8;
 constexpr int kLightStride = NSKY_LIGHT_FLOATS;
 enum { L_P = 0, L_A = 3, L_COS_INNER = 6, L_COS_OUTER = 7, L_RHO = 8, L_CLEARANCE = 9, L_MIN_DISTANCE = 10, L_I = 12 };
-enum { P_RADIUS = 4, P_BIAS = 5 };  // of the march's parameter block (csrc/sphere_trace.hip)
 
 template <int LB>
 __global__ __launch_bounds__(256) void light_transfer_kernel(const float* __restrict__ positions, const float* __restrict__ albedo,
@@ -110,16 +110,9 @@ __global__ __launch_bounds__(256) void light_begin_kernel(const float* __restric
     const float* q = lights + l * kLightStride;
     const double lx = q[L_P], ly = q[L_P + 1], lz = q[L_P + 2];
     float x = o[r], y = o[r + 1], z = o[r + 2];
-    if (d) {
-      const float t = depth[i - l * R];
-      x = fmaf(t, d[r], x), y = fmaf(t, d[r + 1], y), z = fmaf(t, d[r + 2], z);
-      float nx = n[r], ny = n[r + 1], nz = n[r + 2];
-      const double nn = (double)nx * nx + (double)ny * ny + (double)nz * nz;
-      if (nn > 0.0 && nn < (double)INFINITY) {
-        const double inv = 1.0 / sqrt(nn);
-        nx = (float)(nx * inv), ny = (float)(ny * inv), nz = (float)(nz * inv);
-      } else {  // no rendered normal: lift the point towards the light
-        const double wx = lx - x, wy = ly - y, wz = lz - z;
+    if (d)  // (no rendered normal: the point is lifted towards the lamp)
+      lifted_start(o + r, d + r, depth[i - l * R], n + r, bias, [=](float ux, float uy, float uz, float& nx, float& ny, float& nz) {
+        const double wx = lx - ux, wy = ly - uy, wz = lz - uz;
         const double ww = wx * wx + wy * wy + wz * wz;
         if (ww > 0.0) {
           const double inv = 1.0 / sqrt(ww);
@@ -127,9 +120,7 @@ __global__ __launch_bounds__(256) void light_begin_kernel(const float* __restric
         } else {
           nx = 0.0f, ny = 0.0f, nz = 1.0f;
         }
-      }
-      x = fmaf(bias, nx, x), y = fmaf(bias, ny, y), z = fmaf(bias, nz, z);
-    }
+      }, x, y, z);
     const double vx = lx - x, vy = ly - y, vz = lz - z;
     const double len = sqrt(vx * vx + vy * vy + vz * vz);
     float sx = 0.0f, sy = 0.0f, sz = 1.0f, t_end = 0.0f, tan_half = 0.0f;
@@ -138,15 +129,8 @@ __global__ __launch_bounds__(256) void light_begin_kernel(const float* __restric
       t_end = (float)(len - (double)q[L_CLEARANCE]);
       tan_half = (float)((double)q[L_RHO] / len);
     }
-    state[i] = x;
-    state[T + i] = y;
-    state[2 * T + i] = z;
-    state[3 * T + i] = 0.0f;
-    state[4 * T + i] = 1.0f;
     // rule step 1 of iteration 0, t = 0: the ray is at its light already, or starts beyond the radius
-    const bool leaves = !(0.0f < t_end) || fmaf(z, z, fmaf(y, y, x * x)) >= radius2;
-    reinterpret_cast<int32_t*>(state)[5 * T + i] = leaves ? NSKY_TRACE_ESCAPED : NSKY_TRACE_ALIVE;
-    points[i * 3] = x, points[i * 3 + 1] = y, points[i * 3 + 2] = z;
+    store_begun(state, points, T, i, x, y, z, radius2, !(0.0f < t_end));
     ray_dirs[i * 3] = sx, ray_dirs[i * 3 + 1] = sy, ray_dirs[i * 3 + 2] = sz;
     bounds[i] = t_end;
     bounds[T + i] = tan_half;
@@ -182,8 +166,6 @@ __global__ __launch_bounds__(256) void lights_composite_kernel(const float* __re
     }
   }
 }
-
-unsigned grid_for(int64_t threads) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((threads + 255) / 256, 256 * 8)); }
 
 int launch_begin(const char* name, const float* o, const float* d, const float* depth, const float* n, const float* lights, int64_t R, int32_t L,
                  const float* params, float* state, float* points, float* ray_dirs, float* bounds, nsky_stream_t stream) {

@@ -52,7 +52,7 @@ class GemmDesc(C.Structure):
 
 _lib.nsky_last_error.restype = C.c_char_p
 _lib.nsky_abi_version.restype = C.c_int
-ABI_VERSION = 16  # the ctypes structures below mirror this version of include/neusky_hip.h
+ABI_VERSION = 17  # the ctypes structures below mirror this version of include/neusky_hip.h
 if _lib.nsky_abi_version() != ABI_VERSION:
     raise NeuSkyHipError(f"libneusky_hip.so has ABI version {_lib.nsky_abi_version()}, this package binds version {ABI_VERSION}: rebuild (build.sh)")
 
@@ -1635,14 +1635,16 @@ _sphere_trace_begin = _sig("nsky_sphere_trace_begin", C.c_void_p, C.c_void_p, C.
                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sphere_trace_begin_points = _sig("nsky_sphere_trace_begin_points", C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p)
-_sphere_trace_step = _sig("nsky_sphere_trace_step", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
-                          C.c_int32, C.c_int32, C.c_void_p, C.c_void_p)
+_sphere_trace_step = _sig("nsky_sphere_trace_step", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                          C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p)
 _sphere_trace_finish = _sig("nsky_sphere_trace_finish", C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
 
-def _trace_buffers(T, params, state, points):
+def _trace_buffers(T, params, state, points, ray_dirs=None, bounds=None):
+    """the buffers of a march of T rays; with ray_dirs [T, 3] and bounds [2, T] (t_end, tan_half): of rays that end at a light"""
     assert params.shape == (TRACE_PARAMS,) and state.shape == (6, T) and points.shape == (T, 3)
-    assert all(x.dtype == torch.float32 and x.is_contiguous() for x in (params, state, points))
+    assert (ray_dirs is None) == (bounds is None) and (bounds is None or (ray_dirs.shape == (T, 3) and bounds.shape == (2, T)))
+    assert all(x is None or (x.dtype == torch.float32 and x.is_contiguous()) for x in (params, state, points, ray_dirs, bounds))
 
 
 def sphere_trace_begin(origins, directions, depth, normals, suns, params, state, points):
@@ -1675,14 +1677,18 @@ def trace_dir_div(directions, M: int, T: int) -> int:
     return M
 
 
-def sphere_trace_step(state, sdf, directions, dir_div: int, params, iteration: int, steps: int, grace: int, points):
-    """one round of the march: state [6, T], sdf fp32 [T] at `points`, directions [T / dir_div, 3] -> state, points [T, 3]"""
+def sphere_trace_step(state, sdf, directions, dir_div: int, params, iteration: int, steps: int, grace: int, points, bounds=None):
+    """one round of the march: state [6, T], sdf fp32 [T] at `points`, directions [T / dir_div, 3] -> state, points [T, 3].  bounds
+    [2, T] (t_end, tan_half): the round of rays that end at a light, each with a direction of its own (dir_div 1, directions [T, 3])"""
     T = points.shape[0]
-    _trace_buffers(T, params, state, points)
+    if bounds is not None and not (dir_div == 1 and directions.shape == (T, 3) and bounds.shape == (2, T)):
+        raise NeuSkyHipError(f"sphere_trace_step: bounds [2, {T}] go with dir_div 1 and directions [{T}, 3], got bounds "
+                             f"{tuple(bounds.shape)}, dir_div {dir_div}, directions {tuple(directions.shape)}")
+    _trace_buffers(T, params, state, points, None if bounds is None else directions, bounds)
     assert sdf.dtype == torch.float32 and sdf.numel() == T and directions.dtype == torch.float32
     assert dir_div >= 1 and directions.shape == (-(-T // dir_div), 3) and 0 <= iteration < steps
-    check(_sphere_trace_step(ptr(state), _c(sdf), _c(directions), T, dir_div, ptr(params), iteration, steps, grace, ptr(points), stream_ptr()),
-          "nsky_sphere_trace_step")
+    check(_sphere_trace_step(ptr(state), _c(sdf), _c(directions), ptr(bounds), T, dir_div, ptr(params), iteration, steps, grace, ptr(points),
+                             stream_ptr()), "nsky_sphere_trace_step")
 
 
 def sphere_trace_finish(state, vis, status, t):
@@ -1694,7 +1700,7 @@ def sphere_trace_finish(state, vis, status, t):
     check(_sphere_trace_finish(ptr(state), T, ptr(vis), ptr(status), ptr(t), stream_ptr()), "nsky_sphere_trace_finish")
 
 
-# ---- point and spot lights inside the scene (relight/lights.py, csrc/lights.hip; the bounded step: csrc/sphere_trace.hip)
+# ---- point and spot lights inside the scene (relight/lights.py, csrc/lights.hip; their march: sphere_trace_step with bounds)
 LIGHT_FLOATS = 16  # NSKY_LIGHT_FLOATS: p (0..2), a (3..5), cos_inner, cos_outer, rho, clearance, min_distance, -, I (12..14), -
 _light_transfer = _sig("nsky_light_transfer", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                        C.c_void_p, C.c_void_p)
@@ -1702,8 +1708,6 @@ _light_trace_begin = _sig("nsky_light_trace_begin", C.c_void_p, C.c_void_p, C.c_
                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _light_trace_begin_points = _sig("nsky_light_trace_begin_points", C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
-_sphere_trace_step_bounded = _sig("nsky_sphere_trace_step_bounded", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                  C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p)
 _lights_composite = _sig("nsky_lights_composite", C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                          C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
@@ -1712,12 +1716,6 @@ def _lights_block(lights):
     L = lights.shape[0]
     assert lights.shape == (L, LIGHT_FLOATS) and L >= 1 and lights.dtype == torch.float32 and lights.is_contiguous()
     return L
-
-
-def _light_trace_buffers(T, params, state, points, ray_dirs, bounds):
-    _trace_buffers(T, params, state, points)
-    assert ray_dirs.shape == (T, 3) and bounds.shape == (2, T)
-    assert all(x.dtype == torch.float32 and x.is_contiguous() for x in (ray_dirs, bounds))
 
 
 def light_transfer(positions, albedo, normals, weights, lights, out):
@@ -1736,7 +1734,7 @@ def light_trace_begin(origins, directions, depth, normals, lights, params, state
     R, L = origins.shape[0], _lights_block(lights)
     assert origins.shape == (R, 3) and directions.shape == (R, 3) and normals.shape == (R, 3) and depth.numel() == R
     assert all(x.dtype == torch.float32 for x in (origins, directions, depth, normals))
-    _light_trace_buffers(L * R, params, state, points, ray_dirs, bounds)
+    _trace_buffers(L * R, params, state, points, ray_dirs, bounds)
     check(_light_trace_begin(_c(origins), _c(directions), _c(depth), _c(normals), ptr(lights), R, L, ptr(params), ptr(state), ptr(points),
                              ptr(ray_dirs), ptr(bounds), stream_ptr()), "nsky_light_trace_begin")
 
@@ -1745,19 +1743,9 @@ def light_trace_begin_points(starts, lights, params, state, points, ray_dirs, bo
     """starts: fp32 [M, 3]; lights [L, 16] (every start under every light, ray l M + r) -> state, points, ray_dirs, bounds"""
     M, L = starts.shape[0], _lights_block(lights)
     assert starts.shape == (M, 3) and M >= 1 and starts.dtype == torch.float32
-    _light_trace_buffers(L * M, params, state, points, ray_dirs, bounds)
+    _trace_buffers(L * M, params, state, points, ray_dirs, bounds)
     check(_light_trace_begin_points(_c(starts), ptr(lights), M, L, ptr(params), ptr(state), ptr(points), ptr(ray_dirs), ptr(bounds),
                                     stream_ptr()), "nsky_light_trace_begin_points")
-
-
-def sphere_trace_step_bounded(state, sdf, ray_dirs, bounds, params, iteration: int, steps: int, grace: int, points):
-    """one round of the march of rays that end at a light: state [6, T], sdf fp32 [T] at `points`, ray_dirs [T, 3], bounds [2, T] ->
-    state, points [T, 3]"""
-    T = points.shape[0]
-    _light_trace_buffers(T, params, state, points, ray_dirs, bounds)
-    assert sdf.dtype == torch.float32 and sdf.numel() == T and 0 <= iteration < steps
-    check(_sphere_trace_step_bounded(ptr(state), _c(sdf), ptr(ray_dirs), ptr(bounds), T, ptr(params), iteration, steps, grace, ptr(points),
-                                     stream_ptr()), "nsky_sphere_trace_step_bounded")
 
 
 def lights_composite(base, t, vis, acc, acc_threshold, lights, rgb, lin=None, light_lin=None, visibility=None):

@@ -23,9 +23,11 @@ from ..relight.lights import lights_block, trace_light_shadows
 from ..relight.shadows import trace_params, trace_sun_shadows
 from ..relight.transfer import bake_rows
 
-SUN_KEYS = ("rgb", "lin", "shadow_map", "shadow_difference")
-SDF_SHADOW_KEYS = ("shadow_status",)  # joins them under sun_shadows="sdf"
-LIGHT_KEYS = ("light_lin", "light_visibility")  # of a frame with lights; `light_status` joins them under light_shadows
+# how what lights a chunk travels inside `shade`, the light's index leading: images [Kb, R, 3], one per sun (Kb = 1 for a frame without
+# suns); the suns' maps [K, R]; the lamps' maps [L, R].  Every other output is per ray: [R, ...]
+IMAGES = ("rgb", "lin", "atmosphere_inscatter")
+SUN_MAPS = ("shadow_map", "shadow_difference", "shadow_status")
+LIGHT_MAPS = ("light_visibility", "light_status")
 
 
 # the static buffers of a frame, as FrameRenderer.static keeps them; a member that is none of the entry's own (`data`, `convention`, `scale`,
@@ -114,29 +116,45 @@ def shade(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -
     """what the active frame's shading mode adds to a chunk's outputs: `rgb` under the sky alone; `rgb`, `lin`, `shadow_map` and
     `shadow_difference` with suns, under the frame's sky or a daylight sky of each sun's own; the transfer keys and no `rgb` for a bake
     (no light enters).  A sky frame asked for its linear image adds `lin`: what the renderer's kernel computes beside `rgb` and drops.
-    An atmosphere is applied last, to whatever lit the chunk, and never to a bake."""
-    out = _lit_outputs(model, light, so, ray_bundle)
-    if light.atmosphere is None or light.shading == "bake":
-        return out
-    return _apply_atmosphere(model, light, so, ray_bundle, out)
-
-
-def _lit_outputs(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -> Dict[str, torch.Tensor]:
-    if light.shading == "sky":
-        if light.lights is not None:  # (the lamps add to the linear image: the frame carries it)
-            return _add_lights(model, light.lights, so, ray_bundle, _sky_outputs(model, so), suns=False)
-        return _sky_outputs(model, so) if light.linear or light.atmosphere is not None else {"rgb": model.render_lambertian(so)}
-    if light.shading in ("sun", "daylight"):
+    An atmosphere is applied last, to whatever lit the chunk, and never to a bake.  Between the functions below the outputs travel with
+    the light's index leading; the chunk's own form is made here, once: ray-major views of that storage, [0] for a frame without suns."""
+    if light.shading == "bake":
+        fo = so["field_outputs"]
+        visibility = so["visibility_dict"]["visibility"] if model.config.use_visibility else None
+        return bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], so["weights"][..., 0], so["illumination_directions"],
+                         visibility, light.bake)
+    if light.sun is not None:
         out = _sun_outputs(model, light.sun, so, ray_bundle, light.daylight, light.trace)
-        return out if light.lights is None else _add_lights(model, light.lights, so, ray_bundle, out, suns=True)
-    fo = so["field_outputs"]
-    visibility = so["visibility_dict"]["visibility"] if model.config.use_visibility else None
-    return bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], so["weights"][..., 0], so["illumination_directions"],
-                     visibility, light.bake)
+    elif light.linear or light.lights is not None or light.atmosphere is not None:  # (lamps and fog add to the linear image)
+        out = _sky_outputs(model, so)
+    else:
+        out = {"rgb": model.render_lambertian(so)[None]}
+    if light.lights is not None:
+        out = _add_lights(model, light.lights, so, ray_bundle, out)
+    if light.atmosphere is not None:
+        out = _apply_atmosphere(model, light, so, ray_bundle, out)
+    image = (lambda t: t.permute(1, 0, 2)) if light.sun is not None else (lambda t: t[0])
+    return {k: image(v) if k in IMAGES else v.t() if k in SUN_MAPS + LIGHT_MAPS else v for k, v in out.items()}
+
+
+def chunk_keys(lighting: FrameLighting, linear: bool = False):
+    """(keys, sun_keys): the keys `shade` adds to a chunk of a frame lit by `lighting` (linear: FrameRenderer.begin's), and those of them
+    that carry the K suns: ray-major [n, K, ...] in a chunk, K leading in the frame"""
+    if lighting.bake is not None:
+        return ("transfer", "transfer_acc") + (("transfer_exponents",) if lighting.bake == "fp16" else ()), ()
+    suns, fogged = lighting.suns is not None, lighting.atmosphere is not None
+    keys = ["rgb", "lin"] if suns or linear or lighting.lights or fogged else ["rgb"]  # (lamps and fog add to the linear image)
+    if suns:
+        keys += ["shadow_map", "shadow_difference"] + (["shadow_status"] if lighting.sun_shadows == "sdf" else [])
+    if fogged:
+        keys += ["atmosphere_transmittance", "atmosphere_inscatter"]  # (the inscatter is shaped as `lin`)
+    if lighting.lights:
+        keys += ["light_lin", "light_visibility"] + (["light_status"] if lighting.light_trace is not None else [])
+    return tuple(keys), tuple(k for k in keys if suns and k in IMAGES + SUN_MAPS)
 
 
 def _sky_outputs(model, so: Dict[str, Any]) -> Dict[str, torch.Tensor]:
-    """render_lambertian's kernel on the same inputs, keeping both of its outputs: rgb (the same bits) and lin [R, 3]"""
+    """render_lambertian's kernel on the same inputs, keeping both of its outputs: rgb (the same bits) and lin [1, R, 3]"""
     fo = so["field_outputs"]
     a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
     R, dev = a.shape[0], a.device
@@ -145,19 +163,18 @@ def _sky_outputs(model, so: Dict[str, Any]) -> Dict[str, torch.Tensor]:
                            so["hdr_illumination_colours"].contiguous(), so["cam_of_ray"],
                            so["visibility_dict"]["visibility"].contiguous() if model.config.use_visibility else None,
                            so["hdr_background_colours"].contiguous(), rgb, lin)
-    return {"rgb": rgb, "lin": lin}
+    return {"rgb": rgb[None], "lin": lin[None]}
 
 
 def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundle, daylight: Optional[FrameDaylight] = None,
                  trace: Optional[FrameTrace] = None) -> Dict[str, torch.Tensor]:
     """a chunk lit by its sky and the frame's K suns (include/neusky_hip.h): the hemisphere kernel's linear image, one DDF query per
-    (ray, sun), the sun transfer and the composite.  Ray-major views of the [K, R, ...] results: rgb, lin [R, K, 3], shadow_map,
-    shadow_difference [R, K].
+    (ray, sun), the sun transfer and the composite: rgb, lin [K, R, 3], shadow_map, shadow_difference [K, R].
     Under a daylight sky the linear image is one per sun [K, R, 3]: the chunk's radiance transfer (fp32, in a scratch) relit by the K
     skies at the frame's directions, over the K backgrounds sample_illumination_compact evaluated at the rays.
     With `trace` the K visibilities come from a march through the SDF instead of the DDF (whether or not the model has one), from the
     chunk's rendered depth along the ray and its rendered normal; `shadow_difference`, a DDF quantity, is then zero, and `shadow_status`
-    [R, K] (int8) is the march's own verdict on each shadow ray (relight.shadows: HIT, ESCAPED, EXHAUSTED), before the set-sun and
+    [K, R] (int8) is the march's own verdict on each shadow ray (relight.shadows: HIT, ESCAPED, EXHAUSTED), before the set-sun and
     accumulation rules."""
     fo = so["field_outputs"]
     a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
@@ -193,18 +210,17 @@ def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundl
     composite(lin_sky, t, vis, acc, sun.acc_threshold, sun.dirs, sun.colours, rgb, lin, shadow)
     on = (acc > sun.acc_threshold)[:, None] & (sun.dirs[:, 2] > 0)[None]
     diff = torch.where(on, diff, torch.zeros((), device=dev)) if diff is not None else torch.zeros(R, K, device=dev)
-    out = {"rgb": rgb.permute(1, 0, 2), "lin": lin.permute(1, 0, 2), "shadow_map": shadow.t(), "shadow_difference": diff}
+    out = {"rgb": rgb, "lin": lin, "shadow_map": shadow, "shadow_difference": diff.t()}
     if status is not None:
-        out["shadow_status"] = status.t()
+        out["shadow_status"] = status
     return out
 
 
-def _add_lights(model, lights: FrameLights, so: Dict[str, Any], ray_bundle: RayBundle, out: Dict[str, torch.Tensor],
-                suns: bool) -> Dict[str, torch.Tensor]:
-    """the frame's L lamps on top of a chunk lit by its sky (out: rgb, lin [R, 3]) or by sky and K suns (ray-major views of [K, R, 3]):
-    the lamps' transfer at the samples' positions, a march from each ray's rendered surface point to each lamp (or none), and the
-    composite, which adds the one lamp image to every base image (include/neusky_hip.h).  `rgb` and `lin` are replaced by the lit
-    ones; light_lin [R, 3], light_visibility [R, L] and, with shadows, light_status [R, L] (int8) join them."""
+def _add_lights(model, lights: FrameLights, so: Dict[str, Any], ray_bundle: RayBundle, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """the frame's L lamps on top of a chunk lit by its sky or by sky and K suns (out: rgb, lin [Kb, R, 3]): the lamps' transfer at the
+    samples' positions, a march from each ray's rendered surface point to each lamp (or none), and the composite, which adds the one
+    lamp image to every base image (include/neusky_hip.h).  `rgb` and `lin` are replaced by the lit ones; light_lin [R, 3],
+    light_visibility [L, R] and, with shadows, light_status [L, R] (int8) join them."""
     fo = so["field_outputs"]
     a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
     w = so["weights"][..., 0].contiguous()
@@ -217,28 +233,23 @@ def _add_lights(model, lights: FrameLights, so: Dict[str, Any], ray_bundle: RayB
         march = trace_light_shadows(model.field, ray_bundle.origins, ray_bundle.directions, so["p2p_dist"], so["normal"], lights.block,
                                     lights.params, lights.steps, lights.grace)
         vis, status = march.visibility, march.status
-    base = out["lin"].permute(1, 0, 2).contiguous() if suns else out["lin"]  # [K, R, 3] (the storage _sun_outputs holds) or [R, 3]
-    Kb = base.shape[0] if suns else 1
-    rgb, lin = torch.empty(Kb, R, 3, device=dev), torch.empty(Kb, R, 3, device=dev)
-    light_lin, V = torch.empty(R, 3, device=dev), torch.empty(L, R, device=dev)
+    base = out["lin"]
+    rgb, lin, light_lin, V = torch.empty_like(base), torch.empty_like(base), torch.empty(R, 3, device=dev), torch.empty(L, R, device=dev)
     hip.lights_composite(base, t, vis, so["accumulation"].reshape(-1).contiguous(), lights.acc_threshold, lights.block, rgb, lin, light_lin, V)
-    out = {**out, "rgb": rgb.permute(1, 0, 2) if suns else rgb[0], "lin": lin.permute(1, 0, 2) if suns else lin[0], "light_lin": light_lin,
-           "light_visibility": V.t()}
+    out = {**out, "rgb": rgb, "lin": lin, "light_lin": light_lin, "light_visibility": V}
     if status is not None:
-        out["light_status"] = status.t()
+        out["light_status"] = status
     return out
 
 
 def _apply_atmosphere(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """the frame's medium in front of a lit chunk (include/neusky_hip.h: height fog): out holds rgb, lin [R, 3] or, under K suns, the
-    ray-major views of [K, R, 3], which the kernel reads through their strides.  With shaft samples M the K suns are queried once more
-    at M points along every ray, by the frame's own shadow mode: M R rows through the DDF (with no visibility network: no shadow, as
-    for the surface) or through the march, which lifts a start point with no normal along the sun's direction.  `rgb` and `lin` are
-    replaced by the fogged ones, `light_lin` is scaled in place; atmosphere_transmittance [R, 3] and atmosphere_inscatter (shaped as
-    lin) join them."""
+    """the frame's medium in front of a lit chunk (include/neusky_hip.h: height fog): out holds rgb, lin [Kb, R, 3].  With shaft samples
+    M the K suns are queried once more at M points along every ray, by the frame's own shadow mode: M R rows through the DDF (with no
+    visibility network: no shadow, as for the surface) or through the march, which lifts a start point with no normal along the sun's
+    direction.  `rgb` and `lin` are replaced by the fogged ones, `light_lin` is scaled in place; atmosphere_transmittance [R, 3] and
+    atmosphere_inscatter (shaped as lin) join them."""
     atm, sun = light.atmosphere, light.sun
-    suns = sun is not None
-    lin_in = out["lin"].permute(1, 0, 2) if suns else out["lin"][None]  # [Kb, R, 3]: under suns the storage _sun_outputs holds
+    suns, lin_in = sun is not None, out["lin"]
     Kb, R, dev = lin_in.shape[0], lin_in.shape[1], lin_in.device
     o, d = ray_bundle.origins.detach().contiguous(), ray_bundle.directions.detach().contiguous()
     M, vis = atm.samples, None
@@ -257,9 +268,7 @@ def _apply_atmosphere(model, light: FrameLight, so: Dict[str, Any], ray_bundle: 
     hip.atmosphere_apply(o, d, so["p2p_dist"].detach().reshape(-1).contiguous(), so["accumulation"].reshape(-1).contiguous(), lin_in,
                          so["hdr_background_colours"].contiguous(), atm.abar, sun.dirs if suns else None, sun.colours if suns else None, vis,
                          atm.params, M, lin, rgb, inscatter, transmittance, out.get("light_lin"))
-    ray_major = (lambda t: t.permute(1, 0, 2)) if suns else (lambda t: t[0])
-    return {**out, "rgb": ray_major(rgb), "lin": ray_major(lin), "atmosphere_transmittance": transmittance,
-            "atmosphere_inscatter": ray_major(inscatter)}
+    return {**out, "rgb": rgb, "lin": lin, "atmosphere_transmittance": transmittance, "atmosphere_inscatter": inscatter}
 
 
 class FrameRenderer:
@@ -449,17 +458,8 @@ class FrameRenderer:
         linear = display is not None or antialias is not None
         self.begin(camera_index, lighting, linear=linear)
         suns = lighting.suns
-        sun_keys = list(SUN_KEYS + (SDF_SHADOW_KEYS if lighting.sun_shadows == "sdf" else ())) if suns is not None else []
-        fogged = lighting.atmosphere is not None and lighting.bake is None
-        if fogged and suns is not None:  # (shaped as `lin`: K leads)
-            sun_keys.append("atmosphere_inscatter")
-        keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + sun_keys[1:]
-        if (linear or lighting.lights or fogged) and suns is None:
-            keys.append("lin")
-        if fogged:
-            keys += ["atmosphere_transmittance"] + (["atmosphere_inscatter"] if suns is None else [])
-        if lighting.lights:
-            keys += list(LIGHT_KEYS) + (["light_status"] if lighting.light_trace is not None else [])
+        lit, sun_keys = chunk_keys(lighting, linear)
+        keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + [k for k in lit if k != "rgb"]
         out = {k: [] for k in keys}
         early = to_cpu and antialias is None  # (the second pass resolves on the device: its frame goes to the host afterwards)
         try:

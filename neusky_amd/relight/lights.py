@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 
 from .. import hip
-from .shadows import SHADOW_DEFAULTS, SphereTrace, _sdf_function, trace_params, trace_settings
+from .shadows import SHADOW_DEFAULTS, SphereTrace, _march, _start, trace_params, trace_settings
 
 MAX_LIGHTS = 64
 # the march towards a lamp: the sun's, but the penumbra's width is the lamp's radius over each ray's length, not an angular diameter
@@ -135,22 +135,6 @@ def save_lights(path, lights) -> None:
         json.dump([{k: getattr(x, k) for k in _KEYS if getattr(x, k) is not None} for x in as_lights(lights)], f, indent=1)
 
 
-def _march_to(sdf, state, points, ray_dirs, bounds, params, steps: int, grace: int, shape) -> SphereTrace:
-    """`steps` bounded rounds from a begun state, and the finish (relight.shadows._march with the rays' own directions and ends)"""
-    f = _sdf_function(sdf)
-    with torch.no_grad():
-        for i in range(steps):
-            hip.sphere_trace_step_bounded(state, f(points), ray_dirs, bounds, params, i, steps, grace, points)
-    T, dev = points.shape[0], points.device
-    vis, t, status = torch.empty(T, device=dev), torch.empty(T, device=dev), torch.empty(T, dtype=torch.int8, device=dev)
-    hip.sphere_trace_finish(state, vis, status, t)
-    return SphereTrace(vis.view(shape), status.view(shape), t.view(shape))
-
-
-def _trace_buffers(T: int, dev):
-    return (torch.empty(6, T, device=dev), torch.empty(T, 3, device=dev), torch.empty(T, 3, device=dev), torch.empty(2, T, device=dev))
-
-
 def trace_visibility_to(sdf, origins: torch.Tensor, lights, *, steps: int = 96, eps: float = 1e-3, relax: float = 1.0,
                         min_step: float = 1e-3, grace: int = 16, radius: float = 1.0) -> SphereTrace:
     """March shadow rays from the start points `origins` [M, 3] to each of L lights (PointLight, a sequence of them, or a device block
@@ -158,21 +142,16 @@ def trace_visibility_to(sdf, origins: torch.Tensor, lights, *, steps: int = 96, 
     light and is then ESCAPED, as one that leaves the scene bound is; its penumbra has the tangent radius / distance."""
     p = trace_settings({"steps": steps, "eps": eps, "relax": relax, "min_step": min_step, "grace": grace, "radius": radius},
                        {**LIGHT_TRACE_DEFAULTS, "radius": 1.0})
-    if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape[0] < 1:
-        raise ValueError(f"origins [M, 3], got {tuple(origins.shape)}")
-    origins = origins.detach().to(torch.float32).contiguous()
-    M, dev = origins.shape[0], origins.device
     block = lights.to(torch.float32).contiguous() if torch.is_tensor(lights) else lights_block(lights)
     if block.dim() != 2 or block.shape[1] != hip.LIGHT_FLOATS or not 1 <= block.shape[0] <= MAX_LIGHTS:
         raise ValueError(f"lights: 1 to {MAX_LIGHTS} of them, a block [L, {hip.LIGHT_FLOATS}], got {tuple(block.shape)}")
-    block = block.to(dev)
     L = block.shape[0]
-    if hasattr(sdf, "invalidate_weight_cache"):
-        sdf.invalidate_weight_cache()  # its prepared weights are built once for all rounds, from the parameters as they are now
+    origins, state, points = _start(sdf, origins, lambda M: L * M, f"origins [M, 3], got {tuple(origins.shape)}")
+    dev = origins.device
     params = trace_params({**p, "bias": 0.0}).to(dev)
-    state, points, ray_dirs, bounds = _trace_buffers(L * M, dev)
-    hip.light_trace_begin_points(origins, block, params, state, points, ray_dirs, bounds)
-    return _march_to(sdf, state, points, ray_dirs, bounds, params, p["steps"], p["grace"], (L, M))
+    ray_dirs, bounds = torch.empty_like(points), torch.empty(2, points.shape[0], device=dev)
+    hip.light_trace_begin_points(origins, block.to(dev), params, state, points, ray_dirs, bounds)
+    return _march(sdf, state, points, ray_dirs, 1, params, p["steps"], p["grace"], (L, origins.shape[0]), bounds)
 
 
 def trace_light_shadows(sdf, origins: torch.Tensor, directions: torch.Tensor, depth: torch.Tensor, normals: torch.Tensor,
@@ -182,7 +161,9 @@ def trace_light_shadows(sdf, origins: torch.Tensor, directions: torch.Tensor, de
     the device block of trace_params, whose bias lifts the start point o + depth d along the normal.  Results [L, R].  Nothing is read
     on the host and every shape is static: a captured chunk replays with new lights and a new parameter block."""
     R, L, dev = origins.shape[0], lights.shape[0], origins.device
-    state, points, ray_dirs, bounds = _trace_buffers(L * R, dev)
+    T = L * R
+    state, points, ray_dirs, bounds = (torch.empty(6, T, device=dev), torch.empty(T, 3, device=dev), torch.empty(T, 3, device=dev),
+                                       torch.empty(2, T, device=dev))
     hip.light_trace_begin(origins.detach().contiguous(), directions.detach().contiguous(), depth.detach().reshape(-1).contiguous(),
                           normals.detach().contiguous(), lights, params, state, points, ray_dirs, bounds)
-    return _march_to(sdf, state, points, ray_dirs, bounds, params, steps, grace, (L, R))
+    return _march(sdf, state, points, ray_dirs, 1, params, steps, grace, (L, R), bounds)

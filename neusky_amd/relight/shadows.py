@@ -67,17 +67,27 @@ def _sdf_function(sdf) -> Callable[[torch.Tensor], torch.Tensor]:
     return call
 
 
-def _march(sdf, state, points, directions, dir_div: int, params, steps: int, grace: int, shape) -> SphereTrace:
+def _march(sdf, state, points, directions, dir_div: int, params, steps: int, grace: int, shape, bounds=None) -> SphereTrace:
     """`steps` rounds from a begun state, and the finish.  `points` is one buffer, rewritten by every round: an `sdf` that keeps it must
-    copy it."""
+    copy it.  bounds: of rays that end at a light (relight.lights)."""
     f = _sdf_function(sdf)
     with torch.no_grad():
         for i in range(steps):
-            hip.sphere_trace_step(state, f(points), directions, dir_div, params, i, steps, grace, points)
+            hip.sphere_trace_step(state, f(points), directions, dir_div, params, i, steps, grace, points, bounds)
     T, dev = points.shape[0], points.device
     vis, t, status = torch.empty(T, device=dev), torch.empty(T, device=dev), torch.empty(T, dtype=torch.int8, device=dev)
     hip.sphere_trace_finish(state, vis, status, t)
     return SphereTrace(vis.view(shape), status.view(shape), t.view(shape))
+
+
+def _start(sdf, origins: torch.Tensor, rays: Callable[[int], int], error: str, ok: bool = True):
+    """the start points [M, 3] of a march, checked, as contiguous fp32, and the state and points of its rays(M) rays"""
+    if not ok or origins.dim() != 2 or origins.shape[1] != 3 or origins.shape[0] < 1:
+        raise ValueError(error)
+    if hasattr(sdf, "invalidate_weight_cache"):
+        sdf.invalidate_weight_cache()  # its prepared weights are built once for all rounds, from the parameters as they are now
+    T, dev = rays(origins.shape[0]), origins.device
+    return origins.detach().to(torch.float32).contiguous(), torch.empty(6, T, device=dev), torch.empty(T, 3, device=dev)
 
 
 def trace_visibility(sdf: Union[Callable[[torch.Tensor], torch.Tensor], object], origins: torch.Tensor, directions: torch.Tensor, *,
@@ -92,19 +102,15 @@ def trace_visibility(sdf: Union[Callable[[torch.Tensor], torch.Tensor], object],
     (the model's sphere collider has 1); a ray leaves the march there, and one that starts beyond it escapes at once."""
     p = trace_settings({"steps": steps, "eps": eps, "relax": relax, "min_step": min_step, "grace": grace, "radius": radius,
                         "angular_diameter_deg": angular_diameter_deg}, TRACE_DEFAULTS)
-    if origins.dim() != 2 or origins.shape[1] != 3 or directions.dim() != 2 or directions.shape[1] != 3 or origins.shape[0] < 1:
-        raise ValueError(f"origins [M, 3] and directions [M, 3] or [K, 3], got {tuple(origins.shape)} and {tuple(directions.shape)}")
-    origins, directions = origins.detach().to(torch.float32).contiguous(), directions.detach().to(torch.float32).contiguous()
-    M, K, dev = origins.shape[0], directions.shape[0], origins.device
-    per_ray = K == M
-    T = M if per_ray else K * M
-    if hasattr(sdf, "invalidate_weight_cache"):
-        sdf.invalidate_weight_cache()  # its prepared weights are built once for all rounds, from the parameters as they are now
-    params = trace_params(p).to(dev)
-    state, points = torch.empty(6, T, device=dev), torch.empty(T, 3, device=dev)
+    ok = directions.dim() == 2 and directions.shape[1] == 3
+    K = directions.shape[0] if ok else 0
+    origins, state, points = _start(sdf, origins, lambda M: M if K == M else K * M, "origins [M, 3] and directions [M, 3] or [K, 3], got "
+                                    f"{tuple(origins.shape)} and {tuple(directions.shape)}", ok)
+    M, directions = origins.shape[0], directions.detach().to(torch.float32).contiguous()
+    params = trace_params(p).to(origins.device)
     hip.sphere_trace_begin_points(origins, directions, params, state, points)
-    return _march(sdf, state, points, directions, hip.trace_dir_div(directions, M, T), params, p["steps"], p["grace"],
-                  (M,) if per_ray else (K, M))
+    return _march(sdf, state, points, directions, hip.trace_dir_div(directions, M, points.shape[0]), params, p["steps"], p["grace"],
+                  (M,) if K == M else (K, M))
 
 
 def trace_sun_shadows(sdf, origins: torch.Tensor, directions: torch.Tensor, depth: torch.Tensor, normals: torch.Tensor, suns: torch.Tensor,

@@ -1,12 +1,14 @@
 """The frame render's state (models/frame.py: model.frames): a failure inside a frame leaves none active, the chunk-graph key is a function
-of the frame's parts only, a FrameLighting handed to the owner renders the frame of its keywords, a training forward ignores an active
-frame, and the runner cache evicts as documented.  The fixture is the one
+of the frame's parts only, a FrameLighting handed to the owner renders the frame of its keywords, a chunk carries the keys its lighting
+declares, a training forward ignores an active frame, and the runner cache evicts as documented.  The fixture is the one
 of the frame tests: 13 x 16 rays of one camera at chunk 64, three whole chunks and a padded one."""
 import pytest
 import torch
 
 from util_frames import frame_scene
-from neusky_amd.relight import EnvironmentMap, FrameLighting, bake_transfer, z_rotation
+from neusky_amd.models import neusky_model
+from neusky_amd.models.frame import chunk_keys
+from neusky_amd.relight import Atmosphere, DaylightSky, DisplayTransform, EnvironmentMap, FrameLighting, PointLight, bake_transfer, z_rotation
 from neusky_amd.relight.sun import SunLight
 
 pytestmark = pytest.mark.gpu
@@ -106,6 +108,58 @@ def test_a_frame_lighting_renders_the_frame_of_its_keywords(scene, keywords):
     assert out.keys() == ref.keys()
     for k, v in ref.items():
         assert out[k].dtype == v.dtype and out[k].shape == v.shape and torch.equal(out[k], v), k
+
+
+OTHER = SunLight(250.0, 15.0, (3.0, 2.0, 0.5))
+SKY = DaylightSky(turbidity=3.0, exposure=0.1)
+LAMP = PointLight((0.3, -0.2, 0.6), (2.0, 1.8, 1.5), radius=0.03)
+SDF = {"sun_shadows": "sdf", "shadow_trace": {"steps": 4}}
+FOG = {M: Atmosphere(1.5, scale_height=0.3, shaft_samples=M) for M in (0, 2)}
+# the frame's keywords; `linear` is set by a display transform, as FrameRenderer.render sets it
+LIGHTINGS = {
+    "sky": {},
+    "sky, linear": {"display": DisplayTransform()},
+    "one sun": {"sun": SUN},
+    "two suns, sdf shadows": {"sun": [SUN, OTHER], **SDF},
+    "daylight sweep": {"daylight": SKY, "sun": SKY.sun_path(100.0, 8.0, 190.0, 62.0, 3)},
+    "lamp over the sky": {"lights": LAMP, "light_trace": {"steps": 4}},
+    "lamp without shadows over the sky": {"lights": LAMP, "light_shadows": False},
+    "lamp over a sun": {"sun": SUN, "lights": LAMP, "light_trace": {"steps": 4}},
+    "lamp without shadows over two suns": {"sun": [SUN, OTHER], "lights": [LAMP], "light_shadows": False},
+    "fog": {"atmosphere": FOG[0]},
+    "fog under a sun": {"sun": SUN, "atmosphere": FOG[0]},
+    "shafts under two suns": {"sun": [SUN, OTHER], "atmosphere": FOG[2]},
+    "shafts under sdf shadows": {"sun": [SUN, OTHER], **SDF, "atmosphere": FOG[2]},
+    "bake": {"bake": "fp32"},
+    "bake, fp16": {"bake": "fp16"},
+}
+
+
+@pytest.mark.parametrize("name", LIGHTINGS)
+def test_a_chunk_carries_the_keys_its_lighting_declares(scene, monkeypatch, name):
+    pipe, rb, render = scene
+    kw = dict(LIGHTINGS[name])
+    display = kw.pop("display", None)
+    keys, sun_keys = chunk_keys(FrameLighting.of(**kw), linear=display is not None)
+    real, seen = neusky_model.shade, []
+
+    def shade(*args):
+        out = real(*args)
+        seen.append(sorted(out))
+        return out
+    monkeypatch.setattr(neusky_model, "shade", shade)
+    if "bake" in kw:  # (a bake has no frame to assemble: its rows go to the transfer)
+        bake_transfer(pipe.model, rb, storage=kw["bake"], chunk=CHUNK, use_graph=False, camera_index=1)
+        assert len(seen) == 4 and all(s == sorted(keys) for s in seen) and sun_keys == ()
+        return
+    out = render(use_graph=False, display=display, **kw)
+    assert len(seen) == 4 and all(s == sorted(keys) for s in seen), (seen[0], keys)  # three whole chunks and a padded one
+    assert len(set(keys)) == len(keys) and set(keys) <= set(out) and set(sun_keys) <= set(keys)
+    suns = kw.get("sun")
+    assert bool(sun_keys) == (suns is not None) and (suns is None or {"rgb", "lin", "shadow_map", "shadow_difference"} <= set(sun_keys))
+    lead = (len(suns),) if isinstance(suns, list) else ()  # (a single SunLight drops its K = 1)
+    for k in keys:
+        assert out[k].shape[:-1] == ((*lead, H, W) if k in sun_keys else (H, W)), (k, out[k].shape)
 
 
 def test_training_ignores_an_active_frame(scene):

@@ -111,7 +111,7 @@ def test_one_bounded_step_on_hand_made_states(it, copies):
     before = state.clone()
     points = torch.full((T, 3), 7.0, device=DEV)
     bounds = _dev(np.stack([t_end, tan_half]))
-    hip.sphere_trace_step_bounded(state, _dev(f), _dev(s), bounds, _dev(PARAMS), it, STEPS, GRACE, points)
+    hip.sphere_trace_step(state, _dev(f), _dev(s), 1, _dev(PARAMS), it, STEPS, GRACE, points, bounds)
     torch.cuda.synchronize()
 
     P, d = PARAMS.astype(np.float64), np.float64

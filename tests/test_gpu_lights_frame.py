@@ -86,8 +86,8 @@ def _march_by_hand(m, rb, out, lamps, trace):
                               normal[a:b].contiguous(), block, params, state, points, ray_dirs, bounds)
         with torch.no_grad():
             for i in range(p["steps"]):
-                hip.sphere_trace_step_bounded(state, m.field.get_sdf_at_pos(points).reshape(-1), ray_dirs, bounds, params, i, p["steps"],
-                                              p["grace"], points)
+                hip.sphere_trace_step(state, m.field.get_sdf_at_pos(points).reshape(-1), ray_dirs, 1, params, i, p["steps"], p["grace"],
+                                      points, bounds)
         v, t, s = torch.empty(T, device=DEV), torch.empty(T, device=DEV), torch.empty(T, dtype=torch.int8, device=DEV)
         hip.sphere_trace_finish(state, v, s, t)
         vis.append(v.view(L, b - a))

@@ -1,12 +1,13 @@
 """The sphere-trace kernels (csrc/sphere_trace.hip) and relight.trace_visibility against the float64 restatement of the march rule
 (sphere_trace_cpu.py): one `step` launch on hand-made states, one per branch of the rule, at the scalar and the 16-byte launch shape; the
-whole march through the analytic plane-and-sphere scene at sizes on both sides of the shapes' divide; and the march through a model's
+step given bounds against the step without them, at every edge of its dispatch, and what it refuses; the whole march through the analytic plane-and-sphere scene at sizes on both sides of the shapes' divide; and the march through a model's
 SDF field, whose first points are the rendered surface points lifted along their normals."""
 import numpy as np
 import pytest
 import torch
 
 import sphere_trace_cpu as ST
+import test_gpu_lights as TL  # the hand-made rays of the step with bounds: a direction, a t_end and a tan_half each
 from neusky_amd import hip
 from neusky_amd.relight import shadows
 
@@ -46,15 +47,20 @@ def _hand_made(copies):
     return col(0, np.float32), col(1, np.float32), col(2, np.float32), col(3, np.float32), col(4, np.int32), col(5, np.int32), col(6, np.float32)
 
 
+def _state(x, t, m, status, outside):
+    state = torch.empty(6, x.shape[0], device=DEV)
+    state[:3] = torch.from_numpy(x.T.copy()).to(DEV)
+    state[3], state[4] = torch.from_numpy(t).to(DEV), torch.from_numpy(m).to(DEV)
+    state.view(torch.int32)[5] = torch.from_numpy(status | (outside << 8)).to(DEV)
+    return state
+
+
 @pytest.mark.parametrize("copies", (1, 4), ids=("11 rays: 4-byte accesses", "44 rays: 16-byte accesses"))
 @pytest.mark.parametrize("it", (2, GRACE, STEPS - 1), ids=("in grace", "grace over", "last round"))
 def test_one_step_on_hand_made_states(it, copies):
     x, s, t, m, status, outside, f = _hand_made(copies)
     T = x.shape[0]
-    state = torch.empty(6, T, device=DEV)
-    state[:3] = torch.from_numpy(x.T.copy()).to(DEV)
-    state[3], state[4] = torch.from_numpy(t).to(DEV), torch.from_numpy(m).to(DEV)
-    state.view(torch.int32)[5] = torch.from_numpy(status | (outside << 8)).to(DEV)
+    state = _state(x, t, m, status, outside)
     before = state.clone()
     points = torch.full((T, 3), 7.0, device=DEV)
     params = torch.from_numpy(PARAMS).to(DEV)
@@ -93,6 +99,74 @@ def test_one_step_on_hand_made_states(it, copies):
     # finish: m, t and the status, a ray still marching reported as exhausted
     assert torch.equal(vis.cpu(), got[4]) and torch.equal(t_out.cpu(), got[3])
     assert np.array_equal(st_out.cpu().numpy(), np.where(status2 == ST.ALIVE, ST.EXHAUSTED, status2).astype(np.int8))
+
+
+# ---------------------------------------------------------------------------------------------- one step kernel, with and without bounds
+def _lamp_rays(T):
+    """the first T of the hand-made rays of test_gpu_lights, four times over -> state, sdf, directions [T, 3], bounds [2, T], params"""
+    col = lambda j, dt: np.array([r[j] for r in list(TL.RAYS.values()) * 4][:T], dt)  # noqa: E731
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)  # noqa: E731
+    state = _state(col(0, np.float32), col(2, np.float32), col(3, np.float32), col(4, np.int32), col(5, np.int32))
+    return state, dev(col(6, np.float32)), dev(col(1, np.float32)), dev(np.stack([col(7, np.float32), col(8, np.float32)])), dev(TL.PARAMS)
+
+
+def _step(state, sdf, dirs, bounds, params, it, dir_div=1):
+    """one step on a copy of `state` -> the state and the points it leaves"""
+    state, points = state.clone(), torch.full((state.shape[1], 3), 7.0, device=DEV)
+    hip.sphere_trace_step(state, sdf, dirs, dir_div, params, it, TL.STEPS, TL.GRACE, points, bounds)
+    return state, points
+
+
+def _one_float_in(t):
+    """`t` as a contiguous view that starts 4 bytes into a larger allocation: no 16-byte access may touch it"""
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
+    assert buf.data_ptr() % 16 == 0
+    out = buf[1:1 + t.numel()].view(t.shape)
+    out.copy_(t)
+    assert out.is_contiguous() and out.data_ptr() % 16 == 4
+    return out
+
+
+@pytest.mark.parametrize("T", (11, 44), ids=("11 rays: 4-byte accesses", "44 rays: 16-byte accesses"))
+@pytest.mark.parametrize("it", (2, TL.GRACE, TL.STEPS - 1), ids=("in grace", "grace over", "last round"))
+def test_bounds_that_never_bind_are_the_step_without_them(it, T):
+    """march_ray with t_end = +inf and each ray's tan_half equal to the block's computes the expressions of its unbounded branch"""
+    state, sdf, dirs, _, params = _lamp_rays(T)
+    bounds = torch.stack([torch.full((T,), float("inf"), device=DEV), params[3].expand(T)]).contiguous()
+    with_bounds, without = _step(state, sdf, dirs, bounds, params, it), _step(state, sdf, dirs, None, params, it)
+    assert torch.equal(with_bounds[0], without[0]) and torch.equal(with_bounds[1], without[1])
+    assert not torch.equal(without[0], state) and not (without[1] == 7.0).any()  # (the step ran)
+
+
+@pytest.mark.parametrize("it", (2, TL.STEPS - 1), ids=("in grace", "last round"))
+def test_the_access_width_changes_no_result(it):
+    state, sdf, dirs, bounds, params = _lamp_rays(44)
+    wide = _step(state, sdf, dirs, bounds, params, it)
+    plain = _step(state, sdf, dirs, None, params, it)
+    assert not torch.equal(wide[0], plain[0])  # (these bounds bind)
+    for name, args in (("bounds", (sdf, dirs, _one_float_in(bounds))), ("directions", (sdf, _one_float_in(dirs), bounds)),
+                       ("sdf", (_one_float_in(sdf), dirs, bounds))):
+        got = _step(state, *args, params, it)
+        assert torch.equal(got[0], wide[0]) and torch.equal(got[1], wide[1]), name
+    got = _step(state, _one_float_in(sdf), dirs, None, params, it)
+    assert torch.equal(got[0], plain[0]) and torch.equal(got[1], plain[1])
+    # 43 rays: no group of four; the rays are those of the 44-ray call
+    got = _step(*_lamp_rays(43)[:4], params, it)
+    assert torch.equal(got[0], wide[0][:, :43]) and torch.equal(got[1], wide[1][:43])
+    got = _step(*_lamp_rays(43)[:3], None, params, it)
+    assert torch.equal(got[0], plain[0][:, :43]) and torch.equal(got[1], plain[1][:43])
+
+
+def test_the_step_refuses_bounds_it_cannot_take():
+    state, sdf, dirs, bounds, params = _lamp_rays(44)
+    before, points = state.clone(), torch.full((44, 3), 7.0, device=DEV)
+    for d, dir_div, b in ((dirs[:22].contiguous(), 2, bounds),  # rays that share a direction
+                          (dirs, 1, bounds.t().contiguous()),  # bounds [T, 2]
+                          (dirs[:4].contiguous(), 1, bounds)):  # directions [K, 3]
+        with pytest.raises(hip.NeuSkyHipError):
+            hip.sphere_trace_step(state, sdf, d, dir_div, params, 2, TL.STEPS, TL.GRACE, points, b)
+    torch.cuda.synchronize()
+    assert torch.equal(state, before) and (points == 7.0).all()  # nothing was launched
 
 
 # ---------------------------------------------------------------------------------------------- the whole march, analytic scene

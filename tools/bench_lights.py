@@ -99,7 +99,7 @@ def kernels(iters, inner, counts, R=4096, S=96):
         against_a_copy("light_trace_begin", begin, R * 40 + T * (36 + 20), iters, inner, R=R, L=L)
         begin()
         bounds[0].fill_(1e30)  # (no ray reaches its lamp during the timed rounds)
-        step = lambda: hip.sphere_trace_step_bounded(state, sdf, ray_dirs, bounds, params, 20, 1 << 30, 16, points)  # noqa: E731
+        step = lambda: hip.sphere_trace_step(state, sdf, ray_dirs, 1, params, 20, 1 << 30, 16, points, bounds)  # noqa: E731
         sb = against_a_copy("sphere_trace_step_bounded", step, T * (28 + 20 + 24), iters, inner, T=T)
         hip.sphere_trace_begin(o, d, depth, n, suns, params, state, points)
         plain = lambda: hip.sphere_trace_step(state, sdf, suns, R, params, 20, 1 << 30, 16, points)  # noqa: E731
