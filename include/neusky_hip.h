@@ -27,7 +27,7 @@ extern "C" {
 typedef void* nsky_stream_t; /* hipStream_t */
 
 const char* nsky_last_error(void);
-int nsky_abi_version(void); /* 17 (bumped when a struct layout or an entry point's signature changes) */
+int nsky_abi_version(void); /* 18 (bumped when a struct layout or an entry point's signature changes) */
 
 /* ------------------------------------------------------------------------------------------
  * Dense layer on the matrix cores: C[M,N] = epilogue( sum_k A(m,k) * B(n,k) + bias[n] )
@@ -1074,15 +1074,17 @@ int nsky_transfer_relight_short(const void* C, int32_t storage, const int32_t* e
  * nsky_sun_transfer:  albedo, normals [R,S,3]; weights [R,S]; suns [K,3]  ->  out [K,R,3].  One wave per ray, the samples read once
  *                     per pass of up to 8 suns; any S >= 1, any K.  The cosine is taken in fp64 and the sums in fp32: an entry is within
  *                     (3 + S / 64 + 6) 2^-24 sum_s |weights albedo| of its definition.
- * nsky_sun_composite: lin_sky [R,3]; t [K,R,3]; vis [K,R] or NULL; acc [R]; acc_threshold [1] (device memory: a captured graph
- *                     reads a new threshold on replay); suns, colours [K,3]  ->  rgb [K,R,3] and, unless NULL, lin [K,R,3] (the sum in
- *                     fp64, rounded once) and shadow [K,R] (= V).
+ * nsky_sun_composite: lin_sky [R,3] with sky_stride 0, one sky under all K suns, or [K,R,3] with sky_stride 3 R, a sky of each sun's
+ *                     own (the daylight model below): lin[k,r,c] = lin_sky[k,r,c] + C[k,c] V[k,r] t[k,r,c], and K copies of one sky
+ *                     give the one sky's results bit for bit; t [K,R,3]; vis [K,R] or NULL; acc [R]; acc_threshold [1] (device
+ *                     memory: a captured graph reads a new threshold on replay); suns, colours [K,3]  ->  rgb [K,R,3] and, unless
+ *                     NULL, lin [K,R,3] (the sum in fp64, rounded once) and shadow [K,R] (= V).
  * Flat indices are int64.  No atomics and a fixed reduction order: every output is bitwise repeatable.  Nothing is read on the host. */
 int nsky_sun_transfer(const float* albedo, const float* normals, const float* weights, const float* suns, int64_t R, int32_t S, int32_t K,
                       float* out, nsky_stream_t stream);
-int nsky_sun_composite(const float* lin_sky, const float* t, const float* vis, const float* acc, const float* acc_threshold,
-                       const float* suns, const float* colours, int64_t R, int32_t K, float* rgb, float* lin, float* shadow,
-                       nsky_stream_t stream);
+int nsky_sun_composite(const float* lin_sky, int64_t sky_stride, const float* t, const float* vis, const float* acc,
+                       const float* acc_threshold, const float* suns, const float* colours, int64_t R, int32_t K, float* rgb, float* lin,
+                       float* shadow, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * A clear-sky daylight model whose sky follows the sun (neusky_amd/relight/daylight.py, csrc/daylight.hip): Preetham, Shirley, Smits,
@@ -1114,15 +1116,10 @@ int nsky_sun_composite(const float* lin_sky, const float* t, const float* vis, c
  *                     (zenith values over F0) are worked out once per sun and workgroup in fp64 and kept in LDS, up to 256 suns per
  *                     launch; a thread owns a direction, reads it once, forms 1 + A a in fp64 and walks the suns in fp32; each
  *                     sun's row is written with coalesced stores.
- * nsky_sun_composite_skies: nsky_sun_composite with lin_skies [K,R,3], a sky of each sun's own:
- *                     lin[k,r,c] = lin_skies[k,r,c] + C[k,c] V[k,r] t[k,r,c].  The same device code with a stride between the skies;
- *                     K copies of one sky give nsky_sun_composite's results bit for bit.
+ *                     Its K skies meet their suns in nsky_sun_composite with sky_stride 3 N.
  * Flat indices are int64.  No atomics: every output is bitwise repeatable.  Nothing is read on the host. */
 int nsky_daylight_eval(const float* directions, const float* suns, const float* turbidity, const float* exposure, const float* ground,
                        int64_t N, int32_t K, float* out, nsky_stream_t stream);
-int nsky_sun_composite_skies(const float* lin_skies, const float* t, const float* vis, const float* acc, const float* acc_threshold,
-                             const float* suns, const float* colours, int64_t R, int32_t K, float* rgb, float* lin, float* shadow,
-                             nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Sphere-traced shadow rays through the SDF, with penumbrae (neusky_amd/relight/shadows.py, csrc/sphere_trace.hip): the sun's shadow

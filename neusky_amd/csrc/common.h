@@ -28,6 +28,9 @@ void nsky_set_error(const char* fmt, ...);
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
+// a grid of n workgroups, capped at per_cu for each of the 256 CUs (the kernels stride over what is left); never empty
+static inline unsigned capped_grid(int64_t n, int per_cu) { return (unsigned)(n < 1 ? 1 : n < 256 * (int64_t)per_cu ? n : 256 * (int64_t)per_cu); }
+
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

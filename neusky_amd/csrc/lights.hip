@@ -4,98 +4,57 @@
 //   t[l,r,c]   = sum_s w[r,s] alb[r,s,c] clamp(n[r,s].u, 0, 1) spot(-u.a_l) / max(|p_l - x[r,s]|^2, min_distance_l^2),  u = (p_l - x) / |p_l - x|
 //   lin[k,r,c] = base[k,r,c] + sum_l I[l,c] V[l,r] t[l,r,c]
 //   lights     fp32 [L][16] in device memory: p (0..2), a (3..5), cos_inner, cos_outer, rho, clearance, min_distance, -, I (12..14), -
-//   transfer   nsky_sun_transfer's shape: one wave per ray, lanes stride the samples, a sample (40 bytes) is read once per pass and meets
+//   transfer   nsky_sun_transfer's kernel (ray_transfer_kernel, csrc/light_pass.h): a sample (40 bytes) is read once per pass and meets
 //              up to 8 lights; the factor cosine spot / max(q, min_distance^2) is formed in fp64 (a square root and two divisions per
-//              sample and light) and rounded once; a lane keeps 24 fp32 sums, finished with wave_sum.
+//              sample and light) and rounded once.
 //   begin      one thread per shadow ray i = l R + r: the start point as nsky_sphere_trace_begin forms it, then the ray's own direction,
 //              end and penumbra width in fp64, rounded once (the start point and the store of the begun ray: csrc/trace.h).  The march
 //              itself is nsky_sphere_trace_step with these bounds (csrc/sphere_trace.hip).
 //   composite  one thread per (ray, channel): the L terms in fp64, l ascending, added to each of the Kb base images with one rounding.
 // No atomics, a fixed reduction order: two runs agree bit for bit.  Flat indices are 64-bit.  Nothing here synchronises with the host.
-#include <algorithm>
-
+#include "light_pass.h"
 #include "numerics.h"
 #include "trace.h"
 
 namespace {
 
-constexpr int kMaxLightsPerPass = 8;
 constexpr int kLightStride = NSKY_LIGHT_FLOATS;
 enum { L_P = 0, L_A = 3, L_COS_INNER = 6, L_COS_OUTER = 7, L_RHO = 8, L_CLEARANCE = 9, L_MIN_DISTANCE = 10, L_I = 12 };
 
-template <int LB>
-__global__ __launch_bounds__(256) void light_transfer_kernel(const float* __restrict__ positions, const float* __restrict__ albedo,
-                                                             const float* __restrict__ normals, const float* __restrict__ weights,
-                                                             const float* __restrict__ lights, int64_t R, int S, float* __restrict__ out) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double px[LB], py[LB], pz[LB], ax[LB], ay[LB], az[LB], ci[LB], co[LB], md2[LB];  // (uniform)
-#pragma unroll
-  for (int l = 0; l < LB; ++l) {
-    const float* q = lights + l * kLightStride;
-    px[l] = q[L_P], py[l] = q[L_P + 1], pz[l] = q[L_P + 2];
-    ax[l] = q[L_A], ay[l] = q[L_A + 1], az[l] = q[L_A + 2];
-    ci[l] = q[L_COS_INNER], co[l] = q[L_COS_OUTER];
-    md2[l] = (double)q[L_MIN_DISTANCE] * (double)q[L_MIN_DISTANCE];
+// a lamp of the per-ray transfer sum (csrc/light_pass.h): cosine spot / max(q, min_distance^2) towards the lamp from the sample at x
+struct Lamp {
+  static constexpr int kFloats = kLightStride;
+  static constexpr bool kPositions = true;
+  double px, py, pz, ax, ay, az, ci, co, md2;
+  __device__ __forceinline__ void load(const float* q) {
+    px = q[L_P], py = q[L_P + 1], pz = q[L_P + 2];
+    ax = q[L_A], ay = q[L_A + 1], az = q[L_A + 2];
+    ci = q[L_COS_INNER], co = q[L_COS_OUTER];
+    md2 = (double)q[L_MIN_DISTANCE] * (double)q[L_MIN_DISTANCE];
   }
-  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < R; r += (int64_t)gridDim.x * 4) {
-    float a[LB][3];
-#pragma unroll
-    for (int l = 0; l < LB; ++l) a[l][0] = a[l][1] = a[l][2] = 0.0f;
-    for (int s = lane; s < S; s += 64) {
-      const int64_t i = r * S + s, o = i * 3;
-      const float w = weights[i];
-      const float g0 = w * albedo[o], g1 = w * albedo[o + 1], g2 = w * albedo[o + 2];
-      const double nx = normals[o], ny = normals[o + 1], nz = normals[o + 2];
-      const double x = positions[o], y = positions[o + 1], z = positions[o + 2];
-#pragma unroll
-      for (int l = 0; l < LB; ++l) {
-        const double vx = px[l] - x, vy = py[l] - y, vz = pz[l] - z;
-        const double q = fma(vz, vz, fma(vy, vy, vx * vx));
-        float factor = 0.0f;
-        if (q > 0.0) {
-          const double inv = 1.0 / sqrt(q);
-          const double ux = vx * inv, uy = vy * inv, uz = vz * inv;
-          const double cosine = fmin(fmax(fma(nz, uz, fma(ny, uy, nx * ux)), 0.0), 1.0);
-          const double c = -fma(uz, az[l], fma(uy, ay[l], ux * ax[l]));
-          double spot = 1.0;
-          if (!(c >= ci[l])) {
-            if (c <= co[l]) {
-              spot = 0.0;
-            } else {
-              const double h = (c - co[l]) / (ci[l] - co[l]);
-              spot = h * h * (3.0 - 2.0 * h);
-            }
-          }
-          factor = (float)(cosine * spot / fmax(q, md2[l]));
+  __device__ __forceinline__ float factor(double nx, double ny, double nz, double x, double y, double z) const {
+    const double vx = px - x, vy = py - y, vz = pz - z;
+    const double q = fma(vz, vz, fma(vy, vy, vx * vx));
+    float factor = 0.0f;
+    if (q > 0.0) {
+      const double inv = 1.0 / sqrt(q);
+      const double ux = vx * inv, uy = vy * inv, uz = vz * inv;
+      const double cosine = fmin(fmax(fma(nz, uz, fma(ny, uy, nx * ux)), 0.0), 1.0);
+      const double c = -fma(uz, az, fma(uy, ay, ux * ax));
+      double spot = 1.0;
+      if (!(c >= ci)) {
+        if (c <= co) {
+          spot = 0.0;
+        } else {
+          const double h = (c - co) / (ci - co);
+          spot = h * h * (3.0 - 2.0 * h);
         }
-        a[l][0] = fmaf(g0, factor, a[l][0]);
-        a[l][1] = fmaf(g1, factor, a[l][1]);
-        a[l][2] = fmaf(g2, factor, a[l][2]);
       }
+      factor = (float)(cosine * spot / fmax(q, md2));
     }
-#pragma unroll
-    for (int l = 0; l < LB; ++l) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) a[l][c] = wave_sum(a[l][c]);
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int l = 0; l < LB; ++l) {
-        const int64_t o = ((int64_t)l * R + r) * 3;
-        out[o] = a[l][0];
-        out[o + 1] = a[l][1];
-        out[o + 2] = a[l][2];
-      }
-    }
+    return factor;
   }
-}
-
-template <int LB>
-void launch_transfer(hipStream_t st, const float* positions, const float* albedo, const float* normals, const float* weights,
-                     const float* lights, int64_t R, int S, float* out) {
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((R + 3) / 4, 256 * 8));
-  hipLaunchKernelGGL((light_transfer_kernel<LB>), dim3(grid), dim3(256), 0, st, positions, albedo, normals, weights, lights, R, S, out);
-}
+};
 
 // o, d, n [R][3] and depth [R] (d, depth, n all NULL: o holds the start points); ray i = l R + r
 __global__ __launch_bounds__(256) void light_begin_kernel(const float* __restrict__ o, const float* __restrict__ d,
@@ -188,23 +147,7 @@ extern "C" int nsky_light_transfer(const float* positions, const float* albedo, 
   if (R == 0 || L == 0) return NSKY_OK;
   NSKY_CHECK_ARG(positions && albedo && normals && weights && lights && out,
                  "nsky_light_transfer: NULL positions / albedo / normals / weights / lights / out");
-  hipStream_t st = (hipStream_t)stream;
-  for (int l0 = 0; l0 < L; l0 += kMaxLightsPerPass) {
-    const float* q = lights + (int64_t)l0 * kLightStride;
-    float* o = out + (int64_t)l0 * R * 3;
-    switch (std::min(kMaxLightsPerPass, L - l0)) {
-      case 1: launch_transfer<1>(st, positions, albedo, normals, weights, q, R, S, o); break;
-      case 2: launch_transfer<2>(st, positions, albedo, normals, weights, q, R, S, o); break;
-      case 3: launch_transfer<3>(st, positions, albedo, normals, weights, q, R, S, o); break;
-      case 4: launch_transfer<4>(st, positions, albedo, normals, weights, q, R, S, o); break;
-      case 5: launch_transfer<5>(st, positions, albedo, normals, weights, q, R, S, o); break;
-      case 6: launch_transfer<6>(st, positions, albedo, normals, weights, q, R, S, o); break;
-      case 7: launch_transfer<7>(st, positions, albedo, normals, weights, q, R, S, o); break;
-      default: launch_transfer<8>(st, positions, albedo, normals, weights, q, R, S, o); break;
-    }
-    NSKY_CHECK_LAUNCH("nsky_light_transfer");
-  }
-  return NSKY_OK;
+  return launch_ray_transfer<Lamp>("nsky_light_transfer", positions, albedo, normals, weights, lights, R, S, L, out, (hipStream_t)stream);
 }
 
 extern "C" int nsky_light_trace_begin(const float* origins, const float* directions, const float* depth, const float* normals,

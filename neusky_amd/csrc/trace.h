@@ -14,7 +14,7 @@ enum { S_X = 0, S_Y, S_Z, S_T, S_M, S_FLAGS };  // the state's planes
 constexpr int kOutside = 0x100, kStatusMask = 0xff;
 enum { P_EPS = 0, P_RELAX, P_MIN_STEP, P_TAN_HALF, P_RADIUS, P_BIAS };
 
-static inline unsigned grid_for(int64_t threads) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((threads + 255) / 256, 256 * 8)); }
+static inline unsigned grid_for(int64_t threads) { return capped_grid((threads + 255) / 256, 8); }
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

@@ -11,11 +11,11 @@
 //            each LDS read of a light shared by the 4 rows; fp32 accumulation; one fixed butterfly reduces every sum of the wave.
 // No atomics: every output is a pure function of the inputs, so two runs agree bit for bit.  Flat indices are 64-bit.  Nothing
 // here synchronises with the host.
-#include <hip/hip_fp16.h>
-
 #include <algorithm>
 
+#include "light_pass.h"
 #include "numerics.h"
+#include "transfer_rows.h"
 #include "../../include/neusky_hip.h"
 
 namespace {
@@ -114,11 +114,7 @@ __global__ __launch_bounds__(256) void transfer_bake_kernel(const float* __restr
     if (lane == 0) red[wave] = mx;
     __syncthreads();
     mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-    // row maximum = m 2^x with m in [0.5, 1): the stored row is T 2^(-x), a power-of-two scale (exact); a zero (or non-finite) maximum takes 0
-    if (mx > 0.0 && mx < (double)__builtin_inff()) {
-      frexp(mx, &ex);
-      ex = -ex;
-    }
+    ex = row_exponent(mx);
   }
   if (threadIdx.x == 0) {
     acc[r] = (float)(((redw[0] + redw[1]) + redw[2]) + redw[3]);
@@ -156,26 +152,6 @@ __global__ __launch_bounds__(256) void transfer_bake_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------ relight
-template <bool HALF>
-struct TVec;
-template <>
-struct TVec<false> {
-  static constexpr int kElems = 4;
-  float4 raw;
-  __device__ __forceinline__ void load(const void* T, int64_t elem) { raw = *(const float4*)((const float*)T + elem); }
-  __device__ __forceinline__ float get(int e) const { return e == 0 ? raw.x : e == 1 ? raw.y : e == 2 ? raw.z : raw.w; }
-};
-template <>
-struct TVec<true> {
-  static constexpr int kElems = 8;
-  uint4 raw;
-  __device__ __forceinline__ void load(const void* T, int64_t elem) { raw = *(const uint4*)((const __half*)T + elem); }
-  __device__ __forceinline__ float get(int e) const {
-    const unsigned w = e < 2 ? raw.x : e < 4 ? raw.y : e < 6 ? raw.z : raw.w;
-    return __half2float(__ushort_as_half((unsigned short)((e & 1) ? (w >> 16) : (w & 0xffffu))));
-  }
-};
-
 // Sum each of the NV values of a lane over the 64 lanes with the fewest exchanges: while the count is even, a lane hands half of its
 // values to its partner and keeps the other half (so the count halves with the stride doubling); the rest is a plain butterfly.
 // Afterwards lane l < 2^h holds, in slot i, the total of value i + first(l), where h is the number of halvings.
@@ -216,7 +192,7 @@ __global__ __launch_bounds__(256) void transfer_relight_kernel(const void* __res
                                                                const float* __restrict__ acc, const float* __restrict__ lights,
                                                                const float* __restrict__ bg, int64_t R, int D, float* __restrict__ rgb,
                                                                float* __restrict__ lin) {
-  using Vec = TVec<HALF>;
+  using Vec = RowVec<HALF>;
   constexpr int VE = Vec::kElems;
   constexpr int P = kRowsPerWave;
   extern __shared__ __attribute__((aligned(16))) float sL[];  // [KB][N]
@@ -317,7 +293,7 @@ __global__ __launch_bounds__(256) void transfer_relight_any_kernel(const void* _
         for (int q = 0; q < 3; ++q) {
           const int j = i + 64 * q;
           if (j < N) {
-            const float t = HALF ? __half2float(((const __half*)T)[r * N + j]) : ((const float*)T)[r * N + j];
+            const float t = row_element<HALF>(T, r * N + j);
             a[q] = fmaf(t, lights[(int64_t)k * N + j], a[q]);
           }
         }
@@ -340,30 +316,7 @@ __global__ __launch_bounds__(256) void transfer_relight_any_kernel(const void* _
   }
 }
 
-template <int NQ>
-void launch_bake(bool half, hipStream_t st, const float* albedo, const float* normals, const float* weights, const float* dirs,
-                 const float* vis, int R, int S, int D, void* T, int64_t row0, int* exps, float* acc) {
-  if (half)
-    hipLaunchKernelGGL((transfer_bake_kernel<NQ, true>), dim3(R), dim3(256), 0, st, albedo, normals, weights, dirs, vis, R, S, D, T, row0,
-                       exps, acc);
-  else
-    hipLaunchKernelGGL((transfer_bake_kernel<NQ, false>), dim3(R), dim3(256), 0, st, albedo, normals, weights, dirs, vis, R, S, D, T, row0,
-                       exps, acc);
-}
-
 int workgroups_per_cu(size_t lds) { return lds == 0 ? 4 : (int)std::min<size_t>(4, (160 * 1024) / lds); }
-
-template <int KB>
-void launch_relight(bool half, hipStream_t st, const void* T, const int* exps, const float* acc, const float* lights, const float* bg,
-                    int64_t R, int D, float* rgb, float* lin) {
-  const size_t lds = (size_t)KB * D * 3 * sizeof(float);
-  const int64_t units = (R + kRowsPerWave - 1) / kRowsPerWave;
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((units + 3) / 4, 256 * workgroups_per_cu(lds)));
-  if (half)
-    hipLaunchKernelGGL((transfer_relight_kernel<KB, true>), dim3(grid), dim3(256), lds, st, T, exps, acc, lights, bg, R, D, rgb, lin);
-  else
-    hipLaunchKernelGGL((transfer_relight_kernel<KB, false>), dim3(grid), dim3(256), lds, st, T, exps, acc, lights, bg, R, D, rgb, lin);
-}
 
 }  // namespace
 
@@ -377,15 +330,15 @@ extern "C" int nsky_transfer_bake(const float* albedo, const float* normals, con
   NSKY_CHECK_ARG(albedo && normals && weights && dirs && T && acc, "nsky_transfer_bake: NULL albedo / normals / weights / dirs / T / acc");
   const bool half = storage == NSKY_TRANSFER_FP16;
   NSKY_CHECK_ARG(!half || exponents, "nsky_transfer_bake: fp16 storage needs the row exponents");
-  const int nq = (D + 63) / 64;
   hipStream_t st = (hipStream_t)stream;
-  if (nq <= 1) launch_bake<1>(half, st, albedo, normals, weights, dirs, vis, R, S, D, T, row0, exponents, acc);
-  else if (nq <= 2) launch_bake<2>(half, st, albedo, normals, weights, dirs, vis, R, S, D, T, row0, exponents, acc);
-  else if (nq <= 4) launch_bake<4>(half, st, albedo, normals, weights, dirs, vis, R, S, D, T, row0, exponents, acc);
-  else if (nq <= 8) launch_bake<8>(half, st, albedo, normals, weights, dirs, vis, R, S, D, T, row0, exponents, acc);
-  else launch_bake<16>(half, st, albedo, normals, weights, dirs, vis, R, S, D, T, row0, exponents, acc);
-  NSKY_CHECK_LAUNCH("nsky_transfer_bake");
-  return NSKY_OK;
+  return with_count<1, 2, 4, 8, 16>((D + 63) / 64, [&](auto nq) {
+    return with_storage(half, [&](auto h) {
+      hipLaunchKernelGGL((transfer_bake_kernel<decltype(nq)::value, decltype(h)::value>), dim3(R), dim3(256), 0, st, albedo, normals, weights,
+                         dirs, vis, R, S, D, T, row0, exponents, acc);
+      NSKY_CHECK_LAUNCH("nsky_transfer_bake");
+      return NSKY_OK;
+    });
+  });
 }
 
 extern "C" int nsky_transfer_relight(const void* T, int32_t storage, const int32_t* exponents, const float* acc, const float* lights,
@@ -399,36 +352,24 @@ extern "C" int nsky_transfer_relight(const void* T, int32_t storage, const int32
   NSKY_CHECK_ARG(!half || exponents, "nsky_transfer_relight: fp16 storage needs the row exponents");
   hipStream_t st = (hipStream_t)stream;
   const int64_t N = (int64_t)D * 3;
-  if (D % (half ? 8 : 4) != 0) {
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((R + 3) / 4, 256 * 8));
-    if (half)
-      hipLaunchKernelGGL((transfer_relight_any_kernel<true>), dim3(grid), dim3(256), 0, st, T, exponents, acc, lights, bg, R, (int)D, (int)K,
-                         rgb, lin);
-    else
-      hipLaunchKernelGGL((transfer_relight_any_kernel<false>), dim3(grid), dim3(256), 0, st, T, exponents, acc, lights, bg, R, (int)D,
-                         (int)K, rgb, lin);
-    NSKY_CHECK_LAUNCH("nsky_transfer_relight");
-    return NSKY_OK;
-  }
+  if (D % (half ? 8 : 4) != 0)
+    return with_storage(half, [&](auto h) {
+      hipLaunchKernelGGL((transfer_relight_any_kernel<decltype(h)::value>), dim3(capped_grid((R + 3) / 4, 8)), dim3(256), 0, st, T, exponents, acc,
+                         lights, bg, R, (int)D, (int)K, rgb, lin);
+      NSKY_CHECK_LAUNCH("nsky_transfer_relight");
+      return NSKY_OK;
+    });
   // the lights of one pass share the workgroup's LDS: up to 8, fewer when D is large; T is read once per pass
   const int per_pass = (int)std::min<int64_t>(kMaxLightsPerPass, kLdsBudget / (N * (int64_t)sizeof(float)));
-  for (int k0 = 0; k0 < K; k0 += per_pass) {
-    const int kb = std::min(per_pass, K - k0);
-    const float* l = lights + k0 * N;
-    const float* b = bg + (int64_t)k0 * R * 3;
-    float* o = rgb + (int64_t)k0 * R * 3;
-    float* ol = lin ? lin + (int64_t)k0 * R * 3 : nullptr;
-    switch (kb) {
-      case 1: launch_relight<1>(half, st, T, exponents, acc, l, b, R, D, o, ol); break;
-      case 2: launch_relight<2>(half, st, T, exponents, acc, l, b, R, D, o, ol); break;
-      case 3: launch_relight<3>(half, st, T, exponents, acc, l, b, R, D, o, ol); break;
-      case 4: launch_relight<4>(half, st, T, exponents, acc, l, b, R, D, o, ol); break;
-      case 5: launch_relight<5>(half, st, T, exponents, acc, l, b, R, D, o, ol); break;
-      case 6: launch_relight<6>(half, st, T, exponents, acc, l, b, R, D, o, ol); break;
-      case 7: launch_relight<7>(half, st, T, exponents, acc, l, b, R, D, o, ol); break;
-      default: launch_relight<8>(half, st, T, exponents, acc, l, b, R, D, o, ol); break;
-    }
-    NSKY_CHECK_LAUNCH("nsky_transfer_relight");
-  }
-  return NSKY_OK;
+  const int64_t units = (R + kRowsPerWave - 1) / kRowsPerWave;
+  return for_each_pass<kMaxLightsPerPass>(K, [&](int k0, auto kb) {
+    const size_t lds = (size_t)kb * D * 3 * sizeof(float);
+    const int64_t o = (int64_t)k0 * R * 3;
+    return with_storage(half, [&](auto h) {
+      hipLaunchKernelGGL((transfer_relight_kernel<decltype(kb)::value, decltype(h)::value>), dim3(capped_grid((units + 3) / 4, workgroups_per_cu(lds))),
+                         dim3(256), lds, st, T, exponents, acc, lights + k0 * N, bg + o, R, D, rgb + o, lin ? lin + o : nullptr);
+      NSKY_CHECK_LAUNCH("nsky_transfer_relight");
+      return NSKY_OK;
+    });
+  }, per_pass);
 }

@@ -14,11 +14,11 @@
 //                  doubles.  The sums are fp64 (the products are exact), folded over the lanes of the row, and leave through LDS: a
 //                  light's rows of the tile are consecutive in bg, lin and rgb, read and written as whole lines, rounded once.
 // No atomics and a fixed order everywhere: two runs agree bit for bit.  Flat indices are 64-bit.  Nothing synchronises with the host.
-#include <hip/hip_fp16.h>
-
 #include <algorithm>
 
+#include "light_pass.h"
 #include "numerics.h"
+#include "transfer_rows.h"
 #include "../../include/neusky_hip.h"
 
 namespace {
@@ -32,18 +32,6 @@ constexpr int kDirBlock = 16;                // directions per block: 48 floats 
 constexpr int kBlockElems = kDirBlock * 3;   // 12 groups of 4
 constexpr int kTileStride = 52;              // dwords between the rows of the LDS tile: 4 x an odd number, so that the 16 lanes a 16-byte
                                              // read serves together (16 rows, all different mod 16) meet 64 different banks
-
-__device__ __forceinline__ float half_bits_to_float(unsigned short h) { return __half2float(__ushort_as_half(h)); }
-
-// the scale of pack_fp16: mx = m 2^x with m in [0.5, 1) -> -x; a zero or non-finite maximum takes 0
-__device__ __forceinline__ int row_exponent(float mx) {
-  int ex = 0;
-  if (mx > 0.0f && mx < __builtin_inff()) {
-    frexpf(mx, &ex);
-    ex = -ex;
-  }
-  return ex;
-}
 
 template <int JT, bool HALF>
 __global__ __launch_bounds__(256) void transfer_project_kernel(const void* __restrict__ T, const int* __restrict__ exps,
@@ -85,13 +73,7 @@ __global__ __launch_bounds__(256) void transfer_project_kernel(const void* __res
             const int rr = i / G, k = k0 + 4 * (i % G);
             const bool in = i < items && r0 + rr < R && k < N;
             const int64_t e = in ? (r0 + rr) * (int64_t)N + k : 0;
-            if (HALF) {
-              const uint2 raw = *(const uint2*)((const __half*)T + e);
-              v[u] = make_float4(half_bits_to_float((unsigned short)(raw.x & 0xffffu)), half_bits_to_float((unsigned short)(raw.x >> 16)),
-                                 half_bits_to_float((unsigned short)(raw.y & 0xffffu)), half_bits_to_float((unsigned short)(raw.y >> 16)));
-            } else {
-              v[u] = *(const float4*)((const float*)T + e);
-            }
+            v[u] = row_load4<HALF>(T, e);
             if (!in) v[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
           }
 #pragma unroll
@@ -104,10 +86,7 @@ __global__ __launch_bounds__(256) void transfer_project_kernel(const void* __res
         for (int i = threadIdx.x; i < rows * kBlockElems; i += 256) {
           const int rr = i / kBlockElems, kk = i % kBlockElems;
           float v = 0.0f;
-          if (r0 + rr < R && k0 + kk < N) {
-            const int64_t e = (r0 + rr) * (int64_t)N + k0 + kk;
-            v = HALF ? __half2float(((const __half*)T)[e]) : ((const float*)T)[e];
-          }
+          if (r0 + rr < R && k0 + kk < N) v = row_element<HALF>(T, (r0 + rr) * (int64_t)N + k0 + kk);
           sT[rr * kTileStride + kk] = v;
         }
       }
@@ -196,17 +175,18 @@ ProjectShape project_shape(int J, int64_t R) {
 }
 
 template <int JT>
-void launch_project(bool half, hipStream_t st, const void* T, const int* exps, const float* B, int64_t R, int D, int J, int njw, void* C,
-                    int64_t row0, int* cexps, int out_half) {
+int launch_project(bool half, hipStream_t st, const void* T, const int* exps, const float* B, int64_t R, int D, int J, int njw, void* C,
+                   int64_t row0, int* cexps, int out_half) {
   const int rows = 64 * (4 / njw);
   const size_t lds = ((size_t)rows * kTileStride + (size_t)kDirBlock * JT * njw + (size_t)njw * rows) * sizeof(float);
   const int64_t tiles = (R + rows - 1) / rows;
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds));
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, 256 * per_cu));
-  if (half)
-    hipLaunchKernelGGL((transfer_project_kernel<JT, true>), dim3(grid), dim3(256), lds, st, T, exps, B, R, D, J, njw, C, row0, cexps, out_half);
-  else
-    hipLaunchKernelGGL((transfer_project_kernel<JT, false>), dim3(grid), dim3(256), lds, st, T, exps, B, R, D, J, njw, C, row0, cexps, out_half);
+  return with_storage(half, [&](auto h) {
+    hipLaunchKernelGGL((transfer_project_kernel<JT, decltype(h)::value>), dim3(capped_grid(tiles, per_cu)), dim3(256), lds, st, T, exps, B, R, D,
+                       J, njw, C, row0, cexps, out_half);
+    NSKY_CHECK_LAUNCH("nsky_transfer_project");
+    return NSKY_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------------------ relight of short rows
@@ -222,7 +202,7 @@ __global__ __launch_bounds__(256) void transfer_relight_short_kernel(const void*
                                                                      const float* __restrict__ acc, const float* __restrict__ lights,
                                                                      const float* __restrict__ bg, int64_t R, int J, int stride, int lsh,
                                                                      float* __restrict__ rgb, float* __restrict__ lin) {
-  constexpr int VE = HALF ? 8 : 4;  // elements of a 16-byte load
+  constexpr int VE = RowVec<HALF>::kElems;  // elements of a 16-byte load
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int N = 3 * J;
   const int units = (N + 11) / 12;
@@ -248,22 +228,13 @@ __global__ __launch_bounds__(256) void transfer_relight_short_kernel(const void*
       float x[VE];
       const int64_t e = e0 + v;
       if (e + VE <= total) {
-        if (HALF) {
-          const uint4 raw = *(const uint4*)((const __half*)Cm + e);
-          const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+        RowVec<HALF> raw;
+        raw.load(Cm, e);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            x[2 * i] = half_bits_to_float((unsigned short)(w[i] & 0xffffu));
-            x[2 * i + 1] = half_bits_to_float((unsigned short)(w[i] >> 16));
-          }
-        } else {
-          const float4 raw = *(const float4*)((const float*)Cm + e);
-          x[0] = raw.x; x[1] = raw.y; x[2] = raw.z; x[3] = raw.w;
-        }
+        for (int i = 0; i < VE; ++i) x[i] = raw.get(i);
       } else {
 #pragma unroll
-        for (int i = 0; i < VE; ++i)
-          x[i] = e + i < total ? (HALF ? __half2float(((const __half*)Cm)[e + i]) : ((const float*)Cm)[e + i]) : 0.0f;
+        for (int i = 0; i < VE; ++i) x[i] = e + i < total ? row_element<HALF>(Cm, e + i) : 0.0f;
       }
       int rr = v / N, k = v % N;
 #pragma unroll
@@ -329,8 +300,8 @@ __global__ __launch_bounds__(256) void transfer_relight_short_kernel(const void*
 }
 
 template <int KB>
-void launch_relight_short(bool half, hipStream_t st, const void* C, const int* exps, const float* acc, const float* lights, const float* bg,
-                          int64_t R, int J, float* rgb, float* lin) {
+int launch_relight_short(bool half, hipStream_t st, const void* C, const int* exps, const float* acc, const float* lights, const float* bg,
+                         int64_t R, int J, float* rgb, float* lin) {
   const int stride = short_stride(J);
   const int n12 = (3 * J + 11) / 12 * 12;
   auto bytes = [&](int rows) { return ((size_t)2 * KB * n12 + (size_t)rows * stride + (size_t)2 * KB * rows * 3) * sizeof(float); };
@@ -341,18 +312,14 @@ void launch_relight_short(bool half, hipStream_t st, const void* C, const int* e
   const size_t lds = bytes(rows);
   const int64_t tiles = (R + rows - 1) / rows;
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, 256 * per_cu));
-  if (lds > 64 * 1024) {  // (above the default limit of dynamic LDS)
-    const void* fn = half ? reinterpret_cast<const void*>(&transfer_relight_short_kernel<KB, true>)
-                          : reinterpret_cast<const void*>(&transfer_relight_short_kernel<KB, false>);
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  if (half)
-    hipLaunchKernelGGL((transfer_relight_short_kernel<KB, true>), dim3(grid), dim3(256), lds, st, C, exps, acc, lights, bg, R, J, stride, lsh,
-                       rgb, lin);
-  else
-    hipLaunchKernelGGL((transfer_relight_short_kernel<KB, false>), dim3(grid), dim3(256), lds, st, C, exps, acc, lights, bg, R, J, stride, lsh,
-                       rgb, lin);
+  return with_storage(half, [&](auto h) {
+    const auto kernel = &transfer_relight_short_kernel<KB, decltype(h)::value>;
+    if (lds > 64 * 1024)  // (above the default limit of dynamic LDS)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(kernel, dim3(capped_grid(tiles, per_cu)), dim3(256), lds, st, C, exps, acc, lights, bg, R, J, stride, lsh, rgb, lin);
+    NSKY_CHECK_LAUNCH("nsky_transfer_relight_short");
+    return NSKY_OK;
+  });
 }
 
 }  // namespace
@@ -371,16 +338,9 @@ extern "C" int nsky_transfer_project(const void* T, int32_t storage, const int32
   NSKY_CHECK_ARG((!half || exponents) && (!out_half || out_exponents), "nsky_transfer_project: fp16 storage needs the row exponents");
   hipStream_t st = (hipStream_t)stream;
   const ProjectShape s = project_shape(J, R);
-  switch (s.jt) {
-    case 4: launch_project<4>(half, st, T, exponents, B, R, D, J, s.njw, C, row0, out_exponents, out_half); break;
-    case 12: launch_project<12>(half, st, T, exponents, B, R, D, J, s.njw, C, row0, out_exponents, out_half); break;
-    case 16: launch_project<16>(half, st, T, exponents, B, R, D, J, s.njw, C, row0, out_exponents, out_half); break;
-    case 24: launch_project<24>(half, st, T, exponents, B, R, D, J, s.njw, C, row0, out_exponents, out_half); break;
-    case 28: launch_project<28>(half, st, T, exponents, B, R, D, J, s.njw, C, row0, out_exponents, out_half); break;
-    default: launch_project<36>(half, st, T, exponents, B, R, D, J, s.njw, C, row0, out_exponents, out_half); break;
-  }
-  NSKY_CHECK_LAUNCH("nsky_transfer_project");
-  return NSKY_OK;
+  return with_count<4, 12, 16, 24, 28, 36>(s.jt, [&](auto jt) {  // (the values of project_shape)
+    return launch_project<decltype(jt)::value>(half, st, T, exponents, B, R, D, J, s.njw, C, row0, out_exponents, out_half);
+  });
 }
 
 extern "C" int nsky_transfer_relight_short(const void* C, int32_t storage, const int32_t* exponents, const float* acc, const float* lights,
@@ -395,23 +355,8 @@ extern "C" int nsky_transfer_relight_short(const void* C, int32_t storage, const
   NSKY_CHECK_ARG(((uintptr_t)C & 15) == 0, "nsky_transfer_relight_short: C must start on a 16-byte boundary");
   hipStream_t st = (hipStream_t)stream;
   const int64_t N = (int64_t)J * 3;
-  for (int k0 = 0; k0 < K; k0 += kMaxLightsPerPass) {  // C is read once per pass
-    const int kb = std::min(kMaxLightsPerPass, K - k0);
-    const float* l = lights + k0 * N;
-    const float* b = bg + (int64_t)k0 * R * 3;
-    float* o = rgb + (int64_t)k0 * R * 3;
-    float* ol = lin ? lin + (int64_t)k0 * R * 3 : nullptr;
-    switch (kb) {
-      case 1: launch_relight_short<1>(half, st, C, exponents, acc, l, b, R, J, o, ol); break;
-      case 2: launch_relight_short<2>(half, st, C, exponents, acc, l, b, R, J, o, ol); break;
-      case 3: launch_relight_short<3>(half, st, C, exponents, acc, l, b, R, J, o, ol); break;
-      case 4: launch_relight_short<4>(half, st, C, exponents, acc, l, b, R, J, o, ol); break;
-      case 5: launch_relight_short<5>(half, st, C, exponents, acc, l, b, R, J, o, ol); break;
-      case 6: launch_relight_short<6>(half, st, C, exponents, acc, l, b, R, J, o, ol); break;
-      case 7: launch_relight_short<7>(half, st, C, exponents, acc, l, b, R, J, o, ol); break;
-      default: launch_relight_short<8>(half, st, C, exponents, acc, l, b, R, J, o, ol); break;
-    }
-    NSKY_CHECK_LAUNCH("nsky_transfer_relight_short");
-  }
-  return NSKY_OK;
+  return for_each_pass<kMaxLightsPerPass>(K, [&](int k0, auto kb) {  // C is read once per pass
+    const int64_t o = (int64_t)k0 * R * 3;
+    return launch_relight_short<decltype(kb)::value>(half, st, C, exponents, acc, lights + k0 * N, bg + o, R, J, rgb + o, lin ? lin + o : nullptr);
+  });
 }

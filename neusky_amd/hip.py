@@ -52,7 +52,7 @@ class GemmDesc(C.Structure):
 
 _lib.nsky_last_error.restype = C.c_char_p
 _lib.nsky_abi_version.restype = C.c_int
-ABI_VERSION = 17  # the ctypes structures below mirror this version of include/neusky_hip.h
+ABI_VERSION = 18  # the ctypes structures below mirror this version of include/neusky_hip.h
 if _lib.nsky_abi_version() != ABI_VERSION:
     raise NeuSkyHipError(f"libneusky_hip.so has ABI version {_lib.nsky_abi_version()}, this package binds version {ABI_VERSION}: rebuild (build.sh)")
 
@@ -1504,14 +1504,35 @@ def _transfer_storage(T, exponents) -> int:
     return TRANSFER_FP16
 
 
+def _ray_samples(albedo, normals, weights, positions=None):
+    """(R, S) of the samples along a batch of rays: albedo, normals and, if given, positions fp32 [R, S, 3]; weights fp32 [R, S]"""
+    R, S, _ = albedo.shape
+    assert albedo.shape == (R, S, 3) and normals.shape == (R, S, 3) and weights.shape == (R, S)
+    assert positions is None or positions.shape == (R, S, 3)
+    assert all(t is None or t.dtype == torch.float32 for t in (albedo, normals, weights, positions))
+    return R, S
+
+
+def _relight_operands(rows, exponents, acc, lights, bg, rgb, lin):
+    """(R, n, K, storage) of a relight: rows fp32 or fp16 [R, n, 3] (+ exponents int32 [R]); acc fp32 [R]; lights fp32 [K, n, 3]; bg, rgb
+    and, if given, lin fp32 [K, R, 3]"""
+    R, n, _ = rows.shape
+    K = lights.shape[0]
+    assert lights.shape == (K, n, 3) and bg.shape == (K, R, 3) and rgb.shape == (K, R, 3) and acc.shape[0] == R
+    assert lin is None or lin.shape == (K, R, 3)
+    assert all(t.dtype == torch.float32 for t in (acc, lights, bg, rgb)) and (lin is None or lin.dtype == torch.float32)
+    assert exponents is None or exponents.shape[0] == R
+    return R, n, K, _transfer_storage(rows, exponents)
+
+
 def transfer_bake(albedo, normals, weights, dirs, vis, T, row0: int, exponents, acc):
     """albedo, normals: fp32 [R, S, 3]; weights [R, S]; dirs [D, 3]; vis [R, D] or None -> rows [row0, row0 + R) of T (fp32 or fp16
     [rows, D, 3]), exponents: int32 [R] (fp16 storage, else None), acc: fp32 [R]"""
-    R, S, _ = albedo.shape
+    R, S = _ray_samples(albedo, normals, weights)
     D = dirs.shape[0]
     if T.dim() != 3 or tuple(T.shape[1:]) != (D, 3) or not 0 <= row0 <= T.shape[0] - R:
         raise ValueError(f"rows [{row0}, {row0 + R}) of a transfer shaped {tuple(T.shape)} for D = {D}")
-    assert weights.shape == (R, S) and acc.shape[0] == R and (vis is None or vis.shape == (R, D))
+    assert acc.shape[0] == R and (vis is None or vis.shape == (R, D))
     assert exponents is None or exponents.shape[0] == R
     check(_transfer_bake(_c(albedo), _c(normals), _c(weights), _c(dirs), _c(vis), R, S, D, _transfer_storage(T, exponents), _c(T), row0,
                          _c(exponents), _c(acc), stream_ptr()), "nsky_transfer_bake")
@@ -1520,14 +1541,9 @@ def transfer_bake(albedo, normals, weights, dirs, vis, T, row0: int, exponents, 
 def transfer_relight(T, exponents, acc, lights, bg, rgb, lin=None):
     """T: fp32 or fp16 [R, D, 3] (+ exponents int32 [R]); acc: fp32 [R]; lights: fp32 [K, D, 3]; bg: fp32 [K, R, 3] -> rgb [K, R, 3]
     (sRGB, clamped) and, if given, lin [K, R, 3]"""
-    R, D, _ = T.shape
-    K = lights.shape[0]
-    assert lights.shape == (K, D, 3) and bg.shape == (K, R, 3) and rgb.shape == (K, R, 3) and acc.shape[0] == R
-    assert lin is None or lin.shape == (K, R, 3)
-    assert all(t.dtype == torch.float32 for t in (acc, lights, bg, rgb)) and (lin is None or lin.dtype == torch.float32)
-    assert exponents is None or exponents.shape[0] == R
-    check(_transfer_relight(_c(T), _transfer_storage(T, exponents), _c(exponents), _c(acc), _c(lights), _c(bg), R, D, K, _c(rgb), _c(lin),
-                            stream_ptr()), "nsky_transfer_relight")
+    R, D, K, storage = _relight_operands(T, exponents, acc, lights, bg, rgb, lin)
+    check(_transfer_relight(_c(T), storage, _c(exponents), _c(acc), _c(lights), _c(bg), R, D, K, _c(rgb), _c(lin), stream_ptr()),
+          "nsky_transfer_relight")
 
 
 # ---- a radiance transfer in a basis of the light directions (relight/transfer_sh.py, csrc/transfer_sh.hip)
@@ -1559,59 +1575,39 @@ def transfer_project(T, exponents, basis, coeffs, row0: int = 0, coeff_exponents
 def transfer_relight_short(coeffs, exponents, acc, lights, bg, rgb, lin=None):
     """transfer_relight for rows of coefficients: coeffs: fp32 or fp16 [R, J, 3] (+ exponents int32 [R]), any J in 1..128; lights: fp32
     [K, J, 3]; bg: fp32 [K, R, 3] -> rgb [K, R, 3] (sRGB, clamped) and, if given, lin [K, R, 3]"""
-    R, J, _ = coeffs.shape
-    K = lights.shape[0]
-    if not 1 <= J <= TRANSFER_MAX_COEFFICIENTS:
-        raise ValueError(f"rows of 1..{TRANSFER_MAX_COEFFICIENTS} coefficients, not {J}")
-    assert lights.shape == (K, J, 3) and bg.shape == (K, R, 3) and rgb.shape == (K, R, 3) and acc.shape[0] == R
-    assert lin is None or lin.shape == (K, R, 3)
-    assert all(t.dtype == torch.float32 for t in (acc, lights, bg, rgb)) and (lin is None or lin.dtype == torch.float32)
-    assert exponents is None or exponents.shape[0] == R
-    check(_transfer_relight_short(_c(coeffs), _transfer_storage(coeffs, exponents), _c(exponents), _c(acc), _c(lights), _c(bg), R, J, K,
-                                  _c(rgb), _c(lin), stream_ptr()), "nsky_transfer_relight_short")
+    if not 1 <= coeffs.shape[1] <= TRANSFER_MAX_COEFFICIENTS:
+        raise ValueError(f"rows of 1..{TRANSFER_MAX_COEFFICIENTS} coefficients, not {coeffs.shape[1]}")
+    R, J, K, storage = _relight_operands(coeffs, exponents, acc, lights, bg, rgb, lin)
+    check(_transfer_relight_short(_c(coeffs), storage, _c(exponents), _c(acc), _c(lights), _c(bg), R, J, K, _c(rgb), _c(lin), stream_ptr()),
+          "nsky_transfer_relight_short")
 
 
 # ---- a directional sun on top of the hemisphere render (relight/sun.py, csrc/sun.hip)
 _sun_transfer = _sig("nsky_sun_transfer", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                      C.c_void_p)
-_sun_composite = _sig("nsky_sun_composite", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sun_composite = _sig("nsky_sun_composite", C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                      C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
 
 def sun_transfer(albedo, normals, weights, suns, out):
     """albedo, normals: fp32 [R, S, 3]; weights [R, S]; suns [K, 3] -> out [K, R, 3]"""
-    R, S, _ = albedo.shape
+    R, S = _ray_samples(albedo, normals, weights)
     K = suns.shape[0]
-    assert normals.shape == (R, S, 3) and weights.shape == (R, S) and suns.shape == (K, 3) and out.shape == (K, R, 3)
-    assert all(t.dtype == torch.float32 for t in (albedo, normals, weights, suns, out))
+    assert suns.shape == (K, 3) and out.shape == (K, R, 3) and suns.dtype == torch.float32 and out.dtype == torch.float32
     check(_sun_transfer(_c(albedo), _c(normals), _c(weights), _c(suns), R, S, K, _c(out), stream_ptr()), "nsky_sun_transfer")
 
 
 def sun_composite(lin_sky, t, vis, acc, acc_threshold, suns, colours, rgb, lin=None, shadow=None):
-    """lin_sky: fp32 [R, 3]; t [K, R, 3]; vis [K, R] or None; acc [R]; acc_threshold [1] (device); suns, colours [K, 3] -> rgb [K, R, 3]
-    (sRGB, clamped) and, if given, lin [K, R, 3] and shadow [K, R]"""
+    """lin_sky: fp32 [R, 3] (one sky under all K suns) or [K, R, 3] (a sky of each sun's own); t [K, R, 3]; vis [K, R] or None; acc [R];
+    acc_threshold [1] (device); suns, colours [K, 3] -> rgb [K, R, 3] (sRGB, clamped) and, if given, lin [K, R, 3] and shadow [K, R]"""
     K, R, _ = t.shape
-    assert lin_sky.shape == (R, 3) and acc.numel() == R and acc_threshold.numel() == 1 and suns.shape == (K, 3) and colours.shape == (K, 3)
+    assert lin_sky.shape in ((R, 3), (K, R, 3)) and acc.numel() == R and acc_threshold.numel() == 1 and suns.shape == (K, 3) and colours.shape == (K, 3)
     assert rgb.shape == (K, R, 3) and (vis is None or vis.shape == (K, R)) and (lin is None or lin.shape == (K, R, 3))
     assert shadow is None or shadow.shape == (K, R)
     assert all(x is None or x.dtype == torch.float32 for x in (lin_sky, t, vis, acc, acc_threshold, suns, colours, rgb, lin, shadow))
-    check(_sun_composite(_c(lin_sky), _c(t), _c(vis), _c(acc), _c(acc_threshold), _c(suns), _c(colours), R, K, _c(rgb), _c(lin), _c(shadow),
-                         stream_ptr()), "nsky_sun_composite")
-
-
-_sun_composite_skies = _sig("nsky_sun_composite_skies", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                            C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
-
-
-def sun_composite_skies(lin_skies, t, vis, acc, acc_threshold, suns, colours, rgb, lin=None, shadow=None):
-    """sun_composite with lin_skies: fp32 [K, R, 3], a sky of each sun's own"""
-    K, R, _ = t.shape
-    assert lin_skies.shape == (K, R, 3) and acc.numel() == R and acc_threshold.numel() == 1 and suns.shape == (K, 3) and colours.shape == (K, 3)
-    assert rgb.shape == (K, R, 3) and (vis is None or vis.shape == (K, R)) and (lin is None or lin.shape == (K, R, 3))
-    assert shadow is None or shadow.shape == (K, R)
-    assert all(x is None or x.dtype == torch.float32 for x in (lin_skies, t, vis, acc, acc_threshold, suns, colours, rgb, lin, shadow))
-    check(_sun_composite_skies(_c(lin_skies), _c(t), _c(vis), _c(acc), _c(acc_threshold), _c(suns), _c(colours), R, K, _c(rgb), _c(lin),
-                               _c(shadow), stream_ptr()), "nsky_sun_composite_skies")
+    stride = 0 if lin_sky.dim() == 2 else R * 3
+    check(_sun_composite(_c(lin_sky), stride, _c(t), _c(vis), _c(acc), _c(acc_threshold), _c(suns), _c(colours), R, K, _c(rgb), _c(lin),
+                         _c(shadow), stream_ptr()), "nsky_sun_composite")
 
 
 # ---- a clear-sky daylight model whose sky follows the sun (relight/daylight.py, csrc/daylight.hip)
@@ -1720,10 +1716,10 @@ def _lights_block(lights):
 
 def light_transfer(positions, albedo, normals, weights, lights, out):
     """positions, albedo, normals: fp32 [R, S, 3]; weights [R, S]; lights [L, 16] -> out [L, R, 3]"""
-    R, S, _ = albedo.shape
+    assert positions is not None
+    R, S = _ray_samples(albedo, normals, weights, positions)
     L = _lights_block(lights)
-    assert positions.shape == (R, S, 3) and normals.shape == (R, S, 3) and weights.shape == (R, S) and out.shape == (L, R, 3)
-    assert all(t.dtype == torch.float32 for t in (positions, albedo, normals, weights, out))
+    assert out.shape == (L, R, 3) and out.dtype == torch.float32
     check(_light_transfer(_c(positions), _c(albedo), _c(normals), _c(weights), ptr(lights), R, S, L, _c(out), stream_ptr()),
           "nsky_light_transfer")
 

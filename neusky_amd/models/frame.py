@@ -206,8 +206,7 @@ def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundl
     t = torch.empty(K, R, 3, device=dev)
     hip.sun_transfer(a, n, w, sun.dirs, t)
     rgb, lin, shadow = torch.empty(K, R, 3, device=dev), torch.empty(K, R, 3, device=dev), torch.empty(K, R, device=dev)
-    composite = hip.sun_composite if daylight is None else hip.sun_composite_skies
-    composite(lin_sky, t, vis, acc, sun.acc_threshold, sun.dirs, sun.colours, rgb, lin, shadow)
+    hip.sun_composite(lin_sky, t, vis, acc, sun.acc_threshold, sun.dirs, sun.colours, rgb, lin, shadow)  # (one sky [R, 3], or a daylight sky each)
     on = (acc > sun.acc_threshold)[:, None] & (sun.dirs[:, 2] > 0)[None]
     diff = torch.where(on, diff, torch.zeros((), device=dev)) if diff is not None else torch.zeros(R, K, device=dev)
     out = {"rgb": rgb, "lin": lin, "shadow_map": shadow, "shadow_difference": diff.t()}

@@ -10,6 +10,8 @@ from __future__ import annotations
 
 from typing import Dict, Optional, Sequence, Tuple, Union
 
+import math
+
 import torch
 
 from .lighting import FrameLighting, light_colours, ray_background
@@ -103,92 +105,129 @@ def relight_passes(baked, model, envmap, camera_index: Optional[int], rotations,
     return single, K, passes()
 
 
-class RadianceTransfer:
-    """One baked frame: T [R, D, 3] (fp32, or fp16 with int32 row exponents [R]), acc [R], the bake's light directions [D, 3], the rays'
-    directions [R, 3] (for the background), the frame shape, and the light-independent outputs of the frame render."""
+class BakedFrame:
+    """What the two baked frames share (RadianceTransfer below, transfer_sh.SHRadianceTransfer): the stored rows [R, n, 3] (fp32, or fp16
+    with int32 row exponents [R]) under the attribute a subclass names, acc [R], the bake's light directions [D, 3], the rays' directions
+    [R, 3] (for the background), the frame shape and the light-independent outputs of the frame render; the file of plain tensors; and the
+    relight driver, whose per-pass kernel call is the subclass's `_relight_pass`."""
+    ROWS = ""            # the stored rows: the attribute, the constructor argument and the key of a saved file
+    FORMAT = 0           # "format" of a saved file
+    EXTRA_KEYS = ()      # attributes of a subclass saved besides the shared ones: constructor arguments of the same names
+    HAS_RESIDUAL = False  # whether _relight_pass returns the [kb] float64 residual of its lights (reported as "light_residual")
 
-    def __init__(self, T: torch.Tensor, exponents: Optional[torch.Tensor], acc: torch.Tensor, dirs: torch.Tensor,
-                 ray_directions: torch.Tensor, shape: Sequence[int], outputs: Dict[str, torch.Tensor], camera_index: int = 0):
-        if T.dtype not in (torch.float32, torch.float16):
-            raise ValueError(f"T is stored as float32 or float16, not {T.dtype}")
-        if (T.dtype == torch.float16) != (exponents is not None):
+    def __init__(self, rows: torch.Tensor, exponents: Optional[torch.Tensor], acc: torch.Tensor, dirs: torch.Tensor,
+                 ray_directions: torch.Tensor, shape: Sequence[int], outputs: Dict[str, torch.Tensor], camera_index: int,
+                 fits: bool = True, others: str = ""):
+        """fits: the subclass's own shape condition (rows against dirs); others: its own tensors' part of the shape message"""
+        if rows.dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"{self.ROWS} is stored as float32 or float16, not {rows.dtype}")
+        if (rows.dtype == torch.float16) != (exponents is not None):
             raise ValueError("float16 storage comes with row exponents, float32 storage without")
-        R, D = T.shape[0], T.shape[1]
-        if tuple(T.shape) != (R, D, 3) or tuple(dirs.shape) != (D, 3) or tuple(ray_directions.shape) != (R, 3) or acc.shape[0] != R:
-            raise ValueError(f"T {tuple(T.shape)}, acc {tuple(acc.shape)}, dirs {tuple(dirs.shape)}, rays {tuple(ray_directions.shape)}")
-        n = 1
-        for v in shape:
-            n *= int(v)
-        if n != R:
+        R, D = rows.shape[0], dirs.shape[0]
+        if (not fits or rows.dim() != 3 or rows.shape[2] != 3 or tuple(dirs.shape) != (D, 3) or tuple(ray_directions.shape) != (R, 3)
+                or acc.shape[0] != R):
+            raise ValueError(f"{self.ROWS} {tuple(rows.shape)}, acc {tuple(acc.shape)}, {others}dirs {tuple(dirs.shape)}, "
+                             f"rays {tuple(ray_directions.shape)}")
+        if math.prod(int(v) for v in shape) != R:
             raise ValueError(f"frame shape {tuple(shape)} does not hold {R} rays")
-        self.T, self.exponents, self.acc, self.dirs, self.ray_directions = T, exponents, acc.reshape(R), dirs, ray_directions
+        setattr(self, self.ROWS, rows)
+        self.exponents, self.acc, self.dirs, self.ray_directions = exponents, acc.reshape(R), dirs, ray_directions
         self.shape = tuple(int(v) for v in shape)
         self.outputs = dict(outputs)
         self.camera_index = int(camera_index)
 
     @property
+    def rows(self) -> torch.Tensor:
+        return getattr(self, self.ROWS)
+
+    @property
     def storage(self) -> str:
-        return "fp32" if self.T.dtype == torch.float32 else "fp16"
+        return "fp32" if self.rows.dtype == torch.float32 else "fp16"
 
     @property
     def device(self) -> torch.device:
-        return self.T.device
+        return self.rows.device
 
     @property
     def nbytes(self) -> int:
-        return self.T.numel() * self.T.element_size()
-
-    def dense(self, dtype: torch.dtype = torch.float32) -> torch.Tensor:
-        """T as a plain [R, D, 3] tensor (the fp16 rows unscaled)"""
-        return self.T.to(dtype) if self.exponents is None else unpack_fp16(self.T, self.exponents, dtype)
+        return self.rows.numel() * self.rows.element_size()
 
     # ------------------------------------------------------------------ persistence: plain tensors
     def save(self, path) -> None:
-        state = {"format": 1, "T": self.T.cpu(), "exponents": None if self.exponents is None else self.exponents.cpu(),
-                 "acc": self.acc.cpu(), "dirs": self.dirs.cpu(), "ray_directions": self.ray_directions.cpu(), "shape": list(self.shape),
-                 "camera_index": self.camera_index, "outputs": {k: v.cpu() for k, v in self.outputs.items()}}
+        state = {"format": self.FORMAT}
+        for k in (self.ROWS, "exponents", "acc", *self.EXTRA_KEYS, "dirs", "ray_directions", "camera_index"):
+            v = getattr(self, k)
+            state[k] = v.cpu() if torch.is_tensor(v) else v
+        state["shape"] = list(self.shape)
+        state["outputs"] = {k: v.cpu() for k, v in self.outputs.items()}
         torch.save(state, path)
 
     @classmethod
-    def load(cls, path, device: Union[str, torch.device] = "cuda") -> "RadianceTransfer":
+    def load(cls, path, device: Union[str, torch.device] = "cuda"):
         state = torch.load(path, map_location="cpu", weights_only=True)
-        if state.get("format") != 1:
-            raise ValueError(f"{path}: not a saved RadianceTransfer")
-        to = lambda t: None if t is None else t.to(device)  # noqa: E731
-        return cls(to(state["T"]), to(state["exponents"]), to(state["acc"]), to(state["dirs"]), to(state["ray_directions"]), state["shape"],
-                   {k: to(v) for k, v in state["outputs"].items()}, state["camera_index"])
+        if state.pop("format", None) != cls.FORMAT:
+            raise ValueError(f"{path}: not a saved {cls.__name__}")
+        state["outputs"] = {k: v.to(device) for k, v in state["outputs"].items()}
+        return cls(**{k: v.to(device) if torch.is_tensor(v) else v for k, v in state.items()})
 
     # ------------------------------------------------------------------ relighting
-    def _light(self, model, envmap, cam: int, rotation: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(L [D, 3], bg [R, 3]) of one light (frame_light)"""
-        return frame_light(model, envmap, self.dirs, self.ray_directions, cam, rotation)
+    def _relight_pass(self, lights, bg, rgb, lin) -> Optional[torch.Tensor]:
+        """the kernel call of one pass: lights [kb, D, 3] and bg [kb, R, 3] -> rgb and, unless None, lin [kb, R, 3]"""
+        raise NotImplementedError
 
     @torch.no_grad()
     def relight(self, model=None, *, envmap=None, camera_index: Optional[int] = None, rotations=None, exposure=None,
                 return_linear: bool = False, display=None) -> Dict[str, torch.Tensor]:
         """The frame under new light: the keys of get_outputs_for_camera_ray_bundle.  envmap: a relight.EnvironmentMap, else the
         illumination latent of `camera_index` (default: the bake's camera) of `model`.  rotations: None or one [3, 3] matrix -> rgb
-        [*shape, 3]; a sequence or a [K, 3, 3] tensor -> rgb [K, *shape, 3], processed in batches of 8 lights per pass over T.
+        [*shape, 3]; a sequence or a [K, 3, 3] tensor -> rgb [K, *shape, 3], processed in batches of 8 lights per pass over the rows.
         exposure: a float or a 0-d tensor multiplying the light (on top of the map's own exposure).  display: a relight.DisplayTransform
         of the linear image, metered where acc exceeds its meter_mask_threshold: adds display_rgb8, display_rgb and display_exposure.
-        Nothing synchronises with the host."""
-        from .. import hip
+        A frame in a light basis adds "light_residual" ([K], or 0-d for a single light), a device tensor.  Nothing synchronises with
+        the host."""
         from .display import frame_display
         single, K, passes = relight_passes(self, model, envmap, camera_index, rotations, exposure)
-        R, dev = self.T.shape[0], self.device
+        R, dev = self.rows.shape[0], self.device
         rgb = torch.empty(K, R, 3, dtype=torch.float32, device=dev)
         lin = torch.empty(K, R, 3, dtype=torch.float32, device=dev) if return_linear or display is not None else None
+        residual = torch.empty(K, dtype=torch.float64, device=dev) if self.HAS_RESIDUAL else None
         for k0, lights, bg in passes:
             kb = lights.shape[0]
-            hip.transfer_relight(self.T, self.exponents, self.acc, lights, bg, rgb[k0:k0 + kb], None if lin is None else lin[k0:k0 + kb])
+            res = self._relight_pass(lights, bg, rgb[k0:k0 + kb], None if lin is None else lin[k0:k0 + kb])
+            if residual is not None:
+                residual[k0:k0 + kb] = res
         lead = () if single else (K,)
         out = {"rgb": rgb.view(*lead, *self.shape, 3)}
+        if residual is not None:
+            out["light_residual"] = residual[0] if single else residual
         if return_linear:
             out["linear"] = lin.view(*lead, *self.shape, 3)
         out.update(self.outputs)
         if display is not None:
             out.update(frame_display(display, lin.view(*lead, *self.shape, 3), self.shape, self.acc))
         return out
+
+
+class RadianceTransfer(BakedFrame):
+    """One baked frame: T [R, D, 3] (fp32, or fp16 with int32 row exponents [R]), acc [R], the bake's light directions [D, 3], the rays'
+    directions [R, 3] (for the background), the frame shape, and the light-independent outputs of the frame render."""
+    ROWS, FORMAT = "T", 1
+
+    def __init__(self, T: torch.Tensor, exponents: Optional[torch.Tensor], acc: torch.Tensor, dirs: torch.Tensor,
+                 ray_directions: torch.Tensor, shape: Sequence[int], outputs: Dict[str, torch.Tensor], camera_index: int = 0):
+        super().__init__(T, exponents, acc, dirs, ray_directions, shape, outputs, camera_index, fits=T.shape[1:2] == dirs.shape[:1])
+
+    def dense(self, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """T as a plain [R, D, 3] tensor (the fp16 rows unscaled)"""
+        return self.T.to(dtype) if self.exponents is None else unpack_fp16(self.T, self.exponents, dtype)
+
+    def _light(self, model, envmap, cam: int, rotation: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(L [D, 3], bg [R, 3]) of one light (frame_light)"""
+        return frame_light(model, envmap, self.dirs, self.ray_directions, cam, rotation)
+
+    def _relight_pass(self, lights, bg, rgb, lin) -> None:
+        from .. import hip
+        hip.transfer_relight(self.T, self.exponents, self.acc, lights, bg, rgb, lin)
 
 
 def _bake_chunks(model, camera_ray_bundle, storage: str, chunk: Optional[int], use_graph: bool, camera_index: Optional[int], open_sink):

@@ -14,13 +14,13 @@ How close an order comes depends on the light, and has not been measured on a tr
 Kernels: csrc/transfer_sh.hip (nsky_transfer_project, nsky_transfer_relight_short); both take any basis."""
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence, Union
+from typing import Dict, Optional, Sequence
 
 import math
 
 import torch
 
-from .transfer import RadianceTransfer, _bake_chunks, _storage_dtype, relight_passes
+from .transfer import BakedFrame, RadianceTransfer, _bake_chunks, _storage_dtype
 
 DEFAULT_ORDER = 5  # a design choice (36 coefficients: a 1080p frame in 0.9 GB of fp32), not a measurement
 MAX_ORDER = 8      # likewise (81 coefficients; the kernels take up to 128)
@@ -88,65 +88,25 @@ def project_lights(Q: torch.Tensor, lights: torch.Tensor):
     return l.to(torch.float32).contiguous(), residual
 
 
-class SHRadianceTransfer:
+class SHRadianceTransfer(BakedFrame):
     """One baked frame in a light basis: C [R, J, 3] = T Q (fp32, or fp16 with int32 row exponents [R]), acc [R], the basis Q [D, J]
     over the bake's light directions dirs [D, 3], the rays' directions [R, 3] (for the background), the frame shape and the
-    light-independent outputs of the frame render."""
+    light-independent outputs of the frame render.
+
+    `relight` takes RadianceTransfer.relight's arguments and returns its keys, the light projected onto the basis, plus "light_residual"
+    ([K], or 0-d for a single light): |L - Q Q^T L|_F / |L|_F, a device tensor (nothing synchronises with the host).  The frame is the
+    dense relight under Q Q^T L: exact where the residual is zero.  Its linear image may be negative where the basis rings: a `display`
+    transform takes such a value as 0, like a NaN, and does not meter it."""
+    ROWS, FORMAT, EXTRA_KEYS, HAS_RESIDUAL = "C", 2, ("Q", "order"), True
 
     def __init__(self, C: torch.Tensor, exponents: Optional[torch.Tensor], acc: torch.Tensor, Q: torch.Tensor, dirs: torch.Tensor,
                  ray_directions: torch.Tensor, shape: Sequence[int], outputs: Dict[str, torch.Tensor], camera_index: int = 0,
                  order: Optional[int] = None):
-        if C.dtype not in (torch.float32, torch.float16):
-            raise ValueError(f"C is stored as float32 or float16, not {C.dtype}")
-        if (C.dtype == torch.float16) != (exponents is not None):
-            raise ValueError("float16 storage comes with row exponents, float32 storage without")
-        R, J, D = C.shape[0], C.shape[1], dirs.shape[0]
-        if (tuple(C.shape) != (R, J, 3) or tuple(Q.shape) != (D, J) or tuple(dirs.shape) != (D, 3) or tuple(ray_directions.shape) != (R, 3)
-                or acc.shape[0] != R):
-            raise ValueError(f"C {tuple(C.shape)}, acc {tuple(acc.shape)}, Q {tuple(Q.shape)}, dirs {tuple(dirs.shape)}, "
-                             f"rays {tuple(ray_directions.shape)}")
-        n = 1
-        for v in shape:
-            n *= int(v)
-        if n != R:
-            raise ValueError(f"frame shape {tuple(shape)} does not hold {R} rays")
-        self.C, self.exponents, self.acc, self.dirs, self.ray_directions = C, exponents, acc.reshape(R), dirs, ray_directions
+        super().__init__(C, exponents, acc, dirs, ray_directions, shape, outputs, camera_index,
+                         fits=tuple(Q.shape) == (dirs.shape[0], *C.shape[1:2]), others=f"Q {tuple(Q.shape)}, ")
         self.Q = Q.to(torch.float32).contiguous()
-        self.shape = tuple(int(v) for v in shape)
-        self.outputs = dict(outputs)
-        self.camera_index = int(camera_index)
-        self.order = math.isqrt(J) - 1 if order is None else int(order)
+        self.order = math.isqrt(C.shape[1]) - 1 if order is None else int(order)
 
-    @property
-    def storage(self) -> str:
-        return "fp32" if self.C.dtype == torch.float32 else "fp16"
-
-    @property
-    def device(self) -> torch.device:
-        return self.C.device
-
-    @property
-    def nbytes(self) -> int:
-        return self.C.numel() * self.C.element_size()
-
-    # ------------------------------------------------------------------ persistence: plain tensors
-    def save(self, path) -> None:
-        state = {"format": 2, "C": self.C.cpu(), "exponents": None if self.exponents is None else self.exponents.cpu(),
-                 "acc": self.acc.cpu(), "Q": self.Q.cpu(), "dirs": self.dirs.cpu(), "ray_directions": self.ray_directions.cpu(),
-                 "shape": list(self.shape), "camera_index": self.camera_index, "order": self.order,
-                 "outputs": {k: v.cpu() for k, v in self.outputs.items()}}
-        torch.save(state, path)
-
-    @classmethod
-    def load(cls, path, device: Union[str, torch.device] = "cuda") -> "SHRadianceTransfer":
-        state = torch.load(path, map_location="cpu", weights_only=True)
-        if state.get("format") != 2:
-            raise ValueError(f"{path}: not a saved SHRadianceTransfer")
-        to = lambda t: None if t is None else t.to(device)  # noqa: E731
-        return cls(to(state["C"]), to(state["exponents"]), to(state["acc"]), to(state["Q"]), to(state["dirs"]), to(state["ray_directions"]),
-                   state["shape"], {k: to(v) for k, v in state["outputs"].items()}, state["camera_index"], state["order"])
-
-    # ------------------------------------------------------------------ relighting
     def _relight_pass(self, lights, bg, rgb, lin) -> torch.Tensor:
         from .. import hip
         l, residual = project_lights(self.Q, lights)  # noqa: E741
@@ -168,31 +128,6 @@ class SHRadianceTransfer:
         out = {"rgb": rgb.view(K, *self.shape, 3), "light_residual": self._relight_pass(lights, bg, rgb, lin)}
         if lin is not None:
             out["linear"] = lin.view(K, *self.shape, 3)
-        return out
-
-    @torch.no_grad()
-    def relight(self, model=None, *, envmap=None, camera_index: Optional[int] = None, rotations=None, exposure=None,
-                return_linear: bool = False, display=None) -> Dict[str, torch.Tensor]:
-        """RadianceTransfer.relight for the frame in its basis: the same arguments and keys, the light projected onto the basis, plus
-        "light_residual" ([K], or 0-d for a single light): |L - Q Q^T L|_F / |L|_F, a device tensor (nothing synchronises with the
-        host).  The frame is the dense relight under Q Q^T L: exact where the residual is zero.  Its linear image may be negative where
-        the basis rings: a `display` transform takes such a value as 0, like a NaN, and does not meter it."""
-        from .display import frame_display
-        single, K, passes = relight_passes(self, model, envmap, camera_index, rotations, exposure)
-        R, dev = self.C.shape[0], self.device
-        rgb = torch.empty(K, R, 3, dtype=torch.float32, device=dev)
-        lin = torch.empty(K, R, 3, dtype=torch.float32, device=dev) if return_linear or display is not None else None
-        residual = torch.empty(K, dtype=torch.float64, device=dev)
-        for k0, lights, bg in passes:
-            kb = lights.shape[0]
-            residual[k0:k0 + kb] = self._relight_pass(lights, bg, rgb[k0:k0 + kb], None if lin is None else lin[k0:k0 + kb])
-        lead = () if single else (K,)
-        out = {"rgb": rgb.view(*lead, *self.shape, 3), "light_residual": residual[0] if single else residual}
-        if return_linear:
-            out["linear"] = lin.view(*lead, *self.shape, 3)
-        out.update(self.outputs)
-        if display is not None:
-            out.update(frame_display(display, lin.view(*lead, *self.shape, 3), self.shape, self.acc))
         return out
 
 

@@ -1,6 +1,6 @@
 """nsky_daylight_eval (csrc/daylight.hip) against the float64 restatement of the model (daylight_cpu.py) on the same fp32 inputs, at
 the lane and tail sizes, with the directions and suns where the definition branches; repeatability; parameters read from device memory;
-and nsky_sun_composite_skies against nsky_sun_composite."""
+and nsky_sun_composite on a sky [R, 3] against its [K, R, 3] expansion."""
 import numpy as np
 import pytest
 import torch
@@ -132,11 +132,11 @@ def test_composite_with_copies_of_one_sky_is_the_composite_on_that_sky(with_vis)
     one = [torch.empty(K, R, 3, device=DEV), torch.empty(K, R, 3, device=DEV), torch.empty(K, R, device=DEV)]
     many = [torch.empty_like(x) for x in one]
     hip.sun_composite(lin_sky, t, vis, acc, thr, suns, colours, *one)
-    hip.sun_composite_skies(lin_sky[None].expand(K, R, 3).contiguous(), t, vis, acc, thr, suns, colours, *many)
+    hip.sun_composite(lin_sky[None].expand(K, R, 3).contiguous(), t, vis, acc, thr, suns, colours, *many)
     for a, b in zip(one, many):
         assert torch.equal(a, b)
     skies = (torch.rand(K, R, 3, generator=g) * 2.0).to(DEV)  # and each sun meets its own sky
-    hip.sun_composite_skies(skies, t, vis, acc, thr, suns, colours, *many)
+    hip.sun_composite(skies, t, vis, acc, thr, suns, colours, *many)
     for k in range(K):
         hip.sun_composite(skies[k].contiguous(), t, vis, acc, thr, suns, colours, *one)
         assert torch.equal(one[1][k], many[1][k]) and torch.equal(one[0][k], many[0][k])

@@ -43,8 +43,10 @@ def _mixed_lights(L, g):
     return out
 
 
-# one ray; a sample tail; a full pass of 8 lights; a pass boundary; rays across workgroups
-@pytest.mark.parametrize("R, S, L", ((1, 1, 1), (3, 63, 1), (65, 96, 8), (17, 65, 9), (257, 24, 3)))
+# one ray; a sample tail; a full pass of 8 lights; a pass boundary; rays across workgroups; then the pass rule and the ray loop the kernel
+# shares with the suns' (a full pass, a pass of one behind it, two passes and one) at R = 5 (a second workgroup with one live wave) and
+# S = 65 (one sample behind a full lane stride)
+@pytest.mark.parametrize("R, S, L", ((1, 1, 1), (3, 63, 1), (65, 96, 8), (17, 65, 9), (257, 24, 3), (5, 65, 8), (5, 65, 9), (5, 65, 17)))
 def test_transfer_is_within_its_bound(R, S, L):
     g = np.random.default_rng(100 * R + S + L)
     x = g.normal(size=(R, S, 3))

@@ -10,6 +10,9 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SHAPES = [(1, 1, 1), (3, 5, 1), (5, 67, 9), (130, 96, 8)]  # (R, S, K): smallest; S below a wave; S across 64 lanes and K across the 8-sun
 #                                                             pass; the workload's S with R no multiple of the 4 waves of a workgroup
+# the pass rule and the ray loop the kernel shares with the lamps': a full pass, a pass of one behind it, two passes and one; R = 5: a second
+# workgroup with one live wave; S = 65: one sample behind a full lane stride
+SHAPES += [(5, 65, 8), (5, 65, 9), (5, 65, 17)]
 
 
 def _unit(rng, n):
@@ -104,3 +107,16 @@ def test_sun_composite(R, K, with_vis):
         assert np.all(np.abs(lin.astype(np.float64) - ref32) <= 2.0 * np.spacing(np.abs(ref32)).astype(np.float64))
         np.testing.assert_allclose(rgb, ref_rgb, rtol=1e-4, atol=1e-6)  # the srgb_fwd bar of test_gpu_render.py
         assert rgb.min() >= 0.0 and rgb.max() <= 1.0
+
+
+@pytest.mark.parametrize("sky", [(4, 5, 3), (5, 4), (1, 5, 3), (15,)], ids=("K+1 skies", "R x 4", "one of K skies", "flat"))
+def test_sun_composite_rejects_a_sky_of_another_shape(sky):
+    """lin_sky is [R, 3] or [K, R, 3] (here K = 3, R = 5): [K + 1, R, 3], [R, 4] and their like never reach the kernel"""
+    K, R = 3, 5
+    z = lambda *s: torch.zeros(*s, device=DEV)  # noqa: E731
+    rgb = torch.full((K, R, 3), 7.0, device=DEV)
+    with pytest.raises(AssertionError):
+        hip.sun_composite(z(*sky), z(K, R, 3), None, z(R), z(1), z(K, 3), z(K, 3), rgb)
+    assert (rgb == 7.0).all()
+    for good in ((R, 3), (K, R, 3)):
+        hip.sun_composite(z(*good), z(K, R, 3), None, z(R), z(1), z(K, 3), z(K, 3), rgb)

@@ -121,3 +121,11 @@ def test_relight_at_full_frame_size_crosses_two_to_the_31():
     print(f"full-size relight: worst error / magnitude {(err / mag).max().item():.3e} (bound {D * EPS + HALF:.3e})")
     assert (err <= (D * EPS + HALF) * mag).all()
     assert (rgb[0, rows].double() - TC.linear_to_srgb(lin[0, rows].double())).abs().max().item() <= 2e-6
+
+
+@pytest.mark.parametrize("storage", ["fp32", "fp16"])
+@pytest.mark.parametrize("D", [6, 8])
+def test_relight_of_nine_lights_over_short_rows(D, storage):
+    """a pass of 8 lights and a pass of one behind it, at the smallest rows of each kernel: D = 6 takes the any-D kernel in both storages,
+    D = 8 the 16-byte one (two loads of a fp32 row, one of a fp16 row); the restatement and the bars of the test above"""
+    test_relight_matches_the_restatement(D, 9, storage)

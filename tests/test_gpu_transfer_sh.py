@@ -212,3 +212,17 @@ def test_relight_of_coefficient_rows_at_full_frame_size():
     assert (err <= (J * EPS + HALF) * mag).all()
     assert (rgb[0, rows].double() - TC.linear_to_srgb(lin[0, rows].double())).abs().max().item() <= 2e-6
     assert np.isfinite(rgb.sum().item())
+
+
+@pytest.mark.parametrize("D", [6, 8])
+def test_projection_of_short_rows_onto_five_coefficients(D):
+    """J = 5 is no multiple of the 4 coefficients a lane reads at a time; D = 6 takes the scalar loads of a block, D = 8 the 8- and
+    16-byte ones; both storages in and out, the restatement and the bars of test_projection_matches_the_restatement"""
+    test_projection_matches_the_restatement(D, 5)
+
+
+@pytest.mark.parametrize("storage", ["fp32", "fp16"])
+def test_relight_of_five_coefficients_under_nine_lights(storage):
+    """a pass of 8 lights and a pass of one behind it over rows of 15 numbers (padded to 24 in LDS); the restatement and the bars of
+    test_relight_of_coefficient_rows_matches_the_restatement"""
+    test_relight_of_coefficient_rows_matches_the_restatement(5, 9, storage)

@@ -156,6 +156,42 @@ def test_save_load_round_trip_and_each_loader_refuses_the_other_format(tmp_path,
         SHRadianceTransfer.load(tmp_path / "dense.pt", "cpu")
 
 
+SHARED_KEYS = ["format", "exponents", "acc", "dirs", "ray_directions", "shape", "camera_index", "outputs"]
+FILES = {  # class: (file name, "format", keys of the saved dictionary, fields to compare after a load)
+    RadianceTransfer: ("dense.pt", 1, SHARED_KEYS + ["T"], ["T", "exponents", "acc", "dirs", "ray_directions", "shape", "camera_index"]),
+    SHRadianceTransfer: ("sh.pt", 2, SHARED_KEYS + ["C", "Q", "order"],
+                         ["C", "exponents", "acc", "Q", "dirs", "ray_directions", "shape", "camera_index", "order"]),
+}
+
+
+@pytest.mark.parametrize("storage", ["fp32", "fp16"])
+def test_the_two_file_formats_keep_their_keys(tmp_path, storage):
+    """what a saved file holds is written out here, not read off the classes: format 1 and 2, their key sets, every field back after a
+    load, and each loader's message for the other's file"""
+    g = torch.Generator().manual_seed(3)
+    sh = _frame(storage, g)
+    T = torch.rand(12, 64, 3, generator=g)
+    T, exps = X.pack_fp16(T) if storage == "fp16" else (T, None)
+    dense = RadianceTransfer(T, exps, sh.acc, sh.dirs, sh.ray_directions, (3, 4), sh.outputs, camera_index=2)
+    for frame in (dense, sh):
+        name, fmt, keys, fields = FILES[type(frame)]
+        frame.save(tmp_path / name)
+        state = torch.load(tmp_path / name, map_location="cpu", weights_only=True)
+        assert state["format"] == fmt and sorted(state) == sorted(keys)
+        assert state["shape"] == [3, 4] and state["camera_index"] == 2 and sorted(state["outputs"]) == sorted(X.FRAME_KEYS)
+        assert (state["exponents"] is None) == (storage == "fp32")
+        back = type(frame).load(tmp_path / name, "cpu")
+        assert type(back) is type(frame) and back.storage == storage
+        for f in fields:
+            a, b = getattr(frame, f), getattr(back, f)
+            assert (a is None and b is None) or (torch.equal(a, b) if torch.is_tensor(a) else a == b), f
+        assert all(torch.equal(frame.outputs[k], back.outputs[k]) for k in X.FRAME_KEYS)
+    with pytest.raises(ValueError, match="dense.pt: not a saved SHRadianceTransfer"):
+        SHRadianceTransfer.load(tmp_path / "dense.pt", "cpu")
+    with pytest.raises(ValueError, match="sh.pt: not a saved RadianceTransfer"):
+        RadianceTransfer.load(tmp_path / "sh.pt", "cpu")
+
+
 def test_constructor_rejects_mismatched_parts():
     g = torch.Generator().manual_seed(1)
     a = _frame("fp32", g)
