@@ -1419,6 +1419,67 @@ int nsky_aa_subpixel_rays(const float* origins, const float* directions, const f
 int nsky_aa_resolve(float* F, int64_t fs_k, int64_t fs_p, const float* X, int64_t xs_k, int64_t xs_e, int64_t xs_s, const int64_t* pixels,
                     int32_t K, int64_t P, int64_t E, int32_t S1, int32_t C, float* rgb, int64_t rs_k, int64_t rs_p, nsky_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Depth of field of a frame (neusky_amd/relight/depth_of_field.py, csrc/dof.hip): the first pass of a frame is a pinhole's, one ray through
+ * the lens centre and every pixel centre: sample 0.  A circle of confusion per pixel from that pass's depth and accumulation, a mark on
+ * every pixel some blurred pixel's disc reaches, S - 1 thin-lens rays through each marked pixel, and nsky_aa_resolve (above, as it is)
+ * averages the S samples in linear light.  A frame is H x W pixels, P = H W, pixel p = y W + x.  All fp32 arithmetic is rounded once per
+ * operation, no fused multiply-add, division and square root correctly rounded: a float32 restatement in the same order has the same
+ * bits for the circle of confusion and the same mask.
+ *
+ *   lens:       float [12] on the device = r^ (3), s^ (3), w^ (3), a, 1 / z_f, a f_px.  With D = directions * directions_norm and g_x, g_y
+ *               of the rays rule above taken at the centre pixel (W / 2, H / 2) (integer division): r^ = g_x / |g_x|, s^ = g_y / |g_y|,
+ *               w^ = +-(r^ x s^) with the sign that makes D . w^ > 0: the image plane's axes and the optical axis, from the bundle alone,
+ *               no camera.  f_px = 1 / |g_x|: the focal length in pixels, for D has D . w^ = 1 in a pinhole bundle.  a: the lens radius in
+ *               scene units.  z_f: the depth of the plane in focus along w^, in the units of the frame's `depth` = p2p_dist /
+ *               directions_norm (a pinhole's z-depth); 1 / z_f = 0 focuses at infinity.  The caller forms the block in fp64 and rounds it.
+ *   coc:        iz_p = 1 / depth_p when accumulation_p > covered and not depth_p <= 0, else 0: an uncovered pixel is at infinity (a
+ *               comparison with a NaN is false: a covered pixel's NaN depth stays a NaN, an uncovered pixel's does not count).
+ *               c_p = (a f_px) * |iz_p - 1 / z_f|: the blur radius, in pixels, of a point at that depth, for a lens point at offset l
+ *               shifts the image of a point at depth z by f_px l (1 / z - 1 / z_f).  A NaN c marks nothing.
+ *               With focus_pixel >= 0 the plane of focus goes through what the first pass saw at that pixel: 1 / z_f = 1 / depth there
+ *               when its accumulation > covered and its depth > 0, else 0; it is read on the device, used in place of lens[10] and
+ *               written to lens[10] (by one thread; no thread reads lens[10] in that case).  With focus_pixel < 0, lens[10] is read.
+ *   mark:       p is marked when some pixel q of the image has |q_x - p_x| <= reach, |q_y - p_y| <= reach, c_q >= threshold and
+ *               c_q + 0.5f >= (float) max(|q_x - p_x|, |q_y - p_y|); q = p counts.  The scatter of every blurred pixel's disc, in its
+ *               square (conservative) form, written as a gather: a sharp pixel behind a blurred foreground edge, a sharp pixel in front
+ *               of a blurred background and every pixel that is itself out of focus take lens samples.  Two approximations: `reach`
+ *               (1..64) caps how far a disc marks (the lens rays themselves are exact at any blur), and a surface the pinhole pass
+ *               never saw can appear only inside marked regions.  Evaluated as: r_q = min(reach, floor(c_q + 0.5f)) where c_q >=
+ *               threshold, else -1 (the distances are integers, so c_q + 0.5f >= d is d <= r_q); m(x, y') = the largest r_q among the q
+ *               of row y' with |q_x - x| <= r_q, else -1; p is marked when |y' - p_y| <= m(p_x, y') for some row y'.  The same set.
+ *   table:      [S - 1, 4] rows (dx, dy, u, v), made on the host in fp64 and rounded: row s = 1 .. S - 1 from t = frac(0.5 + s (1 / g,
+ *               1 / g^2, 1 / g^3, 1 / g^4)), g the real root of g^5 = g + 1 (the R2 sequence in four dimensions); (dx, dy) = (t_0, t_1) -
+ *               0.5; (u, v) the concentric square-to-disc map (Shirley and Chiu) of (a, b) = 2 (t_2, t_3) - 1: (0, 0) at a = b = 0; for
+ *               |a| > |b|, a (cos phi, sin phi) with phi = (pi / 4) (b / a); else b (cos phi, sin phi) with phi = pi / 2 - (pi / 4)
+ *               (a / b).  |dx|, |dy| <= 0.5, u^2 + v^2 <= 1.  Sample 0 is the first pass: dx = dy = u = v = 0.
+ *   lens rays:  D' = (D + dx g_x) + dy g_y with pixel p's own g_x, g_y: the antialiasing rule.  With `rotate`, theta = (float) h * tau,
+ *               tau = 2 pi 2^-24 rounded to fp32, h = hash(p) >> 8 (the top 24 bits), and (u, v) <- (u cos theta - v sin theta,
+ *               u sin theta + v cos theta), sine and cosine in fp32; hash is on the low 32 bits of p, all in uint32:
+ *                 x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *               (without the turn every pixel repeats one lens pattern: S ghost images instead of noise).  l = a * (u r^ + v s^) per
+ *               component; k = D' . w^ = (x x' + y y') + z z'; t = k * (1 / z_f); D'' = D' - t * l; origins' = o + l; directions' =
+ *               D'' / |D''|; directions_norm' = |D''| / k, so that depth = p2p_dist / directions_norm stays the z-depth and focus at
+ *               infinity needs no case of its own.  Every lens ray of a pixel passes through o + D' z_f / k.  pixel_area and
+ *               camera_indices are the pixel's.  Ray (e, s) of the E pixels and S - 1 rows is row e (S - 1) + s: pixel-major.
+ * nsky_dof_coc:        depth, accumulation [P]; lens [12] (lens[10] written when focus_pixel >= 0); focus_pixel in [-1, P)  ->  coc [P].
+ *                      One thread per pixel.
+ * nsky_dof_mark:       coc [P]; reach in 1..64  ->  mask uint8 [P], 1 marked, 0 not.  One block of 256 threads per 64 x 64 pixels, the
+ *                      radii of the tile and its halo and the row pass's result in LDS ((64 + 2 reach)^2 + (64 + 2 reach) 64 bytes).
+ *                      Pixels outside the image have no disc.  H <= 65535 * 64.
+ * nsky_dof_lens_rays:  the bundle as for nsky_aa_subpixel_rays; pixels int64 [E]; table [S1, 4]; lens [12]; rotate 0 or 1  ->  the same
+ *                      members for the E S1 rays.  One thread per ray.  A pixel index outside [0, P) is clamped into it (no access
+ *                      leaves the frame); the caller checks its own list.
+ * threshold = 0.5 pixel, reach = 16, covered = 0.5 and S = 16 are the defaults of relight.DepthOfField: design choices, not measurements.
+ * Flat indices are int64.  No atomics: every output is bitwise repeatable.  Nothing is read on the host. */
+int nsky_dof_coc(const float* depth, const float* accumulation, float* lens, int32_t H, int32_t W, int64_t focus_pixel, float covered,
+                 float* coc, nsky_stream_t stream);
+int nsky_dof_mark(const float* coc, int32_t H, int32_t W, float threshold, int32_t reach, uint8_t* mask, nsky_stream_t stream);
+int nsky_dof_lens_rays(const float* origins, const float* directions, const float* norm, const float* pixel_area,
+                       const int64_t* camera_indices, const int64_t* pixels, const float* table, const float* lens, int32_t H, int32_t W,
+                       int64_t E, int32_t S1, int32_t rotate, float* out_origins, float* out_directions, float* out_norm,
+                       float* out_pixel_area, int64_t* out_camera_indices, nsky_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

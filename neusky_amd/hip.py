@@ -1943,3 +1943,52 @@ def aa_resolve(frame, samples, pixels, rgb=None):
     rs_k, rs_p = (0, 0) if rgb is None else _aa_strided(rgb, K, P, Cn, "a frame's rgb")
     check(_aa_resolve(ptr(frame), fs_k, fs_p, ptr(samples), xs_k, xs_e, xs_s, ptr(_typed(pixels, torch.int64, E)), K, P, E, S1, Cn, ptr(rgb),
                       rs_k, rs_p, stream_ptr()), "nsky_aa_resolve")
+
+
+# ---- depth of field of a frame: circle of confusion, mark, lens rays (relight/depth_of_field.py, csrc/dof.hip)
+DOF_LENS_FLOATS = 12  # r^, s^, w^, a, 1 / z_f, a f_px
+DOF_MAX_REACH = 64
+_dof_coc = _sig("nsky_dof_coc", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_void_p)
+_dof_mark = _sig("nsky_dof_mark", C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p)
+_dof_lens_rays = _sig("nsky_dof_lens_rays", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                      C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                      C.c_void_p)
+
+
+def dof_coc(depth, accumulation, lens, focus_pixel: int, covered: float, coc):
+    """depth, accumulation: fp32 [H, W]; lens: fp32 [12] (with focus_pixel >= 0 its 1 / z_f is written from that pixel, on the device);
+    focus_pixel: a flat index, or -1: lens[10] as it is -> coc fp32 [H, W]"""
+    if depth.dim() != 2:
+        raise ValueError(f"the depth of a frame is float32 [H, W], got {tuple(depth.shape)}")
+    H, W = depth.shape
+    if not -1 <= int(focus_pixel) < H * W:
+        raise ValueError(f"focus_pixel: a flat index into {H} x {W} pixels or -1, got {focus_pixel}")
+    check(_dof_coc(ptr(_typed(depth, torch.float32, H, W)), ptr(_typed(accumulation, torch.float32, H, W)),
+                   ptr(_typed(lens, torch.float32, DOF_LENS_FLOATS)), H, W, int(focus_pixel), covered, ptr(_typed(coc, torch.float32, H, W)),
+                   stream_ptr()), "nsky_dof_coc")
+
+
+def dof_mark(coc, threshold: float, reach: int, mask):
+    """coc: fp32 [H, W]; reach in 1..64 -> mask uint8 [H, W]"""
+    if coc.dim() != 2:
+        raise ValueError(f"the circles of confusion of a frame are float32 [H, W], got {tuple(coc.shape)}")
+    H, W = coc.shape
+    if not 1 <= int(reach) <= DOF_MAX_REACH:
+        raise ValueError(f"reach is an integer in 1..{DOF_MAX_REACH}, got {reach!r}")
+    check(_dof_mark(ptr(_typed(coc, torch.float32, H, W)), H, W, threshold, int(reach), ptr(_typed(mask, torch.uint8, H, W)), stream_ptr()),
+          "nsky_dof_mark")
+
+
+def dof_lens_rays(origins, directions, norm, pixel_area, camera_indices, H: int, W: int, pixels, table, lens, rotate: bool, out_origins,
+                  out_directions, out_norm, out_pixel_area=None, out_camera_indices=None):
+    """a frame's flat bundle as for aa_subpixel_rays; pixels int64 [E] (indices in [0, H W): the caller's to check); table fp32 [S1, 4] =
+    (dx, dy, u, v); lens fp32 [12] -> the same members for the E S1 lens rays"""
+    P, E, S1 = H * W, pixels.shape[0], table.shape[0]
+    N = E * S1
+    check(_dof_lens_rays(ptr(_typed(origins, torch.float32, P, 3)), ptr(_typed(directions, torch.float32, P, 3)),
+                         ptr(_typed(norm, torch.float32, P, 1)), ptr(_typed(pixel_area, torch.float32, P, 1)),
+                         ptr(_typed(camera_indices, torch.int64, P, 1)), ptr(_typed(pixels, torch.int64, E)),
+                         ptr(_typed(table, torch.float32, S1, 4)), ptr(_typed(lens, torch.float32, DOF_LENS_FLOATS)), H, W, E, S1,
+                         1 if rotate else 0, ptr(_typed(out_origins, torch.float32, N, 3)), ptr(_typed(out_directions, torch.float32, N, 3)),
+                         ptr(_typed(out_norm, torch.float32, N, 1)), ptr(_typed(out_pixel_area, torch.float32, N, 1)),
+                         ptr(_typed(out_camera_indices, torch.int64, N, 1)), stream_ptr()), "nsky_dof_lens_rays")

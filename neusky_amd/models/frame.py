@@ -427,7 +427,8 @@ class FrameRenderer:
 
     @torch.no_grad()
     def render(self, camera_ray_bundle: RayBundle, lighting: FrameLighting, *, to_cpu: bool = False, camera_index: Optional[int] = None,
-               chunk: Optional[int] = None, use_graph: bool = True, display=None, antialias=None) -> Dict[str, torch.Tensor]:
+               chunk: Optional[int] = None, use_graph: bool = True, display=None, antialias=None,
+               depth_of_field=None) -> Dict[str, torch.Tensor]:
         """model.get_outputs_for_camera_ray_bundle, which documents the chunking and the outputs.  display: a relight.DisplayTransform of
         the frame's linear image, metered where the accumulation exceeds its meter_mask_threshold: adds display_rgb8, display_rgb and
         display_exposure (and, to a frame under the sky alone, its `lin`); it runs on the assembled frame, after the chunks, so its
@@ -435,7 +436,11 @@ class FrameRenderer:
         marks, through the same runner and inside the same begin / end, resolved into `lin` (and `rgb` from it), `albedo`, `accumulation`
         and `shadow_map`; adds aa_mask and aa_fraction (and `lin` as `display` does); `display` then sees the resolved frame.  Under an
         atmosphere both see the fogged frame: every sub-pixel sample is fogged at its own depth; atmosphere_transmittance and
-        atmosphere_inscatter stay the centre ray's, as `depth` does."""
+        atmosphere_inscatter stay the centre ray's, as `depth` does.  depth_of_field: a relight.DepthOfField: a second pass of thin-lens
+        rays through the pixels a blurred pixel's disc reaches, through the same runner, resolved into the same keys; adds dof_coc,
+        dof_mask, dof_fraction and dof_focus.  With antialias as well the edge mask is taken on the first pass, the lens pass runs, and
+        the antialiasing pass takes the edge-marked pixels the lens did not mark (their lens samples are jittered inside the pixel
+        already): aa_mask reports exactly those."""
         model = self.model
         assert not model.training, "call model.eval() first"
         chunk = chunk or max(model.config.eval_num_rays_per_chunk, 4096)
@@ -454,13 +459,23 @@ class FrameRenderer:
                 raise ValueError("a bake takes the place of the shading: antialias has no image to resolve")
             if len(shape) != 2:
                 raise ValueError(f"antialias reads a pixel's neighbours: it needs the ray bundle of a frame, [H, W], not {tuple(shape)}")
-        linear = display is not None or antialias is not None
+        if depth_of_field is not None:
+            from ..relight.depth_of_field import DepthOfField, depth_of_field_frame
+            if not isinstance(depth_of_field, DepthOfField):
+                raise ValueError(f"depth_of_field: a relight.DepthOfField, got {depth_of_field!r}")
+            if lighting.bake is not None:
+                raise ValueError("a bake takes the place of the shading: depth_of_field has no image to resolve")
+            if len(shape) != 2 or shape[0] < 2 or shape[1] < 2:
+                raise ValueError(f"a lens is made from the ray bundle of a frame, [H, W] with H, W >= 2, not {tuple(shape)}")
+            depth_of_field.focus_index(int(shape[0]), int(shape[1]))  # (a focus pixel outside the frame: refused before anything runs)
+        passes = antialias is not None or depth_of_field is not None
+        linear = display is not None or passes
         self.begin(camera_index, lighting, linear=linear)
         suns = lighting.suns
         lit, sun_keys = chunk_keys(lighting, linear)
         keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + [k for k in lit if k != "rgb"]
         out = {k: [] for k in keys}
-        early = to_cpu and antialias is None  # (the second pass resolves on the device: its frame goes to the host afterwards)
+        early = to_cpu and not passes  # (a second pass resolves on the device: its frame goes to the host afterwards)
         try:
             runner = self.runner(chunk, flat, use_graph)
             for i in range(0, num_rays, chunk):
@@ -474,10 +489,18 @@ class FrameRenderer:
                     full = torch.cat(out.pop(k))
                     out[k] = [full.reshape(num_rays, K, -1).transpose(0, 1).reshape(*lead, *shape, -1)]
             res = {k: torch.cat(v).view(*shape, -1) if k not in sun_keys else v[0] for k, v in out.items()}
+            K = 0 if suns is None else len(suns)
+            edges = None
+            if depth_of_field is not None:
+                if antialias is not None:  # the edges of the first pass, before the lens resolves into it
+                    edges = antialias.edge_mask(res["depth"], res["normal"], res["accumulation"], res["lin"])
+                res.update(depth_of_field_frame(depth_of_field, runner, flat, shape, res, K))
+                if edges is not None:
+                    edges = edges * (1 - res["dof_mask"].view_as(edges))
             if antialias is not None:
-                res.update(antialias_frame(antialias, runner, flat, shape, res, 0 if suns is None else len(suns)))
-                if to_cpu:
-                    res = {k: v.cpu() if torch.is_tensor(v) else v for k, v in res.items()}
+                res.update(antialias_frame(antialias, runner, flat, shape, res, K, mask=edges))
+            if passes and to_cpu:
+                res = {k: v.cpu() if torch.is_tensor(v) else v for k, v in res.items()}
         finally:
             self.end()
         if display is not None:

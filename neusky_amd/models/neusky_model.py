@@ -901,7 +901,7 @@ class NeuSkyFactoModel(ModelBase):
                                           accumulation_mask_threshold: float = 0.0, daylight=None, sun_shadows: str = "ddf",
                                           shadow_trace: Optional[dict] = None, display=None, antialias=None, lights=None,
                                           light_shadows: bool = True, light_trace: Optional[dict] = None,
-                                          atmosphere=None) -> Dict[str, torch.Tensor]:
+                                          atmosphere=None, depth_of_field=None) -> Dict[str, torch.Tensor]:
         """neusky_model.py:1369-1501: chunked full-frame render.  The reference chunks at eval_num_rays_per_chunk = 256
         (8100 python iterations per 1080p frame); any chunk size gives the same image, so a larger static chunk is used
         and its forward is captured once in a HIP graph and replayed per chunk (BASELINE config 5).
@@ -909,9 +909,11 @@ class NeuSkyFactoModel(ModelBase):
         (rotation, envmap, sun, the thresholds, daylight, sun_shadows, shadow_trace, lights, light_shadows, light_trace, atmosphere):
         relight.FrameLighting, which documents and checks them.
         display: a relight.DisplayTransform of the frame's linear image (FrameRenderer.render): display_rgb8, display_rgb, display_exposure.
-        antialias: a relight.Antialias: sub-pixel rays through the pixels its edge rule marks, resolved in linear light: aa_mask, aa_fraction."""
+        antialias: a relight.Antialias: sub-pixel rays through the pixels its edge rule marks, resolved in linear light: aa_mask, aa_fraction.
+        depth_of_field: a relight.DepthOfField: thin-lens rays through the pixels a blurred pixel's disc reaches, resolved in linear light:
+        dof_coc, dof_mask, dof_fraction, dof_focus."""
         lighting = FrameLighting.of(rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold,
                                     daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace, lights=lights,
                                     light_shadows=light_shadows, light_trace=light_trace, atmosphere=atmosphere)
         return self.frames.render(camera_ray_bundle, lighting, to_cpu=to_cpu, camera_index=camera_index, chunk=chunk, use_graph=use_graph,
-                                  display=display, antialias=antialias)
+                                  display=display, antialias=antialias, depth_of_field=depth_of_field)

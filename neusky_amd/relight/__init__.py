@@ -31,6 +31,10 @@ sRGB and 8 bits; the frame render and both transfers' `relight` take one as `dis
 `Antialias` (antialias.py, csrc/antialias.hip): adaptive supersampling of a frame: an edge mask from the frame's own G-buffer and linear
 image, `subpixel_rays` through the marked pixels, a resolve in linear light; the frame render takes one as `antialias=` (`--antialias`).
 
+`DepthOfField` (depth_of_field.py, csrc/dof.hip): a thin lens in place of the pinhole: a circle of confusion per pixel from the frame's own
+depth, a mark on every pixel a blurred pixel's disc reaches, `lens_rays` through the marked pixels, the same resolve; the frame render
+takes one as `depth_of_field=` (`--dof-aperture`).
+
 `Atmosphere` (atmosphere.py, csrc/atmosphere.hip): height fog and haze between the camera and the frame, with the suns' in-scatter
 shadowed along the ray by the frame's own shadow mode; the frame render takes one as `atmosphere=` (`--fog-density`, `--fog-shafts`).
 
@@ -43,6 +47,8 @@ from .antialias import Antialias, r2_offsets, subpixel_rays
 from .atmosphere import Atmosphere
 from .cameras import CameraPath, camera_rays, load_camera_path
 from .daylight import DaylightSky
+from .depth_of_field import (DepthOfField, circle_of_confusion, depth_of_field_frame, lens_block, lens_frame, lens_rays, lens_table,
+                             mark_pixels)
 from .display import DisplayTransform, bloom_weights, frame_display
 from .envmap import EnvironmentMap, envmap_labels, envmap_lookup, project_envmap, z_rotation
 from .envmap_sun import SunExtraction, extract_sun
@@ -60,4 +66,5 @@ __all__ = ["ALIVE", "Antialias", "Atmosphere", "CameraPath", "DaylightSky", "Dis
            "bake_transfer_sh", "bloom_weights", "camera_rays", "compress_transfer", "envmap_labels", "envmap_lookup", "extract_sun", "frame_display", "light_basis",
            "load_camera_path", "pack_fp16", "project_envmap", "project_lights", "r2_offsets", "read_envmap", "sh_basis", "srgb_to_linear", "sun_direction",
            "subpixel_rays", "sun_path", "sun_solid_angle", "trace_sun_shadows", "trace_visibility", "unpack_fp16", "z_rotation", "as_lights", "lights_block", "load_lights", "save_lights",
-           "trace_light_shadows", "trace_visibility_to"]
+           "trace_light_shadows", "trace_visibility_to", "DepthOfField", "circle_of_confusion", "depth_of_field_frame", "lens_block", "lens_frame",
+           "lens_rays", "lens_table", "mark_pixels"]

@@ -120,6 +120,19 @@ def build_parser() -> argparse.ArgumentParser:
     aa.add_argument("--aa-accumulation", type=float, metavar="T", help="mark a difference of accumulation above T (default 0.1)")
     aa.add_argument("--aa-all", action="store_true", help="mark every pixel: plain supersampling")
     aa.add_argument("--aa-mask", action="store_true", help="also write the marked pixels of each frame as aa_CCCC_FFF.png (0 or 255)")
+    lens = ap.add_argument_group("depth of field", "a thin lens in place of the pinhole (relight.DepthOfField): the pixels a blurred pixel's "
+                                 "disc reaches take further rays from points of the lens, averaged in linear light")
+    lens.add_argument("--dof-aperture", type=float, metavar="A", help="the lens radius in scene units; turns the feature on, the flags below need it")
+    lens.add_argument("--dof-focus-distance", type=float, metavar="Z",
+                      help="the depth of the plane in focus along the optical axis, in the units of the frame's depth")
+    lens.add_argument("--dof-focus-pixel", type=int, nargs=2, metavar=("X", "Y"),
+                      help="focus on what the frame shows at this pixel (default: the centre pixel); excludes --dof-focus-distance")
+    lens.add_argument("--dof-samples", type=int, metavar="S", help="samples per marked pixel, the pinhole's ray included (2..64, default 16)")
+    lens.add_argument("--dof-threshold", type=float, metavar="PIXELS", help="a pixel blurred over at least this radius marks its disc (default 0.5)")
+    lens.add_argument("--dof-reach", type=int, metavar="PIXELS", help="how far a disc marks at the most (1..64, default 16)")
+    lens.add_argument("--dof-all", action="store_true", help="mark every pixel")
+    lens.add_argument("--dof-map", action="store_true",
+                      help="also write the circle of confusion of each frame as coc_CCCC_FFF.png (8 bits: min(c / reach, 1))")
     lamps = ap.add_argument_group("lights", "point and spot lights inside the scene (relight.PointLight), on top of the sky and any sun, with "
                                   "shadow rays sphere-traced through the SDF to each lamp")
     lamps.add_argument("--light", type=float, nargs=6, action="append", metavar=("X", "Y", "Z", "R", "G", "B"),
@@ -245,6 +258,26 @@ def parse_antialias(ap: argparse.ArgumentParser, args):
         ap.error(f"--antialias {args.antialias} traces further rays through the marked pixels: it goes with --transfer off, not --transfer {args.transfer}")
     try:
         return Antialias(samples=args.antialias, every_pixel=args.aa_all, **{k: v for k, v in given.items() if v is not None})
+    except ValueError as e:
+        ap.error(str(e))
+
+
+def parse_depth_of_field(ap: argparse.ArgumentParser, args):
+    """the relight.DepthOfField of --dof-aperture and its flags; None without it"""
+    given = {"focus_distance": args.dof_focus_distance, "focus_pixel": None if args.dof_focus_pixel is None else tuple(args.dof_focus_pixel),
+             "samples": args.dof_samples, "threshold": args.dof_threshold, "reach": args.dof_reach}
+    flags = [("--dof-aperture", args.dof_aperture)] + [("--dof-" + k.replace("_", "-"), v) for k, v in given.items()]
+    flags += [("--dof-all", args.dof_all or None), ("--dof-map", args.dof_map or None)]
+    if args.transfer != "off":
+        refuse_given(ap, flags, "a lens traces further rays through the marked pixels: {} goes with --transfer off, not --transfer " + args.transfer)
+    if args.dof_aperture is None:
+        refuse_given(ap, flags[1:], "{} needs --dof-aperture")
+        return None
+    if args.dof_focus_distance is not None and args.dof_focus_pixel is not None:
+        ap.error("--dof-focus-distance and --dof-focus-pixel exclude each other")
+    from .depth_of_field import DepthOfField
+    try:
+        return DepthOfField(args.dof_aperture, every_pixel=args.dof_all, **{k: v for k, v in given.items() if v is not None})
     except ValueError as e:
         ap.error(str(e))
 
@@ -454,6 +487,7 @@ def main(argv=None) -> int:
     sun_shadows, shadow_trace = parse_shadows(ap, args)
     display = parse_display(ap, args)
     antialias = parse_antialias(ap, args)
+    depth_of_field = parse_depth_of_field(ap, args)
     lights, light_shadows, light_trace, light_path = parse_lights(ap, args)
     atmosphere = parse_atmosphere(ap, args)
 
@@ -464,6 +498,11 @@ def main(argv=None) -> int:
 
     t0 = time.perf_counter()
     cams = load_camera_path(args.camera_path)
+    if depth_of_field is not None:
+        try:
+            depth_of_field.focus_index(cams.height, cams.width)
+        except ValueError as e:
+            ap.error(str(e))
     model, envmap, extraction = load_scene(args, daylight, suns)
     tally = Tally(t_load=time.perf_counter() - t0)
     os.makedirs(args.output_dir, exist_ok=True)
@@ -484,7 +523,7 @@ def main(argv=None) -> int:
     writer = FrameWriter(args, display, tally)
     shared = {"chunk": args.chunk, "display": display, "floats": writer.floats, "deferred": writer.deferred}
     if args.transfer == "off":
-        source = RenderSource(model, base, tally, antialias=antialias, extraction=extraction, **shared)
+        source = RenderSource(model, base, tally, antialias=antialias, extraction=extraction, depth_of_field=depth_of_field, **shared)
     else:
         source = BakedSource(model, envmap, tally, storage=args.transfer, sh_order=args.sh_order, **shared)
     t1 = time.perf_counter()
@@ -498,7 +537,7 @@ def main(argv=None) -> int:
     tally.t_render = time.perf_counter() - t1
     suns_per_render = 0 if sun is None else len(suns) if shots[0].sweep else 1
     tally.report(args, (cams.width, cams.height), display, antialias, shadow_trace, lights, light_trace, atmosphere, suns_per_render,
-                 bool(model.config.use_visibility))
+                 bool(model.config.use_visibility), depth_of_field=depth_of_field)
     return 0
 
 

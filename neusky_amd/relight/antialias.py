@@ -10,7 +10,8 @@ a Python float) join the outputs.
 
 S = 4, the thresholds (colour 0.1, depth 0.02, normal 15 degrees, accumulation 0.1, covered 0.5) and the slices of 2^18 marked pixels are
 design choices, not measurements.  The list of marked pixels is torch.nonzero of the mask: one host synchronisation per frame, for the
-count that sizes the second pass."""
+count that sizes the second pass.  `second_pass` is that pass without its mask: the slices, the chunks and the resolve, for any function
+from a slice of marked pixels to their rays; the lens of depth_of_field.py runs through it too."""
 from __future__ import annotations
 
 import math
@@ -170,26 +171,16 @@ def resolve(frame: torch.Tensor, samples: torch.Tensor, pixels: torch.Tensor, rg
     hip.aa_resolve(frame, samples.permute(2, 0, 1, 3), pixels, rgb)
 
 
-def antialias_frame(antialias: Antialias, runner, flat: RayBundle, shape, res: Dict[str, torch.Tensor], suns: int) -> Dict[str, torch.Tensor]:
-    """the second pass of FrameRenderer.render, between its chunk loop and `end`: res, the assembled first pass on the device (sun keys
-    with K leading), is resolved in place; -> aa_mask, aa_fraction.  suns: K, 0 for a frame under the sky alone.
-    The second pass's rays form one pixel-major stream that is cut into the runner's chunks at multiples of its chunk size, wherever a
-    slice of `batch_pixels` ends: a chunk that straddles two slices is run for each, so every ray sees the same chunk whatever the
-    slices, and the same bits."""
-    H, W = (int(v) for v in shape)
-    P, K = H * W, max(int(suns), 1)
-    mask = antialias.edge_mask(res["depth"], res["normal"], res["accumulation"], res["lin"])
-    if antialias.every_pixel:
-        pixels = torch.arange(P, device=mask.device)
-    else:
-        pixels = torch.nonzero(mask.view(-1)).view(-1)  # ascending; the one host synchronisation: the count sizes the second pass
-    E = int(pixels.shape[0])
-    added = {"aa_mask": mask.view(H, W, 1), "aa_fraction": E / max(P, 1)}
-    if E == 0:
-        return added
-    flat = _flat_float(flat)
-    offsets = antialias.sample_offsets(mask.device)
-    S1, chunk = antialias.samples - 1, runner.chunk
+def second_pass(runner, res: Dict[str, torch.Tensor], P: int, suns: int, pixels: torch.Tensor, rays, samples: int, batch_pixels: int) -> None:
+    """a frame's further rays, between FrameRenderer.render's chunk loop and its `end`: res, the assembled first pass on the device (sun
+    keys with K leading), is resolved in place at `pixels` [E] (ascending, pairwise distinct, not empty).  rays: a function from a slice of
+    `pixels` to the flat bundle of its samples - 1 rays per pixel, pixel-major; samples: S, the first pass included.  suns: K, 0 for a
+    frame under the sky alone.
+    The rays form one pixel-major stream that is cut into the runner's chunks at multiples of its chunk size, wherever a slice of
+    `batch_pixels` ends: a chunk that straddles two slices is run for each, so every ray sees the same chunk whatever the slices, and
+    the same bits."""
+    K, E = max(int(suns), 1), int(pixels.shape[0])
+    S1, chunk = samples - 1, runner.chunk
     total = E * S1
     # key -> (the frame [K', P, C], its rgb or None, K' of the chunk's rows [n, K', C] or [n, C])
     frames = {}
@@ -197,13 +188,13 @@ def antialias_frame(antialias: Antialias, runner, flat: RayBundle, shape, res: D
         if k in res:
             lead = K if (suns and k in ("lin", "shadow_map")) else 1
             frames[k] = (res[k].view(lead, P, -1), res["rgb"].view(lead, P, -1) if k == "lin" else None, lead)
-    for a in range(0, E, antialias.batch_pixels):
-        b = min(a + antialias.batch_pixels, E)
+    for a in range(0, E, batch_pixels):
+        b = min(a + batch_pixels, E)
         r0, r1 = a * S1, b * S1  # this slice's rays in the stream
         c0, c1 = r0 // chunk, -(-r1 // chunk)  # the chunks that hold them
         g1 = min(c1 * chunk, total)
         pa, pb = c0 * chunk // S1, -(-g1 // S1)  # the pixels those chunks touch
-        sub = _subpixel_flat(flat, H, W, pixels[pa:pb], offsets)
+        sub = rays(pixels[pa:pb])
         base = pa * S1
         X = {k: torch.empty(r1 - r0, lead, f.shape[-1], device=f.device) for k, (f, _, lead) in frames.items()}
         for c in range(c0, c1):
@@ -214,4 +205,27 @@ def antialias_frame(antialias: Antialias, runner, flat: RayBundle, shape, res: D
                 x[u - r0:v - r0].copy_(out[k][u - lo:v - lo].reshape(v - u, *x.shape[1:]))
         for k, (f, rgb, lead) in frames.items():
             resolve(f, X[k].view(b - a, S1, lead, -1), pixels[a:b], rgb)
+
+
+def antialias_frame(antialias: Antialias, runner, flat: RayBundle, shape, res: Dict[str, torch.Tensor], suns: int,
+                    mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """the antialiasing pass of FrameRenderer.render (`second_pass`): res is resolved in place; -> aa_mask, aa_fraction.  mask: uint8
+    [H, W] in place of the edge mask of `res`: what a frame with a depth of field, which takes the edge mask on its first pass and
+    leaves the pixels its lens marks to the lens, hands over."""
+    H, W = (int(v) for v in shape)
+    P = H * W
+    given = mask is not None
+    if not given:
+        mask = antialias.edge_mask(res["depth"], res["normal"], res["accumulation"], res["lin"])
+    if antialias.every_pixel and not given:
+        pixels = torch.arange(P, device=mask.device)
+    else:
+        pixels = torch.nonzero(mask.view(-1)).view(-1)  # ascending; the one host synchronisation: the count sizes the second pass
+    E = int(pixels.shape[0])
+    added = {"aa_mask": mask.view(H, W, 1), "aa_fraction": E / max(P, 1)}
+    if E == 0:
+        return added
+    flat = _flat_float(flat)
+    offsets = antialias.sample_offsets(mask.device)
+    second_pass(runner, res, P, suns, pixels, lambda px: _subpixel_flat(flat, H, W, px, offsets), antialias.samples, antialias.batch_pixels)
     return added

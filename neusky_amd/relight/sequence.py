@@ -14,6 +14,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from .depth_of_field import DepthOfField
 from .display import DisplayTransform
 from .envmap import z_rotation
 from .io import srgb_to_linear
@@ -68,6 +69,7 @@ class Frame:
     exposure: Optional[torch.Tensor] = None  # with a display transform and lamps: what the render showed the frame at, for the lamps' picture
     transmittance: Optional[torch.Tensor] = None  # under an atmosphere: T to each ray's depth (a sweep's frames share it)
     inscatter: Optional[torch.Tensor] = None  # under an atmosphere: what the medium added to the frame's `lin`
+    coc: Optional[torch.Tensor] = None  # with a depth of field: the circle of confusion in pixels (a sweep's frames share it)
 
 
 class Tally:
@@ -81,9 +83,10 @@ class Tally:
         self.light_rays = self.light_exhausted = 0  # of the lamps' shadow march
         self.sh_residual = self.sh_store = None  # of --sh-order: the largest light_residual so far, and a camera's (coefficients, bytes)
         self.transmittances = []  # of --fog-density: every render's mean transmittance, device tensors
+        self.focuses, self.lens_marked = [], []  # of --dof-aperture: every render's 1 / z_f (device tensors) and share of marked pixels
 
     def report(self, args, size, display, antialias, shadow_trace, lights, light_trace, atmosphere=None, suns: int = 0,
-               ddf_shadows: bool = True) -> None:
+               ddf_shadows: bool = True, depth_of_field=None) -> None:
         """size: the frames' (width, height); shadow_trace: of --sun-shadows sdf, else None; suns: per render; ddf_shadows: whether the
         model has a visibility network (without one the DDF mode shadows nothing); the rest as the parse_* functions return them"""
         transfer = "" if args.transfer == "off" else f" | transfer {args.transfer}: bake {self.t_bake:.3f}s relight {self.t_relight:.3f}s"
@@ -100,6 +103,11 @@ class Tally:
             how = "every pixel" if antialias.every_pixel else "the pixels its edge rule marks"
             print(f"antialias: {antialias.samples} samples through {how} | share of marked pixels: smallest {min(self.marked):.4g} "
                   f"largest {max(self.marked):.4g}")
+        if depth_of_field is not None and self.lens_marked:
+            how = "every pixel" if depth_of_field.every_pixel else "the pixels a blurred pixel's disc reaches"
+            z = [1.0 / v if v > 0.0 else math.inf for v in torch.cat([f.reshape(-1) for f in self.focuses]).tolist()]
+            print(f"depth of field: {depth_of_field.samples} samples through {how} | focus distance: smallest {min(z):.4g} largest {max(z):.4g} "
+                  f"| share of marked pixels: smallest {min(self.lens_marked):.4g} largest {max(self.lens_marked):.4g}")
         still = "{} of {} shadow rays ({:.3f}%) were still marching after {} steps (raise {} if that is too many)"
         if shadow_trace is not None:
             share = 100.0 * self.exhausted / max(self.shadow_rays, 1)
@@ -126,11 +134,12 @@ class RenderSource:
     """a shot's frames from model.frames.render: direct renders, sweeps, moving lamps, and extracted suns, which turn with their map.
     base: the run's FrameLighting; a shot replaces its rotation and, with them, the extracted sun and the first lamp."""
 
-    def __init__(self, model, base, tally: Tally, *, chunk: int, display, antialias, extraction, floats: bool, deferred: bool):
+    def __init__(self, model, base, tally: Tally, *, chunk: int, display, antialias, extraction, floats: bool, deferred: bool,
+                 depth_of_field=None):
         self.model, self.base, self.tally, self.chunk, self.extraction = model, base, tally, chunk, extraction
         self.display, self.floats, self.deferred = display, floats, deferred
         self.camera = self.rays = None  # of `open`
-        self.shown = {k: v for k, v in (("display", display), ("antialias", antialias)) if v is not None}
+        self.shown = {k: v for k, v in (("display", display), ("antialias", antialias), ("depth_of_field", depth_of_field)) if v is not None}
 
     def open(self, camera: int, rays) -> None:
         self.camera, self.rays = camera, rays
@@ -153,6 +162,10 @@ class RenderSource:
             tally.exposures.append(out["display_exposure"])
         if "antialias" in self.shown:
             tally.marked.append(out["aa_fraction"])
+        lens = "depth_of_field" in self.shown
+        if lens:
+            tally.focuses.append(out["dof_focus"])
+            tally.lens_marked.append(out["dof_fraction"])
         fogged = base.atmosphere is not None
         if fogged:
             tally.transmittances.append(out["atmosphere_transmittance"].mean())
@@ -161,7 +174,7 @@ class RenderSource:
             frame = Frame(self.camera, f, shadow=own("shadow_map") if base.suns is not None else None,
                           light_lin=out["light_lin"] if base.lights else None, aa_mask=out["aa_mask"] if "antialias" in self.shown else None,
                           transmittance=out["atmosphere_transmittance"] if fogged else None,
-                          inscatter=own("atmosphere_inscatter") if fogged else None)
+                          inscatter=own("atmosphere_inscatter") if fogged else None, coc=out["dof_coc"] if lens else None)
             if self.floats:
                 frame.rgb = own("rgb").clamp(0.0, 1.0).cpu().numpy()
             if display is not None:
@@ -217,7 +230,7 @@ class FrameWriter:
     The lamps' share of a frame goes through the frame's own path to a picture."""
 
     def __init__(self, args, display, tally: Tally):
-        """args: output_dir, sun_path and the flags save_hdr, save_linear, shadow_map, aa_mask, light_map, fog_map.  What the sources ask the
+        """args: output_dir, sun_path and the flags save_hdr, save_linear, shadow_map, aa_mask, light_map, fog_map, dof_map (and dof_reach, its scale).  What the sources ask the
         writer: floats, whether anything reads a frame's float image on the host, and deferred: under "sequence" the frames of a sun
         path are metered by the one render that yields them; any others are not rendered together, and wait"""
         self.args, self.display, self.tally = args, display, tally
@@ -246,6 +259,10 @@ class FrameWriter:
             Image.fromarray(grey, mode="L").save(self._path("shadow", frame, ".png"))
         if args.aa_mask and frame.aa_mask is not None:
             Image.fromarray(frame.aa_mask[..., 0].cpu().numpy() * np.uint8(255), mode="L").save(self._path("aa", frame, ".png"))
+        if frame.coc is not None and getattr(args, "dof_map", False):
+            reach = self.args.dof_reach if getattr(self.args, "dof_reach", None) is not None else DepthOfField.reach
+            c8 = torch.round((frame.coc[..., 0] / reach).clamp(0.0, 1.0).nan_to_num(0.0) * 255.0).to(torch.uint8)
+            Image.fromarray(c8.cpu().numpy(), mode="L").save(self._path("coc", frame, ".png"))
         if frame.transmittance is not None:
             if args.fog_map:
                 T8 = np.round(frame.transmittance.clamp(0.0, 1.0).cpu().numpy() * 255.0).astype(np.uint8)
