@@ -1239,6 +1239,64 @@ int nsky_lights_composite(const float* base, int64_t base_stride, const float* t
                           float* light_lin, float* visibility, nsky_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Solid props placed in a frame (neusky_amd/relight/props.py, csrc/props.hip): spheres and yawed boxes that the frame's light shades,
+ * that the scene shadows and that shadow the scene.  Every shading kernel of a frame is a sum over a ray's samples, and every shadow a
+ * factor on a visibility tensor, so a prop changes none of them: its hit becomes one more sample of the ray, and every visibility the
+ * frame forms is multiplied by an analytic occlusion test.
+ *   props:  fp32 [P,16] in device memory, 1 <= P <= NSKY_MAX_PROPS; columns kind (0 sphere, 1 box), centre c (1..3), half-extents h
+ *           (4..6; a sphere: its radius r three times), cos yaw, sin yaw (7, 8), albedo (9..11), visible (12: 0 or 1), casts_shadows
+ *           (13: 0 or 1), pad (14, 15).  Only P is by value: a captured graph replays under props that moved, turned, changed size,
+ *           colour or flags.
+ *   interval:  of a line x(t) = o + t d inside prop p, formed in fp64 from the fp32 inputs, each product, sum and quotient rounded once
+ *           (no fused multiply-add).  d need not be unit.
+ *           sphere:  oc = o - c, a = <d,d>, b = <oc,d>, q = <oc,oc> - r r, disc = b b - a q (dot products x, y, z ascending).  No
+ *                    interval unless disc > 0; then t_in = (-b - sqrt(disc)) / a, t_out = (-b + sqrt(disc)) / a.
+ *           box:     o' = (cos oc_x + sin oc_y, cos oc_y - sin oc_x, oc_z) and d' likewise: oc and d turned by -yaw about z.  Axis i with
+ *                    d'_i != 0 gives the slab parameters (-h_i - o'_i) / d'_i and (h_i - o'_i) / d'_i; an axis with d'_i == 0 gives no
+ *                    interval unless |o'_i| < h_i, and otherwise constrains nothing.  t_in is the largest of the per-axis minima
+ *                    (-inf when no axis constrains), t_out the smallest of the per-axis maxima (+inf).  An interval only if
+ *                    t_in < t_out.  The entry axis is the one that gave t_in, ties to the lowest axis.
+ *   seen:   only props with `visible`.  A ray enters prop p at t_in when it has an interval and t_in > 0: a camera inside a prop does
+ *           not see it.  The smallest t_in wins, ties to the lowest index.  The normal is the outward unit normal at the entry point:
+ *           a sphere's (oc + t_in d) / r divided by its length; a box's entry axis signed against d' (-1 when d'_axis > 0), turned
+ *           back by +yaw: (s cos, s sin, 0), (-s sin, s cos, 0) or (0, 0, s), the block's fp32 cos and sin as they are.  t_hit, the
+ *           normal and the albedo are rounded once to fp32.
+ *   insert: sample s < S of a ray is in front when fl32(fl32(starts + ends) / 2) < t_hit, the midpoint Frustums.get_positions forms.
+ *           Its new weight is its weight if in front, else 0; its starts, ends, albedo and normal are copied bit for bit.  Sample S is the
+ *           prop: weight clamp(1 - sum of the weights in front, 0, 1), the sum in fp64 in sample order, rounded once (the transmittance
+ *           nsky_hemi_composite_fwd's own background term bg (1 - acc) would use there), 0 when the ray enters no prop; albedo and
+ *           normal the prop's, zeros when none; starts = ends = t_hit, or ends[S-1] when none, so that the global depth bounds of
+ *           nsky_ray_reduce_fwd see no infinity.  A sample that straddles t_hit is kept or dropped whole: that is the approximation of
+ *           this seam, as good as the sampler's spacing at the prop.
+ *   shadow: entry (m, n) of a visibility tensor is the light n reaches from point m.  x' = x + bias n^ in fp64, n^ the normal divided
+ *           by its length in fp64; a zero or non-finite normal, or none, gives no lift (nsky_sphere_trace_begin's rule, without its
+ *           fallback).  Towards a light at infinity the line is x' + t d_n with t_max = +inf.  Towards a lamp at p_n with clearance_n:
+ *           v = p_n - x', len = |v|, d = v / len, t_max = len - clearance_n; len == 0 leaves the entry.  The entry is multiplied by 0
+ *           when some prop with `casts_shadows` has an interval with t_out > 0 and t_in < t_max, and is otherwise neither read nor
+ *           written.  Shadow edges are hard: a penumbra for analytic props is out of scope.
+ * nsky_props_intersect:  origins, directions [R,3]; props [P,16]  ->  t_hit [R] (+inf for none), id [R] (int32, -1), normal, albedo [R,3]
+ *                        (zeros for none).  One thread per ray, the block staged once per workgroup in LDS.
+ * nsky_props_insert:     weights, starts, ends [R,S]; albedo, normals [R,S,3]; t_hit, id, hit_normal, hit_albedo as above  ->  the five
+ *                        arrays with S + 1 samples.  One wave per ray; any S >= 1.
+ * nsky_props_occlude:    x [M,3]; normals [M,3] or NULL; either directions [N,3], or targets [N,3] with clearance [N]; bias [1] (device
+ *                        memory); props  ->  vis, in place, entry (m, n) at vis[m stride_m + n stride_n] (strides in floats, >= 0): the
+ *                        sky's [R,D], the suns' [K,R], the lamps' [L,R] and the shafts' rows without a transpose.  One thread per entry,
+ *                        consecutive threads along the smaller stride, the block in LDS.
+ * prop_bias = 1e-2, the midpoint rule and NSKY_MAX_PROPS = 64 (the block then fills 4 KiB of LDS) are design choices, not measurements.
+ * Flat indices are int64.  No atomics, no reduction across threads but the ordered sum: every output is bitwise repeatable.  Nothing is
+ * read on the host. */
+#define NSKY_PROP_FLOATS 16
+#define NSKY_MAX_PROPS 64
+int nsky_props_intersect(const float* origins, const float* directions, const float* props, int64_t R, int32_t P, float* t_hit, int32_t* id,
+                         float* normal, float* albedo, nsky_stream_t stream);
+int nsky_props_insert(const float* weights, const float* starts, const float* ends, const float* albedo, const float* normals,
+                      const float* t_hit, const int32_t* id, const float* hit_normal, const float* hit_albedo, int64_t R, int32_t S,
+                      float* weights_out, float* starts_out, float* ends_out, float* albedo_out, float* normals_out, nsky_stream_t stream);
+int nsky_props_occlude(const float* x, const float* normals, const float* directions, const float* targets, const float* clearance,
+                       const float* bias, const float* props, int64_t M, int64_t N, int32_t P, float* vis, int64_t stride_m,
+                       int64_t stride_n, nsky_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Height fog and haze with shadowed sun shafts (neusky_amd/relight/atmosphere.py, csrc/atmosphere.hip): a participating medium between
  * the camera and what a frame shows, applied to a chunk's linear image after its suns and lamps.
  * The medium:

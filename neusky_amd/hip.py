@@ -1758,6 +1758,68 @@ def lights_composite(base, t, vis, acc, acc_threshold, lights, rgb, lin=None, li
                             _c(visibility), stream_ptr()), "nsky_lights_composite")
 
 
+# ---- solid props placed in a frame (relight/props.py, csrc/props.hip)
+PROP_FLOATS = 16  # NSKY_PROP_FLOATS: kind, c (1..3), h (4..6), cos yaw, sin yaw, albedo (9..11), visible, casts_shadows, -, -
+MAX_PROPS = 64  # NSKY_MAX_PROPS
+_props_intersect = _sig("nsky_props_intersect", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                        C.c_void_p, C.c_void_p)
+_props_insert = _sig("nsky_props_insert", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                     C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_props_occlude = _sig("nsky_props_occlude", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                      C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
+
+
+def _props_block(props):
+    P = props.shape[0]
+    assert props.shape == (P, PROP_FLOATS) and 1 <= P <= MAX_PROPS and props.dtype == torch.float32 and props.is_contiguous()
+    return P
+
+
+def props_intersect(origins, directions, props, t_hit, prop_id, normal, albedo):
+    """origins, directions: fp32 [R, 3]; props [P, 16] -> t_hit [R] (+inf for none), prop_id int32 [R] (-1), normal, albedo [R, 3]"""
+    R, P = origins.shape[0], _props_block(props)
+    assert origins.shape == (R, 3) and directions.shape == (R, 3) and normal.shape == (R, 3) and albedo.shape == (R, 3)
+    assert t_hit.shape == (R,) and prop_id.shape == (R,) and prop_id.dtype == torch.int32
+    assert all(x.dtype == torch.float32 for x in (origins, directions, t_hit, normal, albedo))
+    check(_props_intersect(_c(origins), _c(directions), ptr(props), R, P, _c(t_hit), _c(prop_id), _c(normal), _c(albedo), stream_ptr()),
+          "nsky_props_intersect")
+
+
+def props_insert(weights, starts, ends, albedo, normals, t_hit, prop_id, hit_normal, hit_albedo, weights_out, starts_out, ends_out, albedo_out,
+                 normals_out):
+    """weights, starts, ends: fp32 [R, S]; albedo, normals [R, S, 3]; the four outputs of props_intersect -> the five arrays with S + 1
+    samples"""
+    R, S = _ray_samples(albedo, normals, weights)
+    assert S >= 1 and starts.shape == (R, S) and ends.shape == (R, S) and t_hit.shape == (R,) and prop_id.shape == (R,)
+    assert hit_normal.shape == (R, 3) and hit_albedo.shape == (R, 3) and prop_id.dtype == torch.int32
+    assert all(x.shape == (R, S + 1) for x in (weights_out, starts_out, ends_out)) and albedo_out.shape == (R, S + 1, 3)
+    assert normals_out.shape == (R, S + 1, 3)
+    assert all(x.dtype == torch.float32 for x in (starts, ends, t_hit, hit_normal, hit_albedo, weights_out, starts_out, ends_out, albedo_out,
+                                                  normals_out))
+    check(_props_insert(_c(weights), _c(starts), _c(ends), _c(albedo), _c(normals), _c(t_hit), _c(prop_id), _c(hit_normal), _c(hit_albedo), R, S,
+                        _c(weights_out), _c(starts_out), _c(ends_out), _c(albedo_out), _c(normals_out), stream_ptr()), "nsky_props_insert")
+
+
+def props_occlude(x, normals, bias, props, vis, directions=None, targets=None, clearance=None):
+    """x: fp32 [M, 3]; normals [M, 3] or None; either directions [N, 3] (lights at infinity) or targets [N, 3] with clearance [N] (lamps);
+    bias [1] (device); props [P, 16] -> vis: fp32 [M, N] through its strides (a transposed view of [N, M] serves), in place: 0 where a
+    shadow-casting prop stands between point m and light n"""
+    M, P = x.shape[0], _props_block(props)
+    towards = directions if directions is not None else targets
+    assert (directions is None) != (targets is None) and (targets is None) == (clearance is None)
+    N = towards.shape[0]
+    assert x.shape == (M, 3) and towards.shape == (N, 3) and (normals is None or normals.shape == (M, 3)) and bias.numel() == 1
+    assert clearance is None or clearance.shape == (N,)
+    assert all(t is None or t.dtype == torch.float32 for t in (x, normals, towards, clearance, bias, vis))
+    if tuple(vis.shape) != (M, N):
+        raise ValueError(f"vis: [{M}, {N}] (points, lights), got {tuple(vis.shape)}")
+    sm, sn = vis.stride()
+    if vis.numel() and not (((N == 1 or sn >= 1) and (M == 1 or sm >= N * sn)) or ((M == 1 or sm >= 1) and (N == 1 or sn >= M * sm))):
+        raise ValueError(f"vis: strides {vis.stride()} of {tuple(vis.shape)} overlap")
+    check(_props_occlude(_c(x), _c(normals), _c(directions), _c(targets), _c(clearance), ptr(bias), ptr(props), M, N, P, ptr(vis), max(sm, 0),
+                         max(sn, 0), stream_ptr()), "nsky_props_occlude")
+
+
 # ---- height fog and haze with shadowed sun shafts (relight/atmosphere.py, csrc/atmosphere.hip)
 ATMOSPHERE_FLOATS = 12  # NSKY_ATMOSPHERE_FLOATS: density (0..2), albedo (3..5), H (0: homogeneous), base_height, g, far, background, -
 ATMOSPHERE_MAX_SHAFTS = 64

@@ -20,6 +20,7 @@ from ..cameras.rays import RayBundle
 from ..field_components.neusky_fieldheadnames import FieldHeadNames, NeuSkyFieldHeadNames
 from ..relight.lighting import FrameLighting, light_colours
 from ..relight.lights import lights_block, trace_light_shadows
+from ..relight.props import PROP_BIAS, as_props, occlude_by_props, props_block
 from ..relight.shadows import trace_params, trace_sun_shadows
 from ..relight.transfer import bake_rows
 
@@ -52,6 +53,9 @@ FrameLights = namedtuple("FrameLights", "block acc_threshold params steps grace 
 # a relight.Atmosphere: params: the kernels' parameter block [12] (include/neusky_hip.h: every number of the medium); abar [Kb, 3]: the
 # mean light colour of each base image's sky; samples: shaft_samples M, a Python number, a by-value argument of both kernels
 FrameAtmosphere = namedtuple("FrameAtmosphere", "params abar samples")
+# P relight.Prop placed in the frame: block [P, 16] (include/neusky_hip.h) and the parameter block [1]: prop_bias, the lift of a shadow
+# ray's start point off the rendered surface.  Geometry, not light: it travels beside the FrameLighting, not in it
+FrameProps = namedtuple("FrameProps", "block params")
 
 
 @dataclass
@@ -61,7 +65,7 @@ class FrameLight:
     daylight sky (which takes the place of the latent's: `cols` is then not decoded and not read), a shadow march in place of the suns'
     DDF queries, lamps inside the scene on top of whichever of these lights it; `linear`: a frame under the sky alone also keeps its
     linear image `lin` (a sun frame and a frame with lamps or an atmosphere always do), for a display transform; a medium the frame is
-    seen through, applied last"""
+    seen through, applied last; props placed in the scene, which are no light at all but travel with it into every chunk"""
     dirs: torch.Tensor
     cols: torch.Tensor
     sel: torch.Tensor
@@ -76,6 +80,7 @@ class FrameLight:
     linear: bool = False
     lights: Optional[FrameLights] = None
     atmosphere: Optional[FrameAtmosphere] = None
+    props: Optional[FrameProps] = None
     key: tuple = field(init=False)
 
     def __post_init__(self, rotation_values):
@@ -86,7 +91,8 @@ class FrameLight:
         angular diameter does; a sky frame that keeps its linear image says so (its chunk has one more output); a frame with lamps adds
         their number, whether their shadows are marched and that march's length and leaving phase, so a new position, intensity, cone,
         radius, eps or bias replays the chunk; a frame seen through an atmosphere adds its shaft samples and nothing else, so a new
-        density, height, albedo, anisotropy, far or background flag replays the chunk."""
+        density, height, albedo, anisotropy, far or background flag replays the chunk; a frame with props adds their number and nothing
+        else, so a prop that moves, turns, changes size, colour or flags, or a new prop_bias, replays the chunk."""
         env = self.envmap
         key = (self.cam, rotation_values) if env is None else ("envmap", env.data.data_ptr(), tuple(env.data.shape), env.convention)
         if self.daylight is not None:  # no latent is read: one chunk graph serves every camera
@@ -105,6 +111,8 @@ class FrameLight:
             key = (key, ("lights", self.lights.block.shape[0], self.lights.shadows, self.lights.steps, self.lights.grace))
         if self.atmosphere is not None:
             key = (key, ("atmosphere", self.atmosphere.samples))
+        if self.props is not None:
+            key = (key, ("props", self.props.block.shape[0]))
         self.key = key
 
     @property
@@ -120,21 +128,46 @@ def shade(model, light: FrameLight, so: Dict[str, Any], ray_bundle: RayBundle) -
     the light's index leading; the chunk's own form is made here, once: ray-major views of that storage, [0] for a frame without suns."""
     if light.shading == "bake":
         fo = so["field_outputs"]
-        visibility = so["visibility_dict"]["visibility"] if model.config.use_visibility else None
+        visibility = sky_visibility(model, so)
         return bake_rows(fo[NeuSkyFieldHeadNames.ALBEDO], fo[FieldHeadNames.NORMALS], so["weights"][..., 0], so["illumination_directions"],
                          visibility, light.bake)
     if light.sun is not None:
-        out = _sun_outputs(model, light.sun, so, ray_bundle, light.daylight, light.trace)
+        out = _sun_outputs(model, light.sun, so, ray_bundle, light.daylight, light.trace, light)
     elif light.linear or light.lights is not None or light.atmosphere is not None:  # (lamps and fog add to the linear image)
         out = _sky_outputs(model, so)
     else:
         out = {"rgb": model.render_lambertian(so)[None]}
     if light.lights is not None:
-        out = _add_lights(model, light.lights, so, ray_bundle, out)
+        out = _add_lights(model, light.lights, so, ray_bundle, out, light)
     if light.atmosphere is not None:
         out = _apply_atmosphere(model, light, so, ray_bundle, out)
     image = (lambda t: t.permute(1, 0, 2)) if light.sun is not None else (lambda t: t[0])
     return {k: image(v) if k in IMAGES else v.t() if k in SUN_MAPS + LIGHT_MAPS else v for k, v in out.items()}
+
+
+def sky_visibility(model, so: Dict[str, Any]) -> Optional[torch.Tensor]:
+    """the sky's visibility [R, D] of a chunk, or None: the DDF's, or, in a frame with props, the one their occlusion was applied to
+    (sample_and_forward_field: ones times the occlusion on a model without a visibility field)"""
+    if "prop_sky_visibility" in so:
+        return so["prop_sky_visibility"]
+    return so["visibility_dict"]["visibility"].contiguous() if model.config.use_visibility else None
+
+
+def ray_points(origins: torch.Tensor, directions: torch.Tensor, depth: torch.Tensor) -> torch.Tensor:
+    """the points [R, 3] a prop's shadow is looked up from: o + d depth in fp32, the product and the sum rounded once each"""
+    return (origins.detach() + directions.detach() * depth.detach().reshape(-1, 1)).contiguous()
+
+
+def _occluded(light: FrameLight, so: Dict[str, Any], vis: Optional[torch.Tensor], n: int, **towards) -> Optional[torch.Tensor]:
+    """vis [n, R], a chunk's visibility of n lights from its rendered surface points (None: ones), times the props' occlusion towards
+    them; untouched in a frame without props"""
+    if light.props is None:
+        return vis
+    x = so["prop_points"]
+    if vis is None:
+        vis = torch.ones(n, x.shape[0], device=x.device)
+    occlude_by_props(vis.t(), x, so["normal"].detach().contiguous(), light.props.params, light.props.block, **towards)
+    return vis
 
 
 def chunk_keys(lighting: FrameLighting, linear: bool = False):
@@ -161,13 +194,12 @@ def _sky_outputs(model, so: Dict[str, Any]) -> Dict[str, torch.Tensor]:
     rgb, lin = torch.empty(R, 3, device=dev), torch.empty(R, 3, device=dev)
     hip.hemi_composite_fwd(a, n, so["weights"][..., 0].contiguous(), so["illumination_directions"].contiguous(),
                            so["hdr_illumination_colours"].contiguous(), so["cam_of_ray"],
-                           so["visibility_dict"]["visibility"].contiguous() if model.config.use_visibility else None,
-                           so["hdr_background_colours"].contiguous(), rgb, lin)
+                           sky_visibility(model, so), so["hdr_background_colours"].contiguous(), rgb, lin)
     return {"rgb": rgb[None], "lin": lin[None]}
 
 
 def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundle, daylight: Optional[FrameDaylight] = None,
-                 trace: Optional[FrameTrace] = None) -> Dict[str, torch.Tensor]:
+                 trace: Optional[FrameTrace] = None, light: Optional[FrameLight] = None) -> Dict[str, torch.Tensor]:
     """a chunk lit by its sky and the frame's K suns (include/neusky_hip.h): the hemisphere kernel's linear image, one DDF query per
     (ray, sun), the sun transfer and the composite: rgb, lin [K, R, 3], shadow_map, shadow_difference [K, R].
     Under a daylight sky the linear image is one per sun [K, R, 3]: the chunk's radiance transfer (fp32, in a scratch) relit by the K
@@ -175,13 +207,14 @@ def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundl
     With `trace` the K visibilities come from a march through the SDF instead of the DDF (whether or not the model has one), from the
     chunk's rendered depth along the ray and its rendered normal; `shadow_difference`, a DDF quantity, is then zero, and `shadow_status`
     [K, R] (int8) is the march's own verdict on each shadow ray (relight.shadows: HIT, ESCAPED, EXHAUSTED), before the set-sun and
-    accumulation rules."""
+    accumulation rules.  In a frame with props (`light`) the K visibilities, ones when there are none, are multiplied by the props'
+    occlusion along the K sun directions before the composite: `shadow_map` shows the props' shadows too."""
     fo = so["field_outputs"]
     a, n = fo[NeuSkyFieldHeadNames.ALBEDO].contiguous(), fo[FieldHeadNames.NORMALS].contiguous()
     w = so["weights"][..., 0].contiguous()
     R, K, dev = a.shape[0], sun.dirs.shape[0], a.device
     use_visibility = model.config.use_visibility
-    vis_sky = so["visibility_dict"]["visibility"].contiguous() if use_visibility else None
+    vis_sky = sky_visibility(model, so)
     if daylight is None:
         lin_sky = torch.empty(R, 3, device=dev)
         hip.hemi_composite_fwd(a, n, w, so["illumination_directions"].contiguous(), so["hdr_illumination_colours"].contiguous(),
@@ -203,6 +236,8 @@ def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundl
                                               sun.scale, compute_shadow_map=True, sel=sun.sel)
         vis = vd["visibility"].t().contiguous()  # [K, R]
         diff = vd["difference"].view(R, K)
+    if light is not None:
+        vis = _occluded(light, so, vis, K, directions=sun.dirs)
     t = torch.empty(K, R, 3, device=dev)
     hip.sun_transfer(a, n, w, sun.dirs, t)
     rgb, lin, shadow = torch.empty(K, R, 3, device=dev), torch.empty(K, R, 3, device=dev), torch.empty(K, R, device=dev)
@@ -215,7 +250,8 @@ def _sun_outputs(model, sun: FrameSuns, so: Dict[str, Any], ray_bundle: RayBundl
     return out
 
 
-def _add_lights(model, lights: FrameLights, so: Dict[str, Any], ray_bundle: RayBundle, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+def _add_lights(model, lights: FrameLights, so: Dict[str, Any], ray_bundle: RayBundle, out: Dict[str, torch.Tensor],
+                light: Optional[FrameLight] = None) -> Dict[str, torch.Tensor]:
     """the frame's L lamps on top of a chunk lit by its sky or by sky and K suns (out: rgb, lin [Kb, R, 3]): the lamps' transfer at the
     samples' positions, a march from each ray's rendered surface point to each lamp (or none), and the composite, which adds the one
     lamp image to every base image (include/neusky_hip.h).  `rgb` and `lin` are replaced by the lit ones; light_lin [R, 3],
@@ -232,6 +268,8 @@ def _add_lights(model, lights: FrameLights, so: Dict[str, Any], ray_bundle: RayB
         march = trace_light_shadows(model.field, ray_bundle.origins, ray_bundle.directions, so["p2p_dist"], so["normal"], lights.block,
                                     lights.params, lights.steps, lights.grace)
         vis, status = march.visibility, march.status
+    if light is not None:  # (a prop between the point and the lamp; one behind the lamp shadows nothing)
+        vis = _occluded(light, so, vis, L, lights=lights.block)
     base = out["lin"]
     rgb, lin, light_lin, V = torch.empty_like(base), torch.empty_like(base), torch.empty(R, 3, device=dev), torch.empty(L, R, device=dev)
     hip.lights_composite(base, t, vis, so["accumulation"].reshape(-1).contiguous(), lights.acc_threshold, lights.block, rgb, lin, light_lin, V)
@@ -252,16 +290,22 @@ def _apply_atmosphere(model, light: FrameLight, so: Dict[str, Any], ray_bundle: 
     Kb, R, dev = lin_in.shape[0], lin_in.shape[1], lin_in.device
     o, d = ray_bundle.origins.detach().contiguous(), ray_bundle.directions.detach().contiguous()
     M, vis = atm.samples, None
-    if M > 0 and (light.trace is not None or model.config.use_visibility):
+    props = light.props if suns else None  # (shafts are the suns': a sky frame has none to occlude)
+    if M > 0 and (light.trace is not None or model.config.use_visibility or props is not None):
         rows_o, rows_d, rows_t = torch.empty(M * R, 3, device=dev), torch.empty(M * R, 3, device=dev), torch.empty(M * R, device=dev)
         hip.atmosphere_rows(o, d, atm.params, M, rows_o, rows_d, rows_t)
         if light.trace is not None:
             march = trace_sun_shadows(model.field, rows_o, rows_d, rows_t, torch.zeros(M * R, 3, device=dev), sun.dirs, light.trace.params,
                                       light.trace.steps, light.trace.grace)
             vis = march.visibility.view(Kb, M, R).permute(1, 0, 2)
-        else:
+        elif model.config.use_visibility:
             vd = model.compute_visibility_compact(rows_o, rows_d, rows_t[:, None], sun.dirs, sun.threshold, sun.scale, sel=sun.sel)
             vis = vd["visibility"].view(M, R, Kb).permute(0, 2, 1)
+        else:
+            vis = torch.ones(M, R, Kb, device=dev).permute(0, 2, 1)
+        if props is not None:  # every (row, sun) entry, from the rows' own points; no normal, so no lift.  (a view, or an error)
+            occlude_by_props(vis.permute(0, 2, 1).view(M * R, Kb), ray_points(rows_o, rows_d, rows_t), None, props.params, props.block,
+                    directions=sun.dirs)
     rgb, lin, inscatter = torch.empty(Kb, R, 3, device=dev), torch.empty(Kb, R, 3, device=dev), torch.empty(Kb, R, 3, device=dev)
     transmittance = torch.empty(R, 3, device=dev)
     hip.atmosphere_apply(o, d, so["p2p_dist"].detach().reshape(-1).contiguous(), so["accumulation"].reshape(-1).contiguous(), lin_in,
@@ -278,8 +322,8 @@ class FrameRenderer:
         self.active: Optional[FrameLight] = None
         # the static buffers, one named tuple per key, kept for the model's lifetime (a captured chunk holds their pointers): "sky" ->
         # FrameSky; ("envmap", device) -> FrameEnvmap; ("suns", K, device) -> FrameSuns; ("daylight", K, D, device) -> FrameDaylight;
-        # ("trace", device) -> FrameTrace; ("lights", L, device) -> FrameLights; ("atmosphere", Kb, device) -> FrameAtmosphere.  Only "sky"
-        # is ever allocated again, on a new D or device, and takes the runners with it
+        # ("trace", device) -> FrameTrace; ("lights", L, device) -> FrameLights; ("atmosphere", Kb, device) -> FrameAtmosphere;
+        # ("props", P, device) -> FrameProps.  Only "sky" is ever allocated again, on a new D or device, and takes the runners with it
         self.static: Dict[Any, tuple] = {}
         # a chunk graph cached under a rotation's values reads the rotation through the pointer it was captured with: the first tensor
         # seen with these values is kept, and serves every later frame that asks for them (one entry per value ever seen)
@@ -293,10 +337,12 @@ class FrameRenderer:
             st = self.static[key] = allocate()
         return st
 
-    def begin(self, camera_index: int, lighting: FrameLighting, *, linear: bool = False) -> None:
+    def begin(self, camera_index: int, lighting: FrameLighting, *, linear: bool = False, props=None, prop_bias: float = PROP_BIAS) -> None:
         """the device state of a frame lit by `lighting`, active until `end`: the rotation pinned, the static buffers filled.  linear: a
-        frame under the sky alone keeps its linear image `lin` too (it joins the chunk runner's key only when set)"""
+        frame under the sky alone keeps its linear image `lin` too (it joins the chunk runner's key only when set).  props: a
+        relight.Prop or a sequence of them, placed in the scene; prop_bias: the lift of their shadow rays off the rendered surface"""
         model = self.model
+        props = self._props(props, prop_bias, lighting)  # (refused before anything is written)
         rotation, envmap = lighting.rotation, lighting.envmap
         fixed = model.config.fix_test_illumination_directions
         dirs, sel = model.illumination_sampler.on_device(model.device, apply_random_rotation=False if fixed else None)
@@ -320,7 +366,7 @@ class FrameRenderer:
         daylight = self._daylight(lighting.daylight, sky.dirs, suns)
         self.active = FrameLight(sky.dirs, sky.cols, sky.sel, cam, rotation, values, self._envmap(envmap, rotation), suns, lighting.bake,
                                  daylight, self._trace(lighting.shadow_trace), bool(linear), self._lights(lighting),
-                                 self._atmosphere(lighting.atmosphere, sky, suns, daylight))
+                                 self._atmosphere(lighting.atmosphere, sky, suns, daylight), props)
 
     def _envmap(self, envmap, rotation) -> Optional[FrameEnvmap]:
         if envmap is None:
@@ -406,6 +452,21 @@ class FrameRenderer:
         st.abar.copy_(sky.cols[0].mean(0, keepdim=True).expand(Kb, 3) if daylight is None else daylight.lights.mean(1))
         return st._replace(samples=atmosphere.shaft_samples)
 
+    def _props(self, props, prop_bias: float, lighting: FrameLighting) -> Optional[FrameProps]:
+        props = as_props(props)
+        if not props:
+            return None
+        if lighting.bake is not None:
+            raise ValueError("a bake keeps the scene's own transfer: props are placed in a rendered frame, not in a bake")
+        bias = float(prop_bias)
+        if not (bias >= 0.0 and bias < float("inf")):
+            raise ValueError(f"prop_bias is finite and >= 0, got {prop_bias!r}")
+        P, dev = len(props), self.model.device
+        st = self._static(("props", P, str(dev)), lambda: FrameProps(torch.empty(P, hip.PROP_FLOATS, device=dev), torch.empty(1, device=dev)))
+        st.block.copy_(props_block(props))
+        st.params.copy_(torch.tensor([bias], dtype=torch.float32))
+        return st
+
     def end(self) -> None:
         self.active = None
 
@@ -428,7 +489,7 @@ class FrameRenderer:
     @torch.no_grad()
     def render(self, camera_ray_bundle: RayBundle, lighting: FrameLighting, *, to_cpu: bool = False, camera_index: Optional[int] = None,
                chunk: Optional[int] = None, use_graph: bool = True, display=None, antialias=None,
-               depth_of_field=None) -> Dict[str, torch.Tensor]:
+               depth_of_field=None, props=None, prop_bias: float = PROP_BIAS) -> Dict[str, torch.Tensor]:
         """model.get_outputs_for_camera_ray_bundle, which documents the chunking and the outputs.  display: a relight.DisplayTransform of
         the frame's linear image, metered where the accumulation exceeds its meter_mask_threshold: adds display_rgb8, display_rgb and
         display_exposure (and, to a frame under the sky alone, its `lin`); it runs on the assembled frame, after the chunks, so its
@@ -440,7 +501,10 @@ class FrameRenderer:
         rays through the pixels a blurred pixel's disc reaches, through the same runner, resolved into the same keys; adds dof_coc,
         dof_mask, dof_fraction and dof_focus.  With antialias as well the edge mask is taken on the first pass, the lens pass runs, and
         the antialiasing pass takes the edge-marked pixels the lens did not mark (their lens samples are jittered inside the pixel
-        already): aa_mask reports exactly those."""
+        already): aa_mask reports exactly those.  props, prop_bias: relight.Prop placed in the scene (`begin`): every output is then that of
+        the scene with the props in it; adds prop_id (int32: the nearest visible prop the pixel's ray enters, -1 for none, whatever
+        stands in front of it) and prop_weight (the share of the pixel that is the prop), which both second passes resolve as they
+        do `accumulation`, keeping the centre ray's prop_id."""
         model = self.model
         assert not model.training, "call model.eval() first"
         chunk = chunk or max(model.config.eval_num_rays_per_chunk, 4096)
@@ -470,10 +534,12 @@ class FrameRenderer:
             depth_of_field.focus_index(int(shape[0]), int(shape[1]))  # (a focus pixel outside the frame: refused before anything runs)
         passes = antialias is not None or depth_of_field is not None
         linear = display is not None or passes
-        self.begin(camera_index, lighting, linear=linear)
+        self.begin(camera_index, lighting, linear=linear, props=props, prop_bias=prop_bias)
         suns = lighting.suns
         lit, sun_keys = chunk_keys(lighting, linear)
         keys = ["rgb", "albedo", "accumulation", "depth", "p2p_dist", "normal"] + [k for k in lit if k != "rgb"]
+        if self.active.props is not None:
+            keys += ["prop_id", "prop_weight"]
         out = {k: [] for k in keys}
         early = to_cpu and not passes  # (a second pass resolves on the device: its frame goes to the host afterwards)
         try:

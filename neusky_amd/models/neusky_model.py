@@ -37,7 +37,8 @@ from ..model_components.renderers import RGBLambertianRendererWithVisibility
 from ..utils.utils import device_rng, device_rng_seed, linear_to_sRGB, to_device_async
 from ..plugin import ConfigBase, ModelBase
 from ..relight.lighting import FrameLighting, ray_background
-from .frame import FrameRenderer, shade
+from ..relight.props import PROP_BIAS, insert_props, occlude_by_props
+from .frame import FrameRenderer, ray_points, shade
 
 
 def _default_loss_inclusions() -> Dict[str, Any]:  # neusky/configs/neusky_config.py:102-126
@@ -507,6 +508,20 @@ class NeuSkyFactoModel(ModelBase):
                     t.record_stream(main)  # allocated on the side stream, consumed on this one from here on
         else:
             dirs, cam_colours, cam_of_ray, hdr_bg, sel = self.sample_illumination_compact(cam, ray_bundle.directions, rotation, randoms)
+        frame = None if self.training else self.frames.active
+        props = None if frame is None else frame.props
+        if props is not None:
+            # the seam of the seen prop (relight/props.py): the nearest prop a ray enters becomes its sample S, the samples behind it lose
+            # their weight.  From here every reduction, shading kernel and shadow query sees the scene with the props in it
+            fr = ray_samples.frustums
+            ps = insert_props(ray_bundle.origins, ray_bundle.directions, weights[..., 0], fr.starts[..., 0], fr.ends[..., 0],
+                              field_outputs[NeuSkyFieldHeadNames.ALBEDO], field_outputs[FieldHeadNames.NORMALS], props.block)
+            S1 = ps.weights.shape[1]
+            weights = ps.weights[..., None]
+            field_outputs = {**field_outputs, NeuSkyFieldHeadNames.ALBEDO: ps.albedo, FieldHeadNames.NORMALS: ps.normals}
+            ray_samples = RaySamples(frustums=Frustums(
+                origins=fr.origins[:, :1].expand(-1, S1, -1), directions=fr.directions[:, :1].expand(-1, S1, -1),
+                starts=ps.starts[..., None], ends=ps.ends[..., None]), camera_indices=ray_samples.camera_indices)
         out: Dict[str, Any] = {
             "ray_samples": ray_samples, "field_outputs": field_outputs, "weights": weights,
             "bg_transmittance": field_outputs["bg_transmittance"], "weights_list": weights_list, "sbins_list": sbins_list,
@@ -525,6 +540,14 @@ class NeuSkyFactoModel(ModelBase):
             out["visibility_dict"] = self.compute_visibility_compact(ray_bundle.origins, ray_bundle.directions, p2p_vis, dirs,
                                                              self.visibility_threshold, self.sigmoid_scale, sel=sel)
             out["depth"] = depth
+        if props is not None:
+            # the seam of the shadowing prop: the sky's visibility [R, D] (ones on a model without a visibility field) times the props'
+            # occlusion from the rendered surface point along the frame's D directions; the suns', the lamps' and the shafts': frame.py
+            x = ray_points(ray_bundle.origins, ray_bundle.directions, p2p_dist)
+            vis = (out["visibility_dict"]["visibility"].contiguous() if self.config.use_visibility
+                   else torch.ones(x.shape[0], dirs.shape[0], device=x.device))
+            out.update(prop_id=ps.prop_id[:, None], prop_weight=ps.weights[:, S1 - 1:S1], prop_points=x,
+                       prop_sky_visibility=occlude_by_props(vis, x, out["normal"].detach().contiguous(), props.params, props.block, directions=dirs))
         if probe is not None:
             # (sic) the reference hands `deltas=gap` ([3]) to get_alpha, which broadcasts [P,1]*[3] -> three alphas
             # per point, one per axis gap (equal for the cubic scene box) (:715-724, :732).  The probe points rode through the field
@@ -583,6 +606,8 @@ class NeuSkyFactoModel(ModelBase):
         outputs["normal_vis"] = (outputs["normal"] + 1.0) / 2.0
         if "grid_density" in so:
             outputs["grid_density"] = so["grid_density"]
+        if "prop_id" in so:  # (a frame with props)
+            outputs.update(prop_id=so["prop_id"], prop_weight=so["prop_weight"])
         if "visibility_dict" in so:
             outputs["visibility_batch"] = so["visibility_dict"]["visibility_batch"]
         return outputs
@@ -593,7 +618,8 @@ class NeuSkyFactoModel(ModelBase):
         return self.lambertian_renderer.forward_compact(
             albedos=fo[NeuSkyFieldHeadNames.ALBEDO], normals=fo[FieldHeadNames.NORMALS],
             light_directions=so["illumination_directions"], cam_colours=so["hdr_illumination_colours"],
-            cam_of_ray=so["cam_of_ray"], visibility=so["visibility_dict"]["visibility"] if self.config.use_visibility else None,
+            cam_of_ray=so["cam_of_ray"], visibility=so["prop_sky_visibility"] if "prop_sky_visibility" in so else
+            so["visibility_dict"]["visibility"] if self.config.use_visibility else None,
             background_illumination=so["hdr_background_colours"], weights=so["weights"])
 
     def get_loss_dict(self, outputs: Dict[str, Any], batch: Dict[str, Any], metrics_dict=None) -> Dict[str, torch.Tensor]:
@@ -882,13 +908,14 @@ class NeuSkyFactoModel(ModelBase):
                     shadow_threshold: Optional[float] = None, shadow_sigmoid_scale: Optional[float] = None,
                     accumulation_mask_threshold: float = 0.0, daylight=None, sun_shadows: str = "ddf",
                     shadow_trace: Optional[dict] = None, lights=None, light_shadows: bool = True,
-                    light_trace: Optional[dict] = None, atmosphere=None) -> None:
+                    light_trace: Optional[dict] = None, atmosphere=None, props=None, prop_bias: float = PROP_BIAS) -> None:
         """decode the illumination of ONE camera for a whole frame (the reference re-decodes it in each of the
         8100 chunks of a 1080p frame, neusky_model.py:1413-1432; the result is the same).  The frame stays active until end_frame.
-        The lighting keywords: relight.FrameLighting, which documents and checks them."""
+        The lighting keywords: relight.FrameLighting, which documents and checks them.  props, prop_bias: FrameRenderer.begin."""
         self.frames.begin(camera_index, FrameLighting.of(rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold,
                                                          daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace, lights=lights,
-                                                         light_shadows=light_shadows, light_trace=light_trace, atmosphere=atmosphere))
+                                                         light_shadows=light_shadows, light_trace=light_trace, atmosphere=atmosphere),
+                          props=props, prop_bias=prop_bias)
 
     def end_frame(self) -> None:
         self.frames.end()
@@ -901,7 +928,8 @@ class NeuSkyFactoModel(ModelBase):
                                           accumulation_mask_threshold: float = 0.0, daylight=None, sun_shadows: str = "ddf",
                                           shadow_trace: Optional[dict] = None, display=None, antialias=None, lights=None,
                                           light_shadows: bool = True, light_trace: Optional[dict] = None,
-                                          atmosphere=None, depth_of_field=None) -> Dict[str, torch.Tensor]:
+                                          atmosphere=None, depth_of_field=None, props=None,
+                                          prop_bias: float = PROP_BIAS) -> Dict[str, torch.Tensor]:
         """neusky_model.py:1369-1501: chunked full-frame render.  The reference chunks at eval_num_rays_per_chunk = 256
         (8100 python iterations per 1080p frame); any chunk size gives the same image, so a larger static chunk is used
         and its forward is captured once in a HIP graph and replayed per chunk (BASELINE config 5).
@@ -911,9 +939,12 @@ class NeuSkyFactoModel(ModelBase):
         display: a relight.DisplayTransform of the frame's linear image (FrameRenderer.render): display_rgb8, display_rgb, display_exposure.
         antialias: a relight.Antialias: sub-pixel rays through the pixels its edge rule marks, resolved in linear light: aa_mask, aa_fraction.
         depth_of_field: a relight.DepthOfField: thin-lens rays through the pixels a blurred pixel's disc reaches, resolved in linear light:
-        dof_coc, dof_mask, dof_fraction, dof_focus."""
+        dof_coc, dof_mask, dof_fraction, dof_focus.
+        props: a relight.Prop or a sequence of them (at most relight.MAX_PROPS; None or empty: none), solid spheres and boxes placed in the
+        scene: geometry, not light, so they are no part of FrameLighting.  Every output is then that of the scene with the props in it;
+        prop_id (int32) and prop_weight join them.  prop_bias: the lift of a prop's shadow rays off the rendered surface."""
         lighting = FrameLighting.of(rotation, envmap, sun, shadow_threshold, shadow_sigmoid_scale, accumulation_mask_threshold,
                                     daylight=daylight, sun_shadows=sun_shadows, shadow_trace=shadow_trace, lights=lights,
                                     light_shadows=light_shadows, light_trace=light_trace, atmosphere=atmosphere)
         return self.frames.render(camera_ray_bundle, lighting, to_cpu=to_cpu, camera_index=camera_index, chunk=chunk, use_graph=use_graph,
-                                  display=display, antialias=antialias, depth_of_field=depth_of_field)
+                                  display=display, antialias=antialias, depth_of_field=depth_of_field, props=props, prop_bias=prop_bias)

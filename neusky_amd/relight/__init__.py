@@ -40,6 +40,10 @@ shadowed along the ray by the frame's own shadow mode; the frame render takes on
 
 `FrameLighting` (lighting.py): all of the above as the one value a frame's light is said in, with the rules between its options.
 
+`Prop` (props.py, csrc/props.hip): solid spheres and boxes placed in a frame as one more sample per ray and an analytic factor on every
+visibility the frame forms: lit by the frame's light, shadowed by the scene and shadowing it.  Geometry, not light: the frame render
+takes them beside its lighting, as `props=` (`--prop-sphere`, `--prop-box`, `--props`).
+
 sequence.py: the run of the command line: the plan of a camera's renders, the two sources of its frames, the writer of its files, the
 tally of its closing lines.
 """
@@ -56,6 +60,7 @@ from .io import read_envmap, srgb_to_linear
 from .lighting import FrameLighting
 from .lights import (LIGHT_TRACE_DEFAULTS, MAX_LIGHTS, PointLight, as_lights, lights_block, load_lights, save_lights, trace_light_shadows,
                      trace_visibility_to)
+from .props import MAX_PROPS, PROP_BIAS, Prop, as_props, load_props, props_block, save_props
 from .shadows import ALIVE, ESCAPED, EXHAUSTED, HIT, SHADOW_DEFAULTS, TRACE_DEFAULTS, SphereTrace, trace_sun_shadows, trace_visibility
 from .sun import SunLight, sun_direction, sun_path, sun_solid_angle
 from .transfer import RadianceTransfer, bake_transfer, pack_fp16, unpack_fp16
@@ -67,4 +72,5 @@ __all__ = ["ALIVE", "Antialias", "Atmosphere", "CameraPath", "DaylightSky", "Dis
            "load_camera_path", "pack_fp16", "project_envmap", "project_lights", "r2_offsets", "read_envmap", "sh_basis", "srgb_to_linear", "sun_direction",
            "subpixel_rays", "sun_path", "sun_solid_angle", "trace_sun_shadows", "trace_visibility", "unpack_fp16", "z_rotation", "as_lights", "lights_block", "load_lights", "save_lights",
            "trace_light_shadows", "trace_visibility_to", "DepthOfField", "circle_of_confusion", "depth_of_field_frame", "lens_block", "lens_frame",
-           "lens_rays", "lens_table", "mark_pixels"]
+           "lens_rays", "lens_table", "mark_pixels", "MAX_PROPS", "PROP_BIAS", "Prop", "as_props", "load_props",
+           "props_block", "save_props"]

@@ -162,6 +162,18 @@ def build_parser() -> argparse.ArgumentParser:
                           "shadow queries per ray and sun")
     fog.add_argument("--fog-clear-background", action="store_true", help="leave the sky behind the scene as it is (a daylight sky has its own atmosphere)")
     fog.add_argument("--fog-map", action="store_true", help="also write the transmittance of each frame as fog_CCCC_FFF.png")
+    props = ap.add_argument_group("props", "solid spheres and boxes placed in the scene (relight.Prop): lit by the frame's light, shadowed by the "
+                                  "scene and shadowing it under every sky, sun, lamp and fog")
+    props.add_argument("--prop-sphere", type=float, nargs=7, action="append", metavar=("X", "Y", "Z", "RADIUS", "R", "G", "B"),
+                       help="a sphere at X Y Z (scene units) of linear albedo R G B; repeatable")
+    props.add_argument("--prop-box", type=float, nargs=10, action="append", metavar=("X", "Y", "Z", "HX", "HY", "HZ", "YAW", "R", "G", "B"),
+                       help="a box at X Y Z with half-extents HX HY HZ, turned YAW degrees about +z, of linear albedo R G B; repeatable")
+    props.add_argument("--props", metavar="FILE.json", help="a list of props with every field of relight.Prop; adds to the two above")
+    props.add_argument("--prop-bias", type=float, metavar="B", help="the lift of a prop's shadow rays off the rendered surface (default relight.PROP_BIAS, 1e-2)")
+    props.add_argument("--prop-mask", action="store_true", help="also write the props' share of each pixel as prop_CCCC_FFF.png (8 bits)")
+    props.add_argument("--prop-path", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                       help="the first prop moves along this segment: --prop-steps frames per camera, from one set of chunk graphs")
+    props.add_argument("--prop-steps", type=int, metavar="N", help="frames of --prop-path")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -217,6 +229,42 @@ def parse_lights(ap: argparse.ArgumentParser, args):
         a, b, n = args.light_path[:3], args.light_path[3:], args.light_steps
         path = [tuple(a[i] + (b[i] - a[i]) * (f / (n - 1) if n > 1 else 0.0) for i in range(3)) for f in range(n)]
     return lights, not args.no_light_shadows, trace, path
+
+
+def parse_props(ap: argparse.ArgumentParser, args):
+    """(props, prop_bias, path) of the frame render from the prop flags: (None, None, None) with none of them; path: the --prop-steps
+    positions of the first prop along --prop-path, or None"""
+    dependent = (("--prop-bias", args.prop_bias), ("--prop-mask", args.prop_mask or None), ("--prop-path", args.prop_path),
+                 ("--prop-steps", args.prop_steps))
+    if args.prop_sphere is None and args.prop_box is None and args.props is None:
+        refuse_given(ap, dependent, "{} needs a prop: --prop-sphere, --prop-box or --props")
+        return None, None, None
+    if args.transfer != "off":
+        ap.error("a baked transfer keeps the scene's own samples: --prop-sphere, --prop-box and --props exclude --transfer " + args.transfer)
+    from .props import PROP_BIAS, Prop, as_props, load_props
+    try:
+        props = [Prop("sphere", v[:3], v[3], v[4:]) for v in args.prop_sphere or ()]
+        props += [Prop("box", v[:3], v[3:6], v[7:], yaw_deg=v[6]) for v in args.prop_box or ()]
+        if args.props is not None:
+            props += list(load_props(args.props))
+        props = as_props(props)
+    except (OSError, TypeError, ValueError) as e:
+        ap.error(str(e))
+    if not props:
+        ap.error(f"{args.props}: no props")
+    if args.prop_bias is not None and not (0.0 <= args.prop_bias < math.inf):
+        ap.error("--prop-bias must be finite and >= 0")
+    path = None
+    if (args.prop_path is None) != (args.prop_steps is None):
+        ap.error("--prop-path and --prop-steps go together")
+    if args.prop_path is not None:
+        if args.prop_steps < 1:
+            ap.error("--prop-steps must be >= 1")
+        if args.turntable > 1 or (args.sun_steps or 1) > 1 or (args.light_steps or 1) > 1:
+            ap.error("--prop-path moves a prop from frame to frame: it excludes --turntable, --sun-steps and --light-steps above 1")
+        a, b, n = args.prop_path[:3], args.prop_path[3:], args.prop_steps
+        path = [tuple(a[i] + (b[i] - a[i]) * (f / (n - 1) if n > 1 else 0.0) for i in range(3)) for f in range(n)]
+    return props, PROP_BIAS if args.prop_bias is None else args.prop_bias, path
 
 
 def parse_atmosphere(ap: argparse.ArgumentParser, args):
@@ -490,6 +538,7 @@ def main(argv=None) -> int:
     depth_of_field = parse_depth_of_field(ap, args)
     lights, light_shadows, light_trace, light_path = parse_lights(ap, args)
     atmosphere = parse_atmosphere(ap, args)
+    props, prop_bias, prop_path = parse_props(ap, args)
 
     import torch
 
@@ -506,7 +555,7 @@ def main(argv=None) -> int:
     model, envmap, extraction = load_scene(args, daylight, suns)
     tally = Tally(t_load=time.perf_counter() - t0)
     os.makedirs(args.output_dir, exist_ok=True)
-    shots = frame_plan(args.turntable, args.rotation_deg, suns, args.sun_path is not None, light_path, args.transfer)
+    shots = frame_plan(args.turntable, args.rotation_deg, suns, args.sun_path is not None, light_path, args.transfer, prop_path=prop_path)
     # what every frame shares; a shot then differs by its rotation, its first lamp and, under an extracted sun, its sun: that sun turns
     # with its sky, so the one given here only stands for "one sun" and every shot replaces it
     sun = None
@@ -523,7 +572,8 @@ def main(argv=None) -> int:
     writer = FrameWriter(args, display, tally)
     shared = {"chunk": args.chunk, "display": display, "floats": writer.floats, "deferred": writer.deferred}
     if args.transfer == "off":
-        source = RenderSource(model, base, tally, antialias=antialias, extraction=extraction, depth_of_field=depth_of_field, **shared)
+        placed = {} if props is None else {"props": props, "prop_bias": prop_bias}
+        source = RenderSource(model, base, tally, antialias=antialias, extraction=extraction, depth_of_field=depth_of_field, **placed, **shared)
     else:
         source = BakedSource(model, envmap, tally, storage=args.transfer, sh_order=args.sh_order, **shared)
     t1 = time.perf_counter()
@@ -537,7 +587,7 @@ def main(argv=None) -> int:
     tally.t_render = time.perf_counter() - t1
     suns_per_render = 0 if sun is None else len(suns) if shots[0].sweep else 1
     tally.report(args, (cams.width, cams.height), display, antialias, shadow_trace, lights, light_trace, atmosphere, suns_per_render,
-                 bool(model.config.use_visibility), depth_of_field=depth_of_field)
+                 bool(model.config.use_visibility), depth_of_field=depth_of_field, props=props)
     return 0
 
 

@@ -25,8 +25,9 @@ from ..cameras.rays import RayBundle
 
 MAX_SAMPLES = 64
 R2_G = 1.32471795724474602596  # the plastic number: the real root of g^3 = g + 1
-# what the second pass's samples are averaged into (`rgb` follows `lin`); the last two are a frame's with `lights`
-RESOLVED_KEYS = ("lin", "albedo", "accumulation", "shadow_map", "light_lin", "light_visibility")
+# what the second pass's samples are averaged into (`rgb` follows `lin`); `light_*` are a frame's with `lights`, `prop_weight` one's with
+# `props` (its `prop_id` stays the centre ray's)
+RESOLVED_KEYS = ("lin", "albedo", "accumulation", "shadow_map", "light_lin", "light_visibility", "prop_weight")
 
 
 def r2_offsets(samples: int) -> torch.Tensor:

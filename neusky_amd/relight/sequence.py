@@ -18,6 +18,7 @@ from .depth_of_field import DepthOfField
 from .display import DisplayTransform
 from .envmap import z_rotation
 from .io import srgb_to_linear
+from .props import PROP_BIAS
 from .shadows import EXHAUSTED
 from .transfer import LIGHTS_PER_PASS, bake_transfer
 from .transfer_sh import bake_transfer_sh
@@ -29,17 +30,22 @@ class Shot(NamedTuple):
     angles: tuple  # the illumination's turn about +z, radians, one per rotation the call takes; None: exactly none
     lamp: Optional[tuple] = None  # where the first lamp stands, if it moves
     sweep: bool = False  # one render under all the suns of a path: a frame per sun
+    prop: Optional[tuple] = None  # where the first prop stands, if it moves
 
 
 def frame_plan(turntable: int, rotation_deg: float, suns: Optional[list], sun_path: bool, light_path: Optional[list],
-               transfer: str) -> List[Shot]:
-    """The shots of one camera, in order; their frames are 0..F-1, each once.  A moving lamp: a render per position, all at the first
+               transfer: str, prop_path: Optional[list] = None) -> List[Shot]:
+    """The shots of one camera, in order; their frames are 0..F-1, each once.  A moving prop: a render per position, all at the first
+    rotation, first sun and first lamp position.  A moving lamp: a render per position, all at the first
     rotation (a sun path of one step under it is one sun, suns[0]).  A sun path: one render that yields a frame per sun.  A baked
     transfer: one relight pass per LIGHTS_PER_PASS rotations of the turntable.  Else a render per rotation of the turntable."""
     def angle(f):
         a = math.radians(rotation_deg) + 2.0 * math.pi * f / turntable
         return None if a == 0.0 else a
 
+    if prop_path is not None:
+        lamp = None if light_path is None else tuple(light_path[0])
+        return [Shot(range(f, f + 1), (angle(0),), lamp=lamp, prop=tuple(p)) for f, p in enumerate(prop_path)]
     if light_path is not None:
         return [Shot(range(f, f + 1), (angle(0),), lamp=tuple(p)) for f, p in enumerate(light_path)]
     if sun_path:
@@ -70,6 +76,7 @@ class Frame:
     transmittance: Optional[torch.Tensor] = None  # under an atmosphere: T to each ray's depth (a sweep's frames share it)
     inscatter: Optional[torch.Tensor] = None  # under an atmosphere: what the medium added to the frame's `lin`
     coc: Optional[torch.Tensor] = None  # with a depth of field: the circle of confusion in pixels (a sweep's frames share it)
+    prop_weight: Optional[torch.Tensor] = None  # with props: the share of each pixel that is a prop (a sweep's frames share it)
 
 
 class Tally:
@@ -84,9 +91,10 @@ class Tally:
         self.sh_residual = self.sh_store = None  # of --sh-order: the largest light_residual so far, and a camera's (coefficients, bytes)
         self.transmittances = []  # of --fog-density: every render's mean transmittance, device tensors
         self.focuses, self.lens_marked = [], []  # of --dof-aperture: every render's 1 / z_f (device tensors) and share of marked pixels
+        self.prop_shares = []  # of the props: every render's share of pixels with prop_weight > 0.5, device tensors
 
     def report(self, args, size, display, antialias, shadow_trace, lights, light_trace, atmosphere=None, suns: int = 0,
-               ddf_shadows: bool = True, depth_of_field=None) -> None:
+               ddf_shadows: bool = True, depth_of_field=None, props=None) -> None:
         """size: the frames' (width, height); shadow_trace: of --sun-shadows sdf, else None; suns: per render; ddf_shadows: whether the
         model has a visibility network (without one the DDF mode shadows nothing); the rest as the parse_* functions return them"""
         transfer = "" if args.transfer == "off" else f" | transfer {args.transfer}: bake {self.t_bake:.3f}s relight {self.t_relight:.3f}s"
@@ -128,14 +136,20 @@ class Tally:
                 what = (f"{atmosphere.shaft_samples} shaft samples x {suns} sun{'s' if suns > 1 else ''}: {rows} extra "
                         f"{'DDF rows' if shadow_trace is None else 'marched shadow rays'} per ray")
             print(f"fog: mean transmittance smallest {float(T.min()):.4g} largest {float(T.max()):.4g} | {what}")
+        if props is not None and self.prop_shares:
+            share = torch.stack(self.prop_shares)
+            print(f"props: {len(props)} prop{'s' if len(props) > 1 else ''} | share of pixels with prop_weight > 0.5: smallest "
+                  f"{float(share.min()):.4g} largest {float(share.max()):.4g}")
 
 
 class RenderSource:
     """a shot's frames from model.frames.render: direct renders, sweeps, moving lamps, and extracted suns, which turn with their map.
-    base: the run's FrameLighting; a shot replaces its rotation and, with them, the extracted sun and the first lamp."""
+    base: the run's FrameLighting; a shot replaces its rotation and, with them, the extracted sun and the first lamp.  props: the
+    run's relight.Prop, which travel beside the lighting; a shot replaces the first one's position."""
 
     def __init__(self, model, base, tally: Tally, *, chunk: int, display, antialias, extraction, floats: bool, deferred: bool,
-                 depth_of_field=None):
+                 depth_of_field=None, props=None, prop_bias: float = PROP_BIAS):
+        self.props, self.prop_bias = props, prop_bias
         self.model, self.base, self.tally, self.chunk, self.extraction = model, base, tally, chunk, extraction
         self.display, self.floats, self.deferred = display, floats, deferred
         self.camera = self.rays = None  # of `open`
@@ -150,8 +164,14 @@ class RenderSource:
         turned = {} if self.extraction is None else {"suns": (self.extraction.sun(rot),)}
         if shot.lamp is not None:
             turned["lights"] = (dataclasses.replace(base.lights[0], position=shot.lamp),) + tuple(base.lights[1:])
+        placed = {}
+        if self.props is not None:
+            first = self.props[0] if shot.prop is None else self.props[0].moved_to(shot.prop)
+            placed = {"props": (first,) + tuple(self.props[1:]), "prop_bias": self.prop_bias}
         out = self.model.frames.render(self.rays, dataclasses.replace(base, rotation=rot, **turned), camera_index=0, chunk=self.chunk,
-                                       **self.shown)
+                                       **self.shown, **placed)
+        if placed:
+            tally.prop_shares.append((out["prop_weight"] > 0.5).to(torch.float32).mean())
         if base.light_trace is not None:
             tally.light_rays += out["light_status"].numel()
             tally.light_exhausted += int((out["light_status"] == EXHAUSTED).sum())
@@ -174,7 +194,8 @@ class RenderSource:
             frame = Frame(self.camera, f, shadow=own("shadow_map") if base.suns is not None else None,
                           light_lin=out["light_lin"] if base.lights else None, aa_mask=out["aa_mask"] if "antialias" in self.shown else None,
                           transmittance=out["atmosphere_transmittance"] if fogged else None,
-                          inscatter=own("atmosphere_inscatter") if fogged else None, coc=out["dof_coc"] if lens else None)
+                          inscatter=own("atmosphere_inscatter") if fogged else None, coc=out["dof_coc"] if lens else None,
+                          prop_weight=out["prop_weight"] if placed else None)
             if self.floats:
                 frame.rgb = own("rgb").clamp(0.0, 1.0).cpu().numpy()
             if display is not None:
@@ -263,6 +284,9 @@ class FrameWriter:
             reach = self.args.dof_reach if getattr(self.args, "dof_reach", None) is not None else DepthOfField.reach
             c8 = torch.round((frame.coc[..., 0] / reach).clamp(0.0, 1.0).nan_to_num(0.0) * 255.0).to(torch.uint8)
             Image.fromarray(c8.cpu().numpy(), mode="L").save(self._path("coc", frame, ".png"))
+        if frame.prop_weight is not None and getattr(args, "prop_mask", False):
+            w8 = torch.round(frame.prop_weight[..., 0].clamp(0.0, 1.0).nan_to_num(0.0) * 255.0).to(torch.uint8)
+            Image.fromarray(w8.cpu().numpy(), mode="L").save(self._path("prop", frame, ".png"))
         if frame.transmittance is not None:
             if args.fog_map:
                 T8 = np.round(frame.transmittance.clamp(0.0, 1.0).cpu().numpy() * 255.0).astype(np.uint8)
